@@ -9,14 +9,15 @@ Unit: the nets consume 64x64 blocks (+4 px context); one VTM CTU is 128x128 = 4 
 (one library pass: the default chunk is 4096 blocks) and CTU/s = blocks/s / 4 (BASELINE.md section 2).  `value` is CTU/s;
 blocks/s is reported next to it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 N > 1: one process per GPU.  Under torch.distributed.run (RANK / WORLD_SIZE in the environment) this process is one rank;
 started plainly with --gpus N it launches its own N rank processes - fresh children, before this process has made any GPU
 call - relays rank 0's JSON line and exits non-zero if any rank failed.  Blocks are sharded over the ranks (weak scaling:
 --ctus per GPU) with no data-path collective; the one exchange is the RCCL gather of the packed split-flag records to rank 0.
 
-Rank 0 prints ONE JSON line on stdout; diagnostics go to stderr.
+Rank 0 prints ONE JSON line on stdout; diagnostics go to stderr.  --dump-outputs DIR: rank 0 also writes the records of the last
+timed step (all ranks' after the gather) as float32 .npy files, so that two builds can be compared on the same seeded inputs.
 """
 import argparse
 import json
@@ -78,6 +79,26 @@ def pmc_traffic(precision, blocks_per_launch):
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_BYTES = 64 * 10 ** 6        # --dump-outputs in all, .npy headers included
+
+
+def dump_outputs(dirpath, rec):
+    """rec: u8[n, PMP_RECORD_BYTES] packed records (include/pmp.h), unpacked into the four arrays a caller reads from them - hor, ver,
+    qt, dire - as float32 DIR/<name>.npy.  Above DUMP_BYTES in all, a fixed seeded sample of the blocks; block_index.npy (float64)
+    names the blocks written."""
+    from pmp_vvc_tip2023_amd import parallel
+    n = rec.shape[0]
+    idx = np.arange(n)
+    per_block = rec.shape[1] * 4 + 8
+    if n * per_block > DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(n, (DUMP_BYTES - 4096) // per_block, replace=False))
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in zip(("hor", "ver", "qt", "dire"), parallel.unpack_records(rec[idx])):
+        np.save(os.path.join(dirpath, name + ".npy"), a.astype(np.float32))
+    np.save(os.path.join(dirpath, "block_index.npy"), idx.astype(np.float64))
+    log("dump-outputs: %d of %d blocks -> %s" % (len(idx), n, dirpath))
 
 
 def cpu_baseline(sample_blocks, seed, eng=None):
@@ -407,8 +428,12 @@ def main():
     ap.add_argument("--lib", default=None, help="path of another build of libpmp_hip.so (same-box A/B timing, tools/lib_ab.py)")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the side measurements after the timed region (host-buffer end-to-end rate, chroma, per-QP luma)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the split flags of the last timed step as DIR/<name>.npy (float32; at most 64 MB, a seeded block sample above)")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)      # internal: "<blocks>,<seed>,<threads>" (cpu_all_cores)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.cpu_worker:
         b, sd, th = (int(t) for t in args.cpu_worker.split(","))
@@ -485,6 +510,7 @@ def main():
 
     gather_events = []          # (start, end) event pairs around the collective, on the stream it is ordered on
     gather_host_s = [0.0]
+    gathered_host = [None]      # gloo: rank 0's host copies of every rank's records from the latest step
 
     def step(comp=args.comp, qp=args.qp, timed=False):
         chroma = comp == "Chroma"
@@ -504,7 +530,8 @@ def main():
                 eng.synchronize()
                 th = time.perf_counter()
                 rc = res.cpu()
-                dist.gather(rc, [torch.empty_like(rc) for _ in range(world)] if rank == 0 else None, dst=0)
+                gathered_host[0] = [torch.empty_like(rc) for _ in range(world)] if rank == 0 else None
+                dist.gather(rc, gathered_host[0], dst=0)
                 gather_host_s[0] += (time.perf_counter() - th) if timed else 0.0
 
     for _ in range(args.warmup):
@@ -530,6 +557,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:         # before anything else runs a step and overwrites the records
+        last = gathered if gathered is not None else torch.cat(gathered_host[0]) if gathered_host[0] else res
+        dump_outputs(args.dump_outputs, last.cpu().numpy())
     kt = eng.ktime()
     eng.ktime_enable(0)
     multi = None

@@ -126,14 +126,23 @@ def test_512_fresh_blocks_logits_and_end_to_end_flags_vs_oracle(eng, comp, qp):
 def test_conv_kernel_shapes_beyond_the_nets(eng, shape):
     """Convolution shapes the four nets never launch (odd channel-group counts: the unpaired K order of the split kernels;
     1x1; non-square maps): the split datapaths against the exact fp32 MFMA kernel on the same random tensors
-    (pmp_debug_conv_bench, include/pmp.h)."""
+    (pmp_debug_conv_bench, include/pmp.h).  A context on the fp32 datapath compares against the bf16x6 kernel (include/pmp.h): there
+    the comparison must hold too, and give exactly the numbers of a bf16x6 context (both kernels are deterministic, the tensors seeded)."""
     import ctypes as C
-    if eng.get_precision() == "fp32":
-        pytest.skip("the fp32 kernel is the reference of this comparison")
     n, h, w, ci, co, k = shape
-    a, b, d, r = C.c_double(), C.c_double(), C.c_double(), C.c_double()
-    eng._ck(eng.lib.pmp_debug_conv_bench(eng.h, n, h, w, ci, co, k, 1, C.byref(a), C.byref(b), C.byref(d), C.byref(r)))
-    assert r.value > 0.5 and d.value < 1e-4 * max(1.0, r.value), (shape, d.value, r.value)
+
+    def bench():
+        a, b, d, r = C.c_double(), C.c_double(), C.c_double(), C.c_double()
+        eng._ck(eng.lib.pmp_debug_conv_bench(eng.h, n, h, w, ci, co, k, 1, C.byref(a), C.byref(b), C.byref(d), C.byref(r)))
+        return d.value, r.value
+    d, r = bench()
+    assert r > 0.5 and d < 1e-4 * max(1.0, r), (shape, d, r)
+    if eng.get_precision() == "fp32":
+        eng.set_precision("bf16x6")
+        try:
+            assert bench() == (d, r), shape
+        finally:
+            eng.set_precision("fp32")
 
 
 def test_small_calls_need_small_workspaces():
@@ -1136,6 +1145,28 @@ def test_bench_launches_its_own_ranks(tmp_path):
     d1 = json.loads(r1.stdout.strip())
     assert "multi_gpu" not in d1 and "rccl_ranks" not in d1 and d1["n_gpus"] == 1
 
+
+def test_bench_dump_outputs_are_the_timed_steps_flags(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the split flags of its last timed step: the arrays pmp_infer_postprocess returns for the
+    same seeded blocks (recipe R seed 1, Luma QP22, default datapath), as float32, with the block index beside them."""
+    import os, subprocess, sys
+    from pmp_vvc_tip2023_amd import engine, synth
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n = 48
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "0", "--batch", str(n), "--cpu-sample", "0",
+                        "--no-extras", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    got = {k: np.load(tmp_path / "out" / (k + ".npy")) for k in ("hor", "ver", "qt", "dire", "block_index")}
+    assert all(a.dtype == np.float32 for k, a in got.items() if k != "block_index") and got["block_index"].dtype == np.float64
+    assert np.array_equal(got["block_index"], np.arange(n))
+    y, u, v = synth.recipe_r_blocks(n, 1)
+    e = engine.Engine(0, allow_synthetic_mtt=True)
+    try:
+        hor, ver, q8, d8 = e.infer_postprocess("Luma", 22, y)
+    finally:
+        e.close()
+    for k, want, shape in (("hor", hor, (n, 16, 16)), ("ver", ver, (n, 16, 16)), ("qt", q8, (n, 8, 8)), ("dire", d8, (n, 3, 16, 16))):
+        assert got[k].shape == shape and np.array_equal(got[k], want.reshape(shape).astype(np.float32)), k
 
 def test_records_entry_point_equals_the_four_arrays(eng):
     """pmp_infer_postprocess_records_device writes hor | ver | qt | dire of every block as one 1344-byte record: the same bytes

@@ -87,41 +87,23 @@ def test_real_partitionmat_fixture_invariants():
     assert np.array_equal(qt[::2, ::2], qt[1::2, 1::2])            # QT section is 2x2-constant
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="live reference only exists in the build container")
-def test_oracle_against_live_reference(oracle_lib):
-    """Fresh random maps through the imported reference (not a committed fixture)."""
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-    import ref_harness as R
-    from pmp_vvc_tip2023_amd import synth
-    _, _, M2P, _ = R.load()
-    seed = int.from_bytes(os.urandom(2), "little")
+def test_oracle_against_reference_on_seeded_maps(oracle_lib):
+    """Seeded random maps through the reference (g9, tools/gen_golden.py): valid partitions through map_to_parititon, and maps with
+    raw float32 bit patterns (round 6: the kernel is tested against the oracle on these) through eli_structual_error - the QT fix -
+    and map_to_parititon."""
+    g = golden("g9_m2p_seeded.npz")
     for cf in (1, 2):
-        qt, bt, dire = synth.random_partition_batch(40, seed + cf, cf, 0.25)
+        qt, bt, dire = (g["rand_%s_cf%d" % (k, cf)] for k in ("qt", "bt", "dire"))
         h, v, d, _ = oracle_lib.map_to_partition(qt, bt, dire, cf)
+        assert len(qt) == 40
         for i in range(len(qt)):
-            rh, rv, rd = M2P.map_to_parititon(qt[i], bt[i], dire[i], cf)
-            assert np.array_equal(rh, h[i]) and np.array_equal(rv, v[i]) and np.array_equal(rd, d[i]), (seed, cf, i)
-    # ... and on raw random bit patterns (round 6: the kernel is tested against the oracle on these): the QT fix included
-    import warnings
-    import torch
-    _, Met, _, _ = R.load()
-    rng = np.random.default_rng(seed)
-    for cf in (1, 2):
-        for k in range(12):
-            if k % 2:
-                ql, b, d = (rng.integers(0, 2 ** 32, size=sh, dtype=np.uint64).astype(np.uint32).view(np.float32) for sh in ((8, 8), (3, 16, 16), (3, 16, 16)))
-            else:
-                q, b, d = synth.random_partition_maps(rng, cf)
-                ql = (q + rng.normal(0, 0.2, q.shape)).astype(np.float32)
-                for arr in (ql, b, d):
-                    m = rng.random(arr.shape) < 0.15
-                    arr[m] = rng.integers(0, 2 ** 32, size=int(m.sum()), dtype=np.uint64).astype(np.uint32).view(np.float32)
-            with warnings.catch_warnings(), torch.no_grad():
-                warnings.simplefilter("ignore")
-                fixed = Met.eli_structual_error(torch.from_numpy(ql[None, None].copy())).numpy()[0, 0]
-                rh, rv, rd = M2P.map_to_parititon(fixed, b, d, cf)
-            of = oracle_lib.eli_structural_error(ql[None]).reshape(8, 8)
-            oh, ov, od, _ = oracle_lib.map_to_partition(of[None], b[None], d[None], cf)
-            assert np.array_equal(of, fixed, equal_nan=True), (seed, cf, k)
-            assert np.array_equal(rh, oh[0]) and np.array_equal(rv, ov[0]) and np.array_equal(rd, od[0]), (seed, cf, k)
+            assert (np.array_equal(g["rand_hor_cf%d" % cf][i], h[i]) and np.array_equal(g["rand_ver_cf%d" % cf][i], v[i])
+                    and np.array_equal(g["rand_dout_cf%d" % cf][i], d[i])), (cf, i)
+        ql, b, d, fixed = (g["raw_%s_cf%d" % (k, cf)] for k in ("qt", "bt", "dire", "fixed"))
+        assert len(ql) == 12
+        for k in range(len(ql)):
+            of = oracle_lib.eli_structural_error(ql[k][None]).reshape(8, 8)
+            oh, ov, od, _ = oracle_lib.map_to_partition(of[None], b[k][None], d[k][None], cf)
+            assert np.array_equal(of, fixed[k], equal_nan=True), (cf, k)
+            assert (np.array_equal(g["raw_hor_cf%d" % cf][k], oh[0]) and np.array_equal(g["raw_ver_cf%d" % cf][k], ov[0])
+                    and np.array_equal(g["raw_dout_cf%d" % cf][k], od[0])), (cf, k)

@@ -132,6 +132,36 @@ def test_bench_self_launch_propagates_rank_failure():
     assert 1 <= r.stderr.count("no CPU fallback") <= 2 and "stopping the other ranks" in r.stderr
 
 
+def test_bench_dump_outputs_unpacks_records_and_caps_the_size(tmp_path):
+    """bench.py --dump-outputs: packed records (hor | ver | qt | dire) become four float32 arrays; above the size cap a seeded sample of
+    blocks is written, the same one every time, and block_index.npy says which."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(3)
+    for n in (64, 8 * 4096):
+        rec = rng.integers(0, 256, size=(n, 1344), dtype=np.uint8)
+        out = {}
+        for tag in ("a", "b"):
+            bench.dump_outputs(str(tmp_path / ("%d%s" % (n, tag))), rec)
+            out[tag] = {k: np.load(tmp_path / ("%d%s" % (n, tag)) / (k + ".npy")) for k in ("hor", "ver", "qt", "dire", "block_index")}
+        assert all(np.array_equal(out["a"][k], out["b"][k]) for k in out["a"])
+        got = out["a"]
+        idx = got["block_index"].astype(np.int64)
+        assert got["block_index"].dtype == np.float64 and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < n
+        assert sum(os.path.getsize(tmp_path / ("%da" % n) / f) for f in os.listdir(tmp_path / ("%da" % n))) <= bench.DUMP_BYTES
+        if n == 64:
+            assert np.array_equal(idx, np.arange(n))
+        else:
+            assert len(idx) < n
+        r = rec[idx]
+        assert np.array_equal(got["hor"], r[:, :256].reshape(-1, 16, 16).astype(np.float32))
+        assert np.array_equal(got["ver"], r[:, 256:512].reshape(-1, 16, 16).astype(np.float32))
+        assert np.array_equal(got["qt"], r[:, 512:576].reshape(-1, 8, 8).astype(np.float32))
+        assert np.array_equal(got["dire"], r[:, 576:].view(np.int8).reshape(-1, 3, 16, 16).astype(np.float32))
+        assert all(a.dtype == np.float32 for k, a in got.items() if k != "block_index")
+
 def test_spawn_ranks_stops_everyone_when_one_rank_dies(tmp_path):
     """a rank other than 0 that dies first must end the job at once - rank 0 would otherwise sit in its first
     collective until the timeout.  spawn_ranks polls ALL children: here rank 1 exits with code 7 immediately while rank 0 sleeps

@@ -1,5 +1,6 @@
 """CPU: SURVEY.md 8(f) rows N1 / N2 / N4 against the REAL consumer - the reference's patched VTM-10.0, built on Linux from its
-sources where they lie (tools/vtm_build/CMakeLists.txt; nothing is copied into this repository).
+sources where they lie by build() (`make -C oracle ref`: tools/vtm_build/CMakeLists.txt into oracle/_ref/vtm; nothing is copied into
+this repository); the encoder configuration is the reference's demo cfg, kept as a fixture (tests/golden/encoder_intra_vtm.cfg).
 
   N1  EncoderApp parses a PartitionMat pair written by the product (pmp_write_partition_file) with its own
       EncAppCfg::parsePartitionMatrix (EncAppCfg.cpp:4234-4404), encodes, and DecoderApp decodes the stream with matching MD5s;
@@ -10,36 +11,26 @@ sources where they lie (tools/vtm_build/CMakeLists.txt; nothing is copied into t
   N4  without any file the hook goes in-process through libpmp_hip.so; on this GPU-less box that must end with the library's
       "no CPU fallback" error (the GPU leg is recorded in profiles/r02_n4_inprocess_hook.txt).
 
-Skipped where /root/reference or cmake is absent (the GPU box).  The first run builds VTM (about 3 minutes on 8 cores)."""
+Skipped where build() made no VTM binaries (no reference sources, or no cmake / ninja: the GPU box)."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from conftest import ROOT, golden_path
 
-VTM_SRC = "/root/reference/codec/vtm10.0-source-with-pmp-fast-alg"
-ENC_CFG = "/root/reference/codec/demo/cfg/encoder_intra_vtm.cfg"
-BUILD = os.path.join(ROOT, "tools", "vtm_build", "_build")
+ENC_CFG = golden_path("encoder_intra_vtm.cfg")
+BUILD = os.path.join(ROOT, "oracle", "_ref", "vtm")
 W, H, F, QP = 128, 128, 2, 32
 SEQ = "Tiny_%dx%d_30" % (W, H)
 
 
 @pytest.fixture(scope="module")
 def vtm():
-    if not os.path.isdir(VTM_SRC) or not os.path.isfile(ENC_CFG):
-        pytest.skip("reference VTM sources not present")
-    if shutil.which("cmake") is None or shutil.which("ninja") is None:
-        pytest.skip("cmake / ninja not available")
-    subprocess.check_call(["make", "-s", "-j8", "-C", os.path.join(ROOT, "pmp_vvc_tip2023_amd", "csrc")])   # the hook links it
     bins = {n: os.path.join(BUILD, n) for n in ("EncoderApp", "DecoderApp", "EncoderAppHook")}
     if not all(os.path.isfile(p) for p in bins.values()):
-        subprocess.check_call(["cmake", "-S", os.path.join(ROOT, "tools", "vtm_build"), "-B", BUILD, "-G", "Ninja", "-DCMAKE_BUILD_TYPE=Release"],
-                              stdout=subprocess.DEVNULL)
-    r = subprocess.run(["cmake", "--build", BUILD, "-j8"], capture_output=True, text=True, timeout=3000)   # no-op when up to date
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        pytest.skip("build() made no VTM binaries here (oracle/_ref/vtm): no reference VTM sources, or no cmake / ninja")
     return bins
 
 
@@ -76,7 +67,10 @@ def _workdir(tmp_path, name):
     return d
 
 
-def _encode(binary, cwd, env=None):
+def _encode(binary, cwd):
+    # EncoderAppHook links libpmp_hip.so: found in this tree wherever the tree now lies, not where it was built
+    lib = os.path.join(ROOT, "pmp_vvc_tip2023_amd")
+    env = dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join(p for p in (lib, os.environ.get("LD_LIBRARY_PATH")) if p))
     return subprocess.run([binary, "-c", "seq.cfg", "-c", ENC_CFG, "-f", str(F), "-ts", "1", "-q", str(QP), "-b", "out.bin", "-o", "rec.yuv",
                            "--SEIDecodedPictureHash=1"], cwd=str(cwd), capture_output=True, text=True, timeout=900, env=env)
 

@@ -13,6 +13,9 @@ Every output is produced by calling the reference's own functions:
   G5  Map2Partition.get_sequence_partition_for_VTM (text bytes)            -> g5_seq.npz + g5_partitionmat.txt
   G6  Inference_QBD.output_block_yuv         8-bit and 10-bit frames       -> g6_cut.npz
   G7  first frame of the reference's own demo PartitionMat file            -> g7_racehorses_luma_qp22_frame0.txt
+  G8  trained_models/*_Q_*.pkl through weights.load_pkl: name, shape and sha256 of every tensor -> g8_qt_pkl_digests.npz
+  G9  Map2Partition.map_to_parititon on seeded random maps, and Metrics.eli_structual_error + map_to_parititon on seeded maps
+      with raw float32 bit patterns                                        -> g9_m2p_seeded.npz
 The script also cross-checks the oracle restatements against the reference while it runs.
 """
 import hashlib
@@ -459,8 +462,63 @@ def gen_g7():
     print("G7", len(first), "bytes")
 
 
+# ------------------------------------------------------------------------------------------- G8
+def tensor_digests(tensors):
+    """One line per tensor, sorted by name: "<name> <shape> <sha256 of the float32 bytes>" (tests/test_weights_cpu.py makes the same)."""
+    return np.array(["%s %s %s" % (k, "x".join(map(str, v.shape)), hashlib.sha256(np.ascontiguousarray(v, np.float32).tobytes()).hexdigest())
+                     for k, v in sorted(tensors.items())])
+
+
+def gen_g8():
+    from pmp_vvc_tip2023_amd import weights as W
+    out = {}
+    for comp in ("Luma", "Chroma"):
+        for qp in (22, 27, 32, 37):
+            out["%s_Q_%d" % (comp, qp)] = tensor_digests(W.load_pkl("/root/reference/trained_models/%s_Q_%d.pkl" % (comp, qp)))
+    np.savez_compressed(os.path.join(OUT, "g8_qt_pkl_digests.npz"), meta=np.array(META), **out)
+    print("G8", {k: len(v) for k, v in out.items()})
+
+
+# ------------------------------------------------------------------------------------------- G9
+def gen_g9():
+    """Per cf: 40 random valid partitions (synth.random_partition_batch, seed 900 + cf) through map_to_parititon, and 12 maps of which
+    every second one is raw float32 bit patterns and the others valid maps with 15 % of their values replaced by raw bit patterns,
+    through eli_structual_error (the QT fix) and map_to_parititon."""
+    import warnings
+    out = {}
+    rng = np.random.default_rng(901)
+    for cf in (1, 2):
+        qt, bt, dire = synth.random_partition_batch(40, 900 + cf, cf, 0.25)
+        ref = [M2P.map_to_parititon(qt[i], bt[i], dire[i], cf) for i in range(len(qt))]
+        for k, a in (("qt", qt), ("bt", bt), ("dire", dire)):
+            out["rand_%s_cf%d" % (k, cf)] = a
+        for j, k in enumerate(("hor", "ver", "dout")):
+            out["rand_%s_cf%d" % (k, cf)] = np.stack([r[j] for r in ref])
+        raw = {k: [] for k in ("qt", "bt", "dire", "fixed", "hor", "ver", "dout")}
+        for k in range(12):
+            if k % 2:
+                ql, b, d = (rng.integers(0, 2 ** 32, size=sh, dtype=np.uint64).astype(np.uint32).view(np.float32)
+                            for sh in ((8, 8), (3, 16, 16), (3, 16, 16)))
+            else:
+                q, b, d = synth.random_partition_maps(rng, cf)
+                ql = (q + rng.normal(0, 0.2, q.shape)).astype(np.float32)
+                for arr in (ql, b, d):
+                    m = rng.random(arr.shape) < 0.15
+                    arr[m] = rng.integers(0, 2 ** 32, size=int(m.sum()), dtype=np.uint64).astype(np.uint32).view(np.float32)
+            with warnings.catch_warnings(), torch.no_grad():
+                warnings.simplefilter("ignore")
+                fixed = Met.eli_structual_error(torch.from_numpy(ql[None, None].copy())).numpy()[0, 0]
+                rh, rv, rd = M2P.map_to_parititon(fixed, b, d, cf)
+            for key, a in zip(raw, (ql, b, d, fixed, rh, rv, rd)):
+                raw[key].append(np.asarray(a))
+        for key, a in raw.items():
+            out["raw_%s_cf%d" % (key, cf)] = np.stack(a)
+    np.savez_compressed(os.path.join(OUT, "g9_m2p_seeded.npz"), meta=np.array(META), **out)
+    print("G9", {k: v.shape for k, v in out.items()})
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g2b", "g3", "g3b", "g4", "g5", "g6", "g7"]
+    which = sys.argv[1:] or ["g1", "g2b", "g3", "g3b", "g4", "g5", "g6", "g7", "g8", "g9"]
     if "g1" in which: gen_g1_g2()
     if "g2b" in which: gen_g2b()
     if "g3" in which: gen_g3()
@@ -469,4 +527,6 @@ if __name__ == "__main__":
     if "g5" in which: gen_g5()
     if "g6" in which: gen_g6()
     if "g7" in which: gen_g7()
+    if "g8" in which: gen_g8()
+    if "g9" in which: gen_g9()
     print("done ->", OUT)
