@@ -312,6 +312,32 @@ int pmp_debug_activation_report(pmp_ctx *ctx, int comp, int qp, int exps[5], flo
  *      on = 1 (default) uses the calibrated exponents.  Settles the calls in flight first. ---- */
 int pmp_debug_set_activation_scales(pmp_ctx *ctx, int on);
 
+/* ---- test hook: every intermediate tensor of an inference call, for layer-local checks against a float64 reference
+ *      (oracle/layers64.py, tests/test_gpu_layers.py).  While taps are on (pmp_debug_set_taps(ctx, 1); 0 turns them off and frees
+ *      their memory), every inference call records each tensor the graph produces, by a device-to-device copy on the context's stream
+ *      right behind the launch that wrote it (so an identity-shortcut block that later overwrites its input in place cannot reach the
+ *      copy).  Names carry the net: "q/stem", "q/resblock_q1.t" (a ResidualBlock's intermediate), "q/resblock_q1", "q/x6" (the
+ *      multi-scale pool), "q/resblock_q3" (also inside the fused 16x16 tail), "bd/trunk_M1.3", "bd/att_input1", "bd/trunk_Att1.1"
+ *      (also inside the fused tail), ...; a tensor that a fused kernel keeps in LDS has no tap.  Not recorded: the calibration pass of
+ *      the activation scales, the arena's measuring pass, and the fp32 re-run of the range guard - a test that reads taps runs with the
+ *      saturation policy at PMP_SAT_ERROR or PMP_SAT_IGNORE and checks that nothing saturated.  With taps on, an inference call must
+ *      run as one pass of at most 64 blocks (n <= chunk) with overlap mode off: PMP_E_INVALID otherwise.
+ *      pmp_debug_get_tap (settles the calls in flight) returns the tensor `name` of the last call as dense NCHW float64, padded channels
+ *      included (dims = {n, C padded to 16, H, W}, *c_real = the real channel count), at true scale (the stored value times 2^e of its
+ *      segment on f16x3 with activation scales) and exactly as the consuming kernel reads it: h0 + h1 (split-2), b0 + b1 + b2
+ *      (split-3), the fp32 value - float64 holds these sums exactly.  Returns the element count (out == NULL or cap too small: nothing
+ *      written) or a negative error (PMP_E_INVALID: no such tensor). ---- */
+int pmp_debug_set_taps(pmp_ctx *ctx, int on);
+int64_t pmp_debug_get_tap(pmp_ctx *ctx, const char *name, double *out, int64_t cap, int dims[4], int *c_real);
+
+/* ---- test hook: poisoned workspaces.  pattern 1: before every pass, fill every activation workspace the context uses (its own, the
+ *      second one of overlap mode, one taken over from a destroyed context - the whole buffer) with 0xFF bytes, a NaN in fp32, bf16 and
+ *      fp16; pattern 2: with 0x3C bytes, a finite value (0.0115 in fp32, 1.06 in fp16) that a ReLU would not swallow as it swallows a NaN.
+ *      The context's own logit buffers (fused entry points called without logit pointers, host-pointer entry points) are filled too
+ *      before each call that uses them.  hipMemsetAsync on the context's streams, nothing else; 0 (default) turns it off.  A kernel that
+ *      reads a byte it did not write shows up as a difference from an unpoisoned run (tests/test_gpu_layers.py).  Settles first. ---- */
+int pmp_debug_poison_workspace(pmp_ctx *ctx, int pattern);
+
 /* ---- test hook (host only, no GPU needed): the f16x3 weight packing of one OIHW conv tensor (conv_f16x3.hip).
  *      Writes the power-of-two exponent k of the scale S = 2^k to *scale_exp and, if out != NULL, the packed stream
  *      [K-step][2 splits][cout_pad/16][64 lanes][8] of fp16 bit patterns (h0, h1 with h0 + h1 ~= S*w) to out.

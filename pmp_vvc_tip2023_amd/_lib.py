@@ -74,6 +74,9 @@ SIGNATURES = {
     "pmp_debug_set_fusion": (_I, [_VP, _I]),
     "pmp_debug_set_activation_scales": (_I, [_VP, _I]),
     "pmp_debug_activation_report": (_I, [_VP, _I, _I, C.POINTER(_I), C.POINTER(C.c_float), C.c_char_p, _I64]),
+    "pmp_debug_set_taps": (_I, [_VP, _I]),
+    "pmp_debug_get_tap": (_I64, [_VP, C.c_char_p, _VP, _I64, C.POINTER(_I), C.POINTER(_I)]),
+    "pmp_debug_poison_workspace": (_I, [_VP, _I]),
     "pmp_debug_pack_f16x3": (C.c_int64, [C.POINTER(C.c_float), _I, _I, _I, C.POINTER(C.c_uint16), C.c_int64, C.POINTER(C.c_int)]),
     "pmp_debug_conv_bench": (_I, [_VP, _I, _I, _I, _I, _I, _I, _I] + [C.POINTER(C.c_double)] * 4),
 }

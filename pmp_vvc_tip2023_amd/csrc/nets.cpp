@@ -42,9 +42,19 @@ struct Graph {
     int seg = 0;
     bool scaled() const { return h2() && c->act_scales && w.stem_b_h; }
     int E(int sg) const { return scaled() ? w.act_exp[sg] : 0; }
-    // calibration pass (fp32 datapath, calibrate.cpp: calibrate_mtt): the largest |value| of a tensor just produced, per launch
-    void note(const Act &a, const std::string &name, int sg)
+    // pmp_debug_set_taps: a copy of a tensor just produced, as its consumers read it (not in the calibration pass, the arena's measuring
+    // pass or a range-guard re-run); prefixed by net, "q/" or "bd/"
+    std::string pfx;
+    void tap(const Act &a, const std::string &name, int sg, int c_real)
     {
+        if (!c->taps_on || c->cal_on || c->tap_skip || !live()) return;
+        const int r = tap_record(c, pfx + name, a.p, n, a.C, a.H, a.W, c_real, a.split ? fmt() : 0, E(sg));
+        if (r != PMP_OK && rc == PMP_OK) rc = r;
+    }
+    // calibration pass (fp32 datapath, calibrate.cpp: calibrate_mtt): the largest |value| of a tensor just produced, per launch
+    void note(const Act &a, const std::string &name, int sg, int c_real)
+    {
+        tap(a, name, sg, c_real);
         if (!c->cal_on || !live() || a.split || (int)c->cal_log.size() >= PMP_CAL_SLOTS) return;
         check(launch_amax_f32(c->stream, a.p, (size_t)n * a.C * a.H * a.W, c->d_cal + c->cal_log.size()), "amax");
         c->cal_log.emplace_back(name, sg);
@@ -157,8 +167,8 @@ struct Graph {
                 else b.res = x.p;
                 { KScope ks(c, K_SMALL, 2.0 * px * r.cout * (r.cout * r.k * r.k + (r.has_sc ? r.cin : 0))); check(launch_conv_direct(c->stream, b), "conv_direct"); }
             }
-            note(t, name + ".t", seg);
-            note(y, name, seg);
+            note(t, name + ".t", seg, r.cout);
+            note(y, name, seg, r.cout);
             release(t);
             if (consume) release(x_in);
             return y;
@@ -173,13 +183,13 @@ struct Graph {
         const bool in_place = x_dead && !r.has_sc && !pool && x.split == y_split && x.C == ((r.cout + 15) & ~15);
         Act y = in_place ? x : alloc(r.cout, pool ? H / 2 : H, pool ? W / 2 : W, y_split);
         conv(x, r, false, nullptr, nullptr, nullptr, false, t, 2.0 * px * r.cout * r.cin * r.k * r.k, kclass(r.k, r.cin, r.cout));
-        note(t, name + ".t", seg);
+        note(t, name + ".t", seg, r.cout);
         // a gated block ends its attention segment: its output is (this segment) x (the gate operand, a trunk tensor of segment 0) and
         // opens the next segment - the three exponents meet in the out_scale of the convolution whose epilogue multiplies
         conv(t, r, true, r.has_sc ? &x : nullptr, r.has_sc ? nullptr : &x, gate, pool, y,
              2.0 * px * r.cout * (r.cout * r.k * r.k + (r.has_sc ? r.cin : 0)), kclass(r.k, r.cout, r.cout),
              gate ? E(seg) + E(0) - E(seg + 1) : 0);
-        note(y, name, gate ? seg + 1 : seg);
+        note(y, name, gate ? seg + 1 : seg, r.cout);
         release(t);
         if (x_dead && !in_place) release(x);
         return y;
@@ -198,7 +208,7 @@ struct Graph {
         const double macs = msbd ? (double)cin * (k1 * k1 * 16 + 2 * k1 * k2 * 8) : (double)cin * k1 * k1 * 32;
         KScope ks(c, K_STEM, 2.0 * n * S * S * macs);
         check(launch_stem(c->stream, luma, msbd, a), "stem");
-        note(o, "stem", seg);
+        note(o, "stem", seg, 32);
         return o;
     }
 
@@ -225,6 +235,7 @@ struct Graph {
             KScope ks(c, K_CONV_OTHER, 2.0 * n * S * S * r.cout * (r.cin * 9 + r.cout * 9 + r.cin));
             check(launch_rbfuse32(c->stream, a), "rbfuse32(att)");
         }
+        tap(y, name, seg, r.cout);
         return y;
     }
     bool fused32_att(const std::string &name) const
@@ -246,6 +257,7 @@ struct Graph {
             KScope ks(c, K_CONV_OTHER, 2.0 * px * r.cout * (r.cin * 9 + r.cout * 9 + r.cin));
             check(launch_rbfuse32(c->stream, a), "rbfuse32");
         }
+        tap(y, name, seg, r.cout);
         release(x);
         return y;
     }
@@ -281,6 +293,7 @@ int forward_q(pmp_ctx *c, bool luma, const NetWeights &w, const uint8_t *by, con
               int n, float *qt)
 {
     Graph g{c, w, n};
+    g.pfx = "q/";
     Act x2 = g.stem(luma, false, by, bu, bv, nullptr);
     Act x3 = g.rb(x2, "resblock_q1", luma);            // luma: + max_pool2d(2); chroma: no pool (:179)
     Act x4 = g.rb(x3, "resblock_q2", true);
@@ -298,6 +311,7 @@ int forward_q(pmp_ctx *c, bool luma, const NetWeights &w, const uint8_t *by, con
             KScope ks(c, K_CONV_OTHER, flops);
             g.check(launch_qt_tail16(c->stream, a), "qt_tail16");
         }
+        g.tap(x5, "resblock_q3", g.seg, 32);
         g.release(x5);
         g.release(x4);
         return g.rc;
@@ -308,6 +322,7 @@ int forward_q(pmp_ctx *c, bool luma, const NetWeights &w, const uint8_t *by, con
         KScope ks(c, K_SMALL, 0.0);
         g.check(launch_multipool_concat(c->stream, x5.p, x6.split ? nullptr : x6.p, n, x6.split ? x6.s() : nullptr, x6.stride, g.fmt(), g.sat()), "multipool_concat");
     }
+    g.tap(x6, "x6", g.seg, 128);
     g.release(x5);
     Act x7 = g.rb(x6, "resblock_q4");
     Act x8 = g.rb(x7, "resblock_q5", true, nullptr, true);    // fp32: 8x8 tail runs on the direct kernel
@@ -322,6 +337,7 @@ int forward_msbd(pmp_ctx *c, bool luma, const NetWeights &w, const uint8_t *by, 
                  const float *qt, int n, float *bt, float *dire)
 {
     Graph g{c, w, n};
+    g.pfx = "bd/";
     Act x = g.stem(luma, true, by, bu, bv, qt);
     x = g.rb(x, "trunk_M1.0");
     for (int i = 1; i < 5; ++i) x = g.rb(x, "trunk_M1." + std::to_string(i));
@@ -347,6 +363,7 @@ int forward_msbd(pmp_ctx *c, bool luma, const NetWeights &w, const uint8_t *by, 
             KScope ks(c, K_CONV_OTHER, flops);
             g.check(launch_msbd_branch16(c->stream, a), "msbd_branch16");
         }
+        g.tap(xb, "trunk_Att1.1", 2, 64);
         g.release(xb);
         g.release(x5);
     } else {
@@ -363,7 +380,7 @@ int forward_msbd(pmp_ctx *c, bool luma, const NetWeights &w, const uint8_t *by, 
             KScope ks(c, K_SMALL, 0.0);
             g.check(launch_att_input(c->stream, qt, bt, dire, 0, ai.split ? nullptr : ai.p, n, 16, ai.split ? ai.s() : nullptr, ai.stride, g.fmt(), g.sat(), std::ldexp(1.f, -g.E(1))), "att_input");
         }
-        g.note(ai, "att_input1", 1);
+        g.note(ai, "att_input1", 1, 3);
         Act a1 = g.rb(ai, "trunk_Att1.0");
         Act xb1 = g.rb(a1, "trunk_Att1.1", false, &x5);
         g.release(x5);
@@ -385,7 +402,7 @@ int forward_msbd(pmp_ctx *c, bool luma, const NetWeights &w, const uint8_t *by, 
             KScope ks(c, K_SMALL, 0.0);
             g.check(launch_att_input(c->stream, qt, bt, dire, 1, aj.split ? nullptr : aj.p, n, 32, aj.split ? aj.s() : nullptr, aj.stride, g.fmt(), g.sat(), std::ldexp(1.f, -g.E(3))), "att_input");
         }
-        g.note(aj, "att_input2", 3);
+        g.note(aj, "att_input2", 3, 3);
         a2 = g.rb(aj, "trunk_Att2.0");
     }
     Act xb3 = g.rb(a2, "trunk_Att2.1", false, &x4);

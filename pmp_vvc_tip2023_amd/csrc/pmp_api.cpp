@@ -143,6 +143,10 @@ static int run_graph(pmp_ctx *c, F &&fwd)
     c->arena.cap = c->ws.cap;
     c->arena.measuring = false;
     c->arena.reset();
+    if (c->poison && c->ws.p) {   // pmp_debug_poison_workspace: the whole buffer (own, second or taken over), stream-ordered before the pass
+        const hipError_t e = hipMemsetAsync(c->ws.p, c->poison == 1 ? 0xFF : 0x3C, c->ws.cap, c->stream);
+        if (e != hipSuccess) return hip_fail(c, e, "poison workspace");
+    }
     return fwd();
 }
 
@@ -196,6 +200,7 @@ static int infer_passes(pmp_ctx *c, bool luma, NetWeights &wq, NetWeights &wb, c
 
 // ---- f16x3 range guard (include/pmp.h) ----------------------------------------------------------------------------------
 constexpr int PMP_SAT_SLOTS = 64;
+constexpr int PMP_TAP_MAX_BLOCKS = 64;        // pmp_debug_set_taps: tap memory is one copy of every tensor of the call
 
 // Reads and clears the device-side saturation word (synchronises the stream): PMP_SAT_IGNORE contexts, whose calls take no snapshots.
 static int sat_fetch(pmp_ctx *c, unsigned *out)
@@ -277,8 +282,11 @@ static int infer_device_impl(pmp_ctx *c, int comp, int qp, const uint8_t *by, co
     NetWeights *wq = find_net(c, id_q, qp);
     NetWeights *wb = find_net(c, id_b, qp);
     if (!wq || !wb) return set_err(c, PMP_E_NOWEIGHTS, "pmp_infer: weights for this (comp, qp) are not loaded");
+    if (c->taps_on && (n > c->chunk || n > PMP_TAP_MAX_BLOCKS || c->overlap))
+        return set_err(c, PMP_E_INVALID, "pmp_infer: with taps on, one pass of at most 64 blocks (n <= chunk) and overlap mode off");
     int rc = resolve_pending(c, false);          // earlier calls whose snapshot has landed by now: no wait
     if (rc != PMP_OK) return rc;
+    if (c->taps_on) c->ntaps = 0;                // the taps are this call's (a re-run resolved above is recorded by nobody)
     rc = infer_passes(c, luma, *wq, *wb, by, bu, bv, n, qt, bt, dire);
     if (rc != PMP_OK || c->precision != PMP_PRECISION_F16X3 || c->sat_policy == PMP_SAT_IGNORE || n == 0) return rc;
     // f16x3 range guard: snapshot the flag behind this call's passes and reset it for the next call - all stream-ordered, the host
@@ -299,7 +307,9 @@ static int infer_device_impl(pmp_ctx *c, int comp, int qp, const uint8_t *by, co
         // matter for a call that is this rare.  Not fired: the call's logits were in the context's buffers, which an earlier re-run has
         // overwritten - the same call again, on the datapath it ran on.
         if (fired) c->precision = PMP_PRECISION_F32;
+        c->tap_skip = 1;          // pmp_debug_set_taps records the call as it first ran, not its re-run
         const int r2 = infer_passes(c, luma, *rq, *rb, by, bu, bv, n, qt, bt, dire);
+        c->tap_skip = 0;
         c->precision = PMP_PRECISION_F16X3;
         return r2;
     }});
@@ -337,8 +347,13 @@ static int ensure_logits(pmp_ctx *c, int64_t n)
     if ((need[0] > c->d_logit[0].cap || need[1] > c->d_logit[1].cap || need[2] > c->d_logit[2].cap) && !c->pending.empty() &&
         (rc = settle(c)) != PMP_OK)
         return rc;
-    for (int i = 0; i < 3; ++i)
+    for (int i = 0; i < 3; ++i) {
         if ((rc = ensure(c, c->d_logit[i], need[i])) != PMP_OK) return rc;
+        if (c->poison) {          // pmp_debug_poison_workspace: whoever uses them next must write every byte it later reads
+            const hipError_t e = hipMemsetAsync(c->d_logit[i].p, c->poison == 1 ? 0xFF : 0x3C, need[i], c->stream);
+            if (e != hipSuccess) return hip_fail(c, e, "poison logits");
+        }
+    }
     return PMP_OK;
 }
 
@@ -353,6 +368,22 @@ int settle(pmp_ctx *c)
 {
     int rc = resolve_pending(c, true);
     return rc != PMP_OK ? rc : sync(c);
+}
+
+// pmp_debug_set_taps: the tensor a kernel has just written, copied on the same stream right behind that launch - later launches
+// (an identity-shortcut block writing its output in place, a tensor reusing freed arena bytes) cannot reach it before the copy.
+int tap_record(pmp_ctx *c, const std::string &name, const void *p, int n, int C, int H, int W, int c_real, int fmt, int exp)
+{
+    const size_t bytes = (size_t)n * C * H * W * (fmt == 1 ? 6 : 4);
+    if (c->ntaps >= (int)c->taps.size()) c->taps.emplace_back();
+    TapRec &t = c->taps[c->ntaps];
+    int rc = ensure(c, t.buf, bytes);
+    if (rc != PMP_OK) return rc;
+    const hipError_t e = hipMemcpyAsync(t.buf.p, p, bytes, hipMemcpyDeviceToDevice, c->stream);
+    if (e != hipSuccess) return hip_fail(c, e, "tap copy");
+    t.name = name; t.n = n; t.C = C; t.H = H; t.W = W; t.c_real = c_real; t.fmt = fmt; t.exp = exp;
+    ++c->ntaps;
+    return PMP_OK;
 }
 
 // Host-pointer entry points stage through the context's own buffers (d_in, d_logit, d_out) and return final results.  A *_device call
@@ -444,6 +475,7 @@ int pmp_destroy(pmp_ctx *c)
     DevBuf *bufs[] = {&c->ws, &c->ws2, &c->d_in[0], &c->d_in[1], &c->d_in[2], &c->d_logit[0], &c->d_logit[1], &c->d_logit[2],
                       &c->d_out[0], &c->d_out[1], &c->d_out[2], &c->d_out[3], &c->d_frames[0], &c->d_frames[1], &c->d_frames[2]};
     for (DevBuf *b : bufs) if (b->p) hipFree(b->p);
+    for (TapRec &t : c->taps) if (t.buf.p) hipFree(t.buf.p);
     if (c->d_sat) hipFree(c->d_sat);
     if (c->d_cal) hipFree(c->d_cal);
     if (c->d_calbuf.p) hipFree(c->d_calbuf.p);
@@ -901,6 +933,75 @@ int pmp_debug_conv_bench(pmp_ctx *c, int n, int h, int w, int cin, int cout, int
     abl_bench_free(ab);
     for (void *p : {(void *)dx, (void *)dy, (void *)dy2, (void *)dwp, (void *)dxs, (void *)dys, (void *)dwx}) if (p) hipFree(p);
     return rc;
+}
+
+int pmp_debug_poison_workspace(pmp_ctx *c, int pattern)
+{
+    CHECK_CTX(c);
+    if (pattern < 0 || pattern > 2) return set_err(c, PMP_E_INVALID, "pmp_debug_poison_workspace: 0 (off), 1 (0xFF bytes) or 2 (0x3C bytes)");
+    const int rc = settle(c);
+    if (rc != PMP_OK) return rc;
+    c->poison = pattern;
+    return PMP_OK;
+}
+
+int pmp_debug_set_taps(pmp_ctx *c, int on)
+{
+    CHECK_CTX(c);
+    const int rc = settle(c);
+    if (rc != PMP_OK) return rc;
+    c->taps_on = on ? 1 : 0;
+    c->ntaps = 0;
+    if (!on) {
+        for (TapRec &t : c->taps) if (t.buf.p) hipFree(t.buf.p);
+        c->taps.clear();
+    }
+    return PMP_OK;
+}
+
+static double f16_value(uint16_t h)
+{
+    const int e = (h >> 10) & 31, m = h & 1023;
+    const double v = e == 0 ? std::ldexp((double)m, -24) : e == 31 ? (m ? NAN : INFINITY) : std::ldexp((double)(m | 1024), e - 25);
+    return (h & 0x8000) ? -v : v;
+}
+
+static double bf16_value(uint16_t b)
+{
+    const uint32_t u = (uint32_t)b << 16;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+
+int64_t pmp_debug_get_tap(pmp_ctx *c, const char *name, double *out, int64_t cap, int dims[4], int *c_real)
+{
+    CHECK_CTX(c);
+    if (!name) return set_err(c, PMP_E_INVALID, "pmp_debug_get_tap: null name");
+    int rc = settle(c);
+    if (rc != PMP_OK) return rc;
+    const TapRec *t = nullptr;
+    for (int i = c->ntaps - 1; i >= 0 && !t; --i) if (c->taps[i].name == name) t = &c->taps[i];
+    if (!t) return set_err(c, PMP_E_INVALID, std::string("pmp_debug_get_tap: no tensor ") + name + " in the last call");
+    const size_t elems = (size_t)t->n * t->C * t->H * t->W;
+    if (dims) { dims[0] = t->n; dims[1] = t->C; dims[2] = t->H; dims[3] = t->W; }
+    if (c_real) *c_real = t->c_real;
+    if (!out || (int64_t)elems > cap) return (int64_t)elems;
+    std::vector<uint16_t> raw(elems * (t->fmt == 0 ? 2 : t->fmt == 1 ? 3 : 2));
+    const hipError_t e = hipMemcpy(raw.data(), t->buf.p, raw.size() * 2, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(c, e, "pmp_debug_get_tap");
+    const float *f = reinterpret_cast<const float *>(raw.data());
+    const int G = t->C / 16;
+    for (size_t i = 0; i < elems; ++i) {        // blocked [n][C/16][H][W][16] -> dense NCHW
+        double v;
+        if (t->fmt == 0) v = f[i];
+        else if (t->fmt == 2) v = f16_value(raw[i]) + f16_value(raw[elems + i]);                                   // exact in float64
+        else v = bf16_value(raw[i]) + bf16_value(raw[elems + i]) + bf16_value(raw[2 * elems + i]);
+        const size_t cl = i & 15, x = (i >> 4) % t->W, y = (i >> 4) / t->W % t->H, g = (i >> 4) / ((size_t)t->W * t->H) % G,
+                     b = (i >> 4) / ((size_t)t->W * t->H * G);
+        out[((b * t->C + g * 16 + cl) * t->H + y) * t->W + x] = std::ldexp(v, t->exp);
+    }
+    return (int64_t)elems;
 }
 
 // ---- timing ------------------------------------------------------------------------------------------------

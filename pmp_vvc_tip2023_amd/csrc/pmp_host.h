@@ -113,6 +113,16 @@ struct Arena {
 
 struct KTimeRec { hipEvent_t a, b; double flops; };
 
+// pmp_debug_set_taps: a stream-ordered copy of one tensor as the consuming kernel reads it (raw planes, blocked layout)
+struct TapRec {
+    std::string name;                  // "q/<tensor>" or "bd/<tensor>"
+    DevBuf buf;                        // tap-owned device memory
+    int n = 0, C = 0, H = 0, W = 0;    // C padded to 16; layout [n][C/16][H][W][16] per plane
+    int c_real = 0;
+    int fmt = 0;                       // 0 fp32, 1 split-3 (three bf16 planes), 2 split-2 (two fp16 planes)
+    int exp = 0;                       // the stored value times 2^exp is the true value (f16x3 activation scales)
+};
+
 // f16x3 range guard, deferred (include/pmp.h): every inference call snapshots the device flag into a pinned host word behind its
 // passes and records an event; the word is read when the event has completed - at a later call (polled), at pmp_synchronize /
 // pmp_get_saturation or at the end of a host-pointer call (waited for).  A call whose flag fired is run again on the fp32 MFMA
@@ -163,6 +173,12 @@ struct pmp_ctx {
     pmp::DevBuf d_calbuf;                  // calibration blocks and their logits
     hipStream_t cal_stream = nullptr;      // calibration runs on its own stream and workspace: it neither waits for the passes in flight on the
     pmp::DevBuf ws_cal;                    // context's stream nor touches their workspace (created on first use; 44 MB for 16-block fp32 passes)
+    // test hooks (include/pmp.h): tensor taps and workspace poisoning
+    int taps_on = 0;
+    int tap_skip = 0;                      // set while a range-guard re-run replays a call: its passes are not recorded
+    std::vector<pmp::TapRec> taps;         // slots, reused call after call; the first ntaps hold the last inference call's tensors in launch order
+    int ntaps = 0;
+    int poison = 0;                        // 0 off, 1 0xFF bytes, 2 0x3C bytes into every activation workspace before each pass
     // kernel-class timing
     uint32_t kmask = 0;
     std::vector<pmp::KTimeRec> krec[pmp::K_NCLASS];
@@ -189,6 +205,8 @@ int ensure(pmp_ctx *c, DevBuf &b, size_t bytes);                    // grow-only
 NetWeights *find_net(pmp_ctx *c, int net_id, int qp);               // loaded weights of (net, qp) or nullptr
 int run_graph_fn(pmp_ctx *c, const std::function<int()> &fwd);      // a forward graph twice: measuring pass, then the real one in c->ws
 int settle(pmp_ctx *c);                                             // everything asked of the context so far is done and final
+// pmp_debug_set_taps: copies a tensor just produced on c->stream into tap-owned memory (stream-ordered, before anything can overwrite it)
+int tap_record(pmp_ctx *c, const std::string &name, const void *p, int n, int C, int H, int W, int c_real, int fmt, int exp);
 
 // calibrate.cpp
 int calibrate_mtt(pmp_ctx *c, bool luma, NetWeights &wq, NetWeights &wb);
