@@ -117,8 +117,10 @@ int pmp_get_precision(const pmp_ctx *ctx);
 /* Range guard of the f16x3 datapath.  Its activations travel as two fp16 terms, so a value beyond +-65504 is clamped when it
  * is stored (the reference's nets stay below 3e3 on 8-bit content with the trained QT weights; trained MTT weights are not
  * in the reference checkout).  Every kernel that stores such a tensor raises a per-context device flag when the clamp fires
- * (a NaN raises it too).  Every pmp_infer* call snapshots the flag behind its passes - stream-ordered, into pinned host memory -
- * and the snapshot is LOOKED AT LATER, so that the *_device entry points never stall the host: by the next call of the context
+ * (a NaN raises it too), and never otherwise; it compares the value as stored, true x 2^-e of its segment.  Evidence:
+ * tests/test_gpu_range_sites.py over-drives one tensor at a time, fused and unfused, by the weight gains of oracle/range_cases.py.
+ * Every pmp_infer* call snapshots the flag behind its passes - stream-ordered, into pinned host memory - and the snapshot is
+ * LOOKED AT LATER, so that the *_device entry points never stall the host: by the next call of the context
  * (polled: only snapshots that have landed), and by pmp_synchronize / pmp_get_saturation / any host-pointer call (waited for).
  *   PMP_SAT_RERUN (default)  a call whose flag fired is run AGAIN on the exact fp32 MFMA datapath (fp32 range and arithmetic) into
  *                            the same output buffers, and every post-processing call that was enqueued after it is replayed in

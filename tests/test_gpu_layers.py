@@ -3,7 +3,6 @@ tensor by tensor, poisoned workspaces, and block-order independence of the persi
 
 Taps (pmp_debug_get_tap, include/pmp.h) give each intermediate tensor exactly as its consumer read it; oracle/layers64.py recomputes
 each launch in float64 with the bound its datapath's arithmetic allows (tests/test_layer_bound_cpu.py shows the bound is sharp)."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -11,54 +10,14 @@ import pytest
 import torch
 
 import trained_like  # tools/trained_like.py: test-weight data
-from conftest import golden
-from oracle import layers64 as L
+from oracle import layers64 as L, range_cases as RC, taps as T
 
 pytestmark = pytest.mark.gpu
 
 
 # ------------------------------------------------------------------------------------------------ helpers
-def _edge_blocks(n_random=2, seed=77):
-    """13 luma / chroma blocks (with n_random = 2) chosen for edges: all 0, all 255, 1-pixel checkerboard, horizontal and vertical stripes, one bright
-    pixel at each corner of the 68x68 block (and of the 34x34 chroma planes), two golden blocks (g1_qt.npz), recipe-R blocks."""
-    from pmp_vvc_tip2023_amd import synth
-    g1 = golden("g1_qt.npz")
-    ys, us, vs = [], [], []
-
-    def add(y, u, v):
-        ys.append(y.astype(np.uint8)); us.append(u.astype(np.uint8)); vs.append(v.astype(np.uint8))
-    i68, i34 = np.indices((68, 68)), np.indices((34, 34))
-    add(np.zeros((68, 68)), np.zeros((34, 34)), np.zeros((34, 34)))
-    add(np.full((68, 68), 255), np.full((34, 34), 255), np.full((34, 34), 255))
-    add(255 * ((i68[0] + i68[1]) & 1), 255 * ((i34[0] + i34[1]) & 1), 255 * ((i34[0] + i34[1] + 1) & 1))
-    add(255 * (i68[0] & 1), 255 * (i34[0] & 1), 255 * (i34[1] & 1))
-    add(255 * (i68[1] & 1), 255 * (i34[1] & 1), 255 * (i34[0] & 1))
-    for r, c in ((0, 0), (0, -1), (-1, 0), (-1, -1)):
-        y, u, v = np.zeros((68, 68)), np.zeros((34, 34)), np.zeros((34, 34))
-        y[r, c] = 255; u[r, c] = 255; v[r, c] = 255
-        add(y, u, v)
-    for k in (0, 5):
-        add(g1["block_y"][k], g1["block_u"][k], g1["block_v"][k])
-    if n_random:
-        ry, ru, rv = synth.recipe_r_blocks(n_random, seed)
-        for k in range(n_random):
-            add(ry[k], ru[k], rv[k])
-    return np.stack(ys), np.stack(us), np.stack(vs)
-
-
-def _taps_on(e, on):
-    e._ck(e.lib.pmp_debug_set_taps(e.h, 1 if on else 0))
-
-
-def _tap(e, name):
-    """-> (float64 [n, C padded, H, W], real channel count); None if the last call has no such tensor."""
-    dims, cr = (C.c_int * 4)(), C.c_int()
-    n = e.lib.pmp_debug_get_tap(e.h, name.encode(), None, 0, dims, C.byref(cr))
-    if n < 0:
-        return None
-    out = np.empty(int(n), np.float64)
-    assert e.lib.pmp_debug_get_tap(e.h, name.encode(), out.ctypes.data_as(C.c_void_p), n, dims, C.byref(cr)) == n
-    return out.reshape(tuple(dims)), cr.value
+_edge_blocks = RC.edge_blocks       # 13 edge-case blocks (oracle/range_cases.py; also the site-by-site range tests' source)
+_taps_on, _tap = T.taps_on, T.tap   # oracle/taps.py, shared with tests/test_gpu_range_sites.py
 
 
 def _poison(e, pattern):
