@@ -9,7 +9,13 @@ Unit: the nets consume 64x64 blocks (+4 px context); one VTM CTU is 128x128 = 4 
 (one library pass: the default chunk is 4096 blocks) and CTU/s = blocks/s / 4 (BASELINE.md section 2).  `value` is CTU/s;
 blocks/s is reported next to it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the line: `value`, `ms_per_step`, and
+the roofline of the dominant kernel class, which comes from the timed steps themselves.  --full adds everything that takes runs of
+its own, after the timed region and never part of `value`: the CPU baseline of the oracle with the parity of its sample, the
+host-buffer end-to-end rate, chroma, per-QP luma, overlap mode, the trained-like and exact-fp32 datapaths, the per-class breakdown and
+the chroma roofline (tens of seconds; --no-extras and --cpu-sample 0 leave parts of it out).
 
 N > 1: one process per GPU.  Under torch.distributed.run (RANK / WORLD_SIZE in the environment) this process is one rank;
 started plainly with --gpus N it launches its own N rank processes - fresh children, before this process has made any GPU
@@ -329,7 +335,7 @@ def fp32_exact_extra(eng, n, step, timed):
 
 
 def measure_extras(eng, args, dev, n, y, u, v, step):
-    """Side measurements AFTER the timed region (they never enter `value`), N = 1 only:
+    """Side measurements AFTER the timed region (they never enter `value`), N = 1 and --full only:
     * e2e_host_buffers: the same step through the host-pointer boundary (pmp_infer_postprocess: H2D of the u8 blocks, the
       pass, D2H of the split flags) - SURVEY.md 8(d) config 2's "end-to-end" number next to the device-resident one;
     * chroma and per-QP luma throughput of the device-resident step (3 steps each)."""
@@ -420,14 +426,17 @@ def main():
     ap.add_argument("--comp", default="Luma", choices=["Luma", "Chroma"])
     ap.add_argument("--qp", type=int, default=22)
     ap.add_argument("--chunk", type=int, default=0, help="blocks per pass inside the library (0 = library default)")
-    ap.add_argument("--cpu-sample", type=int, default=512, help="blocks for the CPU baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also take the CPU baseline with its parity sample and the side measurements "
+                         "(host-buffer end-to-end rate, chroma, per-QP luma, overlap, other datapaths, per-class breakdown)")
+    ap.add_argument("--cpu-sample", type=int, default=512, help="blocks for the CPU baseline of --full (0 = skip)")
     ap.add_argument("--precision", default="f16x3", choices=["f16x3", "bf16x6", "fp32"],
                     help="conv datapath: 2-term fp16 split (3 MFMA products) or 3-term bf16 split (6 products), both "
                          "fp32-equivalent, or exact fp32 MFMA")
     ap.add_argument("--breakdown", action="store_true", help="extra pass with every kernel class timed (stderr)")
     ap.add_argument("--lib", default=None, help="path of another build of libpmp_hip.so (same-box A/B timing, tools/lib_ab.py)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the side measurements after the timed region (host-buffer end-to-end rate, chroma, per-QP luma)")
+                    help="with --full: skip the side measurements after the timed region (host-buffer end-to-end rate, chroma, per-QP luma)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write the split flags of the last timed step as DIR/<name>.npy (float32; at most 64 MB, a seeded block sample above)")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)      # internal: "<blocks>,<seed>,<threads>" (cpu_all_cores)
@@ -632,7 +641,7 @@ def main():
         eng.ktime_enable(0)
 
     extras = {}
-    if rank == 0 and n_gpus == 1 and not args.no_extras:
+    if rank == 0 and n_gpus == 1 and args.full and not args.no_extras:
         extras = measure_extras(eng, args, dev, n, y, u, v, step)
 
     if rank == 0:
@@ -658,7 +667,7 @@ def main():
             out["multi_gpu"] = multi
             out["rccl_ranks"] = multi["rccl_ranks"]
         out.update(extras)
-        if args.cpu_sample > 0 and n_gpus == 1 and args.comp == "Luma":
+        if args.full and args.cpu_sample > 0 and n_gpus == 1 and args.comp == "Luma":
             out["cpu_baseline"], out["parity"] = cpu_baseline(args.cpu_sample, 1, eng)
         else:
             out["cpu_baseline"] = None

@@ -1073,12 +1073,12 @@ def test_driver_two_ranks_equal_one_rank(tmp_path):
 
 # ------------------------------------------------------------------------------------------------ bench.py contract
 def test_bench_json_contract(tmp_path):
-    """bench.py prints ONE JSON line with the driver's fields, the roofline of the dominant kernel class measured with HIP
+    """bench.py --full prints ONE JSON line with the driver's fields, the roofline of the dominant kernel class measured with HIP
     events on the launch stream, the CPU baseline of a bounded sample and the parity of that sample."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "64",
-                        "--cpu-sample", "8"], capture_output=True, text=True, timeout=600)
+                        "--cpu-sample", "8", "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -1113,6 +1113,28 @@ def test_bench_json_contract(tmp_path):
     assert "samples" in d["sensors"] and "sclk_mhz" in d["sensors"] and "power_w" in d["sensors"]
     ac = cb["all_cores"]
     assert "error" in ac or (ac["processes"] >= 1 and ac["blocks_per_s"] > 0 and "cpu_limits" in ac and cb["host_cores"] >= cb["cores"])
+
+
+def test_bench_plain_run_times_the_steps_only(tmp_path):
+    """A plain `bench.py` run (no --full) prints the same headline fields and the roofline of its timed steps, and takes none of the
+    side measurements: no CPU baseline or parity sample, no host-buffer, chroma, per-QP, other-datapath or per-class runs."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "64"],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "CTU/s" and d["dtype"] == "f16x3" and d["value"] > 0
+    assert abs(d["value"] - 64 / 4.0 / (d["ms_per_step"] * 1e-3)) < 1e-3 * d["value"] + 0.1
+    assert d["roofline"]["kernel"] == "conv_mfma_3x3_c64" and 0 < d["roofline"]["frac"] < 1
+    assert d["cpu_baseline"] is None
+    for k in ("parity", "extra", "e2e_host_buffers", "breakdown", "chroma_roofline"):
+        assert k not in d, k
+    assert "cpu_baseline:" not in r.stderr
 
 
 def test_bench_launches_its_own_ranks(tmp_path):

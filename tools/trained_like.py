@@ -1,6 +1,6 @@
 """TRAINED-LIKE MTT-net weights: test-weight data, NOT product code (round 6: moved out of pmp_vvc_tip2023_amd/synth.py together with
 trained_like_scales.json).  The reference's *_BD_*.pkl are absent from the mount; the uniform synthetic MTT weights of
-synth.synth_msbd_weights are benign; these stand in for a net with trained-scale activations in tests/, bench.py's extra.trained_like,
+synth.synth_msbd_weights are benign; these stand in for a net with trained-scale activations in tests/, bench.py --full's extra.trained_like,
 tools/gen_golden.py (G2b) and the campaigns.  numpy only.  Import with tools/ on sys.path: `import trained_like`."""
 import json
 import os
