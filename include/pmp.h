@@ -357,6 +357,28 @@ int pmp_debug_read_weights_file(const char *path, int *net_id, int *qp, int *nte
 int pmp_debug_conv_bench(pmp_ctx *ctx, int n, int h, int w, int cin, int cout, int k, int iters, double *ms_f32,
                          double *ms_x6, double *max_abs_diff, double *max_abs_ref);
 
+/* ---- test hook: ONE ResidualBlock (Model_QBD.py:23-44) at any shape the convolution kernels support, through the product's own code:
+ *      the loader's packing of its weights (the f16x3 scales, the second convolution and the 1x1 shortcut sharing one), the graph's
+ *      conversion of the input to the datapath's split format, its dispatch, out_scale and exponent composition, its in-place store of
+ *      an identity-shortcut block and its routing to the fused 32x32 kernel (pmp_debug_set_fusion) - on the context's datapath, in its
+ *      poisoned workspace if pmp_debug_poison_workspace is on (oracle/conv_cases.py, tests/test_gpu_conv_sweep.py).
+ *      The shortcut follows the loader: identity when cin == cout, a 1x1 convolution of the input otherwise.  exp_x / exp_gate / exp_out
+ *      (f16x3 only, ignored elsewhere): the activation-scale exponents of the input (and of .t and an ungated output, which the graph
+ *      keeps in the input's segment), of the gate and of a gated output.  Needs taps on (pmp_debug_set_taps); the call's taps are
+ *      "x" and "gate" (as the kernels read them), "rb.t" (absent when a fused kernel keeps it in LDS) and "rb", read with pmp_debug_get_tap.
+ *      x: [n][cin][h][w], w0: [cout][cin][k][k], w2: [cout][cout][k][k], wsc: [cout][cin] (cin != cout), gate: [n][cout][h][w] (gate
+ *      != 0), host fp32 at true scale.  *saturated (may be NULL): the f16x3 range flag of this call (read and cleared).  kernels (may be
+ *      NULL): the kernel instantiations the call launched, "name\n" each, e.g. "conv_h2_kernel<5,5,4,0,1>" (template arguments as
+ *      integers).  PMP_E_INVALID before any launch for a shape the kernels do not support: cout not 16, 32 or 64, cin not a multiple
+ *      of 16 in 16..256, k not 1, 3 or 5, h or w not a multiple of 16 in 16..256, n not in 1..64, pool together with a gate. ---- */
+typedef struct pmp_rb_case {
+    int n, h, w, cin, cout, k;
+    int gate, pool, out_f32;                /* 0 / 1 */
+    int exp_x, exp_gate, exp_out;
+} pmp_rb_case;
+int pmp_debug_run_resblock(pmp_ctx *ctx, const pmp_rb_case *cs, const float *x, const float *w0, const float *w2, const float *wsc,
+                           const float *gate, int *saturated, char *kernels, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,8 @@ from the exact result?  The answer follows the arithmetic each datapath document
                accumulator + shortcut sum and the gate product in fp32 (two roundings of 2^-24) and store exactly;
   floor_dp     the absolute floor of a split-2 store whose low term is subnormal in fp16 (half its 2^-24 ulp), in stored units:
                times 2^E of the tensor's segment (f16x3 activation scales) at true scale.
+On f16x3 a convolution adds W_FLOOR * 2^-k * sum|x| (below): the absolute error of weights so far below their tensor's maximum that
+their low fp16 term is subnormal (dead channels, a 1x1 shortcut that sets the scale it shares with w2; tests/test_gpu_conv_sweep.py).
 ReLU and max-pool are 1-Lipschitz (the window maximum of the bound), a gate multiplies the bound by |gate|.  Pure data movement (the
 multi-scale pool of the QT nets, the attention inputs) is exact up to the store: bit-exact on fp32 and bf16x6 (split-3 holds any fp32
 value exactly), r_dp / floor_dp on f16x3.  The stems and the 8x8 direct blocks and heads run plain fp32 kernels except where noted.
@@ -40,6 +42,8 @@ The f16x3 MTT stem splits the raw QT logits into two fp16 terms itself, so its l
 
 Pinned fp32 behaviour of the nets stays in oracle/nets_torch.py; this module only reads its weight dicts.
 """
+import math
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -55,6 +59,32 @@ R_DP = {"fp32": 2.0 ** -23, "bf16x6": 2.0 ** -23, "f16x3": 2.0 ** -22}
 FLOOR_DP = {"fp32": 0.0, "bf16x6": 0.0, "f16x3": 2.0 ** -25}
 # data movement: what the store of an fp32 value in the datapath's activation format may change (split-3 holds fp32 exactly)
 R_MOVE = {"fp32": 0.0, "bf16x6": 0.0, "f16x3": 2.0 ** -22}
+# W_FLOOR: the absolute error of one f16x3 weight, in units of its tensor's scale S = 2^k (pack.cpp h2_scale_exp: max |S*w| in [4096, 8192)).
+# pack_h2 stores S*w as h0 + h1, h0 = fp16(S*w), h1 = fp16(S*w - h0).  While h1 is a normal fp16 number its rounding is half an ulp of h1,
+# at most 2^-11 * |S*w - h0| <= 2^-22 * |S*w| - the relative error that C_DP covers.  Once |S*w - h0| < 2^-14, h1 is subnormal (or h0 is,
+# for |S*w| < 2^-14) and the rounding is half the subnormal step, 2^-25, whatever the weight: an ABSOLUTE error of 2^-25 * 2^-k per weight,
+# and 2^-25 * 2^-k * sum|x| over the window of an output.  It overtakes the relative term for weights about 2^15 below their tensor's
+# maximum: dead output channels of trained nets, and the second convolution of a block whose 1x1 shortcut sets the shared scale
+# (weights_pack.cpp load_rb: k2 = min(k(w2), k(wsc))).  The dropped h1 * x1 product has no such floor: x1 is non-zero only for
+# |x0| >= 2^-13, where it is within 2^-11 of x0's relative step.  tests/test_layer_bound_cpu.py::test_weight_floor_is_sharp.
+W_FLOOR = {"fp32": 0.0, "bf16x6": 0.0, "f16x3": 2.0 ** -25}
+
+
+def h2_scale_exp(w):
+    """pack.cpp h2_scale_exp: S = 2^k with max |S*w| in [4096, 8192), k in [-100, 24]; 0 for an all-zero tensor."""
+    m = float(np.abs(np.asarray(w, dtype=np.float32)).max()) if np.size(w) else 0.0
+    if not m > 0 or not np.isfinite(m):
+        return 0
+    return int(min(24, max(-100, 13 - math.frexp(m)[1])))
+
+
+def wfloor(x, w, dp, k):
+    """W_FLOOR * 2^-k * sum|x| over each output's window (zero padding k//2), the same for every output channel."""
+    if not W_FLOOR[dp]:
+        return 0.0
+    ks = w.shape[2]
+    box = F.conv2d(x.abs().sum(1, keepdim=True), torch.ones((1, 1, ks, ks), dtype=x.dtype), padding=ks // 2)
+    return W_FLOOR[dp] * 2.0 ** -k * box
 
 def _t(a):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
@@ -86,17 +116,21 @@ def conv_t64(x, w0, dp, E=0):
     """First launch of a ResidualBlock: relu(conv(x, w0)), pad k//2.  -> (ref, bound)."""
     pre, a = conv64(x, w0, w0.shape[2] // 2)
     t = F.relu(pre)
-    return t, bound(a, t, dp, E)
+    return t, bound(a, t, dp, E) + wfloor(x, w0, dp, h2_scale_exp(w0))
 
 
 def conv_out64(x, t, w2, wsc, dp, gate=None, pool=False, E=0):
-    """Second launch: relu(conv(t, w2) + (conv1x1(x, wsc) or x)) [* gate] [-> 2x2 max-pool].  -> (ref, bound)."""
+    """Second launch: relu(conv(t, w2) + (conv1x1(x, wsc) or x)) [* gate] [-> 2x2 max-pool].  -> (ref, bound).  On f16x3 the 1x1
+    shortcut shares the scale of w2 (weights_pack.cpp load_rb), and with it the weight floor."""
     pre, a = conv64(t, w2, w2.shape[2] // 2)
+    k2 = h2_scale_exp(w2)
     if wsc is not None:
         s, sa = conv64(x, wsc, 0)
+        k2 = min(k2, h2_scale_exp(wsc))
+        fl = wfloor(t, w2, dp, k2) + wfloor(x, wsc, dp, k2)
     else:
-        s, sa = x, x.abs()
-    y, b = F.relu(pre + s), C_DP[dp] * EPS * (a + sa)
+        s, sa, fl = x, x.abs(), wfloor(t, w2, dp, k2)
+    y, b = F.relu(pre + s), C_DP[dp] * EPS * (a + sa) + fl
     if gate is not None:
         y, b = y * gate, b * gate.abs()
     if pool:

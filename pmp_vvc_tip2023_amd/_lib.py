@@ -79,6 +79,7 @@ SIGNATURES = {
     "pmp_debug_poison_workspace": (_I, [_VP, _I]),
     "pmp_debug_pack_f16x3": (C.c_int64, [C.POINTER(C.c_float), _I, _I, _I, C.POINTER(C.c_uint16), C.c_int64, C.POINTER(C.c_int)]),
     "pmp_debug_conv_bench": (_I, [_VP, _I, _I, _I, _I, _I, _I, _I] + [C.POINTER(C.c_double)] * 4),
+    "pmp_debug_run_resblock": (_I, [_VP, _VP] + [C.POINTER(C.c_float)] * 5 + [C.POINTER(_I), C.c_char_p, _I64]),
 }
 
 _lib = None

@@ -279,6 +279,7 @@ template <int KH, int KW>
 static hipError_t launch_x6(hipStream_t s, const ConvX6Args &a)
 {
     const int grid = a.N * (a.H >> 4) * (a.W >> 4);
+    if (a.Cout == 16 || a.Cout == 32 || a.Cout == 64) note_launch("conv_x6_kernel", KH, KW, a.Cout >> 4);
     switch (a.Cout >> 4) {
     case 1: hipLaunchKernelGGL((conv_x6_kernel<KH, KW, 1>), dim3(grid), dim3(256), 0, s, a); break;
     case 2: hipLaunchKernelGGL((conv_x6_kernel<KH, KW, 2>), dim3(grid), dim3(256), 0, s, a); break;

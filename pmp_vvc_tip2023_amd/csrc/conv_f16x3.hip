@@ -530,9 +530,14 @@ __device__ __forceinline__ void h2_epilogue(const ConvX6Args &a, f32x4 (&acc)[Wa
 }
 
 // The 1x1 shortcut source is a separate instantiation: its extra live state would spill in the common kernel.
+#define PMP_H2_LAUNCH_SC(NT, SC, LEAN)                                                                          \
+    do {                                                                                                        \
+        note_launch("conv_h2_kernel", KH, KW, NT, SC, LEAN);                                                    \
+        hipLaunchKernelGGL((conv_h2_kernel<KH, KW, NT, SC, LEAN>), dim3(grid), dim3(256), 0, s, a);             \
+    } while (0)
 #define PMP_H2_LAUNCH(NT)                                                                                       \
-    if (a.x_sc) hipLaunchKernelGGL((conv_h2_kernel<KH, KW, NT, 1>), dim3(grid), dim3(256), 0, s, a);           \
-    else hipLaunchKernelGGL((conv_h2_kernel<KH, KW, NT, 0>), dim3(grid), dim3(256), 0, s, a)
+    if (a.x_sc) PMP_H2_LAUNCH_SC(NT, 1, false);                                                                 \
+    else PMP_H2_LAUNCH_SC(NT, 0, false)
 
 template <int KH, int KW>
 static hipError_t launch_h2(hipStream_t s, const ConvX6Args &a)
@@ -546,23 +551,24 @@ static hipError_t launch_h2(hipStream_t s, const ConvX6Args &a)
             if (a.x_sc && a.Csc == 32) {
                 // RB(32,64,k): the whole 32-channel shortcut tile goes to LDS at once (h2_shortcut32); two workgroups per CU - in the
                 // 168-VGPR form these kernels measure the same (5x5 class 5.94 vs 5.95 ms per 1024 blocks)
-                hipLaunchKernelGGL((conv_h2_kernel<KH, KW, 4, 2>), dim3(grid), dim3(256), 0, s, a);
-                break;
-            }
-            if (!a.x_sc) {
+                PMP_H2_LAUNCH_SC(4, 2, false);
+            } else if (!a.x_sc) {
                 // the Cout = 64 layers without a shortcut source: the 168-VGPR form, three workgroups per CU (3x3: -5.6 %, 5x5: -1.9 %
                 // against the two-workgroup form; the shortcut instantiations would spill 70 registers in this form)
-                hipLaunchKernelGGL((conv_h2_kernel<KH, KW, 4, 0, true>), dim3(grid), dim3(256), 0, s, a);
-                break;
+                PMP_H2_LAUNCH_SC(4, 0, true);
+            } else {
+                PMP_H2_LAUNCH_SC(4, 1, false);   // (no <KH, KW, 4, 0, false> for KH > 1: nothing could reach it)
             }
+        } else {
+            PMP_H2_LAUNCH(4);
         }
-        PMP_H2_LAUNCH(4);
         break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
 #undef PMP_H2_LAUNCH
+#undef PMP_H2_LAUNCH_SC
 
 hipError_t launch_conv_h2(hipStream_t s, const ConvX6Args &a_in)
 {

@@ -255,6 +255,7 @@ template <int KH, int KW, int PIPE, int OCC>
 static hipError_t launch_k(hipStream_t s, const ConvMfmaArgs &a)
 {
     const int grid = a.N * (a.H >> 4) * (a.W >> 4);
+    if (a.Cout == 16 || a.Cout == 32 || a.Cout == 64) note_launch("conv_mfma_kernel", KH, KW, a.Cout >> 4, PIPE, OCC);
     switch (a.Cout >> 4) {
     case 1: hipLaunchKernelGGL((conv_mfma_kernel<KH, KW, 1, PIPE, OCC>), dim3(grid), dim3(256), 0, s, a); break;
     case 2: hipLaunchKernelGGL((conv_mfma_kernel<KH, KW, 2, PIPE, OCC>), dim3(grid), dim3(256), 0, s, a); break;

@@ -40,7 +40,7 @@ struct Graph {
     unsigned *sat() const { return h2() ? c->d_sat : nullptr; }   // f16x3: the context's sticky saturation flag
     // f16x3 activation scales (pmp_host.h: NetWeights::act_exp): the segment the graph is in, and the exponent a segment's tensors carry
     int seg = 0;
-    bool scaled() const { return h2() && c->act_scales && w.stem_b_h; }
+    bool scaled() const { return h2() && c->act_scales && (w.stem_b_h || w.act_given); }
     int E(int sg) const { return scaled() ? w.act_exp[sg] : 0; }
     // pmp_debug_set_taps: a copy of a tensor just produced, as its consumers read it (not in the calibration pass, the arena's measuring
     // pass or a range-guard re-run); prefixed by net, "q/" or "bd/"
@@ -174,6 +174,12 @@ struct Graph {
             return y;
         }
         if (!gate && consume && fused32(x_in, r, pool) && (pool ? out_f32 : !out_f32)) return rb_fused32(x_in, name, r, pool);
+        // the exponent step of a gate product rides on the accumulator's out_scale (conv): an identity residual, added after it, would miss
+        // it - no block of the four nets is gated without a 1x1 shortcut (trunk_Att*.1 are 32 -> 64), so such a block is refused
+        if (gate && !r.has_sc && E(seg) + E(0) != E(seg + 1)) {
+            if (rc == PMP_OK) rc = set_err(c, PMP_E_INVALID, "graph: " + name + ": a gated identity-shortcut block across an activation-scale step");
+            return x_in;
+        }
         Act x = to_conv_input(x_in);
         const bool converted = x.p != x_in.p || x.off != x_in.off;
         if (converted && consume) release(x_in);
@@ -287,6 +293,31 @@ struct Graph {
 };
 
 }  // namespace
+
+// pmp_debug_run_resblock (pmp_api.cpp): block "rb" on an input that reaches it as a trunk tensor reaches a block of the nets - split on the
+// split datapaths (the fp32 input goes through the graph's own conversion first), its bytes the block's to reuse.  A gated block is the
+// last of segment 1 and its gate a segment-0 tensor, as trunk_Att1.1 and x5 (forward_msbd); an ungated block stays in segment 0.
+int run_resblock(pmp_ctx *c, const NetWeights &w, int n, int h, int wd, const float *x_host, const float *gate_host, bool pool, bool out_f32)
+{
+    Graph g{c, w, n};
+    const RBWeights &r = w.rb.at("rb");
+    g.seg = gate_host ? 1 : 0;
+    auto input = [&](const float *src, int C, int sg, const char *name) {
+        Act a = g.alloc(C, h, wd, false);
+        if (g.live()) g.check(hipMemcpyAsync(a.p, src, a.bytes, hipMemcpyHostToDevice, c->stream), "run_resblock: input");
+        Act s = g.to_conv_input(a);
+        if (s.p != a.p || s.off != a.off) g.release(a);
+        g.tap(s, name, sg, C);
+        return s;
+    };
+    Act x = input(x_host, r.cin, g.seg, "x");
+    Act gt{};
+    if (gate_host) gt = input(gate_host, r.cout, 0, "gate");
+    Act y = g.rb(x, "rb", pool, gate_host ? &gt : nullptr, out_f32);
+    g.release(y);
+    if (gate_host) g.release(gt);
+    return g.rc;
+}
 
 // {Luma,Chroma}_Q_Net.forward (Model_QBD.py:78-98, :176-196)
 int forward_q(pmp_ctx *c, bool luma, const NetWeights &w, const uint8_t *by, const uint8_t *bu, const uint8_t *bv,

@@ -386,6 +386,17 @@ int tap_record(pmp_ctx *c, const std::string &name, const void *p, int n, int C,
     return PMP_OK;
 }
 
+// pmp_debug_run_resblock: where the launchers' notes go while it runs (this thread only; nowhere otherwise)
+static thread_local std::string *launch_log = nullptr;
+
+void note_launch(const char *kernel, int t0, int t1, int t2, int t3, int t4)
+{
+    if (!launch_log) return;
+    std::string s = std::string(kernel) + "<" + std::to_string(t0) + "," + std::to_string(t1) + "," + std::to_string(t2);
+    for (int t : {t3, t4}) if (t >= 0) s += "," + std::to_string(t);
+    *launch_log += s + ">\n";
+}
+
 // Host-pointer entry points stage through the context's own buffers (d_in, d_logit, d_out) and return final results.  A *_device call
 // that is still in flight may re-run into those very buffers once its range flag is looked at (and a replayed post-processing call may
 // read them), so everything pending is made final BEFORE the host call stages anything: afterwards the queue holds this call only.
@@ -933,6 +944,64 @@ int pmp_debug_conv_bench(pmp_ctx *c, int n, int h, int w, int cin, int cout, int
     abl_bench_free(ab);
     for (void *p : {(void *)dx, (void *)dy, (void *)dy2, (void *)dwp, (void *)dxs, (void *)dys, (void *)dwx}) if (p) hipFree(p);
     return rc;
+}
+
+int pmp_debug_run_resblock(pmp_ctx *c, const pmp_rb_case *k, const float *x, const float *w0, const float *w2, const float *wsc,
+                           const float *gate, int *saturated, char *kernels, int64_t cap)
+{
+    CHECK_CTX(c);
+    if (!k || !x || !w0 || !w2) return set_err(c, PMP_E_INVALID, "pmp_debug_run_resblock: null argument");
+    const int cin = k->cin, cout = k->cout;
+    if (k->n < 1 || k->n > PMP_TAP_MAX_BLOCKS || k->h < 16 || k->h > 256 || (k->h & 15) || k->w < 16 || k->w > 256 || (k->w & 15) ||
+        cin < 16 || cin > 256 || (cin & 15) || (cout != 16 && cout != 32 && cout != 64) || (k->k != 1 && k->k != 3 && k->k != 5))
+        return set_err(c, PMP_E_INVALID, "pmp_debug_run_resblock: unsupported shape");
+    if ((k->gate && k->pool) || (k->gate && !gate) || (cin != cout && !wsc))
+        return set_err(c, PMP_E_INVALID, "pmp_debug_run_resblock: pool with a gate, or a missing gate / shortcut tensor");
+    if (!c->taps_on) return set_err(c, PMP_E_INVALID, "pmp_debug_run_resblock: turn the taps on first (pmp_debug_set_taps)");
+    int rc = settle(c);
+    unsigned fired = 0;
+    if (rc == PMP_OK) rc = sat_fetch(c, &fired);                 // the flag is this call's
+    if (rc != PMP_OK) return rc;
+    const bool h2 = c->precision == PMP_PRECISION_F16X3;
+    NetWeights nw;
+    nw.act_given = true;
+    nw.act_exp[0] = k->gate ? k->exp_gate : k->exp_x;
+    nw.act_exp[1] = k->exp_x;
+    nw.act_exp[2] = k->exp_out;
+    // the inputs in the graph's blocked layout at their stored scale (x 2^-e, exact: a power of two)
+    auto blocked = [&](const float *src, int C, int e) {
+        const int cp = (C + 15) & ~15;
+        std::vector<float> b((size_t)k->n * cp * k->h * k->w, 0.f);
+        const float s = h2 ? std::ldexp(1.f, -e) : 1.f;
+        for (int n = 0; n < k->n; ++n)
+            for (int ch = 0; ch < C; ++ch)
+                for (int y = 0; y < k->h; ++y)
+                    for (int xx = 0; xx < k->w; ++xx)
+                        b[((((size_t)n * (cp / 16) + ch / 16) * k->h + y) * k->w + xx) * 16 + ch % 16] =
+                            src[(((size_t)n * C + ch) * k->h + y) * k->w + xx] * s;
+        return b;
+    };
+    const std::vector<float> xb = blocked(x, cin, k->exp_x), gb = k->gate ? blocked(gate, cout, k->exp_gate) : std::vector<float>();
+    std::string log;
+    rc = load_single_rb(c, nw, cin, cout, k->k, w0, w2, wsc, 1u << c->precision);
+    if (rc == PMP_OK) {
+        c->ntaps = 0;
+        launch_log = &log;
+        rc = run_graph_fn(c, [&] { return run_resblock(c, nw, k->n, k->h, k->w, xb.data(), k->gate ? gb.data() : nullptr, k->pool != 0, k->out_f32 != 0); });
+        launch_log = nullptr;
+        const hipError_t e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess && rc == PMP_OK) rc = hip_fail(c, e, "pmp_debug_run_resblock");
+    }
+    if (rc == PMP_OK) rc = sat_fetch(c, &fired);
+    free_net_weights(nw);
+    if (rc != PMP_OK) return rc;
+    if (saturated) *saturated = fired ? 1 : 0;
+    if (kernels && cap > 0) {
+        const size_t m = std::min(log.size(), (size_t)cap - 1);
+        memcpy(kernels, log.data(), m);
+        kernels[m] = 0;
+    }
+    return PMP_OK;
 }
 
 int pmp_debug_poison_workspace(pmp_ctx *c, int pattern)

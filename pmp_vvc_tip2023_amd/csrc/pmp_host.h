@@ -62,6 +62,7 @@ struct NetWeights {
     uint64_t fp = 0;                                   // fingerprint_tensors() of `host` (pmp_weights_fingerprint)
     bool act_from_file = false;                        // the exponents came from a manifest ...
     bool act_fp_known = false; uint64_t act_qt_fp = 0; // ... that says which QT partner they were calibrated with
+    bool act_given = false;                            // pmp_debug_run_resblock: act_exp set by the caller, for a net of one block
     float *stem_b_h = nullptr;                         // f16x3: stem biases * 2^-act_exp[0]
     float *head_w_h[3] = {nullptr, nullptr, nullptr};  // f16x3: head weights * 2^act_exp[{0, 2, 4}]
     std::vector<std::string> cal_names;                // calibration record: tensors in launch order ...
@@ -212,6 +213,11 @@ int tap_record(pmp_ctx *c, const std::string &name, const void *p, int n, int C,
 int calibrate_mtt(pmp_ctx *c, bool luma, NetWeights &wq, NetWeights &wb);
 void qt_partner_changed(pmp_ctx *c, int qt_net_id, int qp);         // a QT net was (re)loaded: its MTT partner's exponents may be stale
 int calibrate_if_ready(pmp_ctx *c, int net_id, int qp);             // a (QT, MTT) pair that has just become complete, on the f16x3 datapath
+
+// pmp_debug_run_resblock: one ResidualBlock "rb" packed by the loader's own load_rb into nw (the formats of `mask`); free_net_weights frees it
+int load_single_rb(pmp_ctx *c, NetWeights &nw, int cin, int cout, int k, const float *w0, const float *w2, const float *wsc, unsigned mask);
+// ... and run through the graph's rb() on n blocks; x, gate: blocked fp32 [n][C/16][h][w][16] at stored scale (host), gate may be null
+int run_resblock(pmp_ctx *c, const NetWeights &w, int n, int h, int wd, const float *x, const float *gate, bool pool, bool out_f32);
 
 // nets.cpp: forward graphs on device pointers (n <= chunk); all launches go to c->stream.
 int forward_q(pmp_ctx *c, bool luma, const NetWeights &w, const uint8_t *by, const uint8_t *bu, const uint8_t *bv,

@@ -11,6 +11,10 @@
 
 namespace pmp {
 
+// pmp_debug_run_resblock: the convolution launchers name the instantiation they launch ("kernel<a,b,...>", template arguments as integers,
+// -1 = absent) - host side, and a no-op unless that hook is collecting on this thread (pmp_api.cpp).
+void note_launch(const char *kernel, int t0, int t1, int t2, int t3 = -1, int t4 = -1);
+
 // ------------------------------------------------------------------------------------------------ conv (MFMA)
 // out = epilogue( conv_KHxKW(x, w) [+ conv_1x1(x_sc, w_sc)] [+ res] ), stride 1, zero padding K/2.
 // epilogue: optional ReLU, optional multiply by `gate`, optional 2x2 max-pool.  H, W multiples of 16;

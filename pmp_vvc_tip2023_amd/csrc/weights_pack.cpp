@@ -136,6 +136,20 @@ int load_head(pmp_ctx *c, const Blob &b, Uploader &up, const std::string &name, 
 
 }  // namespace
 
+int load_single_rb(pmp_ctx *c, NetWeights &nw, int cin, int cout, int k, const float *w0, const float *w2, const float *wsc, unsigned mask)
+{
+    std::vector<float> blob(w0, w0 + (size_t)cout * cin * k * k);
+    blob.insert(blob.end(), w2, w2 + (size_t)cout * cout * k * k);
+    if (cin != cout) blob.insert(blob.end(), wsc, wsc + (size_t)cout * cin);
+    const pmp_tensor_desc descs[3] = {{"rb.left.0.weight", 4, {cout, cin, k, k}, 0},
+                                      {"rb.left.2.weight", 4, {cout, cout, k, k}, (int64_t)cout * cin * k * k},
+                                      {"rb.shortcut.0.weight", 4, {cout, cin, 1, 1}, (int64_t)cout * cin * k * k + (int64_t)cout * cout * k * k}};
+    Uploader up{c, &nw};
+    int rc = load_rb(c, Blob{blob.data(), descs, cin != cout ? 3 : 2}, up, "rb", cin, cout, k, false, mask);
+    if (rc != PMP_OK) { up.abandon(); return rc; }
+    return up.finalize();
+}
+
 void free_net_weights(NetWeights &w)
 {
     for (void *p : w.allocs) hipFree(p);

@@ -39,8 +39,8 @@ def _split3(a):
 
 
 def _scale_exp(w):
-    """pack.cpp h2_scale_exp: S = 2^k puts max |S*w| in [4096, 8192)."""
-    return 13 - math.frexp(float(w.abs().max()))[1]
+    """pack.cpp h2_scale_exp: S = 2^k puts max |S*w| in [4096, 8192), k capped to [-100, 24]."""
+    return L.h2_scale_exp(w.numpy())
 
 
 def _conv_seq(x, w, pad, group):
@@ -57,17 +57,18 @@ def _conv_seq(x, w, pad, group):
     return acc.reshape(n, w.shape[0], h, wd)
 
 
-def _conv_dp(x, w, dp, mutant=None):
-    """float32 accumulation of the products datapath dp forms; x holds values of the datapath's activation format."""
+def _conv_dp(x, w, dp, mutant=None, k=None):
+    """float32 accumulation of the products datapath dp forms; x holds values of the datapath's activation format.  k: the f16x3 scale
+    exponent the weights are packed with (default: their own; a 1x1 shortcut is packed with the second convolution's, load_rb)."""
     pad = w.shape[2] // 2
     if mutant == "last_k_group":      # the last 16-channel K group never enters the accumulator
         x = x.clone()
         x[:, -16:] = 0
     if mutant == "border_tap":        # the bottom-centre tap dropped for the top output row only (it reads row 1, inside the map)
-        full = _conv_dp(x, w, dp)
+        full = _conv_dp(x, w, dp, k=k)
         wm = w.clone()
         wm[:, :, -1, w.shape[3] // 2] = 0
-        full[:, :, 0, :] = _conv_dp(x, wm, dp)[:, :, 0, :]
+        full[:, :, 0, :] = _conv_dp(x, wm, dp, k=k)[:, :, 0, :]
         return full
     if dp == "fp32":
         return _conv_seq(x, w, pad, 1)
@@ -77,12 +78,16 @@ def _conv_dp(x, w, dp, mutant=None):
         if mutant == "five_products":     # x0 * w1 dropped
             pairs.remove((0, 1))
         return _conv_seq(torch.cat([a[i] for i, _ in pairs], 1), torch.cat([b[j] for _, j in pairs], 1), pad, 8)
-    k = _scale_exp(w)
+    if k is None or mutant == "sc_own_scale":     # sc_own_scale: the shortcut packed with its own exponent, unpacked with the shared one
+        k, k_out = _scale_exp(w), k
+    else:
+        k_out = k
+    k_out = k if k_out is None else k_out
     x0, x1 = _split2(x)
     w0, w1 = _split2(w * 2.0 ** k)
     pairs = {"two_products_x0w": [(x0, w0), (x0, w1)], "two_products_xw0": [(x0, w0), (x1, w0)]}.get(mutant, [(x0, w0), (x0, w1), (x1, w0)])
     acc = _conv_seq(torch.cat([p for p, _ in pairs], 1), torch.cat([q for _, q in pairs], 1), pad, 8)
-    return acc * 2.0 ** (-k + (1 if mutant == "out_scale" else 0))
+    return acc * 2.0 ** (-k_out + (1 if mutant == "out_scale" else 0))
 
 
 def _store(v, dp, mutant=None):
@@ -102,18 +107,38 @@ def _activation(shape, g, dp):
     return _store(x, dp)
 
 
-def _run(shape, dp, mutant=None, seed=0):
-    """Both launches of a ResidualBlock emulated; -> (max ratio of .t, max ratio of the output)."""
+# weight distributions of the f16x3 edges (oracle/conv_cases.py WDISTS): (gain of w0, gain of w2, gain of wsc relative to w2, per-output-
+# channel spread in powers of two)
+WDISTS = {"randn": (1.0, 1.0, 1.0, 0), "dead20": (1.0, 1.0, 1.0, 20), "dead16": (1.0, 1.0, 1.0, 16), "sc+18": (1.0, 1.0, 2.0 ** 18, 0),
+          "sc-18": (1.0, 1.0, 2.0 ** -18, 0), "sc-12": (1.0, 1.0, 2.0 ** -12, 0), "cap": (2.0 ** -30, 2.0 ** -28, 1.0, 0),
+          "big": (2.0 ** 14, 2.0 ** -14, 1.0, 0)}
+
+
+def _weights(g, cout, cin, k, gain, spread):
+    w = torch.randn((cout, cin, k, k), generator=g) / math.sqrt(cin * k * k)
+    if spread:
+        w = w * torch.exp2(-spread * torch.arange(cout, dtype=torch.float32) / max(cout - 1, 1))[:, None, None, None]
+    return (w * gain).float()
+
+
+def _run(shape, dp, mutant=None, seed=0, wdist="randn", hw=(16, 16)):
+    """Both launches of a ResidualBlock emulated; -> (max ratio of .t, max ratio of the output).  On f16x3 the 1x1 shortcut is packed
+    with the second convolution's scale exponent, min(k(w2), k(wsc)), and shares its accumulator, as load_rb and the kernels do."""
     k, cin, cout, sc, pool = shape
+    g0, g2, gsc, spread = WDISTS[wdist]
     g = torch.Generator().manual_seed(1000 * k + cin + seed)
-    x = _activation((2, cin, 16, 16), g, dp)
-    w0 = torch.randn((cout, cin, k, k), generator=g) / math.sqrt(cin * k * k)
-    w2 = torch.randn((cout, cout, k, k), generator=g) / math.sqrt(cout * k * k)
-    wsc = torch.randn((cout, cin, 1, 1), generator=g) / math.sqrt(cin) if sc else None
+    x = _activation((2, cin) + hw, g, dp)
+    x = _store((x / max(1.0, g0, g0 * g2, gsc if sc else 1.0)).float(), dp)     # every stored value stays inside fp16
+    w0 = _weights(g, cout, cin, k, g0, spread)
+    w2 = _weights(g, cout, cout, k, g2, spread)
+    wsc = _weights(g, cout, cin, 1, 1.0, spread) if sc else None
+    if sc:
+        wsc = (wsc * (gsc * float(w2.abs().max() / wsc.abs().max()))).float()
     t = _store(F.relu(_conv_dp(x.float(), w0, dp, mutant)), dp, mutant)
     t_ref, t_bnd = L.conv_t64(x, w0.double(), dp)
-    acc = _conv_dp(t.float(), w2, dp, mutant)
-    acc = acc + (_conv_dp(x.float(), wsc, dp, None if mutant == "border_tap" else mutant) if sc else x.float())
+    k2 = min(_scale_exp(w2), _scale_exp(wsc)) if sc and dp == "f16x3" else None
+    acc = _conv_dp(t.float(), w2, dp, None if mutant == "sc_own_scale" else mutant, k=k2)
+    acc = acc + (_conv_dp(x.float(), wsc, dp, None if mutant == "border_tap" else mutant, k=k2) if sc else x.float())
     y = F.relu(acc)
     if pool:
         y = F.max_pool2d(y, 2)
@@ -138,6 +163,52 @@ def test_documented_arithmetic_stays_inside_the_bound(shape, dp):
         assert rt <= 1.0 and ry <= 1.0, (dp, shape, rt, ry)
         worst = max(worst, rt, ry)
     assert worst >= 1.0 / 8, (dp, shape, worst)
+
+
+# the f16x3 edges beyond the nets' weights: dead channels, a shortcut far above / below the w2 it shares its scale with, the k = 24 cap, a
+# tensor >= 8192 (negative k); on a 1x1-shortcut shape and a non-square pooled 5x5 one
+EDGE_SHAPES = [((3, 32, 64, True, False), (16, 16)), ((5, 48, 16, True, True), (16, 48))]
+
+
+@pytest.mark.parametrize("wdist", [w for w in WDISTS if w != "randn"])
+@pytest.mark.parametrize("dp", ["fp32", "bf16x6", "f16x3"])
+@pytest.mark.parametrize("shape,hw", EDGE_SHAPES, ids=["3x3_32_64_sc", "5x5_48_16_sc_pool_16x48"])
+def test_weight_edges_stay_inside_the_bound(shape, hw, dp, wdist):
+    rt, ry = _run(shape, dp, wdist=wdist, hw=hw)
+    print("%s %s %s: max ratio .t %.3f, out %.3f" % (dp, wdist, shape, rt, ry))
+    assert rt <= 1.0 and ry <= 1.0, (dp, wdist, shape, rt, ry)
+
+
+# (not sc+18: there the second convolution adds 2^-18 of what the shortcut adds, so a slip in it is legitimately inside the output's bound)
+@pytest.mark.parametrize("wdist", ["sc-12", "dead20", "big"])
+@pytest.mark.parametrize("shape,hw", EDGE_SHAPES, ids=["3x3_32_64_sc", "5x5_48_16_sc_pool_16x48"])
+def test_mutants_exceed_the_bound_at_the_weight_edges(shape, hw, wdist):
+    """At the edges the bound gains a weight floor; a border tap, a last K group or an out_scale slip must still exceed it 16x, and so
+    must a shortcut packed with its own exponent instead of the one it shares with w2 (the shortcut's products off by 2^(ksc - k2))."""
+    for mutant in ("border_tap", "last_k_group", "out_scale") + (("sc_own_scale",) if wdist == "sc-12" else ()):
+        rt, ry = _run(shape, "f16x3", mutant, wdist=wdist, hw=hw)
+        print("f16x3 %s %s %s: max ratio .t %.1f, out %.1f" % (mutant, wdist, shape, rt, ry))
+        assert ry >= 16 and (rt >= 16 or mutant == "sc_own_scale"), (mutant, wdist, shape, rt, ry)
+
+
+def test_weight_floor_is_sharp():
+    """W_FLOOR: weights 2^30 below their tensor's maximum keep an absolute error of half the subnormal fp16 step at the tensor's scale.
+    Every weight of output channel 1 sits at 1.5 * 2^-24 / S, which rounds to 2^-23 / S (ties to even) with a zero low term: the error is
+    2^-25 / S per weight, all of one sign, so the conv output misses by 2^-25 / S * sum|x|.  The bound must hold that and be met within 4x;
+    without the floor it is exceeded by orders of magnitude."""
+    g = torch.Generator().manual_seed(8)
+    x = _store(torch.rand((2, 16, 16, 32), generator=g) * 1024 + 512, "f16x3")
+    w = torch.randn((2, 16, 3, 3), generator=g)
+    k = _scale_exp(w)
+    w[1] = 1.5 * 2.0 ** (-24 - k)
+    w = w.float()
+    assert _scale_exp(w) == k
+    got = _store(F.relu(_conv_dp(x.float(), w, "f16x3")), "f16x3")
+    ref, bnd = L.conv_t64(x, w.double(), "f16x3")
+    r = L.ratio(got[:, 1:], L.Layer("floor", "", ref[:, 1:], bnd[:, 1:]))
+    assert 0.25 <= r <= 1.0, r
+    no_floor = bnd[:, 1:] - L.wfloor(x, w.double(), "f16x3", k)
+    assert L.ratio(got[:, 1:], L.Layer("floor", "", ref[:, 1:], no_floor)) >= 16
 
 
 @pytest.mark.parametrize("mutant,dp", [(m, dp) for dp in ("fp32", "bf16x6", "f16x3") for m in MUTANTS[dp]])
