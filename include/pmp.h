@@ -199,6 +199,41 @@ int pmp_infer_device(pmp_ctx *ctx, int comp, int qp, const uint8_t *d_block_y, c
  *        (set_partition_vector, :348-362: neither == nor > holds) and qt_u8 carries 0 (numpy's .astype(uint8) of NaN on x86-64). */
 int pmp_postprocess(pmp_ctx *ctx, int comp, const float *qt, const float *bt, const float *dire, int64_t n,
                     uint8_t *hor, uint8_t *ver, uint8_t *qt_u8, int8_t *dire_i8);
+
+/* ---- Map2Partition thresholds, per context and per component (PMP_LUMA / PMP_CHROMA).  Map_to_Partition takes them as constructor
+ *      parameters (Map2Partition.py:100) and th_round as its `thd` (:30-35, called with 0.5 at :105).  Every post-processing entry point
+ *      uses the set of its component (pmp_postprocess*, pmp_infer_postprocess*, the *_records_device forms).
+ *        lamb[0] lamb1  a CU stops splitting when count_zero >= (lamb1*h)*w                    default 0.7
+ *        lamb[1] lamb2  the direction map decides when (count_ver+count_hor) >= (lamb2*h)*w  default 0.7
+ *        lamb[2] lamb3  ... horizontal if count_hor >= lamb3*count_ver, else vertical if
+ *                       count_ver >= lamb3*count_hor                                           default 1.5
+ *        lamb[3] lamb4  a split part qualifies if count_minus < num_pixel*lamb4 ...           default 0.3
+ *        lamb[4] lamb5  ... and count_zero > num_pixel*lamb5                                  default 0.7
+ *        thd            th_round: dire >= thd -> 1, dire <= -thd -> -1, else 0                 default 0.5
+ *      Semantics are the reference's at every accepted value, ties included: the counts are compared with the DOUBLE products above in
+ *      Python's evaluation order, and th_round compares the float32 logits with float32(thd) as numpy does.  th_round's third step zeroes
+ *      (-thd, thd) after the first two have written +-1, so for thd > 1 every direction becomes 0: reproduced, not "fixed".  NaN and
+ *      +-inf logits keep the meaning described above.
+ *      Accepted domain (anything else, NaN and +-inf included, is PMP_E_INVALID and leaves the current set in force):
+ *        0 <= lamb1 <= 1,  lamb2 >= 0,  lamb3 >= 0,  0 <= lamb4 <= 1,  0.67 <= lamb5 <= 1,  0 < thd <= 2  (thd as stored, a float).
+ *      Why lamb5 >= 0.67: a BT and a TT split in the same direction can then never both be candidates - each would need more than
+ *      lamb5 of its parts' cells at its target depth, and the TT's outer quarter is half of the BT's half with a target one level
+ *      deeper, impossible for lamb5 >= 2/3 (0.67 keeps the argument clear of how 2/3 rounds).  So a CU has at most three candidates
+ *      - no split, one horizontal and one vertical split - as with the defaults, and the search's worst case (the number of leaves
+ *      of the depth-3 candidate tree) is no larger than with the defaults.
+ *      CAPTURE AT ENQUEUE: a call uses the set that was current when it was made - a *_device call still running, every chunk of an
+ *      overlap-mode call, and a post-processing call that the range guard replays at pmp_synchronize all keep their set, whatever
+ *      pmp_set_partition_params does in between.
+ *      pmp_set_partition_params(ctx, comp, NULL) restores the defaults.  pmp_parse_partition_params is host-only (no context, no GPU):
+ *      it reads "lamb1=0.6,thd=0.45" (keys lamb1..lamb5 and thd, comma-separated, any subset, the last of a repeated key wins) on top
+ *      of *inout and writes *inout only if the text parses and the result lies in the domain; "" leaves *inout as it is. ---- */
+typedef struct {
+    double lamb[5];    /* lamb1..lamb5 */
+    float thd;
+} pmp_partition_params;
+int pmp_set_partition_params(pmp_ctx *ctx, int comp, const pmp_partition_params *p);
+int pmp_get_partition_params(const pmp_ctx *ctx, int comp, pmp_partition_params *out);
+int pmp_parse_partition_params(const char *spec, pmp_partition_params *inout);
 int pmp_postprocess_device(pmp_ctx *ctx, int comp, const float *d_qt, const float *d_bt, const float *d_dire,
                            int64_t n, uint8_t *d_hor, uint8_t *d_ver, uint8_t *d_qt_u8, int8_t *d_dire_i8);
 

@@ -23,6 +23,11 @@ class TensorDesc(C.Structure):
     _fields_ = [("name", C.c_char_p), ("ndim", C.c_int), ("shape", C.c_int * 4), ("offset", C.c_int64)]
 
 
+class PartitionParams(C.Structure):
+    """pmp_partition_params: Map_to_Partition's lamb1..lamb5 (Map2Partition.py:100) and th_round's thd (:105)."""
+    _fields_ = [("lamb", C.c_double * 5), ("thd", C.c_float)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/pmp.h
 _VP, _I, _I64, _U32 = C.c_void_p, C.c_int, C.c_int64, C.c_uint32
 SIGNATURES = {
@@ -52,6 +57,9 @@ SIGNATURES = {
     "pmp_infer_device": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I64, _VP, _VP, _VP]),
     "pmp_postprocess": (_I, [_VP, _I, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP]),
     "pmp_postprocess_device": (_I, [_VP, _I, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP]),
+    "pmp_set_partition_params": (_I, [_VP, _I, C.POINTER(PartitionParams)]),
+    "pmp_get_partition_params": (_I, [_VP, _I, C.POINTER(PartitionParams)]),
+    "pmp_parse_partition_params": (_I, [C.c_char_p, C.POINTER(PartitionParams)]),
     "pmp_infer_postprocess": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "pmp_infer_postprocess_device": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "pmp_postprocess_records_device": (_I, [_VP, _I, _VP, _VP, _VP, _I64, _VP]),

@@ -1,8 +1,10 @@
 // host_emit.cpp — the host-only entry points of include/pmp.h: PartitionMat text / binary emission and frame tiling
-// (Map2Partition.py:385-412; consumer EncAppCfg::parsePartitionMatrix, EncAppCfg.cpp:4234-4404), plus the context-less
-// error string.  No HIP in this file: it is also compiled with -fsanitize=address,undefined into the CPU-only test library
+// (Map2Partition.py:385-412; consumer EncAppCfg::parsePartitionMatrix, EncAppCfg.cpp:4234-4404), the Map2Partition threshold
+// parser and its domain check, plus the context-less error string.  No HIP in this file: it is also compiled with -fsanitize=address,undefined into the CPU-only test library
 // (make hostasan, tests/test_hostasan_cpu.py).
+#include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <new>
@@ -305,6 +307,70 @@ int pmp_tile_partition_rows_records(int W, int block_rows, const uint8_t *rec, u
     const BlockView v{rec, rec + 256, rec + 512, reinterpret_cast<const int8_t *>(rec + 576), PMP_RECORD_BYTES, PMP_RECORD_BYTES, PMP_RECORD_BYTES,
                       PMP_RECORD_BYTES};
     tile_rows(v, 0, block_rows, W / 64, out_hor, out_ver, out_qt, out_dire);
+    return PMP_OK;
+}
+
+}  // extern "C"
+
+// ---- Map2Partition thresholds (include/pmp.h: pmp_partition_params) ------------------------------------------------------
+namespace pmp {
+
+bool partition_params_valid(const pmp_partition_params &p, std::string &why)
+{
+    static const char *const key[5] = {"lamb1", "lamb2", "lamb3", "lamb4", "lamb5"};
+    for (int i = 0; i < 5; ++i)
+        if (!std::isfinite(p.lamb[i])) { why = std::string(key[i]) + " is not finite"; return false; }
+    if (!std::isfinite(p.thd)) { why = "thd is not finite"; return false; }
+    if (!(p.lamb[0] >= 0.0 && p.lamb[0] <= 1.0)) { why = "lamb1 must lie in [0, 1]"; return false; }
+    if (!(p.lamb[1] >= 0.0)) { why = "lamb2 must be >= 0"; return false; }
+    if (!(p.lamb[2] >= 0.0)) { why = "lamb3 must be >= 0"; return false; }
+    if (!(p.lamb[3] >= 0.0 && p.lamb[3] <= 1.0)) { why = "lamb4 must lie in [0, 1]"; return false; }
+    if (!(p.lamb[4] >= 0.67 && p.lamb[4] <= 1.0)) { why = "lamb5 must lie in [0.67, 1] (include/pmp.h: the search's worst case)"; return false; }
+    if (!(p.thd > 0.f && p.thd <= 2.f)) { why = "thd must lie in (0, 2]"; return false; }
+    return true;
+}
+
+}  // namespace pmp
+
+extern "C" {
+
+int pmp_parse_partition_params(const char *spec, pmp_partition_params *inout)
+{
+    if (!spec || !inout) return set_err_global(PMP_E_INVALID, "pmp_parse_partition_params: null argument");
+    pmp_partition_params p = *inout;
+    const char *s = spec;
+    while (*s) {
+        while (*s == ' ' || *s == '\t') ++s;
+        const char *k0 = s;
+        while (*s && *s != '=' && *s != ',' && *s != ' ' && *s != '\t') ++s;
+        const std::string key(k0, s);
+        while (*s == ' ' || *s == '\t') ++s;
+        if (key.empty() && (*s == ',' || !*s)) {          // empty item ("", "a=1,,b=2", a trailing comma)
+            if (*s) ++s;
+            continue;
+        }
+        if (*s != '=') return set_err_global(PMP_E_INVALID, "pmp_parse_partition_params: expected key=value at '" + std::string(k0) + "'");
+        ++s;
+        while (*s == ' ' || *s == '\t') ++s;
+        const char *v0 = s;
+        while (*s && *s != ',') ++s;
+        std::string val(v0, s);
+        while (!val.empty() && (val.back() == ' ' || val.back() == '\t')) val.pop_back();
+        char *end = nullptr;
+        const double d = val.empty() ? 0.0 : std::strtod(val.c_str(), &end);
+        if (val.empty() || end != val.c_str() + val.size())
+            return set_err_global(PMP_E_INVALID, "pmp_parse_partition_params: '" + val + "' is not a number (key " + key + ")");
+        if (key.size() == 5 && key.compare(0, 4, "lamb") == 0 && key[4] >= '1' && key[4] <= '5') p.lamb[key[4] - '1'] = d;
+        else if (key == "thd") {
+            if (!(d > 0.0 && d <= 2.0)) return set_err_global(PMP_E_INVALID, "pmp_parse_partition_params: thd must lie in (0, 2]");
+            p.thd = (float)d;                             // numpy compares the float32 logits with float32(thd)
+        } else
+            return set_err_global(PMP_E_INVALID, "pmp_parse_partition_params: unknown key '" + key + "' (lamb1..lamb5, thd)");
+        if (*s == ',') ++s;
+    }
+    std::string why;
+    if (!pmp::partition_params_valid(p, why)) return set_err_global(PMP_E_INVALID, "pmp_parse_partition_params: " + why);
+    *inout = p;
     return PMP_OK;
 }
 

@@ -316,11 +316,11 @@ static int infer_device_impl(pmp_ctx *c, int comp, int qp, const uint8_t *by, co
     return PMP_OK;
 }
 
-static int post_launch(pmp_ctx *c, int comp, const float *qt, const float *bt, const float *dire, int64_t n, uint8_t *hor, uint8_t *ver,
-                       uint8_t *qt_u8, int8_t *dire_i8, int record_stride)
+static int post_launch(pmp_ctx *c, int comp, const M2PParams &prm, const float *qt, const float *bt, const float *dire, int64_t n,
+                       uint8_t *hor, uint8_t *ver, uint8_t *qt_u8, int8_t *dire_i8, int record_stride)
 {
     KScope ks(c, K_POST, 0.0);
-    hipError_t e = launch_postprocess(c->stream, qt, bt, dire, n, comp == PMP_LUMA ? 1 : 2, hor, ver, qt_u8, dire_i8, record_stride);
+    hipError_t e = launch_postprocess(c->stream, qt, bt, dire, n, comp == PMP_LUMA ? 1 : 2, prm, hor, ver, qt_u8, dire_i8, record_stride);
     return e == hipSuccess ? PMP_OK : hip_fail(c, e, "postprocess");
 }
 
@@ -330,10 +330,11 @@ static int post_device_impl(pmp_ctx *c, int comp, const float *qt, const float *
     if (comp != PMP_LUMA && comp != PMP_CHROMA) return set_err(c, PMP_E_INVALID, "pmp_postprocess: bad comp");
     if (n < 0 || !qt || !bt || !dire || !hor || !ver || !qt_u8 || !dire_i8)
         return set_err(c, PMP_E_INVALID, "pmp_postprocess: null buffer or negative count");
-    const int rc = post_launch(c, comp, qt, bt, dire, n, hor, ver, qt_u8, dire_i8, record_stride);
+    const M2PParams prm = c->m2p[comp];     // the thresholds current at ENQUEUE: the replay below runs with them too (include/pmp.h)
+    const int rc = post_launch(c, comp, prm, qt, bt, dire, n, hor, ver, qt_u8, dire_i8, record_stride);
     // its logits may come from an inference call whose range flag has not been looked at yet: remember the call for the replay
     if (rc == PMP_OK && !c->pending.empty())
-        c->pending.push_back(PendingCall{false, false, nullptr, nullptr, [=](bool) { return post_launch(c, comp, qt, bt, dire, n, hor, ver, qt_u8, dire_i8, record_stride); }});
+        c->pending.push_back(PendingCall{false, false, nullptr, nullptr, [=](bool) { return post_launch(c, comp, prm, qt, bt, dire, n, hor, ver, qt_u8, dire_i8, record_stride); }});
     return rc;
 }
 
@@ -651,6 +652,28 @@ int pmp_has_weights(const pmp_ctx *c, int net_id, int qp)
     if (!c) return 0;
     auto it = c->nets.find(net_id * 100 + qp);
     return it != c->nets.end() && it->second.loaded;
+}
+
+int pmp_set_partition_params(pmp_ctx *c, int comp, const pmp_partition_params *p)
+{
+    CHECK_CTX(c);
+    if (comp != PMP_LUMA && comp != PMP_CHROMA) return set_err(c, PMP_E_INVALID, "pmp_set_partition_params: comp must be PMP_LUMA or PMP_CHROMA");
+    if (!p) { c->m2p[comp] = M2P_DEFAULT; return PMP_OK; }
+    std::string why;
+    if (!partition_params_valid(*p, why)) return set_err(c, PMP_E_INVALID, "pmp_set_partition_params: " + why);
+    // no settling: calls already enqueued captured their set (post_device_impl), so nothing in flight can see this one
+    for (int i = 0; i < 5; ++i) c->m2p[comp].lamb[i] = p->lamb[i];
+    c->m2p[comp].thd = p->thd;
+    return PMP_OK;
+}
+
+int pmp_get_partition_params(const pmp_ctx *c, int comp, pmp_partition_params *out)
+{
+    if (!c || !out) return set_err(nullptr, PMP_E_INVALID, "pmp_get_partition_params: null argument");
+    if (comp != PMP_LUMA && comp != PMP_CHROMA) return set_err(nullptr, PMP_E_INVALID, "pmp_get_partition_params: comp must be PMP_LUMA or PMP_CHROMA");
+    for (int i = 0; i < 5; ++i) out->lamb[i] = c->m2p[comp].lamb[i];
+    out->thd = c->m2p[comp].thd;
+    return PMP_OK;
 }
 
 int pmp_infer_device(pmp_ctx *c, int comp, int qp, const uint8_t *by, const uint8_t *bu, const uint8_t *bv, int64_t n,

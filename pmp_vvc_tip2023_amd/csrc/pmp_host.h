@@ -147,6 +147,7 @@ struct pmp_ctx {
     int fuse16 = 1;                        // f16x3: run the 16x16-resolution tails LDS-resident (chain16.hip: two / three launches per net); 0 = launch per layer (pmp_debug_set_fusion: A/B and the bit-identity tests)
     int act_scales = 1;                    // f16x3: use the MTT nets' calibrated activation scales (NetWeights::act_exp); 0 = exponents of zero (pmp_debug_set_activation_scales: the range-guard tests)
     int fuse32 = 1;                        // f16x3: trunk_B3.1 / B3.2 / Att2.0 (32x32, <= 32 output channels) as one launch per ResidualBlock (rbfuse32.hip); same hook
+    pmp::M2PParams m2p[2] = {pmp::M2P_DEFAULT, pmp::M2P_DEFAULT};   // Map2Partition thresholds per component (pmp_set_partition_params); read at enqueue
     std::string err;
     // f16x3 range guard (include/pmp.h, pmp_set_saturation_policy): device word raised by every kernel that clamps a stored activation.
     // A 256-byte block: word 0 is the flag, bytes 64.. stay zero (the zero line of conv_f16x3_t32.hip's halo DMA)

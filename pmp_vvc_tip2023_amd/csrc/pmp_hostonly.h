@@ -36,4 +36,7 @@ constexpr int PMP_ACT_EXP_ATT_MAX = 6;     // largest exponent of an attention s
 uint64_t fingerprint_tensors(const float *blob, const pmp_tensor_desc *descs, int ndesc);
 int net_id_of(const std::string &net);
 
+// host_emit.cpp: the accepted domain of the Map2Partition thresholds (include/pmp.h); `why` says which bound failed
+bool partition_params_valid(const pmp_partition_params &p, std::string &why);
+
 }  // namespace pmp

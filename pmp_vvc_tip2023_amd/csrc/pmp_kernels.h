@@ -165,10 +165,21 @@ hipError_t launch_att_input(hipStream_t s, const float *q, const float *bt, cons
 hipError_t launch_amax_f32(hipStream_t s, const float *x, size_t n, unsigned *slot);
 
 // ------------------------------------------------------------------------------------------------ post-processing
+// Map_to_Partition's thresholds (include/pmp.h: pmp_partition_params; validated by the caller): lamb1..lamb5 and th_round's thd.
+struct M2PParams {
+    double lamb[5];
+    float thd;
+};
+constexpr M2PParams M2P_DEFAULT = {{0.7, 0.7, 1.5, 0.3, 0.7}, 0.5f};   // Map2Partition.py:100,105
+inline bool m2p_is_default(const M2PParams &p)
+{
+    for (int i = 0; i < 5; ++i) if (p.lamb[i] != M2P_DEFAULT.lamb[i]) return false;
+    return p.thd == M2P_DEFAULT.thd;
+}
 // eli_structual_error + Map_to_Partition, one wavefront per block.  qt raw logits [N][64]; bt, dire [N][3][256].
 // record_stride != 0: the four outputs are fields of one packed record per block (bytes between blocks), else dense arrays.
-hipError_t launch_postprocess(hipStream_t s, const float *qt, const float *bt, const float *dire, int64_t N,
-                              int chroma_factor, uint8_t *hor, uint8_t *ver, uint8_t *qt_u8, int8_t *dire_i8, int record_stride = 0);
+hipError_t launch_postprocess(hipStream_t s, const float *qt, const float *bt, const float *dire, int64_t N, int chroma_factor,
+                              const M2PParams &prm, uint8_t *hor, uint8_t *ver, uint8_t *qt_u8, int8_t *dire_i8, int record_stride = 0);
 
 // Block cutter (Inference_QBD.py:104-149).
 hipError_t launch_cut_blocks(hipStream_t s, const void *y, const void *u, const void *v, int F, int H, int W,

@@ -41,10 +41,11 @@ struct Search {
                       // has no clamp, but the rounded map is only ever compared (`== 0`, `< 0` of msbt - candidate, candidate depths 0..6,
                       // :142,189-190): a value beyond 100 - or NaN, on which both comparisons are False - behaves like 100, one below
                       // -100 like -100.  Pinned by tests/golden/g3b_m2p_range.npz (|bt| up to 3e38, +-inf, NaN; made by the reference)
-    int md[3][4];     // th_round(dire, 0.5) (Map2Partition.py:30-35,105)
+    int md[3][4];     // th_round(dire, thd) (Map2Partition.py:30-35,105; thd = 0.5 there)
     float ob[3][4];   // raw MTT depth logits
     float od[3][4];   // raw direction logits
     int cf;           // chroma_factor
+    double lamb[5];   // Map_to_Partition's lamb1..lamb5 of this call (kernel argument; uniform)
     // tree levels 0..3 (Map_Node, Map2Partition.py:89-96)
     int bt[4][4], dr[4][4];
     int cu[4];        // lane c holds CU c of the level: x | y<<4 | (h-1)<<8 | (w-1)<<12
@@ -107,11 +108,13 @@ __device__ __forceinline__ int can_split(const Search &s, int cu, int &n)
     bool in[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) in[k] = s.row >= x && s.row < x + h && s.col0 + k >= y && s.col0 + k < y + w;
+    // lamb1..lamb5 as Python compares them (Map2Partition.py:144,150-153,194): an int count against a double product, left to right
+    const double l1 = s.lamb[0], l2 = s.lamb[1], l3 = s.lamb[2], l4 = s.lamb[3], l5 = s.lamb[4];
     int zero = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) zero += cnt(in[k] && s.mb[2][k] == s.bt[L][k]);
     n = 1;
-    if ((double)zero >= 0.7 * h * w) return 0;  // lamb1
+    if ((double)zero >= l1 * h * w) return 0;  // lamb1
     int hor = 0, ver = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -119,9 +122,9 @@ __device__ __forceinline__ int can_split(const Search &s, int cu, int &n)
         ver += cnt(in[k] && s.md[L][k] == -1);
     }
     int direction = 0;
-    if ((double)(ver + hor) >= 0.7 * h * w) {  // lamb2, lamb3
-        if ((double)hor >= 1.5 * ver) direction = 1;
-        else if ((double)ver >= 1.5 * hor) direction = 2;
+    if ((double)(ver + hor) >= l2 * h * w) {  // lamb2, lamb3
+        if ((double)hor >= l3 * ver) direction = 1;
+        else if ((double)ver >= l3 * hor) direction = 2;
     }
     const int cf = s.cf;
     int list = 0;
@@ -151,7 +154,7 @@ __device__ __forceinline__ int can_split(const Search &s, int cu, int &n)
                 zer += cnt(ins && s.mb[L][k] == tgt);
             }
             const int np_ = (o1 - o0) * (horiz ? w : h);
-            if ((double)minus < np_ * 0.3 && (double)zer > np_ * 0.7) ++ok;  // lamb4, lamb5
+            if ((double)minus < np_ * l4 && (double)zer > np_ * l5) ++ok;  // lamb4, lamb5
         }
         if (ok == parts) { list |= mode << (3 * n); ++n; }
     }
@@ -252,8 +255,11 @@ __device__ __forceinline__ void expand(Search &s)
 // Four waves per block: the QT leaves under the four 32x32 quadrants are independent searches writing disjoint cells, so wave
 // w takes the nodes of quadrant w (a block that is one 64x64 leaf is searched by wave 0 alone).  Every wave keeps the whole
 // block's maps - the search code is the single-wave one - and has its own pairwise-sum scratch.
+// DEF: the reference's default thresholds as compile-time constants - the code the kernel had before the thresholds became arguments
+// (runtime doubles cost this already spilling kernel 7 more SGPRs and 11 more VGPRs of spill); !DEF: the call's own `prm`.
+template <bool DEF>
 __global__ __launch_bounds__(256, 4) void postprocess_kernel(const float *__restrict__ qt, const float *__restrict__ bt,
-                                                          const float *__restrict__ dire, int64_t N, int cf,
+                                                          const float *__restrict__ dire, int64_t N, int cf, M2PParams prm,
                                                           uint8_t *__restrict__ hor_o, uint8_t *__restrict__ ver_o,
                                                           uint8_t *__restrict__ qt_o, int8_t *__restrict__ dire_o,
                                                           int s_edge, int s_qt, int s_dire)   // bytes between consecutive blocks
@@ -311,6 +317,12 @@ __global__ __launch_bounds__(256, 4) void postprocess_kernel(const float *__rest
     s.row = lane >> 2;
     s.col0 = (lane & 3) << 2;
     s.cf = cf;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) s.lamb[i] = DEF ? M2P_DEFAULT.lamb[i] : prm.lamb[i];
+    // th_round(dire, thd) (Map2Partition.py:30-35) on float32: numpy compares against float32(thd).  Its third np.where zeroes what lies in
+    // (-thd, thd) AFTER the first two have written +-1, so for thd > 1 every direction ends up 0 (NaN never compares: 0 here, as before)
+    const float thd = DEF ? M2P_DEFAULT.thd : prm.thd;
+    const bool thd_keeps = !(1.f < thd);
     s.valb = valb;
     s.vald = vald;
 #pragma unroll
@@ -325,7 +337,7 @@ __global__ __launch_bounds__(256, 4) void postprocess_kernel(const float *__rest
             float r = rintf(fb[k]);                       // np.round: half to even
             r = !(r <= 100.f) ? 100.f : (r < -100.f ? -100.f : r);   // see Search::mb; NaN -> 100
             s.mb[k3][k] = (int)r;
-            s.md[k3][k] = fd[k] >= 0.5f ? 1 : (fd[k] <= -0.5f ? -1 : 0);
+            s.md[k3][k] = !thd_keeps ? 0 : (fd[k] >= thd ? 1 : (fd[k] <= -thd ? -1 : 0));
         }
     }
     if (wv == 0) { horw[lane] = 0; verw[lane] = 0; }
@@ -406,13 +418,18 @@ __global__ __launch_bounds__(256, 4) void postprocess_kernel(const float *__rest
 }
 
 hipError_t launch_postprocess(hipStream_t st, const float *qt, const float *bt, const float *dire, int64_t N,
-                              int chroma_factor, uint8_t *hor, uint8_t *ver, uint8_t *qt_u8, int8_t *dire_i8, int record_stride)
+                              int chroma_factor, const M2PParams &prm, uint8_t *hor, uint8_t *ver, uint8_t *qt_u8, int8_t *dire_i8,
+                              int record_stride)
 {
     if (N <= 0) return hipSuccess;
     // four dense arrays (strides 256 / 256 / 64 / 768 bytes per block), or one packed record per block (include/pmp.h)
     const int se = record_stride ? record_stride : 256, sq = record_stride ? record_stride : 64, sd = record_stride ? record_stride : 768;
-    hipLaunchKernelGGL(postprocess_kernel, dim3((unsigned)N), dim3(256), 0, st, qt, bt, dire, N, chroma_factor, hor, ver,
-                       qt_u8, dire_i8, se, sq, sd);
+    if (m2p_is_default(prm))
+        hipLaunchKernelGGL(postprocess_kernel<true>, dim3((unsigned)N), dim3(256), 0, st, qt, bt, dire, N, chroma_factor, prm, hor, ver,
+                           qt_u8, dire_i8, se, sq, sd);
+    else
+        hipLaunchKernelGGL(postprocess_kernel<false>, dim3((unsigned)N), dim3(256), 0, st, qt, bt, dire, N, chroma_factor, prm, hor, ver,
+                           qt_u8, dire_i8, se, sq, sd);
     return hipGetLastError();
 }
 

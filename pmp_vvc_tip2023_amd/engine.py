@@ -20,6 +20,8 @@ from . import _lib
 from . import weights as W
 
 COMP_ID = {"Luma": _lib.PMP_LUMA, "Chroma": _lib.PMP_CHROMA}
+PARAM_KEYS = ("lamb1", "lamb2", "lamb3", "lamb4", "lamb5", "thd")
+DEFAULT_PARTITION_PARAMS = {"lamb1": 0.7, "lamb2": 0.7, "lamb3": 1.5, "lamb4": 0.3, "lamb5": 0.7, "thd": 0.5}   # Map2Partition.py:100,105
 
 
 def _ptr(a):
@@ -119,6 +121,34 @@ class Engine:
     def synchronize(self):
         self._ck(self.lib.pmp_synchronize(self.h))
 
+    # ------------------------------------------------------------------------------------------ Map2Partition thresholds
+    def set_partition_params(self, comp, **kw):
+        """Thresholds of the post-processing search for `comp` (include/pmp.h: pmp_set_partition_params), named as in the reference:
+        lamb1..lamb5 (Map_to_Partition, Map2Partition.py:100) and thd (th_round, :105).  Keys not given keep their CURRENT value;
+        no keys at all restores the reference's defaults.  Outside the accepted domain: PmpError(PMP_E_INVALID), the old set stays.
+        Calls already enqueued keep the set they were enqueued with."""
+        if not kw:
+            self._ck(self.lib.pmp_set_partition_params(self.h, COMP_ID[comp], None))
+            return
+        p = self._params(comp)
+        for k, v in kw.items():
+            if k == "thd":
+                p.thd = float(v)
+            elif k in PARAM_KEYS[:5]:
+                p.lamb[PARAM_KEYS.index(k)] = float(v)
+            else:
+                raise TypeError("set_partition_params: unknown threshold %r (lamb1..lamb5, thd)" % k)
+        self._ck(self.lib.pmp_set_partition_params(self.h, COMP_ID[comp], C.byref(p)))
+
+    def get_partition_params(self, comp):
+        """{'lamb1': .., ..., 'lamb5': .., 'thd': ..} in force for `comp` (thd as stored: a float32 value)."""
+        return params_dict(self._params(comp))
+
+    def _params(self, comp):
+        p = _lib.PartitionParams()
+        self._ck(self.lib.pmp_get_partition_params(self.h, COMP_ID[comp], C.byref(p)))
+        return p
+
     # ------------------------------------------------------------------------------------------ weights
     def load_pretrain_model(self, net, qp, tensors):
         """net in {Luma_Q, Luma_MSBD, Chroma_Q, Chroma_MSBD}; tensors {state_dict name: float32 ndarray}."""
@@ -192,10 +222,21 @@ class Engine:
         self._ck(self.lib.pmp_postprocess(self.h, COMP_ID[comp], _ptr(qt), _ptr(bt), _ptr(dire), n, _ptr(hor), _ptr(ver), _ptr(q8), _ptr(d8)))
         return hor, ver, q8, d8
 
-    def seq_post_process(self, input_qt_batch, input_bt_batch, input_dire_batch, comp, sub_numfrm, width, height, save_path):
-        """Metrics.py:764-774: post-process every block of a sequence and write the PartitionMat file."""
+    def seq_post_process(self, input_qt_batch, input_bt_batch, input_dire_batch, comp, sub_numfrm, width, height, save_path,
+                         lamb1=None, lamb2=None, lamb3=None, lamb4=None, lamb5=None, thd=None):
+        """Metrics.py:764-774: post-process every block of a sequence and write the PartitionMat file.  lamb1..lamb5 / thd (optional):
+        Map_to_Partition's thresholds for this call only (see set_partition_params); the component's set is restored afterwards."""
         n_expected = int(sub_numfrm) * (int(height) // 64) * (int(width) // 64)
-        hor, ver, q8, d8 = self.post_process(input_qt_batch, input_bt_batch, input_dire_batch, comp)
+        kw = {k: v for k, v in zip(PARAM_KEYS, (lamb1, lamb2, lamb3, lamb4, lamb5, thd)) if v is not None}
+        if kw:
+            old = self._params(comp)
+            self.set_partition_params(comp, **kw)
+            try:
+                hor, ver, q8, d8 = self.post_process(input_qt_batch, input_bt_batch, input_dire_batch, comp)
+            finally:
+                self._ck(self.lib.pmp_set_partition_params(self.h, COMP_ID[comp], C.byref(old)))
+        else:
+            hor, ver, q8, d8 = self.post_process(input_qt_batch, input_bt_batch, input_dire_batch, comp)
         if hor.shape[0] != n_expected:
             raise ValueError("seq_post_process: %d blocks given, geometry needs %d" % (hor.shape[0], n_expected))
         if save_path is not None:
@@ -273,6 +314,25 @@ class Engine:
             if bu is None or bv is None or bu.shape != (n, 34, 34) or bv.shape != (n, 34, 34):
                 raise ValueError("Chroma needs block_u and block_v u8[N,34,34]")
         return n
+
+
+def params_dict(p):
+    d = {k: float(p.lamb[i]) for i, k in enumerate(PARAM_KEYS[:5])}
+    d["thd"] = float(p.thd)
+    return d
+
+
+def parse_partition_params(spec, base=None):
+    """'lamb1=0.6,thd=0.45' on top of `base` (a dict as get_partition_params returns; default: the reference's defaults) through the
+    library's host-only parser (pmp_parse_partition_params: same keys, same domain check); needs no GPU.  PmpError on bad text."""
+    lib = _lib.load()
+    b = dict(DEFAULT_PARTITION_PARAMS, **(base or {}))
+    p = _lib.PartitionParams()
+    for i, k in enumerate(PARAM_KEYS[:5]):
+        p.lamb[i] = b[k]
+    p.thd = b["thd"]
+    _lib.check(lib.pmp_parse_partition_params(str(spec).encode(), C.byref(p)))
+    return params_dict(p)
 
 
 def write_partition_file(path, frames, height, width, hor, ver, qt_u8, dire_i8):

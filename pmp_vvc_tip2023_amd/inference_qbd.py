@@ -157,6 +157,11 @@ def build_parser():
                         "two streams, so one chunk's small launches fill the gaps of the other's large ones; bit-identical files.  Opt-in "
                         "(round 6): it takes 0.2-1.7 %% off a bare 4096-block step but nothing off a whole job (8 x 4K frames, all eight "
                         "files: 1.702 s on, 1.701 s off, profiles/r05e_driver_bench.txt) and costs a second workspace")
+    p.add_argument("--m2p", default=None, metavar="SPEC",
+                   help="Map2Partition thresholds for both components, e.g. 'lamb1=0.6,thd=0.45' (keys lamb1..lamb5, thd; the rest keep "
+                        "the reference's 0.7,0.7,1.5,0.3,0.7 | 0.5; domain in include/pmp.h: pmp_partition_params)")
+    p.add_argument("--m2pChroma", default=None, metavar="SPEC",
+                   help="the same for chroma only, applied on top of --m2p")
     p.add_argument("--hostBlocks", action="store_true",
                    help="keep the cut blocks in host memory and upload them for every (component, QP) pass, as the reference "
                         "does; default: frames are uploaded once, cut on the GPU and the blocks stay device-resident")
@@ -277,6 +282,14 @@ class Stages:
 LAST_STAGES = None      # the Stages of the last inference_VVC_seqs() run in this process (tools/driver_bench.py reads it)
 
 
+def partition_params(args):
+    """--m2p / --m2pChroma -> {comp: thresholds} through the library's own parser (pmp_parse_partition_params); a bad spec is an
+    error before any GPU work."""
+    luma = E.parse_partition_params(args.m2p or "")
+    chroma = E.parse_partition_params(args.m2pChroma or "", luma)
+    return {"Luma": luma, "Chroma": chroma}
+
+
 def inference_VVC_seqs(args):
     """Inference_QBD.py:151-255."""
     global LAST_STAGES
@@ -295,7 +308,15 @@ def inference_VVC_seqs(args):
                                  "lets several ranks share a GPU, for smoke tests only)" % (rank, world, ndev))
             dev_id = local % max(ndev, 1)
     model_dir = resolve_model_dir(args.modelDir)
+    try:
+        m2p = partition_params(args)
+    except E._lib.PmpError as e:
+        raise SystemExit("--m2p / --m2pChroma: %s" % e)
     eng = E.Engine(dev_id, weight_dir=model_dir, allow_synthetic_mtt=args.allowSyntheticMTT)
+    for comp, prm in m2p.items():            # every rank: each one post-processes its own shard
+        eng.set_partition_params(comp, **prm)
+        if rank == 0 and prm != E.DEFAULT_PARTITION_PARAMS:
+            print("Map2Partition thresholds (%s): %s" % (comp, ", ".join("%s=%.9g" % kv for kv in prm.items())), file=sys.stderr, flush=True)
     # --batchSize is the reference's blocks-per-forward-pass (a GPU memory knob there).  Results do not depend on it (tested:
     # ragged chunks are bit-identical to one pass); small passes only leave most of an MI355X idle, so it is ignored unless
     # --strictBatch asks for it (clamped to the library's 4096-block pass; the reference accepts any value)

@@ -9,6 +9,7 @@
 //       reads the frames the encoder is going to code, runs cutter + nets + Map2Partition on the GPU
 //       (pmp_cut_blocks / pmp_infer_postprocess) and tiles the flags with pmp_tile_partition_maps - no file hop at all.
 //       Weights: <Comp>_{Q,BD}_<qp>.pmpw under $PMP_MODEL_DIR (default ./CTU_Models, the reference's place, Inference_QBD.py:219-220).
+//       Map2Partition thresholds: $PMP_M2P_PARAMS / $PMP_M2P_PARAMS_CHROMA, the driver's --m2p / --m2pChroma text.
 // Like the reference's parser it ends the process when it cannot deliver (EncAppCfg.cpp:4252-4263).
 //
 // Built by tools/vtm_build/CMakeLists.txt (-DPMP_HOOK=ON) into EncoderAppHook: the reference's App/EncoderApp sources, with
@@ -162,6 +163,15 @@ bool EncAppCfg::parsePartitionMatrix(int argc, char *argv[], int32_t &partitionR
         const bool wide = m_inputBitDepth[0] > 8;
         pmp_ctx *ctx = nullptr;
         ck(pmp_create(0, &ctx), nullptr, "pmp_create");
+        // Map2Partition thresholds (include/pmp.h: pmp_partition_params): $PMP_M2P_PARAMS for both components ("lamb1=0.6,thd=0.45"),
+        // $PMP_M2P_PARAMS_CHROMA on top of it for chroma; unset: the reference's defaults
+        pmp_partition_params prm;
+        ck(pmp_get_partition_params(ctx, PMP_LUMA, &prm), ctx, "pmp_get_partition_params");
+        const char *const m2p_env[2] = {"PMP_M2P_PARAMS", "PMP_M2P_PARAMS_CHROMA"};
+        for (int k = 0; k < 2; k++) {
+            if (const char *spec = getenv(m2p_env[k])) ck(pmp_parse_partition_params(spec, &prm), nullptr, m2p_env[k]);
+            ck(pmp_set_partition_params(ctx, k ? PMP_CHROMA : PMP_LUMA, &prm), ctx, "pmp_set_partition_params");
+        }
         std::vector<uint8_t> y, u, v;
         read_frames(m_inputFileName, m_iSourceWidth, m_iSourceHeight, F, (int)m_FrameSkip, (int)m_temporalSubsampleRatio, wide, y, u, v);
         const int64_t n = (int64_t)F * (ch / 64) * (cw / 64);
