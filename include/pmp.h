@@ -265,6 +265,59 @@ int pmp_cut_blocks_device(pmp_ctx *ctx, const void *d_y, const void *d_u, const 
                           int height, int width, int bitdepth, uint8_t *d_block_y, uint8_t *d_block_u,
                           uint8_t *d_block_v);
 
+/* ---- training labels: GenMSBtMap.gen_seq_sub_map (GenMSBtMap.py:434-449) = Map_to_SubMap(qt, bt, dire, cf).get_sub_map() per block
+ *      (:89-368), the per-layer MTT depth maps (MSBT) that Train_QBD fits the MSBD net to.  The candidate-tree search of Map2Partition
+ *      with other rules; one workgroup per block (labels.hip).  Inputs in CreateDataSet's dtypes, on which the reference's result
+ *      depends:
+ *        qt   u8[n][8][8]      VTM qtDepth - 1 as GenMSBtMap.main_process passes it (:477; a u8 subtraction, so 0 becomes 255);
+ *                              read at each QT node's top-left cell only (set_sub_map, :314-324)
+ *        bt   u8[n][16][16]    final MTT depth of each 4x4 cell
+ *        dire i8[n][3][16][16] per-layer direction, 1 horizontal, -1 vertical (other values count as neither)
+ *      Outputs: msbt u8[n][3][16][16] (the maps of the best leaf's depth-1 and depth-2 ancestors and of the leaf, :341-363) and
+ *      status u8[n].  cf = the chroma factor, 1 or 2 (the reference's main_process passes is_luma=True, i.e. cf 1, for BOTH components).
+ *      Rules (GenMSBtMap.py), reproduced bit for bit: lamb1..lamb5 = 0.8, 1.0, 1.2, 0.2, 0.2, counts compared with the float64 products
+ *      in Python's order ((lamb1*h)*w, num_pixel*(1 - lamb5) with 1 - 0.2 formed in float64); "no partition" compares the label bt with
+ *      the node's map; a direction map that does not dominate gives [0]; the candidate list starts empty and a CU with an empty list
+ *      leaves its node without children, so leaves can sit above depth 3; the leaf error np.sum(np.abs(leaf - bt)) subtracts two u8
+ *      maps and WRAPS: a leaf one level shallower than the label costs 255 per cell, not 1 (a root leaf's map is i8: it costs sum(bt));
+ *      the first minimum in DFS leaf order wins.  With bt held in a wider integer type the reference picks other labels for some
+ *      blocks: these results are the u8 ones.
+ *      Where the reference gives no usable answer, status bits (OR-ed over the block's QT regions; other regions are unaffected):
+ *        PMP_MSBT_INCONSISTENT  the best leaf of a region is shallower than depth 3 (the reference raises AttributeError, :342-349,
+ *                               ending the whole dataset run).  Carry-down: msbt[k] = the map of the ancestor at depth min(k+1, d),
+ *                               all zeros for d = 0.
+ *        PMP_MSBT_QT_DEEP       a qt value above 3 was reached at a depth-3 node: its region stays zero, which is what the reference
+ *                               produces for 4..~10 (it recurses on empty regions; for larger values practically forever).
+ *        PMP_MSBT_BUDGET        a region's candidate tree has more than PMP_MSBT_LEAF_BUDGET leaves: scoring stops at the first leaf
+ *                               beyond the budget and the best of the leaves scored so far, in the reference's order, is kept.  Valid
+ *                               partitions need at most a few dozen leaves; labels that admit every legal split give up to 2.7 M for a
+ *                               64x64 luma region.  A 1024-block launch of such blocks: profiles/msbt_labels.txt.
+ *      pmp_msbt_labels takes host pointers and runs in passes of at most pmp_set_chunk blocks; pmp_msbt_labels_device takes device
+ *      pointers (qt, bt, dire, msbt 4-byte aligned) and runs stream-ordered on the context's stream.  n = 0 does nothing. ---- */
+#define PMP_MSBT_LEAF_BUDGET 4096
+#define PMP_MSBT_INCONSISTENT 1
+#define PMP_MSBT_QT_DEEP 2
+#define PMP_MSBT_BUDGET 4
+int pmp_msbt_labels(pmp_ctx *ctx, int cf, const uint8_t *qt, const uint8_t *bt, const int8_t *dire, int64_t n, uint8_t *msbt,
+                    uint8_t *status);
+int pmp_msbt_labels_device(pmp_ctx *ctx, int cf, const uint8_t *d_qt, const uint8_t *d_bt, const int8_t *d_dire, int64_t n,
+                           uint8_t *d_msbt, uint8_t *d_status);
+
+/* ---- partition dump of the patched VTM decoder (Save_Depth_fal, Lib/DecoderLib/DecLib.cpp:998-1050) -> CreateDataSet's label blocks
+ *      (CreateDataSet.output_block_partition_map, CreateDataSet.py:188-264).  Host only: no context, no GPU.
+ *      Lines "x y h w depth qtDepth btDepth mtDepth s0 .. s7" (non-negative decimal integers separated by single spaces, trailing
+ *      whitespace allowed), and a line containing "frame" before each frame.  Split codes (UnitPartitioner.h): 2 BT-H, 3 BT-V, 4 TT-H,
+ *      5 TT-V, 2000 none.  is_chroma multiplies the coordinates by 2.  Each CU paints qtDepth, btDepth and, per layer i = 0..2, the
+ *      direction of s[qtDepth + i] into frame matrices of 4x4-pixel cells [frames][height/4][width/4], with numpy's clipping slices; an
+ *      unknown split code keeps the PREVIOUS layer's direction (0 for layer 0) and is counted in *n_unknown (the reference prints
+ *      "Error!!").  The QT matrix is down-sampled [::2, ::2].  Blocks are cut frame-major, row-major, right and bottom remainders dropped:
+ *      n = frames * (height/64) * (width/64) blocks of qt8 u8[n][8][8] (raw qtDepth), bt16 u8[n][16][16], dire16 i8[n][3][16][16].
+ *      PMP_E_INVALID, nothing written, where the reference would index wrongly or crash: more "frame" lines than frames, a CU line before
+ *      the first one, a malformed line (wrong field count, a non-integer or negative field, qtDepth > 5: s[qtDepth + 2] must exist),
+ *      a qtDepth or btDepth outside u8.  PMP_E_IO if the file cannot be read. ---- */
+int pmp_read_depth_dump(const char *path, int frames, int height, int width, int is_chroma, uint8_t *qt8, uint8_t *bt16,
+                        int8_t *dire16, int64_t *n_unknown);
+
 /* ---- PartitionMat text file (Map2Partition.py:385-412): per frame hor, ver, qt, dire[3]; one decimal
  *      integer per line.  Host-side (file I/O); inputs are per-block arrays in block order. ---------------- */
 int pmp_write_partition_file(const char *path, int frames, int height, int width, const uint8_t *hor,

@@ -863,6 +863,63 @@ int pmp_cut_blocks(pmp_ctx *c, const void *y, const void *u, const void *v, int 
     return sync(c);
 }
 
+// ---- training labels: GenMSBtMap (labels.hip) --------------------------------------------------------------------------
+static int msbt_args(pmp_ctx *c, int cf, const void *qt, const void *bt, const void *dire, int64_t n, const void *msbt, const void *status)
+{
+    if (cf != 1 && cf != 2) return set_err(c, PMP_E_INVALID, "pmp_msbt_labels: cf must be 1 or 2");
+    if (n < 0) return set_err(c, PMP_E_INVALID, "pmp_msbt_labels: negative count");
+    if (n > 0 && (!qt || !bt || !dire || !msbt || !status)) return set_err(c, PMP_E_INVALID, "pmp_msbt_labels: null buffer");
+    return PMP_OK;
+}
+
+int pmp_msbt_labels_device(pmp_ctx *c, int cf, const uint8_t *qt, const uint8_t *bt, const int8_t *dire, int64_t n, uint8_t *msbt,
+                           uint8_t *status)
+{
+    CHECK_CTX(c);
+    int rc;
+    if ((rc = msbt_args(c, cf, qt, bt, dire, n, msbt, status))) return rc;
+    if (n == 0) return PMP_OK;
+    if (((uintptr_t)qt | (uintptr_t)bt | (uintptr_t)dire | (uintptr_t)msbt) & 3)
+        return set_err(c, PMP_E_INVALID, "pmp_msbt_labels_device: qt, bt, dire and msbt must be 4-byte aligned");
+    const hipError_t e = launch_msbt_labels(c->stream, qt, bt, dire, n, cf, msbt, status);
+    return e == hipSuccess ? PMP_OK : hip_fail(c, e, "msbt_labels");
+}
+
+int pmp_msbt_labels(pmp_ctx *c, int cf, const uint8_t *qt, const uint8_t *bt, const int8_t *dire, int64_t n, uint8_t *msbt,
+                    uint8_t *status)
+{
+    CHECK_CTX(c);
+    int rc;
+    if ((rc = msbt_args(c, cf, qt, bt, dire, n, msbt, status))) return rc;
+    if (n == 0) return PMP_OK;
+    if ((rc = settle_before_host_call(c))) return rc;
+    // passes of at most `chunk` blocks through the context's own staging buffers (about 1.9 kB per block)
+    const int64_t chunk = c->chunk;
+    const int64_t m0 = n < chunk ? n : chunk;
+    const size_t per[5] = {64, 256, 768, 768, 1};
+    for (int i = 0; i < 5; ++i)
+        if ((rc = ensure(c, c->d_lab[i], (size_t)m0 * per[i]))) return rc;
+    for (int64_t o = 0; o < n; o += chunk) {
+        const int64_t m = (n - o) < chunk ? (n - o) : chunk;
+        if (c->poison) {          // pmp_debug_poison_workspace: the kernel must write every output byte it hands back
+            for (int i = 3; i < 5; ++i) {
+                const hipError_t e = hipMemsetAsync(c->d_lab[i].p, c->poison == 1 ? 0xFF : 0x3C, (size_t)m * per[i], c->stream);
+                if (e != hipSuccess) return hip_fail(c, e, "poison label buffers");
+            }
+        }
+        if ((rc = h2d(c, c->d_lab[0], qt + o * 64, (size_t)m * 64)) || (rc = h2d(c, c->d_lab[1], bt + o * 256, (size_t)m * 256)) ||
+            (rc = h2d(c, c->d_lab[2], dire + o * 768, (size_t)m * 768)))
+            return rc;
+        const hipError_t e = launch_msbt_labels(c->stream, (const uint8_t *)c->d_lab[0].p, (const uint8_t *)c->d_lab[1].p,
+                                                (const int8_t *)c->d_lab[2].p, m, cf, (uint8_t *)c->d_lab[3].p, (uint8_t *)c->d_lab[4].p);
+        if (e != hipSuccess) return hip_fail(c, e, "msbt_labels");
+        if ((rc = d2h(c, msbt + o * 768, c->d_lab[3].p, (size_t)m * 768)) || (rc = d2h(c, status + o, c->d_lab[4].p, (size_t)m)))
+            return rc;
+        if ((rc = sync(c))) return rc;   // the next pass reuses the staging buffers
+    }
+    return PMP_OK;
+}
+
 int pmp_debug_set_conv_variant(int variant)
 {
     int rc;

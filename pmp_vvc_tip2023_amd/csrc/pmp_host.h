@@ -167,6 +167,7 @@ struct pmp_ctx {
     int overlap = 0;                       // two chunks in flight on two streams (PMP_OVERLAP=1 in the environment at pmp_create)
     size_t ws_need = 0;                    // what the largest pass so far needed of it (pmp_get_workspace_bytes)
     pmp::DevBuf d_in[3], d_logit[3], d_out[4], d_frames[3];  // staging for the host-pointer entry points
+    pmp::DevBuf d_lab[5];                  // staging of pmp_msbt_labels: qt, bt, dire in; msbt, status out
     // calibration of the f16x3 activation scales (NetWeights::act_exp): while cal_on, the graph (nets.cpp, running on the fp32 datapath) folds
     // the largest |value| of every tensor it produces into d_cal[slot] and logs (name, segment) per slot
     int cal_on = 0;

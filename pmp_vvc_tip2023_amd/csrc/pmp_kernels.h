@@ -181,6 +181,10 @@ inline bool m2p_is_default(const M2PParams &p)
 hipError_t launch_postprocess(hipStream_t s, const float *qt, const float *bt, const float *dire, int64_t N, int chroma_factor,
                               const M2PParams &prm, uint8_t *hor, uint8_t *ver, uint8_t *qt_u8, int8_t *dire_i8, int record_stride = 0);
 
+// GenMSBtMap (labels.hip): qt u8[N][64], bt u8[N][256], dire i8[N][3][256] -> msbt u8[N][3][256], status u8[N] (include/pmp.h: pmp_msbt_labels).
+hipError_t launch_msbt_labels(hipStream_t s, const uint8_t *qt, const uint8_t *bt, const int8_t *dire, int64_t N, int chroma_factor,
+                              uint8_t *msbt, uint8_t *status);
+
 // Block cutter (Inference_QBD.py:104-149).
 hipError_t launch_cut_blocks(hipStream_t s, const void *y, const void *u, const void *v, int F, int H, int W,
                              int bitdepth, uint8_t *by, uint8_t *bu, uint8_t *bv);

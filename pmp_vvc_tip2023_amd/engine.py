@@ -7,6 +7,8 @@ Same names and argument meaning as the reference so callers (and the parity test
     Metrics.seq_post_process(qt, bt, dire, comp, ...)   Engine.seq_post_process(qt, bt, dire, comp, sub_numfrm, width, height, save_path)
     Inference_QBD.output_block_yuv(...)                 Engine.output_block_yuv(y, u, v, bitdepth)
     Inference_QBD.load_pretrain_model(net, path)        Engine.load_pretrain_model(net_name, qp, weights)
+    GenMSBtMap.gen_seq_sub_map(qt, bt, dire, is_luma)   Engine.gen_seq_sub_map(qt, bt, dire, is_luma)   (training labels)
+    CreateDataSet.output_block_partition_map(...)       output_block_partition_map(...)                 (module level, host only)
 
 numpy arrays in/out for the host API; the *_device methods take raw device pointers (ints), e.g. torch
 tensors' .data_ptr(), and run asynchronously on the engine's stream.  There is no CPU fallback: constructing an
@@ -268,6 +270,31 @@ class Engine:
         self._ck(self.lib.pmp_cut_blocks(self.h, _ptr(y), _ptr(u), _ptr(v), F, H, Wd, int(bitdepth), _ptr(by), _ptr(bu), _ptr(bv)))
         return by, bu, bv
 
+    # ------------------------------------------------------------------------------------------ training labels
+    def gen_seq_sub_map(self, qt_map, bt_map, dire_map, is_luma, return_status=False):
+        """GenMSBtMap.gen_seq_sub_map (GenMSBtMap.py:434-449): qt_map [N,8,8] (qtDepth - 1), bt_map [N,16,16], dire_map [N,3,16,16]
+        -> msbt u8[N,3,16,16] (and status u8[N], include/pmp.h: pmp_msbt_labels, with return_status).  is_luma picks the chroma factor
+        as the reference does (1, else 2).  Values must fit the reference's dtypes (u8, u8, i8): anything else is refused, not wrapped."""
+        qt = _fit(qt_map, np.uint8, "qt_map"); bt = _fit(bt_map, np.uint8, "bt_map"); dire = _fit(dire_map, np.int8, "dire_map")
+        n = qt.size // 64
+        if qt.size != n * 64 or bt.size != n * 256 or dire.size != n * 768:
+            raise ValueError("gen_seq_sub_map: expected qt_map[N,8,8], bt_map[N,16,16], dire_map[N,3,16,16]")
+        msbt = np.empty((n, 3, 16, 16), np.uint8); st = np.empty(n, np.uint8)
+        self._ck(self.lib.pmp_msbt_labels(self.h, 1 if is_luma else 2, _ptr(qt), _ptr(bt), _ptr(dire), n, _ptr(msbt), _ptr(st)))
+        return (msbt, st) if return_status else msbt
+
+    def getSubMap(self, qt_map, bt_map, dire_map, chroma_factor, return_status=False):
+        """GenMSBtMap.getSubMap (:370-375) for one block: qt_map [8,8], bt_map [16,16], dire_map [3,16,16] -> u8[3,16,16]."""
+        if chroma_factor not in (1, 2):
+            raise ValueError("getSubMap: chroma_factor must be 1 or 2")
+        m, st = self.gen_seq_sub_map(np.reshape(qt_map, (1, 8, 8)), np.reshape(bt_map, (1, 16, 16)), np.reshape(dire_map, (1, 3, 16, 16)),
+                                     chroma_factor == 1, return_status=True)
+        return (m[0], int(st[0])) if return_status else m[0]
+
+    def msbt_labels_device(self, cf, d_qt, d_bt, d_dire, n, d_msbt, d_status):
+        """pmp_msbt_labels_device: device pointers (u8 qt, u8 bt, i8 dire in; u8 msbt, u8 status out), stream-ordered."""
+        self._ck(self.lib.pmp_msbt_labels_device(self.h, int(cf), d_qt, d_bt, d_dire, int(n), d_msbt, d_status))
+
     # ------------------------------------------------------------------------------------------ device API
     def infer_device(self, comp, qp, d_by, d_bu, d_bv, n, d_qt, d_bt, d_dire):
         self._ck(self.lib.pmp_infer_device(self.h, COMP_ID[comp], int(qp), d_by, d_bu, d_bv, int(n), d_qt, d_bt, d_dire))
@@ -314,6 +341,36 @@ class Engine:
             if bu is None or bv is None or bu.shape != (n, 34, 34) or bv.shape != (n, 34, 34):
                 raise ValueError("Chroma needs block_u and block_v u8[N,34,34]")
         return n
+
+
+def _fit(a, dtype, name):
+    """a as a contiguous array of `dtype` if every value fits it exactly (the reference's label dtypes); ValueError otherwise."""
+    a = np.asarray(a)
+    if a.dtype == dtype:
+        return np.ascontiguousarray(a)
+    info = np.iinfo(dtype)
+    if a.dtype.kind not in "biuf":
+        raise ValueError("%s: numeric array expected, got %s" % (name, a.dtype))
+    if a.size and (a.dtype.kind == "f" and not np.all(np.isfinite(a) & (a == np.round(a)))
+                   or a.min() < info.min or a.max() > info.max):
+        raise ValueError("%s: values outside %s (the reference's dtype); refusing to wrap them" % (name, np.dtype(dtype).name))
+    return np.ascontiguousarray(a.astype(dtype))
+
+
+def output_block_partition_map(file_path, frm_width, frm_height, frm_num, block_size=64, isChroma=False, return_unknown=False):
+    """CreateDataSet.output_block_partition_map (CreateDataSet.py:188-264) through the host-only C parser (pmp_read_depth_dump; no GPU):
+    the Save_Depth_fal dump of the patched VTM decoder -> qtdepth_block u8[n,8,8] (raw qtDepth), btdepth_block u8[n,16,16],
+    msdirection_block i8[n,3,16,16], n = frm_num * (frm_height // 64) * (frm_width // 64).  return_unknown: also the number of unknown
+    split codes (the reference prints "Error!!" for each).  PmpError(PMP_E_INVALID) where the reference would index wrongly or crash."""
+    if int(block_size) != 64:
+        raise ValueError("output_block_partition_map: block_size must be 64 (the nets' block)")
+    lib = _lib.load()
+    F, H, Wd = int(frm_num), int(frm_height), int(frm_width)
+    n = max(F, 0) * (max(H, 0) // 64) * (max(Wd, 0) // 64)
+    q = np.empty((n, 8, 8), np.uint8); b = np.empty((n, 16, 16), np.uint8); d = np.empty((n, 3, 16, 16), np.int8)
+    unk = C.c_int64(0)
+    _lib.check(lib.pmp_read_depth_dump(str(file_path).encode(), F, H, Wd, int(bool(isChroma)), _ptr(q), _ptr(b), _ptr(d), C.byref(unk)))
+    return (q, b, d, unk.value) if return_unknown else (q, b, d)
 
 
 def params_dict(p):
