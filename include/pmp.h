@@ -303,6 +303,70 @@ int pmp_msbt_labels(pmp_ctx *ctx, int cf, const uint8_t *qt, const uint8_t *bt, 
 int pmp_msbt_labels_device(pmp_ctx *ctx, int cf, const uint8_t *d_qt, const uint8_t *d_bt, const int8_t *d_dire, int64_t n,
                            uint8_t *d_msbt, uint8_t *d_status);
 
+/* ---- validation: how well does a pair of nets predict what VTM decided.  The arithmetic of Metrics.validation_QBD (Metrics.py:313-385),
+ *      Metrics.pre_validation predID 0 / 1 (:196-274) and the losses under them (loss_func_QBD_val, loss_func_MSBD_val, weight_mat,
+ *      :148-194) for ONE batch of n blocks (valstats.hip).  Logits in the library's layouts - qt f32[n][8][8], bt, dire f32[n][3][16][16]
+ *      (layer k = the reference's bd_out_batchK[:, 0] / [:, 1]) - against labels in the dtypes of the label files (gen_labels):
+ *        qt8    u8[n][8][8]       RAW qtDepth as saved (<..>_QTdepth_Block8.npy)
+ *        msbt   u8[n][3][16][16]  (<..>_MSBTdepth_Block16.npy)
+ *        msdire i8[n][3][16][16]  (<..>_MSdirection_Block16.npy)
+ *      converted as the reference's loader converts them (Metrics.py:127-135): bl = float(msbt), dl = float(msdire) and
+ *      ql = float(qt8 - 1) where the subtraction is numpy's ON THE u8 ARRAY: a raw qtDepth of 0 becomes 255.0, not -1.0 (the quirk
+ *      pmp_msbt_labels documents for its qt input).  Reproduced, not "fixed".
+ *      The twenty numbers (elements = how many terms a sum or count runs over):
+ *        S[0]       sum |qt - ql|                                                        64 n
+ *        S[1..3]    sum |bt_k - bl_k|,  k = 0..2                                         256 n each
+ *        S[4..6]    sum |dire_k - dl_k|                                                  256 n each
+ *        S[7..9]    sum |w_k*dire_k - w_k*dl_k|                                          256 n each
+ *        S[10]      sum |w_0*bt_0 - w_0*bl_0|                                            256 n
+ *        S[11,12]   sum |w_k*(bt_k - bt_{k-1}) - w_k*(bl_k - bl_{k-1})|,  k = 1, 2        256 n each
+ *        S[13]      #(round(qt) == ql)                                                   64 n
+ *        S[14..16]  #(round(bt_k) == bl_k)                                               256 n each
+ *        S[17..19]  #(round(dire_k) == dl_k)                                             256 n each
+ *      with w_k = dl_k*dl_k + float32(weight_mat[int((qp - 22) / 5)][k]), weight_mat = 0.5 * {{1.0, 0.73, 0.15}, {2.43, 0.35, 0.10},
+ *      {0.96, 0.23, 0.07}, {0.59, 0.16, 0.05}} (Metrics.py:148-151), and w_0 = 1.0 when qp == 22 (:180-181).  22 <= qp <= 41 (rows 0..3),
+ *      PMP_E_INVALID otherwise.  From them, per batch: an L1 loss is S / elements, an accuracy hits / elements, and
+ *        loss_func_QBD_val  = S0/(64n) + (0.8 S1 + 1.0 S2 + 1.2 S3 + S7 + S8 + S9 + 0.5 (S10 + S11 + S12)) / (256n)
+ *        loss_func_MSBD_val = the same without S0/(64n).
+ *      TERMS: every per-element term is computed as torch computes it - float32 operations in the reference's order (w*out, w*label,
+ *      the subtraction, abs; for S[11], S[12] the two differences first), no fused multiply-add, the float64 weight_mat entry rounded
+ *      to float32 before the add.  round is torch.round: half to even.  A NaN logit is never a hit; NaN / inf logits give NaN / inf sums
+ *      as torch does; nothing is clamped.
+ *      DETERMINISM: the sums are float64, added in a fixed order that depends on n only - one wavefront per block (lane partials in cell
+ *      order, a fixed butterfly over the 64 lanes), per-block partials f64[n][20], then one workgroup that adds them in a fixed order.
+ *      No atomics.  The same inputs give the same bits on every run, stream, context and chunk setting of pmp_val_stats_device; the seven
+ *      counts are integers and exact (stored as float64).  Against the reference's float32 batch means the sums differ by the reference's
+ *      own float32 summation error (about 1e-7 relative on 200-block batches; tests/golden/g12_val.npz records the measured distance).
+ *      FORMS: bt, dire, msbt, msdire all NULL = QT only (pre_validation predID 0): S[0] and S[13] filled, the rest 0.  qt and qt8 both
+ *      NULL = MTT only: S[0] = S[13] = 0.  Any other NULL mix, n < 0 or a NULL stats: PMP_E_INVALID.  n = 0: twenty zeros, no launch.
+ *      pmp_val_stats_device: device pointers (bt, dire 16-byte aligned, msbt, msdire 4-byte aligned: PMP_E_INVALID otherwise), stream-ordered
+ *      on the context's stream, the host does not wait.  d_block_stats (may be NULL): the per-block partials f64[n][20] as an OUTPUT - the
+ *      twenty numbers of each block on its own (hit counts as float64), which is where one looks for the blocks a net gets wrong; d_stats
+ *      is their fixed-order sum.  RANGE GUARD: the logits may come from a pmp_infer*_device call whose range flag has not been looked at
+ *      yet.  Like a post-processing call, a statistics call enqueued behind such a call is REPLAYED, in order, if that call is re-run: once
+ *      pmp_synchronize has returned, d_stats and d_block_stats are those of the FINAL logits (and equal, bit for bit, what a second call
+ *      made after the synchronize gives).  Synchronising the stream yourself is enough only if you know the flag stayed down; logits,
+ *      labels and outputs must stay untouched until then.
+ *      pmp_val_stats: host pointers; runs in passes of at most pmp_set_chunk blocks through staging buffers and returns the statistics of
+ *      the WHOLE call as one batch: the pass results added in pass order in float64.  Its bits therefore depend on the chunk setting (the
+ *      order of the float64 additions does); the counts never do. ---- */
+#define PMP_VAL_NSTATS 20
+int pmp_val_stats(pmp_ctx *ctx, int qp, const float *qt, const float *bt, const float *dire, const uint8_t *qt8, const uint8_t *msbt,
+                  const int8_t *msdire, int64_t n, double stats[PMP_VAL_NSTATS]);
+int pmp_val_stats_device(pmp_ctx *ctx, int qp, const float *d_qt, const float *d_bt, const float *d_dire, const uint8_t *d_qt8,
+                         const uint8_t *d_msbt, const int8_t *d_msdire, int64_t n, double *d_stats, double *d_block_stats);
+
+/* ---- teacher-forced MTT inference: the MTT net of (comp, qp) on the blocks with a GIVEN QT map instead of the QT net's output, what
+ *      pre_validation predID 1 runs (Net(input_batch, qt_label_batch), Metrics.py:226).  qt_in f32[n][8][8] is read, never written
+ *      (for the reference's validation: float(qt8 - 1) with the u8 wrap above).  Everything else is pmp_infer's: the context's datapath,
+ *      overlap mode, chunking, the range guard (a re-run repeats the MTT net only, on the fp32 MFMA datapath) and the f16x3 activation
+ *      scales - which belong to the (QT, MTT) PAIR, so both nets of (comp, qp) must be loaded (PMP_E_NOWEIGHTS otherwise).  With qt_in =
+ *      the QT logits pmp_infer returns, bt and dire are pmp_infer's, bit for bit. ---- */
+int pmp_infer_msbd(pmp_ctx *ctx, int comp, int qp, const uint8_t *block_y, const uint8_t *block_u, const uint8_t *block_v,
+                   const float *qt_in, int64_t n, float *bt, float *dire);
+int pmp_infer_msbd_device(pmp_ctx *ctx, int comp, int qp, const uint8_t *d_block_y, const uint8_t *d_block_u, const uint8_t *d_block_v,
+                          const float *d_qt_in, int64_t n, float *d_bt, float *d_dire);
+
 /* ---- partition dump of the patched VTM decoder (Save_Depth_fal, Lib/DecoderLib/DecLib.cpp:998-1050) -> CreateDataSet's label blocks
  *      (CreateDataSet.output_block_partition_map, CreateDataSet.py:188-264).  Host only: no context, no GPU.
  *      Lines "x y h w depth qtDepth btDepth mtDepth s0 .. s7" (non-negative decimal integers separated by single spaces, trailing

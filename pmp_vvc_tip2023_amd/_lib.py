@@ -10,6 +10,7 @@ HOSTASAN_LIB_PATH = os.path.join(_HERE, "libpmp_hostasan.so")      # make hostas
 PMP_LUMA, PMP_CHROMA = 0, 1
 PMP_RECORD_BYTES = 1344
 PMP_MSBT_LEAF_BUDGET = 4096
+PMP_VAL_NSTATS = 20
 PMP_MSBT_INCONSISTENT, PMP_MSBT_QT_DEEP, PMP_MSBT_BUDGET = 1, 2, 4
 NET_IDS = {"Luma_Q": 0, "Luma_MSBD": 1, "Chroma_Q": 2, "Chroma_MSBD": 3}
 ERRORS = {-1: "PMP_E_INVALID", -2: "PMP_E_HIP", -3: "PMP_E_NOWEIGHTS", -4: "PMP_E_IO", -5: "PMP_E_NOMEM", -6: "PMP_E_NODEVICE", -7: "PMP_E_RANGE"}
@@ -70,6 +71,10 @@ SIGNATURES = {
     "pmp_cut_blocks_device": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP]),
     "pmp_msbt_labels": (_I, [_VP, _I, _VP, _VP, _VP, _I64, _VP, _VP]),
     "pmp_msbt_labels_device": (_I, [_VP, _I, _VP, _VP, _VP, _I64, _VP, _VP]),
+    "pmp_val_stats": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
+    "pmp_val_stats_device": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
+    "pmp_infer_msbd": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
+    "pmp_infer_msbd_device": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
     "pmp_read_depth_dump": (_I, [C.c_char_p, _I, _I, _I, _I, _VP, _VP, _VP, C.POINTER(_I64)]),
     "pmp_write_partition_file": (_I, [C.c_char_p, _I, _I, _I, _VP, _VP, _VP, _VP]),
     "pmp_write_partition_binary": (_I, [C.c_char_p, _I, _I, _I, _VP, _VP, _VP, _VP]),

@@ -153,8 +153,9 @@ static int run_graph(pmp_ctx *c, F &&fwd)
 int run_graph_fn(pmp_ctx *c, const std::function<int()> &fwd) { return run_graph(c, fwd); }   // for calibrate.cpp
 
 static int infer_passes(pmp_ctx *c, bool luma, NetWeights &wq, NetWeights &wb, const uint8_t *by, const uint8_t *bu,
-                        const uint8_t *bv, int64_t n, float *qt, float *bt, float *dire)
+                        const uint8_t *bv, int64_t n, float *qt, float *bt, float *dire, const float *qt_in = nullptr)
 {
+    // qt_in: teacher-forced MTT inference (pmp_infer_msbd) - the MTT net reads this map, the QT net does not run, qt is not written
     int rc0;     // weights are packed per datapath, on first use (the load packed the datapath that was current then)
     if ((rc0 = ensure_datapath(c, wq, c->precision)) != PMP_OK || (rc0 = ensure_datapath(c, wb, c->precision)) != PMP_OK) return rc0;
     // f16x3: the MTT net's activation scales, from one calibration pass when the net is first used on this datapath
@@ -181,11 +182,12 @@ static int infer_passes(pmp_ctx *c, bool luma, NetWeights &wq, NetWeights &wb, c
         const int m = (int)((n - o) < chunk ? (n - o) : chunk);
         const uint8_t *y = by + o * 68 * 68;
         const uint8_t *u = bu ? bu + o * 34 * 34 : nullptr, *v = bv ? bv + o * 34 * 34 : nullptr;
-        float *q = qt + o * 64;
+        float *q = qt_in ? nullptr : qt + o * 64;
+        const float *qi = qt_in ? qt_in + o * 64 : q;
         const bool side = overlap && (k & 1);
         if (side) { c->stream = c->stream2; std::swap(c->ws, c->ws2); }
-        rc = run_graph(c, [&] { return forward_q(c, luma, wq, y, u, v, m, q); });
-        if (rc == PMP_OK) rc = run_graph(c, [&] { return forward_msbd(c, luma, wb, y, u, v, q, m, bt + o * 768, dire + o * 768); });
+        if (!qt_in) rc = run_graph(c, [&] { return forward_q(c, luma, wq, y, u, v, m, q); });
+        if (rc == PMP_OK) rc = run_graph(c, [&] { return forward_msbd(c, luma, wb, y, u, v, qi, m, bt + o * 768, dire + o * 768); });
         if (side) { c->stream = main_stream; std::swap(c->ws, c->ws2); }
     }
     if (overlap) {
@@ -272,10 +274,10 @@ static int resolve_pending(pmp_ctx *c, bool wait)
 }
 
 static int infer_device_impl(pmp_ctx *c, int comp, int qp, const uint8_t *by, const uint8_t *bu, const uint8_t *bv,
-                             int64_t n, float *qt, float *bt, float *dire, bool ctx_logits = false)
+                             int64_t n, float *qt, float *bt, float *dire, bool ctx_logits = false, const float *qt_in = nullptr)
 {
     if (comp != PMP_LUMA && comp != PMP_CHROMA) return set_err(c, PMP_E_INVALID, "pmp_infer: comp must be PMP_LUMA or PMP_CHROMA");
-    if (n < 0 || !by || !qt || !bt || !dire || (comp == PMP_CHROMA && (!bu || !bv)))
+    if (n < 0 || !by || (!qt && !qt_in) || !bt || !dire || (comp == PMP_CHROMA && (!bu || !bv)))
         return set_err(c, PMP_E_INVALID, "pmp_infer: null buffer or negative count");
     const bool luma = comp == PMP_LUMA;
     const int id_q = luma ? PMP_NET_LUMA_Q : PMP_NET_CHROMA_Q, id_b = luma ? PMP_NET_LUMA_MSBD : PMP_NET_CHROMA_MSBD;
@@ -287,7 +289,7 @@ static int infer_device_impl(pmp_ctx *c, int comp, int qp, const uint8_t *by, co
     int rc = resolve_pending(c, false);          // earlier calls whose snapshot has landed by now: no wait
     if (rc != PMP_OK) return rc;
     if (c->taps_on) c->ntaps = 0;                // the taps are this call's (a re-run resolved above is recorded by nobody)
-    rc = infer_passes(c, luma, *wq, *wb, by, bu, bv, n, qt, bt, dire);
+    rc = infer_passes(c, luma, *wq, *wb, by, bu, bv, n, qt, bt, dire, qt_in);
     if (rc != PMP_OK || c->precision != PMP_PRECISION_F16X3 || c->sat_policy == PMP_SAT_IGNORE || n == 0) return rc;
     // f16x3 range guard: snapshot the flag behind this call's passes and reset it for the next call - all stream-ordered, the host
     // does not wait.  Whoever looks at the snapshot later (resolve_pending) re-runs the call on the fp32 MFMA datapath if it fired.
@@ -308,7 +310,7 @@ static int infer_device_impl(pmp_ctx *c, int comp, int qp, const uint8_t *by, co
         // overwritten - the same call again, on the datapath it ran on.
         if (fired) c->precision = PMP_PRECISION_F32;
         c->tap_skip = 1;          // pmp_debug_set_taps records the call as it first ran, not its re-run
-        const int r2 = infer_passes(c, luma, *rq, *rb, by, bu, bv, n, qt, bt, dire);
+        const int r2 = infer_passes(c, luma, *rq, *rb, by, bu, bv, n, qt, bt, dire, qt_in);   // teacher-forced: the MTT net only
         c->tap_skip = 0;
         c->precision = PMP_PRECISION_F16X3;
         return r2;
@@ -485,7 +487,9 @@ int pmp_destroy(pmp_ctx *c)
     park_workspace(c->device, c->ws);
     park_workspace(c->device, c->ws2);
     DevBuf *bufs[] = {&c->ws, &c->ws2, &c->d_in[0], &c->d_in[1], &c->d_in[2], &c->d_logit[0], &c->d_logit[1], &c->d_logit[2],
-                      &c->d_out[0], &c->d_out[1], &c->d_out[2], &c->d_out[3], &c->d_frames[0], &c->d_frames[1], &c->d_frames[2]};
+                      &c->d_out[0], &c->d_out[1], &c->d_out[2], &c->d_out[3], &c->d_frames[0], &c->d_frames[1], &c->d_frames[2],
+                      &c->d_lab[0], &c->d_lab[1], &c->d_lab[2], &c->d_lab[3], &c->d_lab[4], &c->d_val[0], &c->d_val[1], &c->d_val[2],
+                      &c->d_val[3], &c->d_val[4], &c->d_val[5], &c->d_valpart, &c->d_valout};
     for (DevBuf *b : bufs) if (b->p) hipFree(b->p);
     for (TapRec &t : c->taps) if (t.buf.p) hipFree(t.buf.p);
     if (c->d_sat) hipFree(c->d_sat);
@@ -918,6 +922,142 @@ int pmp_msbt_labels(pmp_ctx *c, int cf, const uint8_t *qt, const uint8_t *bt, co
         if ((rc = sync(c))) return rc;   // the next pass reuses the staging buffers
     }
     return PMP_OK;
+}
+
+// ---- validation statistics (valstats.hip) and teacher-forced MTT inference ------------------------------------------------
+namespace {
+struct ValArgs {
+    const float *qt, *bt, *dire;
+    const uint8_t *qt8, *msbt;
+    const int8_t *msdire;
+    int64_t n;
+    float wm[3];
+    int w0_one;
+    double *stats, *block_stats;       // block_stats null: the context's scratch, looked up at launch (a replay may find it regrown)
+};
+}  // namespace
+
+static int val_check(pmp_ctx *c, int qp, const void *qt, const void *bt, const void *dire, const void *qt8, const void *msbt,
+                     const void *msdire, int64_t n, const void *stats, float wm[3], int *w0_one)
+{
+    // Metrics.py:148-151; the float64 entry becomes a float32 scalar when torch adds it to the float32 dl*dl
+    static const double weight_mat[4][3] = {{0.5 * 1.0, 0.5 * 0.73, 0.5 * 0.15}, {0.5 * 2.43, 0.5 * 0.35, 0.5 * 0.10},
+                                            {0.5 * 0.96, 0.5 * 0.23, 0.5 * 0.07}, {0.5 * 0.59, 0.5 * 0.16, 0.5 * 0.05}};
+    if (qp < 22 || qp > 41) return set_err(c, PMP_E_INVALID, "pmp_val_stats: qp must be in 22..41 (rows 0..3 of weight_mat)");
+    if (n < 0 || !stats) return set_err(c, PMP_E_INVALID, "pmp_val_stats: negative count or null stats");
+    const bool q = qt && qt8, noq = !qt && !qt8, m = bt && dire && msbt && msdire, nom = !bt && !dire && !msbt && !msdire;
+    if (n > 0 && !((q && m) || (q && nom) || (noq && m)))
+        return set_err(c, PMP_E_INVALID, "pmp_val_stats: pass (qt, qt8), (bt, dire, msbt, msdire) or both; no other NULL mix");
+    const int row = (qp - 22) / 5;
+    for (int k = 0; k < 3; ++k) wm[k] = (float)weight_mat[row][k];
+    *w0_one = qp == 22;
+    return PMP_OK;
+}
+
+static int val_launch(pmp_ctx *c, const ValArgs &a)
+{
+    double *part = a.block_stats;
+    if (!part) {
+        const int rc = ensure(c, c->d_valpart, (size_t)a.n * PMP_VAL_NSTATS * sizeof(double));
+        if (rc != PMP_OK) return rc;
+        part = (double *)c->d_valpart.p;
+    }
+    const hipError_t e = launch_val_stats(c->stream, a.qt, a.bt, a.dire, a.qt8, a.msbt, a.msdire, a.n, a.wm, a.w0_one, part, a.stats);
+    return e == hipSuccess ? PMP_OK : hip_fail(c, e, "val_stats");
+}
+
+static int val_device_impl(pmp_ctx *c, const ValArgs &a)
+{
+    if (a.n == 0) {
+        const hipError_t e = hipMemsetAsync(a.stats, 0, PMP_VAL_NSTATS * sizeof(double), c->stream);
+        return e == hipSuccess ? PMP_OK : hip_fail(c, e, "val_stats");
+    }
+    const int rc = val_launch(c, a);
+    // its logits may come from an inference call whose range flag has not been looked at yet: remember the call for the replay
+    if (rc == PMP_OK && !c->pending.empty())
+        c->pending.push_back(PendingCall{false, false, nullptr, nullptr, [=](bool) { return val_launch(c, a); }});
+    return rc;
+}
+
+int pmp_val_stats_device(pmp_ctx *c, int qp, const float *qt, const float *bt, const float *dire, const uint8_t *qt8,
+                         const uint8_t *msbt, const int8_t *msdire, int64_t n, double *stats, double *block_stats)
+{
+    CHECK_CTX(c);
+    ValArgs a{qt, bt, dire, qt8, msbt, msdire, n, {0.f, 0.f, 0.f}, 0, stats, block_stats};
+    int rc;
+    if ((rc = val_check(c, qp, qt, bt, dire, qt8, msbt, msdire, n, stats, a.wm, &a.w0_one))) return rc;
+    if (n > 0 && ((((uintptr_t)bt | (uintptr_t)dire) & 15) || (((uintptr_t)qt | (uintptr_t)msbt | (uintptr_t)msdire) & 3) ||
+                  (((uintptr_t)stats | (uintptr_t)block_stats) & 7)))
+        return set_err(c, PMP_E_INVALID, "pmp_val_stats_device: bt, dire must be 16-byte aligned, qt, msbt, msdire 4-byte, the outputs 8-byte");
+    return val_device_impl(c, a);
+}
+
+int pmp_val_stats(pmp_ctx *c, int qp, const float *qt, const float *bt, const float *dire, const uint8_t *qt8, const uint8_t *msbt,
+                  const int8_t *msdire, int64_t n, double stats[PMP_VAL_NSTATS])
+{
+    CHECK_CTX(c);
+    ValArgs a{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, {0.f, 0.f, 0.f}, 0, nullptr, nullptr};
+    int rc;
+    if ((rc = val_check(c, qp, qt, bt, dire, qt8, msbt, msdire, n, stats, a.wm, &a.w0_one))) return rc;
+    for (int i = 0; i < PMP_VAL_NSTATS; ++i) stats[i] = 0.0;
+    if (n == 0) return PMP_OK;
+    if ((rc = settle_before_host_call(c))) return rc;
+    // passes of at most `chunk` blocks through the context's own staging buffers (about 6.9 kB per block); one result row per pass
+    const int64_t chunk = c->chunk, m0 = n < chunk ? n : chunk, passes = (n + chunk - 1) / chunk;
+    const size_t per[6] = {64 * 4, 768 * 4, 768 * 4, 64, 768, 768};
+    const void *src[6] = {qt, bt, dire, qt8, msbt, msdire};
+    for (int i = 0; i < 6; ++i)
+        if (src[i] && (rc = ensure(c, c->d_val[i], (size_t)m0 * per[i]))) return rc;
+    if ((rc = ensure(c, c->d_valout, (size_t)passes * PMP_VAL_NSTATS * sizeof(double)))) return rc;
+    for (int64_t o = 0, p = 0; o < n; o += chunk, ++p) {
+        const int64_t m = (n - o) < chunk ? (n - o) : chunk;
+        for (int i = 0; i < 6; ++i)
+            if (src[i] && (rc = h2d(c, c->d_val[i], (const char *)src[i] + (size_t)o * per[i], (size_t)m * per[i]))) return rc;
+        a.qt = qt ? (const float *)c->d_val[0].p : nullptr;
+        a.bt = bt ? (const float *)c->d_val[1].p : nullptr;
+        a.dire = bt ? (const float *)c->d_val[2].p : nullptr;
+        a.qt8 = qt ? (const uint8_t *)c->d_val[3].p : nullptr;
+        a.msbt = bt ? (const uint8_t *)c->d_val[4].p : nullptr;
+        a.msdire = bt ? (const int8_t *)c->d_val[5].p : nullptr;
+        a.n = m;
+        a.stats = (double *)c->d_valout.p + p * PMP_VAL_NSTATS;
+        if ((rc = val_launch(c, a))) return rc;
+        if ((rc = sync(c))) return rc;   // the next pass reuses the staging buffers
+    }
+    std::vector<double> rows((size_t)passes * PMP_VAL_NSTATS);
+    if ((rc = d2h(c, rows.data(), c->d_valout.p, rows.size() * sizeof(double))) || (rc = sync(c))) return rc;
+    for (int64_t p = 0; p < passes; ++p)          // the whole call as one batch: pass results in pass order
+        for (int i = 0; i < PMP_VAL_NSTATS; ++i) stats[i] += rows[(size_t)p * PMP_VAL_NSTATS + i];
+    return PMP_OK;
+}
+
+int pmp_infer_msbd_device(pmp_ctx *c, int comp, int qp, const uint8_t *by, const uint8_t *bu, const uint8_t *bv, const float *qt_in,
+                          int64_t n, float *bt, float *dire)
+{
+    CHECK_CTX(c);
+    if (!qt_in) return set_err(c, PMP_E_INVALID, "pmp_infer_msbd: qt_in is null");
+    return infer_device_impl(c, comp, qp, by, bu, bv, n, nullptr, bt, dire, false, qt_in);
+}
+
+int pmp_infer_msbd(pmp_ctx *c, int comp, int qp, const uint8_t *by, const uint8_t *bu, const uint8_t *bv, const float *qt_in, int64_t n,
+                   float *bt, float *dire)
+{
+    CHECK_CTX(c);
+    if (n < 0 || !by || !qt_in || !bt || !dire || (comp == PMP_CHROMA && (!bu || !bv)))
+        return set_err(c, PMP_E_INVALID, "pmp_infer_msbd: null buffer or negative count");
+    if (n == 0) return PMP_OK;
+    int rc;
+    if ((rc = settle_before_host_call(c))) return rc;
+    if ((rc = stage_blocks(c, comp, by, bu, bv, n))) return rc;
+    if ((rc = ensure_logits(c, n))) return rc;
+    if ((rc = h2d(c, c->d_logit[0], qt_in, (size_t)n * 64 * 4))) return rc;
+    float *db = (float *)c->d_logit[1].p, *dd = (float *)c->d_logit[2].p;
+    if ((rc = infer_device_impl(c, comp, qp, (const uint8_t *)c->d_in[0].p, (const uint8_t *)c->d_in[1].p, (const uint8_t *)c->d_in[2].p,
+                                n, nullptr, db, dd, true, (const float *)c->d_logit[0].p)))
+        return rc;
+    if ((rc = resolve_pending(c, true))) return rc;      // range guard: a re-run is enqueued before the copies below
+    if ((rc = d2h(c, bt, db, (size_t)n * 768 * 4)) || (rc = d2h(c, dire, dd, (size_t)n * 768 * 4))) return rc;
+    return sync(c);
 }
 
 int pmp_debug_set_conv_variant(int variant)

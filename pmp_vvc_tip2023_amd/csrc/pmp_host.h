@@ -168,6 +168,9 @@ struct pmp_ctx {
     size_t ws_need = 0;                    // what the largest pass so far needed of it (pmp_get_workspace_bytes)
     pmp::DevBuf d_in[3], d_logit[3], d_out[4], d_frames[3];  // staging for the host-pointer entry points
     pmp::DevBuf d_lab[5];                  // staging of pmp_msbt_labels: qt, bt, dire in; msbt, status out
+    pmp::DevBuf d_val[6];                  // staging of pmp_val_stats: qt, bt, dire, qt8, msbt, msdire
+    pmp::DevBuf d_valpart;                 // validation statistics: per-block partials f64[n][20] of a call that passes no d_block_stats
+    pmp::DevBuf d_valout;                  // pmp_val_stats: f64[passes][20]
     // calibration of the f16x3 activation scales (NetWeights::act_exp): while cal_on, the graph (nets.cpp, running on the fp32 datapath) folds
     // the largest |value| of every tensor it produces into d_cal[slot] and logs (name, segment) per slot
     int cal_on = 0;

@@ -185,6 +185,12 @@ hipError_t launch_postprocess(hipStream_t s, const float *qt, const float *bt, c
 hipError_t launch_msbt_labels(hipStream_t s, const uint8_t *qt, const uint8_t *bt, const int8_t *dire, int64_t N, int chroma_factor,
                               uint8_t *msbt, uint8_t *status);
 
+// Validation statistics (valstats.hip; include/pmp.h: pmp_val_stats): logits against labels -> block_stats f64[N][20] (always written:
+// the caller's buffer or scratch) and their fixed-order sum stats f64[20].  qt/qt8 null: MTT only; bt/dire/msbt/msdire null: QT only.
+// wm: float32(weight_mat[row][0..2]); w0_one: qp == 22 (weight_d0 = 1.0).  bt, dire 16-byte aligned, msbt, msdire 4-byte aligned.  N >= 1.
+hipError_t launch_val_stats(hipStream_t s, const float *qt, const float *bt, const float *dire, const uint8_t *qt8, const uint8_t *msbt,
+                            const int8_t *msdire, int64_t N, const float wm[3], int w0_one, double *block_stats, double *stats);
+
 // Block cutter (Inference_QBD.py:104-149).
 hipError_t launch_cut_blocks(hipStream_t s, const void *y, const void *u, const void *v, int F, int H, int W,
                              int bitdepth, uint8_t *by, uint8_t *bu, uint8_t *bv);

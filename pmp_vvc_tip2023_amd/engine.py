@@ -8,6 +8,8 @@ Same names and argument meaning as the reference so callers (and the parity test
     Inference_QBD.output_block_yuv(...)                 Engine.output_block_yuv(y, u, v, bitdepth)
     Inference_QBD.load_pretrain_model(net, path)        Engine.load_pretrain_model(net_name, qp, weights)
     GenMSBtMap.gen_seq_sub_map(qt, bt, dire, is_luma)   Engine.gen_seq_sub_map(qt, bt, dire, is_luma)   (training labels)
+    Metrics.validation_QBD(loader, Net_Q, Net_BD, qp)   Engine.validation_QBD(comp, qp, blocks, qt8, msbt, msdire, batch_size)
+    Metrics.pre_validation(loader, Net, predID, qp)     Engine.pre_validation(comp, qp, pred_id, blocks, qt8[, msbt, msdire], batch_size)
     CreateDataSet.output_block_partition_map(...)       output_block_partition_map(...)                 (module level, host only)
 
 numpy arrays in/out for the host API; the *_device methods take raw device pointers (ints), e.g. torch
@@ -295,6 +297,143 @@ class Engine:
         """pmp_msbt_labels_device: device pointers (u8 qt, u8 bt, i8 dire in; u8 msbt, u8 status out), stream-ordered."""
         self._ck(self.lib.pmp_msbt_labels_device(self.h, int(cf), d_qt, d_bt, d_dire, int(n), d_msbt, d_status))
 
+    # ------------------------------------------------------------------------------------------ validation
+    def val_stats(self, qp, qt=None, bt=None, dire=None, qt8=None, msbt=None, msdire=None):
+        """pmp_val_stats (include/pmp.h): the twenty per-batch numbers S[0..19] of logits against labels, the whole call as one batch.
+        qt f32[N,(1,)8,8] with qt8 u8[N,8,8] (RAW qtDepth), bt / dire f32[N,3,16,16] with msbt u8 / msdire i8 [N,3,16,16]; leave the
+        QT pair or the MTT four out for the MTT-only / QT-only forms.  -> float64[20]."""
+        f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+        qt, bt, dire = f(qt), f(bt), f(dire)
+        qt8 = None if qt8 is None else _fit(qt8, np.uint8, "qt8")
+        msbt = None if msbt is None else _fit(msbt, np.uint8, "msbt")
+        msdire = None if msdire is None else _fit(msdire, np.int8, "msdire")
+        n = _val_count(qt, bt, dire, qt8, msbt, msdire)
+        out = np.zeros(_lib.PMP_VAL_NSTATS, np.float64)
+        self._ck(self.lib.pmp_val_stats(self.h, int(qp), _ptr(qt), _ptr(bt), _ptr(dire), _ptr(qt8), _ptr(msbt), _ptr(msdire), n, _ptr(out)))
+        return out
+
+    def val_stats_device(self, qp, d_qt, d_bt, d_dire, d_qt8, d_msbt, d_msdire, n, d_stats, d_block_stats=None):
+        """pmp_val_stats_device: device pointers (None for the pair / the four left out), f64[20] -> d_stats and, if given, the per-block
+        partials f64[n,20] -> d_block_stats; stream-ordered, final after synchronize() (include/pmp.h: range guard)."""
+        self._ck(self.lib.pmp_val_stats_device(self.h, int(qp), d_qt, d_bt, d_dire, d_qt8, d_msbt, d_msdire, int(n), d_stats, d_block_stats))
+
+    def infer_msbd(self, comp, qp, qt_in, block_y, block_u=None, block_v=None):
+        """Teacher-forced MTT inference (pmp_infer_msbd; Net(input_batch, qt_label_batch), Metrics.py:226): the MTT net of (comp, qp) on
+        the blocks with the GIVEN QT map qt_in f32[N,(1,)8,8] -> bt f32[N,3,16,16], dire f32[N,3,16,16]."""
+        by, bu, bv = _u8(block_y), _u8(block_u), _u8(block_v)
+        n = self._check_blocks(comp, by, bu, bv)
+        q = np.ascontiguousarray(qt_in, np.float32)
+        if q.size != n * 64:
+            raise ValueError("infer_msbd: qt_in must be f32[N,8,8] for the N blocks given")
+        self.load(comp, qp)
+        bt = np.empty((n, 3, 16, 16), np.float32); dire = np.empty((n, 3, 16, 16), np.float32)
+        self._ck(self.lib.pmp_infer_msbd(self.h, COMP_ID[comp], int(qp), _ptr(by), _ptr(bu), _ptr(bv), _ptr(q), n, _ptr(bt), _ptr(dire)))
+        return bt, dire
+
+    def infer_msbd_device(self, comp, qp, d_by, d_bu, d_bv, d_qt_in, n, d_bt, d_dire):
+        self._ck(self.lib.pmp_infer_msbd_device(self.h, COMP_ID[comp], int(qp), d_by, d_bu, d_bv, d_qt_in, int(n), d_bt, d_dire))
+
+    def validation_QBD(self, comp, qp, blocks, qt8, msbt, msdire, batch_size=200, logits=None, return_block_stats=False):
+        """Metrics.validation_QBD (Metrics.py:313-385) on the GPU: both nets on every batch, the QT net's output feeding the MTT net.
+        blocks: block_y u8[N,68,68] (Luma) or (block_y, block_u, block_v) (Chroma); labels as the label files hold them (qt8 RAW
+        qtDepth u8[N,8,8], msbt u8 / msdire i8 [N,3,16,16]).  The set is cut into batches of batch_size IN ORDER (the reference
+        shuffles: its numbers are defined up to that; the ragged last batch weighs like a full one, as there).  Returns the
+        reference's list of 15: [q_L1, b0_L1, b1_L1, b2_L1, d0_L1, d1_L1, d2_L1, q_accu, b0_accu, b1_accu, b2_accu, d0_accu, d1_accu,
+        d2_accu, val_loss], each np.mean over the per-batch values.  logits = (qt, bt, dire): validate these instead of running the
+        nets (blocks may be None).  return_block_stats: also the per-block partials float64[N,20] (include/pmp.h: pmp_val_stats)."""
+        S, ns, blk = self._val_run("qbd", comp, qp, blocks, qt8, msbt, msdire, batch_size, logits, return_block_stats)
+        out = validation_numbers(S, ns, "qbd")
+        return (out, blk) if return_block_stats else out
+
+    def pre_validation(self, comp, qp, pred_id, blocks, qt8, msbt=None, msdire=None, batch_size=200, logits=None, return_block_stats=False):
+        """Metrics.pre_validation (Metrics.py:196-274).  pred_id 0: the QT net alone -> [L1, accuracy] (the ABI has no QT-only inference
+        call: this runs pmp_infer_device and drops the MTT logits, so it costs a full inference step).  pred_id 1: the MTT net,
+        TEACHER-FORCED with the QT label map float(qt8 - 1) (u8 subtraction: raw 0 -> 255.0) -> the reference's list of 13: [b0_L1, b1_L1,
+        b2_L1, d0_L1, d1_L1, d2_L1, b0_accu, b1_accu, b2_accu, d0_accu, d1_accu, d2_accu, val_loss].  Batching, logits and
+        return_block_stats as in validation_QBD (logits = (qt,) for pred_id 0, (bt, dire) for pred_id 1).  pred_id 2 belongs to a
+        direction net the reference's Model_QBD.py no longer has: ValueError."""
+        if pred_id not in (0, 1):
+            raise ValueError("pre_validation: pred_id must be 0 (QT net) or 1 (MTT net, teacher-forced)")
+        mode = "q" if pred_id == 0 else "bd"
+        S, ns, blk = self._val_run(mode, comp, qp, blocks, qt8, msbt, msdire, batch_size, logits, return_block_stats)
+        out = validation_numbers(S, ns, mode)
+        return (out, blk) if return_block_stats else out
+
+    def _val_run(self, mode, comp, qp, blocks, qt8, msbt, msdire, batch_size, logits, want_blocks, group_blocks=16384):
+        """-> (S float64[batches,20], batch sizes, per-block partials or None).  Device-resident: per batch one inference call and one
+        statistics call, both enqueued without waiting; the host synchronises once per GROUP of batches (at most group_blocks blocks,
+        whose logits stay in device memory until then: a range-guard re-run at the synchronize finds every batch's buffers intact)."""
+        import torch
+        if comp not in COMP_ID:
+            raise ValueError("comp must be 'Luma' or 'Chroma'")
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+        use_q, use_m = mode in ("qbd", "q"), mode in ("qbd", "bd")
+        qt8 = _fit(qt8, np.uint8, "qt8")
+        n = qt8.size // 64
+        if qt8.size != n * 64:
+            raise ValueError("qt8 must be u8[N,8,8]")
+        if use_m:
+            if msbt is None or msdire is None:
+                raise ValueError("msbt and msdire labels are needed")
+            msbt = _fit(msbt, np.uint8, "msbt"); msdire = _fit(msdire, np.int8, "msdire")
+            if msbt.size != n * 768 or msdire.size != n * 768:
+                raise ValueError("msbt and msdire must be [N,3,16,16] for the N blocks of qt8")
+        dev = torch.device("cuda", int(self.device))
+        up = lambda a: torch.from_numpy(np.array(a, copy=not a.flags.writeable or not a.flags.c_contiguous)).to(dev)   # memory-mapped files are read-only
+        if logits is None:
+            by, bu, bv = (blocks if isinstance(blocks, (tuple, list)) else (blocks, None, None))
+            by, bu, bv = _u8(by), _u8(bu), _u8(bv)
+            if self._check_blocks(comp, by, bu, bv) != n:
+                raise ValueError("%d blocks for %d label blocks" % (by.shape[0], n))
+            self.load(comp, qp)
+            d_y = up(by); d_u = up(bu) if comp == "Chroma" else None; d_v = up(bv) if comp == "Chroma" else None
+        else:
+            want = {"qbd": (64, 768, 768), "q": (64,), "bd": (768, 768)}[mode]
+            logits = [np.ascontiguousarray(a, np.float32) for a in logits]
+            if len(logits) != len(want) or any(a.size != n * w for a, w in zip(logits, want)):
+                raise ValueError("logits: expected %d arrays of N x %s floats" % (len(want), "/".join(map(str, want))))
+        d_q8 = up(qt8)
+        d_mb = up(msbt) if use_m else None; d_md = up(msdire) if use_m else None
+        d_qin = None
+        if mode == "bd" and logits is None:           # the loader's label map: float(u8(qt8 - 1))
+            d_qin = up((qt8 - np.uint8(1)).astype(np.float32))
+        starts = list(range(0, n, batch_size))
+        ns = [min(batch_size, n - o) for o in starts]
+        S = torch.zeros((len(starts), _lib.PMP_VAL_NSTATS), dtype=torch.float64, device=dev)
+        blk = torch.zeros((n, _lib.PMP_VAL_NSTATS), dtype=torch.float64, device=dev) if want_blocks else None
+        per_group = max(1, int(group_blocks) // batch_size)
+        P = lambda t, o, w, e: None if t is None else t.data_ptr() + o * w * e
+        torch.cuda.synchronize(dev)                   # the uploads above ran on torch's stream; the context has its own
+        for g0 in range(0, len(starts), per_group):
+            grp = list(range(g0, min(g0 + per_group, len(starts))))
+            base, m_all = starts[grp[0]], sum(ns[i] for i in grp)
+            if logits is None:
+                l_q = torch.empty((m_all, 64), dtype=torch.float32, device=dev) if mode != "bd" else None
+                l_b = torch.empty((m_all, 768), dtype=torch.float32, device=dev)
+                l_d = torch.empty((m_all, 768), dtype=torch.float32, device=dev)
+            else:
+                it = iter(logits)
+                l_q = up(next(it).reshape(n, 64)[base:base + m_all]) if use_q else None
+                l_b = up(next(it).reshape(n, 768)[base:base + m_all]) if use_m else None
+                l_d = up(next(it).reshape(n, 768)[base:base + m_all]) if use_m else None
+                torch.cuda.synchronize(dev)
+            for i in grp:
+                o, m, r = starts[i], ns[i], starts[i] - base
+                if logits is None and mode == "bd":
+                    self.infer_msbd_device(comp, qp, P(d_y, o, 68 * 68, 1), P(d_u, o, 34 * 34, 1), P(d_v, o, 34 * 34, 1), P(d_qin, o, 64, 4),
+                                           m, P(l_b, r, 768, 4), P(l_d, r, 768, 4))
+                elif logits is None:
+                    self.infer_device(comp, qp, P(d_y, o, 68 * 68, 1), P(d_u, o, 34 * 34, 1), P(d_v, o, 34 * 34, 1), m,
+                                      P(l_q, r, 64, 4), P(l_b, r, 768, 4), P(l_d, r, 768, 4))
+                self.val_stats_device(qp, P(l_q, r, 64, 4) if use_q else None, P(l_b, r, 768, 4) if use_m else None,
+                                      P(l_d, r, 768, 4) if use_m else None, P(d_q8, o, 64, 1) if use_q else None,
+                                      P(d_mb, o, 768, 1), P(d_md, o, 768, 1), m, S.data_ptr() + i * _lib.PMP_VAL_NSTATS * 8,
+                                      None if blk is None else blk.data_ptr() + o * _lib.PMP_VAL_NSTATS * 8)
+            self.synchronize()                        # final: range flags looked at, re-runs and their statistics replayed
+        return S.cpu().numpy(), ns, (None if blk is None else blk.cpu().numpy())
+
     # ------------------------------------------------------------------------------------------ device API
     def infer_device(self, comp, qp, d_by, d_bu, d_bv, n, d_qt, d_bt, d_dire):
         self._ck(self.lib.pmp_infer_device(self.h, COMP_ID[comp], int(qp), d_by, d_bu, d_bv, int(n), d_qt, d_bt, d_dire))
@@ -355,6 +494,40 @@ def _fit(a, dtype, name):
                    or a.min() < info.min or a.max() > info.max):
         raise ValueError("%s: values outside %s (the reference's dtype); refusing to wrap them" % (name, np.dtype(dtype).name))
     return np.ascontiguousarray(a.astype(dtype))
+
+
+VAL_ELEMS = np.array([64] + [256] * 12 + [64] + [256] * 6, np.float64)      # elements per block behind each of the twenty statistics
+
+
+def _val_count(qt, bt, dire, qt8, msbt, msdire):
+    """Block count of a val_stats call; ValueError on a mix the ABI refuses or on sizes that disagree."""
+    have_q, have_m = qt is not None or qt8 is not None, any(a is not None for a in (bt, dire, msbt, msdire))
+    if have_q and (qt is None or qt8 is None) or have_m and any(a is None for a in (bt, dire, msbt, msdire)) or not (have_q or have_m):
+        raise ValueError("val_stats: pass (qt, qt8), (bt, dire, msbt, msdire) or both")
+    n = (qt.size // 64) if have_q else (bt.size // 768)
+    if have_q and (qt.size != n * 64 or qt8.size != n * 64) or have_m and any(a.size != n * 768 for a in (bt, dire, msbt, msdire)):
+        raise ValueError("val_stats: expected qt[N,8,8], qt8[N,8,8] and bt, dire, msbt, msdire [N,3,16,16] for one N")
+    return n
+
+
+def validation_numbers(S, ns, mode="qbd"):
+    """The reference's result lists from per-batch statistics S float64[batches,20] (include/pmp.h: pmp_val_stats) of batches of ns
+    blocks: "qbd" -> validation_QBD's 15, "q" -> pre_validation predID 0's [L1, accuracy], "bd" -> predID 1's 13.  A per-batch L1 is
+    S / elements, an accuracy hits / elements, the loss loss_func_QBD_val (without the QT term for "bd"); np.mean over the batches."""
+    S = np.asarray(S, np.float64).reshape(-1, _lib.PMP_VAL_NSTATS)
+    nb = np.asarray(ns, np.float64).reshape(-1, 1)
+    if len(S) == 0:
+        raise ValueError("validation of an empty set")
+    with np.errstate(invalid="ignore"):
+        R = S / (VAL_ELEMS[None, :] * nb)
+        loss = (0.8 * S[:, 1] + 1.0 * S[:, 2] + 1.2 * S[:, 3] + S[:, 7] + S[:, 8] + S[:, 9] + 0.5 * (S[:, 10] + S[:, 11] + S[:, 12])) / (256.0 * nb[:, 0])
+        if mode == "qbd":
+            loss = S[:, 0] / (64.0 * nb[:, 0]) + loss
+        cols = {"qbd": [0, 1, 2, 3, 4, 5, 6, 13, 14, 15, 16, 17, 18, 19], "q": [0, 13], "bd": [1, 2, 3, 4, 5, 6, 14, 15, 16, 17, 18, 19]}[mode]
+        out = [float(np.mean(R[:, j])) for j in cols]
+        if mode != "q":
+            out.append(float(np.mean(loss)))
+    return out
 
 
 def output_block_partition_map(file_path, frm_width, frm_height, frm_num, block_size=64, isChroma=False, return_unknown=False):

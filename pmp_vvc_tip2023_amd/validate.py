@@ -1,0 +1,136 @@
+"""Validate a pair of nets against VTM labels on the GPU: Metrics.validation_QBD / pre_validation of the reference.
+
+    python -m pmp_vvc_tip2023_amd.validate --dataDir D --modelDir M --comp Luma|Chroma --qp Q [--dataType Validate]
+           [--mode qbd|bd|q] [--batchSize 200] [--precision f16x3|bf16x6|fp32] [--perBlock out.npy] [--device 0]
+
+Reads the reference's file names from --dataDir (Metrics.Load_Pre_VP_Dataset, Metrics.py:64-146):
+    <dataType>_Y_Block68.npy                           u8[n,68,68]   (+ <dataType>_U_Block34.npy, _V_Block34.npy u8[n,34,34] for Chroma)
+    <dataType>_<comp>_QP<qp>_QTdepth_Block8.npy        u8[n,8,8]     raw qtDepth
+    <dataType>_<comp>_QP<qp>_MSBTdepth_Block16.npy     u8[n,3,16,16] (modes qbd, bd)
+    <dataType>_<comp>_QP<qp>_MSdirection_Block16.npy   i8[n,3,16,16] (modes qbd, bd)
+the three label files being what `python -m pmp_vvc_tip2023_amd.gen_labels` writes.  --mode qbd (default) is validation_QBD (both nets,
+the QT net feeding the MTT net), bd is pre_validation predID 1 (the MTT net teacher-forced with the QT labels), q is predID 0 (the QT
+net alone).  Batches of --batchSize blocks in file order; the reference shuffles, so its numbers are defined up to the batch cut.
+Prints ONE JSON object: the reference's numbers by name (q_L1, b0_L1 .., q_accu .., val_loss) plus comp, qp, mode, blocks, batches,
+batch_size, precision and saturation_reruns.  --perBlock writes the per-block statistics float64[n,20] (include/pmp.h: pmp_val_stats).
+Flags, files, dtypes and shapes are checked before anything touches the GPU: exit status 2 on the first problem.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+COMPS = ("Luma", "Chroma")
+NAMES = {"qbd": ["q_L1", "b0_L1", "b1_L1", "b2_L1", "d0_L1", "d1_L1", "d2_L1", "q_accu", "b0_accu", "b1_accu", "b2_accu", "d0_accu",
+                 "d1_accu", "d2_accu", "val_loss"],
+         "q": ["q_L1", "q_accu"],
+         "bd": ["b0_L1", "b1_L1", "b2_L1", "d0_L1", "d1_L1", "d2_L1", "b0_accu", "b1_accu", "b2_accu", "d0_accu", "d1_accu", "d2_accu",
+                "val_loss"]}
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    p.add_argument("--dataDir", required=True, help="directory of the block and label .npy files")
+    p.add_argument("--modelDir", default=None, help="directory of the nets' weight files (default: the package's search path)")
+    p.add_argument("--comp", required=True)
+    p.add_argument("--qp", required=True, type=int)
+    p.add_argument("--dataType", default="Validate")
+    p.add_argument("--mode", default="qbd")
+    p.add_argument("--batchSize", default=200, type=int)
+    p.add_argument("--precision", default="f16x3")
+    p.add_argument("--perBlock", default=None, help="write the per-block statistics float64[n,20] to this .npy file")
+    p.add_argument("--allowSyntheticMtt", action="store_true", help="fall back to the synthetic MTT weights when the *_BD_* file is missing (tests)")
+    p.add_argument("--device", default=0, type=int)
+    return p
+
+
+def plan(args):
+    """Validates every flag and opens every file (memory-mapped) -> {"blocks": y or (y, u, v), "qt8", "msbt", "msdire", "n"}.
+    SystemExit(2) on the first problem: nothing has touched the GPU yet."""
+    def fail(msg):
+        print("validate: " + msg, file=sys.stderr)
+        raise SystemExit(2)
+    if args.comp not in COMPS:
+        fail("--comp must be Luma or Chroma, got %r" % args.comp)
+    if args.mode not in NAMES:
+        fail("--mode must be qbd, bd or q, got %r" % args.mode)
+    if not 22 <= args.qp <= 41:
+        fail("--qp must be in 22..41 (the rows of the reference's weight_mat), got %d" % args.qp)
+    if args.batchSize < 1:
+        fail("--batchSize must be >= 1")
+    if args.precision not in ("f16x3", "bf16x6", "fp32"):
+        fail("--precision must be f16x3, bf16x6 or fp32, got %r" % args.precision)
+    if not args.dataType or os.sep in args.dataType:
+        fail("--dataType must be a plain name")
+    if not os.path.isdir(args.dataDir):
+        fail("--dataDir %s is not a directory" % args.dataDir)
+    if args.modelDir is not None and not os.path.isdir(args.modelDir):
+        fail("--modelDir %s is not a directory" % args.modelDir)
+    if args.perBlock is not None and not os.path.isdir(os.path.dirname(os.path.abspath(args.perBlock))):
+        fail("--perBlock: directory of %s does not exist" % args.perBlock)
+
+    def read(name, dtype, tail):
+        path = os.path.join(args.dataDir, name)
+        if not os.path.isfile(path):
+            fail("%s not found" % path)
+        try:
+            a = np.load(path, mmap_mode="r", allow_pickle=False)
+        except (ValueError, OSError) as e:
+            fail("%s: %s" % (path, e))
+        if a.dtype != dtype or a.ndim != len(tail) + 1 or a.shape[1:] != tail:
+            fail("%s: expected %s[n,%s], got %s%s" % (path, np.dtype(dtype).name, ",".join(map(str, tail)), a.dtype.name, list(a.shape)))
+        return a
+    stem = "%s_%s_QP%d_" % (args.dataType, args.comp, args.qp)
+    out = {"qt8": read(stem + "QTdepth_Block8.npy", np.uint8, (8, 8)), "msbt": None, "msdire": None}
+    n = out["qt8"].shape[0]
+    if args.mode != "q":
+        out["msbt"] = read(stem + "MSBTdepth_Block16.npy", np.uint8, (3, 16, 16))
+        out["msdire"] = read(stem + "MSdirection_Block16.npy", np.int8, (3, 16, 16))
+    y = read(args.dataType + "_Y_Block68.npy", np.uint8, (68, 68))
+    arrays = [("labels", out["msbt"]), ("labels", out["msdire"]), ("blocks", y)]
+    if args.comp == "Chroma":
+        u = read(args.dataType + "_U_Block34.npy", np.uint8, (34, 34))
+        v = read(args.dataType + "_V_Block34.npy", np.uint8, (34, 34))
+        arrays += [("blocks", u), ("blocks", v)]
+        out["blocks"] = (y, u, v)
+    else:
+        out["blocks"] = y
+    for what, a in arrays:
+        if a is not None and a.shape[0] != n:
+            fail("%d %s for %d QT label blocks" % (a.shape[0], what, n))
+    if n == 0:
+        fail("the set is empty")
+    out["n"] = n
+    return out
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    d = plan(args)
+    from . import engine as E
+    eng = E.Engine(args.device, weight_dir=args.modelDir, allow_synthetic_mtt=args.allowSyntheticMtt)
+    try:
+        eng.set_precision(args.precision)
+        kw = dict(batch_size=args.batchSize, return_block_stats=args.perBlock is not None)
+        if args.mode == "qbd":
+            res = eng.validation_QBD(args.comp, args.qp, d["blocks"], d["qt8"], d["msbt"], d["msdire"], **kw)
+        else:
+            res = eng.pre_validation(args.comp, args.qp, 0 if args.mode == "q" else 1, d["blocks"], d["qt8"], d["msbt"], d["msdire"], **kw)
+        reruns = eng.saturation_reruns()
+    finally:
+        eng.close()
+    if args.perBlock is not None:
+        res, blk = res
+        np.save(args.perBlock, blk)
+    out = {"comp": args.comp, "qp": args.qp, "mode": args.mode, "data_type": args.dataType, "blocks": d["n"],
+           "batches": (d["n"] + args.batchSize - 1) // args.batchSize, "batch_size": args.batchSize, "precision": args.precision,
+           "saturation_reruns": reruns}
+    out.update(zip(NAMES[args.mode], res))
+    print(json.dumps(out))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
