@@ -92,42 +92,33 @@ int calibrate_mtt(pmp_ctx *c, bool luma, NetWeights &wq, NetWeights &wb)
     // its blocks and logits are its own), so it runs beside the passes in flight instead of behind them - a driver that loads the next
     // (component, QP) while the GPU works on this one (pmp_load_weights calibrates a pair as soon as it is complete) pays host time only.
     // Round 5's first form ran it on the context's stream inside the first inference call: 8 x 25 ms of exposed serialisation per 8-file job.
-    hipStream_t user_stream = c->stream;
-    const size_t user_need = c->ws_need;
-    c->stream = c->cal_stream;
-    std::swap(c->ws, c->ws_cal);
-    struct Restore {
-        pmp_ctx *c; hipStream_t s; size_t need;
-        ~Restore() { c->stream = s; std::swap(c->ws, c->ws_cal); c->ws_need = need; c->cal_on = 0; }
-    } restore{c, user_stream, user_need};
+    hipStream_t stream = c->cal_stream;
     char *base = static_cast<char *>(c->d_calbuf.p);
-    if (e == hipSuccess) e = hipMemcpyAsync(base, hy.data(), hy.size(), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(base + o_u, hu.data(), hu.size(), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(base + o_v, hv.data(), hv.size(), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(c->d_cal, 0, PMP_CAL_SLOTS * sizeof(unsigned), c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(base, hy.data(), hy.size(), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(base + o_u, hu.data(), hu.size(), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(base + o_v, hv.data(), hv.size(), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->d_cal, 0, PMP_CAL_SLOTS * sizeof(unsigned), stream);
     if (e != hipSuccess) return hip_fail(c, e, "calibration: staging");
     const uint8_t *dy = (const uint8_t *)base, *du = (const uint8_t *)(base + o_u), *dv = (const uint8_t *)(base + o_v);
     float *dq = (float *)(base + o_q), *dbt = (float *)(base + o_bt), *ddr = (float *)(base + o_dr);
-    const int saved = c->precision;
-    c->precision = PMP_PRECISION_F32;
     // passes of PMP_CAL_PASS blocks in the private workspace (the context's own stays what its calls need: a 4-block call in 11 MB,
-    // include/pmp.h); every pass folds into the same slots, so the log is that of the first pass
+    // include/pmp.h), on the fp32 datapath, recorded by no tap; every pass folds the MTT net's maxima into the same slots, so the log is
+    // that of the first pass
+    Pass pq{stream, c->ws_cal, PMP_PRECISION_F32, /*taps*/ false, /*cal*/ false, /*caller*/ false};
+    Pass pb{stream, c->ws_cal, PMP_PRECISION_F32, /*taps*/ false, /*cal*/ true, /*caller*/ false};
     rc = PMP_OK;
     for (int o = 0; o < n && rc == PMP_OK; o += PMP_CAL_PASS) {
         const int m = std::min(PMP_CAL_PASS, n - o);
         c->cal_log.clear();
-        rc = run_graph_fn(c, [&] { return forward_q(c, luma, wq, dy + (size_t)o * 68 * 68, du + (size_t)o * 34 * 34, dv + (size_t)o * 34 * 34, m, dq + (size_t)o * 64); });
-        c->cal_on = 1;
+        rc = run_graph(c, pq, [&] { return forward_q(c, pq, luma, wq, dy + (size_t)o * 68 * 68, du + (size_t)o * 34 * 34, dv + (size_t)o * 34 * 34, m, dq + (size_t)o * 64); });
         if (rc == PMP_OK)
-            rc = run_graph_fn(c, [&] { return forward_msbd(c, luma, wb, dy + (size_t)o * 68 * 68, du + (size_t)o * 34 * 34, dv + (size_t)o * 34 * 34, dq + (size_t)o * 64, m,
-                                                        dbt + (size_t)o * 768, ddr + (size_t)o * 768); });
-        c->cal_on = 0;
+            rc = run_graph(c, pb, [&] { return forward_msbd(c, pb, luma, wb, dy + (size_t)o * 68 * 68, du + (size_t)o * 34 * 34, dv + (size_t)o * 34 * 34, dq + (size_t)o * 64, m,
+                                                         dbt + (size_t)o * 768, ddr + (size_t)o * 768); });
     }
-    c->precision = saved;
     if (rc != PMP_OK) return rc;
     std::vector<unsigned> bits(PMP_CAL_SLOTS);
-    e = hipMemcpyAsync(bits.data(), c->d_cal, PMP_CAL_SLOTS * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    e = hipMemcpyAsync(bits.data(), c->d_cal, PMP_CAL_SLOTS * sizeof(unsigned), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) return hip_fail(c, e, "calibration: maxima");
     float seg_max[5] = {0, 0, 0, 0, 0};
     wb.cal_names.clear(); wb.cal_seg.clear(); wb.cal_amax.clear();
@@ -189,8 +180,6 @@ void qt_partner_changed(pmp_ctx *c, int qt_net_id, int qp)
 }  // namespace pmp
 
 using namespace pmp;
-
-#define CHECK_CTX(c) do { if (!(c)) return set_err(nullptr, PMP_E_INVALID, "null context"); hipSetDevice((c)->device); } while (0)
 
 extern "C" {
 

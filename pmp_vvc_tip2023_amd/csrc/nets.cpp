@@ -1,7 +1,7 @@
 // nets.cpp — the four Down-Up-CNN forward passes (Model_QBD.py:59-253) as sequences of HIP kernel launches.
 //
-// Every activation is a blocked channels-last tensor [n][C/16][H][W][16] carved from the context's workspace arena,
-// either plain fp32 or "split-3" (three bf16 planes, conv_bf16x6.hip) when the context runs the bf16x6 datapath.
+// Every activation is a blocked channels-last tensor [n][C/16][H][W][16] carved from the pass's workspace arena,
+// either plain fp32 or "split-3" (three bf16 planes, conv_bf16x6.hip) when the pass runs the bf16x6 datapath.
 // Fusions relative to the reference's op-by-op graph:
 //   * conv + ReLU; conv + (identity | 1x1-conv shortcut) + ReLU                 (ResidualBlock.forward :40-44)
 //   * ... + 2x2 max-pool in the same epilogue                                   (:81-82,:89,:136-137,:151)
@@ -31,32 +31,33 @@ struct Act {
 
 struct Graph {
     pmp_ctx *c;
+    Pass &ps;
     const NetWeights &w;
     int n;
     int rc = PMP_OK;
-    bool x6() const { return c->precision != 0; }      // a split datapath (bf16x6 or f16x3) is active
-    bool h2() const { return c->precision == 2; }
-    int fmt() const { return c->precision; }           // split3.h: 0 fp32, 1 split-3, 2 split-2
+    bool x6() const { return ps.precision != 0; }      // a split datapath (bf16x6 or f16x3) is active
+    bool h2() const { return ps.precision == 2; }
+    int fmt() const { return ps.precision; }           // split3.h: 0 fp32, 1 split-3, 2 split-2
     unsigned *sat() const { return h2() ? c->d_sat : nullptr; }   // f16x3: the context's sticky saturation flag
     // f16x3 activation scales (pmp_host.h: NetWeights::act_exp): the segment the graph is in, and the exponent a segment's tensors carry
     int seg = 0;
     bool scaled() const { return h2() && c->act_scales && (w.stem_b_h || w.act_given); }
     int E(int sg) const { return scaled() ? w.act_exp[sg] : 0; }
-    // pmp_debug_set_taps: a copy of a tensor just produced, as its consumers read it (not in the calibration pass, the arena's measuring
-    // pass or a range-guard re-run); prefixed by net, "q/" or "bd/"
+    // pmp_debug_set_taps: a copy of a tensor just produced, as its consumers read it (ps.taps: not in a calibration pass or a range-guard
+    // re-run; never in the arena's measuring pass); prefixed by net, "q/" or "bd/"
     std::string pfx;
     void tap(const Act &a, const std::string &name, int sg, int c_real)
     {
-        if (!c->taps_on || c->cal_on || c->tap_skip || !live()) return;
-        const int r = tap_record(c, pfx + name, a.p, n, a.C, a.H, a.W, c_real, a.split ? fmt() : 0, E(sg));
+        if (!ps.taps || !live()) return;
+        const int r = tap_record(c, ps.stream, pfx + name, a.p, n, a.C, a.H, a.W, c_real, a.split ? fmt() : 0, E(sg));
         if (r != PMP_OK && rc == PMP_OK) rc = r;
     }
     // calibration pass (fp32 datapath, calibrate.cpp: calibrate_mtt): the largest |value| of a tensor just produced, per launch
     void note(const Act &a, const std::string &name, int sg, int c_real)
     {
         tap(a, name, sg, c_real);
-        if (!c->cal_on || !live() || a.split || (int)c->cal_log.size() >= PMP_CAL_SLOTS) return;
-        check(launch_amax_f32(c->stream, a.p, (size_t)n * a.C * a.H * a.W, c->d_cal + c->cal_log.size()), "amax");
+        if (!ps.cal || !live() || a.split || (int)c->cal_log.size() >= PMP_CAL_SLOTS) return;
+        check(launch_amax_f32(ps.stream, a.p, (size_t)n * a.C * a.H * a.W, c->d_cal + c->cal_log.size()), "amax");
         c->cal_log.emplace_back(name, sg);
     }
 
@@ -67,14 +68,14 @@ struct Graph {
         const size_t elems = (size_t)n * cp * H * W;
         // split-3: 3 planes of 2-byte elements = 6 bytes per element; split-2: 2 planes = 4; fp32: 4
         const size_t bytes = elems * (split && !h2() ? 6 : 4);
-        const size_t off = c->arena.take(bytes);
-        return Act{c->arena.ptr(off), cp, H, W, split, elems, off, bytes};
+        const size_t off = ps.arena.take(bytes);
+        return Act{ps.arena.ptr(off), cp, H, W, split, elems, off, bytes};
     }
 
     // The tensor's last consumer has been enqueued (one in-order stream): later allocations may reuse its bytes.
     void release(Act &a)
     {
-        if (a.bytes) c->arena.give(a.off, a.bytes);
+        if (a.bytes) ps.arena.give(a.off, a.bytes);
         a.bytes = 0;
     }
 
@@ -83,7 +84,7 @@ struct Graph {
         if (e != hipSuccess && rc == PMP_OK) rc = hip_fail(c, e, what);
         return rc == PMP_OK;
     }
-    bool live() const { return !c->arena.measuring && rc == PMP_OK; }
+    bool live() const { return !ps.arena.measuring && rc == PMP_OK; }
 
     int kclass(int k, int cin, int cout) const
     {
@@ -98,9 +99,9 @@ struct Graph {
         if (!x6() || x.split) return x;
         Act y = alloc(x.C, x.H, x.W, true);
         if (live()) {
-            KScope ks(c, K_SMALL, 0.0);
-            if (h2()) check(launch_f32_to_split2(c->stream, x.p, y.s(), (size_t)n * x.C * x.H * x.W, y.stride, sat()), "f32_to_split2");
-            else check(launch_f32_to_split3(c->stream, x.p, y.s(), (size_t)n * x.C * x.H * x.W, y.stride), "f32_to_split3");
+            KScope ks(c, ps.stream, K_SMALL, 0.0);
+            if (h2()) check(launch_f32_to_split2(ps.stream, x.p, y.s(), (size_t)n * x.C * x.H * x.W, y.stride, sat()), "f32_to_split2");
+            else check(launch_f32_to_split3(ps.stream, x.p, y.s(), (size_t)n * x.C * x.H * x.W, y.stride), "f32_to_split3");
         }
         return y;
     }
@@ -111,7 +112,7 @@ struct Graph {
               Act &out, double flops, int cls, int xexp = 0)
     {
         if (!live()) return;
-        KScope ks(c, cls, flops);
+        KScope ks(c, ps.stream, cls, flops);
         if (x6()) {
             ConvX6Args a{};
             a.x = x.s(); a.x_stride = x.stride;
@@ -126,8 +127,8 @@ struct Graph {
             if (out.split) { a.out = out.s(); a.out_stride = out.stride; }
             else a.out_f32 = out.p;
             a.N = n; a.H = x.H; a.W = x.W; a.Cin = x.C; a.Cout = out.C; a.KH = a.KW = r.k; a.relu = 1; a.pool = pool ? 1 : 0;
-            if (h2()) check(launch_conv_h2(c->stream, a), "conv_h2");
-            else check(launch_conv_x6(c->stream, a), "conv_x6");
+            if (h2()) check(launch_conv_h2(ps.stream, a), "conv_h2");
+            else check(launch_conv_x6(ps.stream, a), "conv_x6");
         } else {
             ConvMfmaArgs a{};
             a.x = x.p; a.w = second ? r.w2 : r.w0; a.out = out.p;
@@ -135,7 +136,7 @@ struct Graph {
             if (res) a.res = res->p;
             if (gate) a.gate = gate->p;
             a.N = n; a.H = x.H; a.W = x.W; a.Cin = x.C; a.Cout = out.C; a.KH = a.KW = r.k; a.relu = 1; a.pool = pool ? 1 : 0;
-            check(launch_conv_mfma(c->stream, a), "conv_mfma");
+            check(launch_conv_mfma(ps.stream, a), "conv_mfma");
         }
     }
 
@@ -158,14 +159,14 @@ struct Graph {
                 a.x = x.p; a.w = r.w0; a.out = t.p;
                 a.N = n; a.H = H; a.W = W; a.Cin = r.cin; a.CinPad = x.C; a.Cout = r.cout; a.CoutPad = t.C;
                 a.KH = a.KW = r.k; a.relu = 1;
-                { KScope ks(c, K_SMALL, 2.0 * px * r.cout * r.cin * r.k * r.k); check(launch_conv_direct(c->stream, a), "conv_direct"); }
+                { KScope ks(c, ps.stream, K_SMALL, 2.0 * px * r.cout * r.cin * r.k * r.k); check(launch_conv_direct(ps.stream, a), "conv_direct"); }
                 ConvDirectArgs b{};
                 b.x = t.p; b.w = r.w2; b.out = y.p;
                 b.N = n; b.H = H; b.W = W; b.Cin = r.cout; b.CinPad = t.C; b.Cout = r.cout; b.CoutPad = y.C;
                 b.KH = b.KW = r.k; b.relu = 1;
                 if (r.has_sc) { b.x_sc = x.p; b.w_sc = r.wsc; b.Csc = r.cin; b.CscPad = x.C; }
                 else b.res = x.p;
-                { KScope ks(c, K_SMALL, 2.0 * px * r.cout * (r.cout * r.k * r.k + (r.has_sc ? r.cin : 0))); check(launch_conv_direct(c->stream, b), "conv_direct"); }
+                { KScope ks(c, ps.stream, K_SMALL, 2.0 * px * r.cout * (r.cout * r.k * r.k + (r.has_sc ? r.cin : 0))); check(launch_conv_direct(ps.stream, b), "conv_direct"); }
             }
             note(t, name + ".t", seg, r.cout);
             note(y, name, seg, r.cout);
@@ -212,8 +213,8 @@ struct Graph {
                    h2() ? w.stem_wh : nullptr, std::ldexp(1.f, -w.stem_k - e0), sat()};
         const int cin = (luma ? 1 : 3) + (msbd ? 1 : 0), k1 = luma ? 9 : 5, k2 = luma ? 5 : 3;
         const double macs = msbd ? (double)cin * (k1 * k1 * 16 + 2 * k1 * k2 * 8) : (double)cin * k1 * k1 * 32;
-        KScope ks(c, K_STEM, 2.0 * n * S * S * macs);
-        check(launch_stem(c->stream, luma, msbd, a), "stem");
+        KScope ks(c, ps.stream, K_STEM, 2.0 * n * S * S * macs);
+        check(launch_stem(ps.stream, luma, msbd, a), "stem");
         note(o, "stem", seg, 32);
         return o;
     }
@@ -238,8 +239,8 @@ struct Graph {
             a.w0 = r.w0h; a.w2 = r.w2h; a.wsc = r.wsch; a.s0 = std::ldexp(1.f, -r.k0); a.s2 = std::ldexp(1.f, -r.k2);
             a.out = y.s(); a.out_stride = y.stride; a.sat = sat(); a.N = n; a.H = S; a.W = S; a.cin_groups = 1; a.cout_groups = 2;
             a.q = q; a.bt = bt; a.dire = dire; a.att_layer = layer; a.att_scale = std::ldexp(1.f, -E(seg));
-            KScope ks(c, K_CONV_OTHER, 2.0 * n * S * S * r.cout * (r.cin * 9 + r.cout * 9 + r.cin));
-            check(launch_rbfuse32(c->stream, a), "rbfuse32(att)");
+            KScope ks(c, ps.stream, K_CONV_OTHER, 2.0 * n * S * S * r.cout * (r.cin * 9 + r.cout * 9 + r.cin));
+            check(launch_rbfuse32(ps.stream, a), "rbfuse32(att)");
         }
         tap(y, name, seg, r.cout);
         return y;
@@ -260,8 +261,8 @@ struct Graph {
             if (pool_f32) a.out_f32 = y.p; else { a.out = y.s(); a.out_stride = y.stride; }
             a.sat = sat(); a.N = n; a.H = H; a.W = W; a.cin_groups = r.cin_pad / 16; a.cout_groups = r.cout_pad / 16; a.pool_f32 = pool_f32 ? 1 : 0;
             const double px = (double)n * H * W;
-            KScope ks(c, K_CONV_OTHER, 2.0 * px * r.cout * (r.cin * 9 + r.cout * 9 + r.cin));
-            check(launch_rbfuse32(c->stream, a), "rbfuse32");
+            KScope ks(c, ps.stream, K_CONV_OTHER, 2.0 * px * r.cout * (r.cin * 9 + r.cout * 9 + r.cin));
+            check(launch_rbfuse32(ps.stream, a), "rbfuse32");
         }
         tap(y, name, seg, r.cout);
         release(x);
@@ -287,8 +288,8 @@ struct Graph {
     {
         if (!live()) return;
         HeadArgs a{x.p, head_weights(slot, layer), w.head_b[slot], qt, bt, dire, n, x.H, layer};
-        KScope ks(c, K_SMALL, 2.0 * n * x.H * x.W * 72.0 * (layer < 0 ? 1 : 2));
-        check(launch_head(c->stream, a), "head");
+        KScope ks(c, ps.stream, K_SMALL, 2.0 * n * x.H * x.W * 72.0 * (layer < 0 ? 1 : 2));
+        check(launch_head(ps.stream, a), "head");
     }
 };
 
@@ -297,14 +298,14 @@ struct Graph {
 // pmp_debug_run_resblock (pmp_api.cpp): block "rb" on an input that reaches it as a trunk tensor reaches a block of the nets - split on the
 // split datapaths (the fp32 input goes through the graph's own conversion first), its bytes the block's to reuse.  A gated block is the
 // last of segment 1 and its gate a segment-0 tensor, as trunk_Att1.1 and x5 (forward_msbd); an ungated block stays in segment 0.
-int run_resblock(pmp_ctx *c, const NetWeights &w, int n, int h, int wd, const float *x_host, const float *gate_host, bool pool, bool out_f32)
+int run_resblock(pmp_ctx *c, Pass &ps, const NetWeights &w, int n, int h, int wd, const float *x_host, const float *gate_host, bool pool, bool out_f32)
 {
-    Graph g{c, w, n};
+    Graph g{c, ps, w, n};
     const RBWeights &r = w.rb.at("rb");
     g.seg = gate_host ? 1 : 0;
     auto input = [&](const float *src, int C, int sg, const char *name) {
         Act a = g.alloc(C, h, wd, false);
-        if (g.live()) g.check(hipMemcpyAsync(a.p, src, a.bytes, hipMemcpyHostToDevice, c->stream), "run_resblock: input");
+        if (g.live()) g.check(hipMemcpyAsync(a.p, src, a.bytes, hipMemcpyHostToDevice, ps.stream), "run_resblock: input");
         Act s = g.to_conv_input(a);
         if (s.p != a.p || s.off != a.off) g.release(a);
         g.tap(s, name, sg, C);
@@ -320,10 +321,10 @@ int run_resblock(pmp_ctx *c, const NetWeights &w, int n, int h, int wd, const fl
 }
 
 // {Luma,Chroma}_Q_Net.forward (Model_QBD.py:78-98, :176-196)
-int forward_q(pmp_ctx *c, bool luma, const NetWeights &w, const uint8_t *by, const uint8_t *bu, const uint8_t *bv,
+int forward_q(pmp_ctx *c, Pass &ps, bool luma, const NetWeights &w, const uint8_t *by, const uint8_t *bu, const uint8_t *bv,
               int n, float *qt)
 {
-    Graph g{c, w, n};
+    Graph g{c, ps, w, n};
     g.pfx = "q/";
     Act x2 = g.stem(luma, false, by, bu, bv, nullptr);
     Act x3 = g.rb(x2, "resblock_q1", luma);            // luma: + max_pool2d(2); chroma: no pool (:179)
@@ -339,8 +340,8 @@ int forward_q(pmp_ctx *c, bool luma, const NetWeights &w, const uint8_t *by, con
         a.x4 = x4.s(); a.x4_stride = x4.stride; a.x5 = x5.p; a.qt = qt; a.N = n; a.sat = g.sat();
         a.d_w0 = q6->second.w0; a.d_w2 = q6->second.w2; a.d_wsc = q6->second.wsc; a.head_w = w.head_w[0]; a.head_b = w.head_b[0];
         if (g.live()) {
-            KScope ks(c, K_CONV_OTHER, flops);
-            g.check(launch_qt_tail16(c->stream, a), "qt_tail16");
+            KScope ks(c, ps.stream, K_CONV_OTHER, flops);
+            g.check(launch_qt_tail16(ps.stream, a), "qt_tail16");
         }
         g.tap(x5, "resblock_q3", g.seg, 32);
         g.release(x5);
@@ -350,8 +351,8 @@ int forward_q(pmp_ctx *c, bool luma, const NetWeights &w, const uint8_t *by, con
     Act x5 = g.rb(x4, "resblock_q3", false, nullptr, true);   // fp32: read by the multi-scale pool kernel
     Act x6 = g.alloc(128, 16, 16, g.x6());
     if (g.live()) {
-        KScope ks(c, K_SMALL, 0.0);
-        g.check(launch_multipool_concat(c->stream, x5.p, x6.split ? nullptr : x6.p, n, x6.split ? x6.s() : nullptr, x6.stride, g.fmt(), g.sat()), "multipool_concat");
+        KScope ks(c, ps.stream, K_SMALL, 0.0);
+        g.check(launch_multipool_concat(ps.stream, x5.p, x6.split ? nullptr : x6.p, n, x6.split ? x6.s() : nullptr, x6.stride, g.fmt(), g.sat()), "multipool_concat");
     }
     g.tap(x6, "x6", g.seg, 128);
     g.release(x5);
@@ -364,10 +365,10 @@ int forward_q(pmp_ctx *c, bool luma, const NetWeights &w, const uint8_t *by, con
 }
 
 // {Luma,Chroma}_MSBD_Net.forward (Model_QBD.py:127-155, :225-253)
-int forward_msbd(pmp_ctx *c, bool luma, const NetWeights &w, const uint8_t *by, const uint8_t *bu, const uint8_t *bv,
+int forward_msbd(pmp_ctx *c, Pass &ps, bool luma, const NetWeights &w, const uint8_t *by, const uint8_t *bu, const uint8_t *bv,
                  const float *qt, int n, float *bt, float *dire)
 {
-    Graph g{c, w, n};
+    Graph g{c, ps, w, n};
     g.pfx = "bd/";
     Act x = g.stem(luma, true, by, bu, bv, qt);
     x = g.rb(x, "trunk_M1.0");
@@ -391,8 +392,8 @@ int forward_msbd(pmp_ctx *c, bool luma, const NetWeights &w, const uint8_t *by, 
         a.att_scale = std::ldexp(1.f, -g.E(1));
         for (int i = 0; i < 2; ++i) { a.head_w[i] = g.head_weights(i, i); a.head_b[i] = w.head_b[i]; }
         if (g.live()) {
-            KScope ks(c, K_CONV_OTHER, flops);
-            g.check(launch_msbd_branch16(c->stream, a), "msbd_branch16");
+            KScope ks(c, ps.stream, K_CONV_OTHER, flops);
+            g.check(launch_msbd_branch16(ps.stream, a), "msbd_branch16");
         }
         g.tap(xb, "trunk_Att1.1", 2, 64);
         g.release(xb);
@@ -408,8 +409,8 @@ int forward_msbd(pmp_ctx *c, bool luma, const NetWeights &w, const uint8_t *by, 
         g.seg = 1;
         Act ai = g.alloc(16, 16, 16, g.x6());
         if (g.live()) {
-            KScope ks(c, K_SMALL, 0.0);
-            g.check(launch_att_input(c->stream, qt, bt, dire, 0, ai.split ? nullptr : ai.p, n, 16, ai.split ? ai.s() : nullptr, ai.stride, g.fmt(), g.sat(), std::ldexp(1.f, -g.E(1))), "att_input");
+            KScope ks(c, ps.stream, K_SMALL, 0.0);
+            g.check(launch_att_input(ps.stream, qt, bt, dire, 0, ai.split ? nullptr : ai.p, n, 16, ai.split ? ai.s() : nullptr, ai.stride, g.fmt(), g.sat(), std::ldexp(1.f, -g.E(1))), "att_input");
         }
         g.note(ai, "att_input1", 1, 3);
         Act a1 = g.rb(ai, "trunk_Att1.0");
@@ -430,8 +431,8 @@ int forward_msbd(pmp_ctx *c, bool luma, const NetWeights &w, const uint8_t *by, 
     } else {
         Act aj = g.alloc(16, 32, 32, g.x6());
         if (g.live()) {
-            KScope ks(c, K_SMALL, 0.0);
-            g.check(launch_att_input(c->stream, qt, bt, dire, 1, aj.split ? nullptr : aj.p, n, 32, aj.split ? aj.s() : nullptr, aj.stride, g.fmt(), g.sat(), std::ldexp(1.f, -g.E(3))), "att_input");
+            KScope ks(c, ps.stream, K_SMALL, 0.0);
+            g.check(launch_att_input(ps.stream, qt, bt, dire, 1, aj.split ? nullptr : aj.p, n, 32, aj.split ? aj.s() : nullptr, aj.stride, g.fmt(), g.sat(), std::ldexp(1.f, -g.E(3))), "att_input");
         }
         g.note(aj, "att_input2", 3, 3);
         a2 = g.rb(aj, "trunk_Att2.0");

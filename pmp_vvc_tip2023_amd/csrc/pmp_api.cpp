@@ -71,20 +71,24 @@ static bool take_parked(int device, size_t bytes, DevBuf &out)
 
 int ensure(pmp_ctx *c, DevBuf &b, size_t bytes)
 {
-    if ((&b == &c->ws || &b == &c->ws2) && bytes > b.cap && bytes >= ((size_t)64 << 20)) {   // a large activation workspace: a parked one of a destroyed context first (small ones are cheap to allocate and stay small)
-        DevBuf got;
-        if (take_parked(c->device, bytes, got)) {
-            if (b.p) hipFree(b.p);
-            b = got;
-            return PMP_OK;
-        }
-    }
     if (bytes <= b.cap) return PMP_OK;
     if (b.p) { hipFree(b.p); b.p = nullptr; b.cap = 0; }
     hipError_t e = hipMalloc(&b.p, bytes);
     if (e != hipSuccess) { b.p = nullptr; return set_err(c, PMP_E_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e)); }
     b.cap = bytes;
     return PMP_OK;
+}
+
+// A pass's activation workspace: a large one takes a parked one of a destroyed context first (small ones are cheap to allocate and stay small)
+static int ensure_workspace(pmp_ctx *c, DevBuf &b, size_t bytes)
+{
+    DevBuf got;
+    if (bytes > b.cap && bytes >= ((size_t)64 << 20) && take_parked(c->device, bytes, got)) {
+        if (b.p) hipFree(b.p);
+        b = got;
+        return PMP_OK;
+    }
+    return ensure(c, b, bytes);
 }
 
 // ---- kernel-class timing ---------------------------------------------------------------------------------
@@ -96,15 +100,15 @@ static hipEvent_t get_event(pmp_ctx *c)
     return e;
 }
 
-KScope::KScope(pmp_ctx *c_, int cls_, double flops_) : c(c_), cls(cls_), on(false), a(nullptr), b(nullptr), flops(flops_)
+KScope::KScope(pmp_ctx *c_, hipStream_t stream_, int cls_, double flops_) : c(c_), stream(stream_), cls(cls_), on(false), a(nullptr), b(nullptr), flops(flops_)
 {
     on = (c->kmask >> cls) & 1u;
-    if (on) { a = get_event(c); b = get_event(c); hipEventRecord(a, c->stream); }
+    if (on) { a = get_event(c); b = get_event(c); hipEventRecord(a, stream); }
 }
 
 KScope::~KScope()
 {
-    if (on) { hipEventRecord(b, c->stream); c->krec[cls].push_back(KTimeRec{a, b, flops}); }
+    if (on) { hipEventRecord(b, stream); c->krec[cls].push_back(KTimeRec{a, b, flops}); }
 }
 
 static void ktime_drain(pmp_ctx *c)
@@ -127,52 +131,50 @@ NetWeights *find_net(pmp_ctx *c, int net_id, int qp)
     return (it == c->nets.end() || !it->second.loaded) ? nullptr : &it->second;
 }
 
-static int sync(pmp_ctx *c);
+static int poison_byte(const pmp_ctx *c) { return c->poison == 1 ? 0xFF : 0x3C; }   // pmp_debug_poison_workspace: NaN bytes or finite garbage
 
 // Runs forward (measure pass, then real) for n <= chunk blocks.
-template <typename F>
-static int run_graph(pmp_ctx *c, F &&fwd)
+int run_graph(pmp_ctx *c, Pass &ps, const std::function<int()> &fwd)
 {
-    c->arena.measuring = true;
-    c->arena.reset();
+    Arena &ar = ps.arena;
+    ar.measuring = true;
+    ar.reset();
     int rc = fwd();
     if (rc != PMP_OK) return rc;
-    if ((rc = ensure(c, c->ws, c->arena.peak)) != PMP_OK) return rc;
-    if (c->arena.peak > c->ws_need) c->ws_need = c->arena.peak;
-    c->arena.base = static_cast<char *>(c->ws.p);
-    c->arena.cap = c->ws.cap;
-    c->arena.measuring = false;
-    c->arena.reset();
-    if (c->poison && c->ws.p) {   // pmp_debug_poison_workspace: the whole buffer (own, second or taken over), stream-ordered before the pass
-        const hipError_t e = hipMemsetAsync(c->ws.p, c->poison == 1 ? 0xFF : 0x3C, c->ws.cap, c->stream);
+    if ((rc = ensure_workspace(c, ps.ws, ar.peak)) != PMP_OK) return rc;
+    if (ps.caller && ar.peak > c->ws_need) c->ws_need = ar.peak;
+    ar.base = static_cast<char *>(ps.ws.p);
+    ar.cap = ps.ws.cap;
+    ar.measuring = false;
+    ar.reset();
+    if (c->poison && ps.ws.p) {   // pmp_debug_poison_workspace: the whole buffer (own, second or taken over), stream-ordered before the pass
+        const hipError_t e = hipMemsetAsync(ps.ws.p, poison_byte(c), ps.ws.cap, ps.stream);
         if (e != hipSuccess) return hip_fail(c, e, "poison workspace");
     }
     return fwd();
 }
 
-int run_graph_fn(pmp_ctx *c, const std::function<int()> &fwd) { return run_graph(c, fwd); }   // for calibrate.cpp
-
-static int infer_passes(pmp_ctx *c, bool luma, NetWeights &wq, NetWeights &wb, const uint8_t *by, const uint8_t *bu,
+// The passes of one inference call on datapath `precision`; taps: record its tensors (pmp_debug_set_taps).
+static int infer_passes(pmp_ctx *c, int precision, bool taps, bool luma, NetWeights &wq, NetWeights &wb, const uint8_t *by, const uint8_t *bu,
                         const uint8_t *bv, int64_t n, float *qt, float *bt, float *dire, const float *qt_in = nullptr)
 {
     // qt_in: teacher-forced MTT inference (pmp_infer_msbd) - the MTT net reads this map, the QT net does not run, qt is not written
     int rc0;     // weights are packed per datapath, on first use (the load packed the datapath that was current then)
-    if ((rc0 = ensure_datapath(c, wq, c->precision)) != PMP_OK || (rc0 = ensure_datapath(c, wb, c->precision)) != PMP_OK) return rc0;
+    if ((rc0 = ensure_datapath(c, wq, precision)) != PMP_OK || (rc0 = ensure_datapath(c, wb, precision)) != PMP_OK) return rc0;
     // f16x3: the MTT net's activation scales, from one calibration pass when the net is first used on this datapath
-    if (c->precision == PMP_PRECISION_F16X3 && c->act_scales && !wb.calibrated && (rc0 = calibrate_mtt(c, luma, wq, wb)) != PMP_OK) return rc0;
-    if ((rc0 = abl_prepare_pass(c, wq, wb)) != PMP_OK) return rc0;
+    if (precision == PMP_PRECISION_F16X3 && c->act_scales && !wb.calibrated && (rc0 = calibrate_mtt(c, luma, wq, wb)) != PMP_OK) return rc0;
+    if ((rc0 = abl_prepare_pass(c, precision, wq, wb)) != PMP_OK) return rc0;
     // Overlap mode: a call of at least 1024 blocks runs as (at least) two chunks, even ones on the context's stream and workspace, odd
     // ones on a second stream with a second workspace, so that one chunk's small launches (stems, 16x16 tails, HBM-bound 32x32 layers)
     // run beside the other's 64x64 convolutions.  Blocks are independent: the results do not depend on how a call is cut.
     const bool overlap = c->overlap && n >= 1024;
     int64_t chunk = c->chunk;
     if (overlap && (n + 1) / 2 < chunk) chunk = (n + 1) / 2;
-    hipStream_t main_stream = c->stream;
     if (overlap) {
         hipError_t e = hipSuccess;
         if (!c->stream2) e = hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking);
         hipEvent_t ev = get_event(c);
-        if (e == hipSuccess) e = hipEventRecord(ev, main_stream);            // fork: the second stream starts behind everything enqueued so far
+        if (e == hipSuccess) e = hipEventRecord(ev, c->stream);              // fork: the second stream starts behind everything enqueued so far
         if (e == hipSuccess) e = hipStreamWaitEvent(c->stream2, ev, 0);
         c->event_pool.push_back(ev);
         if (e != hipSuccess) return hip_fail(c, e, "overlap: fork");
@@ -185,15 +187,14 @@ static int infer_passes(pmp_ctx *c, bool luma, NetWeights &wq, NetWeights &wb, c
         float *q = qt_in ? nullptr : qt + o * 64;
         const float *qi = qt_in ? qt_in + o * 64 : q;
         const bool side = overlap && (k & 1);
-        if (side) { c->stream = c->stream2; std::swap(c->ws, c->ws2); }
-        if (!qt_in) rc = run_graph(c, [&] { return forward_q(c, luma, wq, y, u, v, m, q); });
-        if (rc == PMP_OK) rc = run_graph(c, [&] { return forward_msbd(c, luma, wb, y, u, v, qi, m, bt + o * 768, dire + o * 768); });
-        if (side) { c->stream = main_stream; std::swap(c->ws, c->ws2); }
+        Pass ps{side ? c->stream2 : c->stream, side ? c->ws2 : c->ws, precision, taps, /*cal*/ false, /*caller*/ true};
+        if (!qt_in) rc = run_graph(c, ps, [&] { return forward_q(c, ps, luma, wq, y, u, v, m, q); });
+        if (rc == PMP_OK) rc = run_graph(c, ps, [&] { return forward_msbd(c, ps, luma, wb, y, u, v, qi, m, bt + o * 768, dire + o * 768); });
     }
     if (overlap) {
         hipEvent_t ev = get_event(c);
         hipError_t e = hipEventRecord(ev, c->stream2);                       // join: the caller's stream continues behind both
-        if (e == hipSuccess) e = hipStreamWaitEvent(main_stream, ev, 0);
+        if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, ev, 0);
         c->event_pool.push_back(ev);
         if (e != hipSuccess && rc == PMP_OK) rc = hip_fail(c, e, "overlap: join");
     }
@@ -289,8 +290,9 @@ static int infer_device_impl(pmp_ctx *c, int comp, int qp, const uint8_t *by, co
     int rc = resolve_pending(c, false);          // earlier calls whose snapshot has landed by now: no wait
     if (rc != PMP_OK) return rc;
     if (c->taps_on) c->ntaps = 0;                // the taps are this call's (a re-run resolved above is recorded by nobody)
-    rc = infer_passes(c, luma, *wq, *wb, by, bu, bv, n, qt, bt, dire, qt_in);
-    if (rc != PMP_OK || c->precision != PMP_PRECISION_F16X3 || c->sat_policy == PMP_SAT_IGNORE || n == 0) return rc;
+    const int precision = c->precision;          // the datapath at enqueue: a re-run that did not fire runs on it again
+    rc = infer_passes(c, precision, c->taps_on != 0, luma, *wq, *wb, by, bu, bv, n, qt, bt, dire, qt_in);
+    if (rc != PMP_OK || precision != PMP_PRECISION_F16X3 || c->sat_policy == PMP_SAT_IGNORE || n == 0) return rc;
     // f16x3 range guard: snapshot the flag behind this call's passes and reset it for the next call - all stream-ordered, the host
     // does not wait.  Whoever looks at the snapshot later (resolve_pending) re-runs the call on the fp32 MFMA datapath if it fired.
     if (count_pending_infer(c) >= PMP_SAT_SLOTS && (rc = resolve_pending(c, true)) != PMP_OK) return rc;
@@ -307,13 +309,8 @@ static int infer_device_impl(pmp_ctx *c, int comp, int qp, const uint8_t *by, co
         // fired: the exact fp32 MFMA datapath - fp32's range, a bit-exact fmaf chain, and on the full-size campaign the closest of the
         // three to the oracle (profiles/r03_parity_campaign.txt: 5.5e-4 against bf16x6's 8.9e-4 on the worst block); its speed does not
         // matter for a call that is this rare.  Not fired: the call's logits were in the context's buffers, which an earlier re-run has
-        // overwritten - the same call again, on the datapath it ran on.
-        if (fired) c->precision = PMP_PRECISION_F32;
-        c->tap_skip = 1;          // pmp_debug_set_taps records the call as it first ran, not its re-run
-        const int r2 = infer_passes(c, luma, *rq, *rb, by, bu, bv, n, qt, bt, dire, qt_in);   // teacher-forced: the MTT net only
-        c->tap_skip = 0;
-        c->precision = PMP_PRECISION_F16X3;
-        return r2;
+        // overwritten - the same call again, on the datapath it ran on.  No taps: pmp_debug_set_taps records the call as it first ran.
+        return infer_passes(c, fired ? PMP_PRECISION_F32 : precision, false, luma, *rq, *rb, by, bu, bv, n, qt, bt, dire, qt_in);   // teacher-forced: the MTT net only
     }});
     return PMP_OK;
 }
@@ -321,7 +318,7 @@ static int infer_device_impl(pmp_ctx *c, int comp, int qp, const uint8_t *by, co
 static int post_launch(pmp_ctx *c, int comp, const M2PParams &prm, const float *qt, const float *bt, const float *dire, int64_t n,
                        uint8_t *hor, uint8_t *ver, uint8_t *qt_u8, int8_t *dire_i8, int record_stride)
 {
-    KScope ks(c, K_POST, 0.0);
+    KScope ks(c, c->stream, K_POST, 0.0);
     hipError_t e = launch_postprocess(c->stream, qt, bt, dire, n, comp == PMP_LUMA ? 1 : 2, prm, hor, ver, qt_u8, dire_i8, record_stride);
     return e == hipSuccess ? PMP_OK : hip_fail(c, e, "postprocess");
 }
@@ -353,7 +350,7 @@ static int ensure_logits(pmp_ctx *c, int64_t n)
     for (int i = 0; i < 3; ++i) {
         if ((rc = ensure(c, c->d_logit[i], need[i])) != PMP_OK) return rc;
         if (c->poison) {          // pmp_debug_poison_workspace: whoever uses them next must write every byte it later reads
-            const hipError_t e = hipMemsetAsync(c->d_logit[i].p, c->poison == 1 ? 0xFF : 0x3C, need[i], c->stream);
+            const hipError_t e = hipMemsetAsync(c->d_logit[i].p, poison_byte(c), need[i], c->stream);
             if (e != hipSuccess) return hip_fail(c, e, "poison logits");
         }
     }
@@ -375,14 +372,14 @@ int settle(pmp_ctx *c)
 
 // pmp_debug_set_taps: the tensor a kernel has just written, copied on the same stream right behind that launch - later launches
 // (an identity-shortcut block writing its output in place, a tensor reusing freed arena bytes) cannot reach it before the copy.
-int tap_record(pmp_ctx *c, const std::string &name, const void *p, int n, int C, int H, int W, int c_real, int fmt, int exp)
+int tap_record(pmp_ctx *c, hipStream_t stream, const std::string &name, const void *p, int n, int C, int H, int W, int c_real, int fmt, int exp)
 {
     const size_t bytes = (size_t)n * C * H * W * (fmt == 1 ? 6 : 4);
     if (c->ntaps >= (int)c->taps.size()) c->taps.emplace_back();
     TapRec &t = c->taps[c->ntaps];
     int rc = ensure(c, t.buf, bytes);
     if (rc != PMP_OK) return rc;
-    const hipError_t e = hipMemcpyAsync(t.buf.p, p, bytes, hipMemcpyDeviceToDevice, c->stream);
+    const hipError_t e = hipMemcpyAsync(t.buf.p, p, bytes, hipMemcpyDeviceToDevice, stream);
     if (e != hipSuccess) return hip_fail(c, e, "tap copy");
     t.name = name; t.n = n; t.C = C; t.H = H; t.W = W; t.c_real = c_real; t.fmt = fmt; t.exp = exp;
     ++c->ntaps;
@@ -424,8 +421,6 @@ static int d2h(pmp_ctx *c, void *dst, const void *src, size_t bytes)
 }  // namespace pmp
 
 using namespace pmp;
-
-#define CHECK_CTX(c) do { if (!(c)) return set_err(nullptr, PMP_E_INVALID, "null context"); hipSetDevice((c)->device); } while (0)
 
 extern "C" {
 
@@ -589,25 +584,49 @@ int pmp_clear_saturation(pmp_ctx *c)
     return rc;
 }
 
-int pmp_load_weights(pmp_ctx *c, int net_id, int qp, const float *blob, const pmp_tensor_desc *descs, int ndesc)
+// The two loaders' common end.  wf: the file the tensors came from (its manifest may carry the activation-scale exponents), or null.
+static int load_weights(pmp_ctx *c, int net_id, int qp, const float *blob, const pmp_tensor_desc *descs, int ndesc, const WeightFile *wf)
 {
-    CHECK_CTX(c);
     // REPLACING a net waits for the calls in flight (a range-guard re-run must still find the weights it ran with, and kernels may
     // be reading them); ADDING one does not - the upload runs next to whatever the stream is doing, so a driver can load the next
     // (component, QP) while the GPU works on this one
-    int rc = pmp_has_weights(c, net_id, qp) ? settle(c) : PMP_OK;
+    int rc = find_net(c, net_id, qp) ? settle(c) : PMP_OK;
     if (rc != PMP_OK) return rc;
     if ((rc = load_net_weights(c, net_id, qp, blob, descs, ndesc)) != PMP_OK) return rc;
     if (net_id == PMP_NET_LUMA_Q || net_id == PMP_NET_CHROMA_Q) qt_partner_changed(c, net_id, qp);
+    if (wf && wf->act_exp.size() == 5 && (net_id == PMP_NET_LUMA_MSBD || net_id == PMP_NET_CHROMA_MSBD)) {
+        // The file carries its activation-scale exponents (tools/calibrate_pmpw.py calibrated once): nothing to run here - IF they belong
+        // to these tensors.  The reader has bounded them (pmpw_file.cpp); "act_fp" says which tensors and which QT partner they were
+        // calibrated on: a manifest whose fingerprints do not match (tensors edited, the QT net replaced since) is stale, and its
+        // exponents are ignored in favour of a calibration pass.  A QT partner that is not loaded yet is checked when it arrives.
+        NetWeights *nw = find_net(c, net_id, qp);
+        NetWeights *wq = find_net(c, net_id == PMP_NET_LUMA_MSBD ? PMP_NET_LUMA_Q : PMP_NET_CHROMA_Q, qp);
+        const bool stale = wf->have_fp && (wf->act_mtt_fp != nw->fp || (wq && wf->act_qt_fp != wq->fp));
+        if (!stale) {
+            if ((rc = set_activation_scales(c, *nw, wf->act_exp.data())) != PMP_OK) return rc;
+            nw->calibrated = true;
+            nw->act_from_file = true;
+            nw->act_fp_known = wf->have_fp;
+            nw->act_qt_fp = wf->act_qt_fp;
+            nw->cal_names.clear(); nw->cal_seg.clear(); nw->cal_amax.clear();
+            return PMP_OK;
+        }
+    }
     return calibrate_if_ready(c, net_id, qp);
+}
+
+int pmp_load_weights(pmp_ctx *c, int net_id, int qp, const float *blob, const pmp_tensor_desc *descs, int ndesc)
+{
+    CHECK_CTX(c);
+    return load_weights(c, net_id, qp, blob, descs, ndesc, nullptr);
 }
 
 int pmp_weights_fingerprint(const pmp_ctx *c, int net_id, int qp, uint64_t *out)
 {
     if (!c || !out) return set_err(nullptr, PMP_E_INVALID, "pmp_weights_fingerprint: null argument");
-    auto it = c->nets.find(net_id * 100 + qp);
-    if (it == c->nets.end() || !it->second.loaded) return PMP_E_NOWEIGHTS;
-    *out = it->second.fp;
+    const NetWeights *w = find_net(const_cast<pmp_ctx *>(c), net_id, qp);
+    if (!w) return PMP_E_NOWEIGHTS;
+    *out = w->fp;
     return PMP_OK;
 }
 
@@ -627,36 +646,10 @@ int pmp_load_weights_file(pmp_ctx *c, int net_id, int qp, const char *path)
         for (int j = 0; j < 4; ++j) descs[i].shape[j] = wf.tensors[i].shape[j];
         descs[i].offset = wf.tensors[i].offset;
     }
-    if (pmp_has_weights(c, net_id, qp) && (rc = settle(c)) != PMP_OK) return rc;   // see pmp_load_weights
-    if ((rc = load_net_weights(c, net_id, qp, wf.payload.data(), descs.data(), (int)descs.size())) != PMP_OK) return rc;
-    if (net_id == PMP_NET_LUMA_Q || net_id == PMP_NET_CHROMA_Q) qt_partner_changed(c, net_id, qp);
-    if (wf.act_exp.size() == 5 && (net_id == PMP_NET_LUMA_MSBD || net_id == PMP_NET_CHROMA_MSBD)) {
-        // The file carries its activation-scale exponents (tools/calibrate_pmpw.py calibrated once): nothing to run here - IF they belong
-        // to these tensors.  The reader has bounded them (pmpw_file.cpp); "act_fp" says which tensors and which QT partner they were
-        // calibrated on: a manifest whose fingerprints do not match (tensors edited, the QT net replaced since) is stale, and its
-        // exponents are ignored in favour of a calibration pass.  A QT partner that is not loaded yet is checked when it arrives.
-        NetWeights *nw = find_net(c, net_id, qp);
-        NetWeights *wq = find_net(c, net_id == PMP_NET_LUMA_MSBD ? PMP_NET_LUMA_Q : PMP_NET_CHROMA_Q, qp);
-        const bool stale = wf.have_fp && (wf.act_mtt_fp != nw->fp || (wq && wf.act_qt_fp != wq->fp));
-        if (!stale) {
-            if ((rc = set_activation_scales(c, *nw, wf.act_exp.data())) != PMP_OK) return rc;
-            nw->calibrated = true;
-            nw->act_from_file = true;
-            nw->act_fp_known = wf.have_fp;
-            nw->act_qt_fp = wf.act_qt_fp;
-            nw->cal_names.clear(); nw->cal_seg.clear(); nw->cal_amax.clear();
-            return PMP_OK;
-        }
-    }
-    return calibrate_if_ready(c, net_id, qp);
+    return load_weights(c, net_id, qp, wf.payload.data(), descs.data(), (int)descs.size(), &wf);
 }
 
-int pmp_has_weights(const pmp_ctx *c, int net_id, int qp)
-{
-    if (!c) return 0;
-    auto it = c->nets.find(net_id * 100 + qp);
-    return it != c->nets.end() && it->second.loaded;
-}
+int pmp_has_weights(const pmp_ctx *c, int net_id, int qp) { return c && find_net(const_cast<pmp_ctx *>(c), net_id, qp); }
 
 int pmp_set_partition_params(pmp_ctx *c, int comp, const pmp_partition_params *p)
 {
@@ -907,7 +900,7 @@ int pmp_msbt_labels(pmp_ctx *c, int cf, const uint8_t *qt, const uint8_t *bt, co
         const int64_t m = (n - o) < chunk ? (n - o) : chunk;
         if (c->poison) {          // pmp_debug_poison_workspace: the kernel must write every output byte it hands back
             for (int i = 3; i < 5; ++i) {
-                const hipError_t e = hipMemsetAsync(c->d_lab[i].p, c->poison == 1 ? 0xFF : 0x3C, (size_t)m * per[i], c->stream);
+                const hipError_t e = hipMemsetAsync(c->d_lab[i].p, poison_byte(c), (size_t)m * per[i], c->stream);
                 if (e != hipSuccess) return hip_fail(c, e, "poison label buffers");
             }
         }
@@ -1207,7 +1200,8 @@ int pmp_debug_run_resblock(pmp_ctx *c, const pmp_rb_case *k, const float *x, con
     if (rc == PMP_OK) {
         c->ntaps = 0;
         launch_log = &log;
-        rc = run_graph_fn(c, [&] { return run_resblock(c, nw, k->n, k->h, k->w, xb.data(), k->gate ? gb.data() : nullptr, k->pool != 0, k->out_f32 != 0); });
+        Pass ps{c->stream, c->ws, c->precision, /*taps*/ true, /*cal*/ false, /*caller*/ true};
+        rc = run_graph(c, ps, [&] { return run_resblock(c, ps, nw, k->n, k->h, k->w, xb.data(), k->gate ? gb.data() : nullptr, k->pool != 0, k->out_f32 != 0); });
         launch_log = nullptr;
         const hipError_t e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess && rc == PMP_OK) rc = hip_fail(c, e, "pmp_debug_run_resblock");

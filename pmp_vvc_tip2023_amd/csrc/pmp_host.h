@@ -73,7 +73,7 @@ struct NetWeights {
 
 // Activation workspace: a first-fit free-list allocator over one device buffer.  Every forward runs twice - a measuring
 // pass (no launches) that replays the graph's alloc/release sequence to find the peak, then the real pass, which makes the
-// same calls and therefore gets the same offsets.  All launches of a context go to one stream in order, so a tensor's
+// same calls and therefore gets the same offsets.  All launches of a pass go to one stream in order, so a tensor's
 // bytes may be handed out again as soon as its last consumer has been ENQUEUED (Graph::release).
 struct Arena {
     char *base = nullptr;
@@ -112,6 +112,18 @@ struct Arena {
     float *ptr(size_t off) const { return measuring ? nullptr : reinterpret_cast<float *>(base + off); }
 };
 
+// What one forward pass runs on and how: built on the stack by whoever starts the pass (infer_passes, calibrate_mtt,
+// pmp_debug_run_resblock) and handed down to the graph, which reads its environment here and never from the context.
+struct Pass {
+    hipStream_t stream;                // every launch of the pass
+    DevBuf &ws;                        // its activation workspace: c->ws, c->ws2 (odd chunks in overlap mode) or c->ws_cal
+    int precision;                     // datapath, PMP_PRECISION_*
+    bool taps;                         // pmp_debug_set_taps: record every tensor (a call's first run only: no re-run, no calibration)
+    bool cal;                          // calibration of an MTT net: fold every tensor's largest |value| into c->d_cal
+    bool caller;                       // a pass of the caller's own calls: its peak counts in c->ws_need
+    Arena arena;                       // host bookkeeping of one graph run (run_graph)
+};
+
 struct KTimeRec { hipEvent_t a, b; double flops; };
 
 // pmp_debug_set_taps: a stream-ordered copy of one tensor as the consuming kernel reads it (raw planes, blocked layout)
@@ -141,9 +153,9 @@ struct PendingCall {
 
 struct pmp_ctx {
     int device = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
+    hipStream_t own_stream = nullptr, stream = nullptr;   // stream: the caller's (pmp_set_stream); a pass runs on its Pass::stream
     int chunk = 4096;   // blocks per pass: the 16x16-resolution layers need >= 4096 tiles to fill 256 CUs x 3 workgroups evenly (+2.5 % over 1024)
-    int precision = 2;                     // 0: fp32 MFMA, 1: bf16x6 split, 2: f16x3 split (default; both splits fp32-equivalent)
+    int precision = 2;                     // 0: fp32 MFMA, 1: bf16x6 split, 2: f16x3 split (default; both splits fp32-equivalent) - the caller's setting; a pass runs on its Pass::precision
     int fuse16 = 1;                        // f16x3: run the 16x16-resolution tails LDS-resident (chain16.hip: two / three launches per net); 0 = launch per layer (pmp_debug_set_fusion: A/B and the bit-identity tests)
     int act_scales = 1;                    // f16x3: use the MTT nets' calibrated activation scales (NetWeights::act_exp); 0 = exponents of zero (pmp_debug_set_activation_scales: the range-guard tests)
     int fuse32 = 1;                        // f16x3: trunk_B3.1 / B3.2 / Att2.0 (32x32, <= 32 output channels) as one launch per ResidualBlock (rbfuse32.hip); same hook
@@ -158,22 +170,20 @@ struct pmp_ctx {
     pmp::AblCtx abl;                       // empty in the product library
     int sat_policy = PMP_SAT_RERUN;
     int sat_seen = 0;                      // sticky: some inference call since pmp_clear_saturation saturated
-    int64_t sat_reruns = 0;                // calls re-run on the bf16x6 datapath
+    int64_t sat_reruns = 0;                // calls re-run on the fp32 MFMA datapath
     std::map<int, pmp::NetWeights> nets;  // key = net_id * 100 + qp
-    pmp::Arena arena;
     pmp::DevBuf ws;                        // activation workspace (its own, or a larger one parked by a destroyed context)
     pmp::DevBuf ws2;                       // second workspace: the passes of odd chunks on `stream2` (overlap mode)
     hipStream_t stream2 = nullptr;         // created on first use
     int overlap = 0;                       // two chunks in flight on two streams (PMP_OVERLAP=1 in the environment at pmp_create)
-    size_t ws_need = 0;                    // what the largest pass so far needed of it (pmp_get_workspace_bytes)
+    size_t ws_need = 0;                    // what the caller's largest pass so far needed of ws / ws2 (pmp_get_workspace_bytes)
     pmp::DevBuf d_in[3], d_logit[3], d_out[4], d_frames[3];  // staging for the host-pointer entry points
     pmp::DevBuf d_lab[5];                  // staging of pmp_msbt_labels: qt, bt, dire in; msbt, status out
     pmp::DevBuf d_val[6];                  // staging of pmp_val_stats: qt, bt, dire, qt8, msbt, msdire
     pmp::DevBuf d_valpart;                 // validation statistics: per-block partials f64[n][20] of a call that passes no d_block_stats
     pmp::DevBuf d_valout;                  // pmp_val_stats: f64[passes][20]
-    // calibration of the f16x3 activation scales (NetWeights::act_exp): while cal_on, the graph (nets.cpp, running on the fp32 datapath) folds
-    // the largest |value| of every tensor it produces into d_cal[slot] and logs (name, segment) per slot
-    int cal_on = 0;
+    // calibration of the f16x3 activation scales (NetWeights::act_exp): in a Pass with `cal`, the graph (nets.cpp, running on the fp32
+    // datapath) folds the largest |value| of every tensor it produces into d_cal[slot] and logs (name, segment) per slot
     unsigned *d_cal = nullptr;             // PMP_CAL_SLOTS device words
     std::vector<std::pair<std::string, int>> cal_log;
     pmp::DevBuf d_calbuf;                  // calibration blocks and their logits
@@ -181,7 +191,6 @@ struct pmp_ctx {
     pmp::DevBuf ws_cal;                    // context's stream nor touches their workspace (created on first use; 44 MB for 16-block fp32 passes)
     // test hooks (include/pmp.h): tensor taps and workspace poisoning
     int taps_on = 0;
-    int tap_skip = 0;                      // set while a range-guard re-run replays a call: its passes are not recorded
     std::vector<pmp::TapRec> taps;         // slots, reused call after call; the first ntaps hold the last inference call's tensors in launch order
     int ntaps = 0;
     int poison = 0;                        // 0 off, 1 0xFF bytes, 2 0x3C bytes into every activation workspace before each pass
@@ -207,12 +216,12 @@ int set_activation_scales(pmp_ctx *c, NetWeights &w, const int exps[5]);
 constexpr int PMP_CAL_SLOTS = 128;
 
 // pmp_api.cpp internals that calibrate.cpp shares
-int ensure(pmp_ctx *c, DevBuf &b, size_t bytes);                    // grow-only device buffer (large workspaces come from the parked pool first)
+int ensure(pmp_ctx *c, DevBuf &b, size_t bytes);                    // grow-only device buffer
 NetWeights *find_net(pmp_ctx *c, int net_id, int qp);               // loaded weights of (net, qp) or nullptr
-int run_graph_fn(pmp_ctx *c, const std::function<int()> &fwd);      // a forward graph twice: measuring pass, then the real one in c->ws
+int run_graph(pmp_ctx *c, Pass &ps, const std::function<int()> &fwd);   // a forward graph twice: measuring pass, then the real one in ps.ws
 int settle(pmp_ctx *c);                                             // everything asked of the context so far is done and final
-// pmp_debug_set_taps: copies a tensor just produced on c->stream into tap-owned memory (stream-ordered, before anything can overwrite it)
-int tap_record(pmp_ctx *c, const std::string &name, const void *p, int n, int C, int H, int W, int c_real, int fmt, int exp);
+// pmp_debug_set_taps: copies a tensor just produced on `stream` into tap-owned memory (stream-ordered, before anything can overwrite it)
+int tap_record(pmp_ctx *c, hipStream_t stream, const std::string &name, const void *p, int n, int C, int H, int W, int c_real, int fmt, int exp);
 
 // calibrate.cpp
 int calibrate_mtt(pmp_ctx *c, bool luma, NetWeights &wq, NetWeights &wb);
@@ -222,21 +231,23 @@ int calibrate_if_ready(pmp_ctx *c, int net_id, int qp);             // a (QT, MT
 // pmp_debug_run_resblock: one ResidualBlock "rb" packed by the loader's own load_rb into nw (the formats of `mask`); free_net_weights frees it
 int load_single_rb(pmp_ctx *c, NetWeights &nw, int cin, int cout, int k, const float *w0, const float *w2, const float *wsc, unsigned mask);
 // ... and run through the graph's rb() on n blocks; x, gate: blocked fp32 [n][C/16][h][w][16] at stored scale (host), gate may be null
-int run_resblock(pmp_ctx *c, const NetWeights &w, int n, int h, int wd, const float *x, const float *gate, bool pool, bool out_f32);
+int run_resblock(pmp_ctx *c, Pass &ps, const NetWeights &w, int n, int h, int wd, const float *x, const float *gate, bool pool, bool out_f32);
 
-// nets.cpp: forward graphs on device pointers (n <= chunk); all launches go to c->stream.
-int forward_q(pmp_ctx *c, bool luma, const NetWeights &w, const uint8_t *by, const uint8_t *bu, const uint8_t *bv,
+// nets.cpp: forward graphs on device pointers (n <= chunk); all launches go to ps.stream.
+int forward_q(pmp_ctx *c, Pass &ps, bool luma, const NetWeights &w, const uint8_t *by, const uint8_t *bu, const uint8_t *bv,
               int n, float *qt);
-int forward_msbd(pmp_ctx *c, bool luma, const NetWeights &w, const uint8_t *by, const uint8_t *bu, const uint8_t *bv,
+int forward_msbd(pmp_ctx *c, Pass &ps, bool luma, const NetWeights &w, const uint8_t *by, const uint8_t *bu, const uint8_t *bv,
                  const float *qt, int n, float *bt, float *dire);
 
 // timing hooks used by nets.cpp
 struct KScope {
-    pmp_ctx *c; int cls; bool on; hipEvent_t a, b; double flops;
-    KScope(pmp_ctx *c, int cls, double flops);
+    pmp_ctx *c; hipStream_t stream; int cls; bool on; hipEvent_t a, b; double flops;
+    KScope(pmp_ctx *c, hipStream_t stream, int cls, double flops);
     ~KScope();
 };
 
 }  // namespace pmp
+
+#define CHECK_CTX(c) do { if (!(c)) return pmp::set_err(nullptr, PMP_E_INVALID, "null context"); hipSetDevice((c)->device); } while (0)
 
 #include "abl_hooks.h"   // hooks/ in the product build (no-op inlines), abl/ in the measurement library

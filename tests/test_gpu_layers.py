@@ -299,3 +299,65 @@ def test_taps_refuse_what_they_cannot_record():
         assert _tap(e, "q/no_such_tensor") is None
     finally:
         e.close()
+
+
+def _g1_luma4():
+    from conftest import golden
+    return np.ascontiguousarray(golden("g1_qt.npz")["block_y"][:4])
+
+
+def test_taps_are_those_of_the_first_run_not_of_the_rerun():
+    """A call whose range flag fired is run again on the fp32 datapath: its logits are the fp32 datapath's, bit for bit, while its taps stay
+    those of the f16x3 run that fired - what a context that ignores the flag records, bit for bit.  Set-up of test_f16x3_range_guard
+    (tests/test_gpu_parity.py): the range-stress MTT weights with activation scales off."""
+    from test_gpu_parity import _range_stress_weights
+    from pmp_vvc_tip2023_amd import engine
+    y, w = _g1_luma4(), _range_stress_weights()
+
+    def run(precision, policy):
+        e = engine.Engine(0, allow_synthetic_mtt=True)
+        try:
+            e.set_precision(precision)
+            e.set_saturation_policy(policy)
+            e.load("Luma", 22)
+            e.load_pretrain_model("Luma_MSBD", 22, w)
+            e.set_activation_scales(False)
+            _taps_on(e, True)
+            logits = e.inference_pre_QBD("Luma", 22, y)
+            taps = {n: t[0] for n, t in ((n, _tap(e, n)) for n in _all_names()) if t is not None}     # shaped by the tap's own dims
+            return logits, taps, e.saturation_reruns()
+        finally:
+            e.close()
+    la, ta, reruns = run("f16x3", "rerun")
+    assert reruns == 1, "the range flag did not fire on these blocks: the test checks nothing"
+    _, tb, _ = run("f16x3", "ignore")
+    assert "q/stem" in tb and "bd/trunk_M1.3" in tb
+    for name, t in tb.items():
+        assert name in ta, name
+        assert ta[name].shape == t.shape, (name, ta[name].shape, t.shape)
+        assert np.array_equal(ta[name], t), "%s: the re-run was recorded" % name
+    lf, _, _ = run("fp32", "rerun")
+    for a, b in zip(la, lf):
+        assert np.array_equal(a, b), "the re-run is not the fp32 datapath"
+
+
+def test_calibration_leaves_no_taps():
+    """A pair loaded under another datapath is calibrated inside its first f16x3 call (fp32 passes of 16 blocks, launch per layer): the
+    call's taps are its own tensors only.  With fusion on q/resblock_q4 stays in LDS, so the call has no such tensor - not the calibration's."""
+    import ctypes as C
+    from pmp_vvc_tip2023_amd import _lib, engine
+    y = _g1_luma4()
+    e = engine.Engine(0, allow_synthetic_mtt=True)
+    try:
+        e.set_precision("fp32")
+        e.load("Luma", 22)
+        e.set_precision("f16x3")
+        e.set_fusion(True)
+        _taps_on(e, True)
+        e.inference_pre_QBD("Luma", 22, y)
+        assert _tap(e, "q/stem")[0].shape[0] == 4
+        with pytest.raises(_lib.PmpError) as ei:
+            e._ck(e.lib.pmp_debug_get_tap(e.h, b"q/resblock_q4", None, 0, (C.c_int * 4)(), None))
+        assert ei.value.code == -1          # PMP_E_INVALID
+    finally:
+        e.close()
