@@ -303,6 +303,42 @@ int pmp_msbt_labels(pmp_ctx *ctx, int cf, const uint8_t *qt, const uint8_t *bt, 
 int pmp_msbt_labels_device(pmp_ctx *ctx, int cf, const uint8_t *d_qt, const uint8_t *d_bt, const int8_t *d_dire, int64_t n,
                            uint8_t *d_msbt, uint8_t *d_status);
 
+/* ---- the labels' own partition: GenMSBtMap.map_to_parititon (GenMSBtMap.py:377-382) = Map_to_SubMap(qt, bt, dire, cf).get_partition()
+ *      (:262-312) per block, cropped to [:16, :16] - the split flags that GenMSBtMap.get_sequence_partition_for_VTM (:384-432) writes
+ *      into a PartitionMat file.  Such a file is a perfect predictor's: fed to the patched VTM it gives the ceiling of speed-up and
+ *      BD-rate that the map representation allows, and it needs no trained net.  Same kernel family (labels.hip), same inputs, dtypes,
+ *      thresholds, u8-wrapping leaf error, first-minimum rule and leaf budget as pmp_msbt_labels above.  What is painted, bit for bit
+ *      as the reference paints it:
+ *        - the QT walk of set_partition_vector (:294-309): a node at depth d whose qt (read at its top-left cell) exceeds d paints the
+ *          cross of its region [2qx, 2qy, 2sms, 2sms], sms = 8 >> d: hor row 2qx+sms over columns 2qy..2qy+2sms-1 and ver column 2qy+sms
+ *          over rows 2qx..2qx+2sms-1 - at d = 3 as well, where the reference then recurses on empty regions and paints nothing more
+ *          (PMP_MSBT_QT_DEEP is set); a node with qt < d paints nothing;
+ *        - a node with qt == d searches its region (set_bt_partition_vector, :262-292) and paints every CU [x, y, h, w] of the best
+ *          leaf: hor[x][y..y+w-1], hor[x+h][y..y+w-1], ver[x..x+h-1][y], ver[x..x+h-1][y+w]; row and column 16 of the reference's
+ *          u8[2][17][17] par_vec are cropped away (:382).
+ *      A best leaf above depth 3 is legal here (set_bt_partition_vector never walks a leaf's parents, so the reference does not raise):
+ *      status bit 1 (PMP_MSBT_INCONSISTENT) is NEVER set by these calls.  Status bits, OR-ed over the block's QT nodes:
+ *        PMP_MSBT_QT_DEEP  a qt value above 3 was reached at a depth-3 node: its cross is painted and nothing else (the reference's result
+ *                          for 4..~10; beyond that it recurses practically forever).
+ *        PMP_MSBT_BUDGET   a region has more than PMP_MSBT_LEAF_BUDGET leaves: the CUs of the best of the first PMP_MSBT_LEAF_BUDGET leaves,
+ *                          in the reference's order, are painted (the reference scores them all and may choose another).
+ *      Outputs: hor, ver u8[n][16][16] (0 / 1) and status u8[n]; every byte is written.  The _records form writes one packed record
+ *      u8[n][PMP_RECORD_BYTES] = hor | ver | qt | dire per block instead, qt and dire being byte copies of the inputs - what the reference
+ *      puts into the file's qt and direction sections (:407-408) - so that pmp_format_partition_rows_records and
+ *      pmp_tile_partition_rows_records take it as they take the post-processing kernel's records.  NOTE on the file: the reference casts
+ *      the direction section to u8 before printing (:413), so -1 appears as "255"; VTM reads it with stoi into an int8_t (Rom.h:247), where
+ *      255 is -1 again.  The writers of this library print "-1", as in every other PartitionMat file they write.
+ *      The same inputs give the same bits on every run (per-wave row masks combined in a fixed order, no atomics).
+ *      pmp_label_partition takes host pointers and runs in passes of at most pmp_set_chunk blocks; the _device forms take device pointers
+ *      (qt, bt, dire, hor, ver, rec 4-byte aligned: PMP_E_INVALID otherwise) and run stream-ordered on the context's stream.  n = 0 does
+ *      nothing and touches no buffer.  cf other than 1 or 2, n < 0 or a NULL pointer with n > 0: PMP_E_INVALID. ---- */
+int pmp_label_partition(pmp_ctx *ctx, int cf, const uint8_t *qt, const uint8_t *bt, const int8_t *dire, int64_t n, uint8_t *hor,
+                        uint8_t *ver, uint8_t *status);
+int pmp_label_partition_device(pmp_ctx *ctx, int cf, const uint8_t *d_qt, const uint8_t *d_bt, const int8_t *d_dire, int64_t n,
+                               uint8_t *d_hor, uint8_t *d_ver, uint8_t *d_status);
+int pmp_label_partition_records_device(pmp_ctx *ctx, int cf, const uint8_t *d_qt, const uint8_t *d_bt, const int8_t *d_dire, int64_t n,
+                                       uint8_t *d_rec, uint8_t *d_status);
+
 /* ---- validation: how well does a pair of nets predict what VTM decided.  The arithmetic of Metrics.validation_QBD (Metrics.py:313-385),
  *      Metrics.pre_validation predID 0 / 1 (:196-274) and the losses under them (loss_func_QBD_val, loss_func_MSBD_val, weight_mat,
  *      :148-194) for ONE batch of n blocks (valstats.hip).  Logits in the library's layouts - qt f32[n][8][8], bt, dire f32[n][3][16][16]

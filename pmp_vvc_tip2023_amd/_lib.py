@@ -71,6 +71,9 @@ SIGNATURES = {
     "pmp_cut_blocks_device": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP]),
     "pmp_msbt_labels": (_I, [_VP, _I, _VP, _VP, _VP, _I64, _VP, _VP]),
     "pmp_msbt_labels_device": (_I, [_VP, _I, _VP, _VP, _VP, _I64, _VP, _VP]),
+    "pmp_label_partition": (_I, [_VP, _I, _VP, _VP, _VP, _I64, _VP, _VP, _VP]),
+    "pmp_label_partition_device": (_I, [_VP, _I, _VP, _VP, _VP, _I64, _VP, _VP, _VP]),
+    "pmp_label_partition_records_device": (_I, [_VP, _I, _VP, _VP, _VP, _I64, _VP, _VP]),
     "pmp_val_stats": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
     "pmp_val_stats_device": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
     "pmp_infer_msbd": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),

@@ -16,6 +16,10 @@
 //     so a root leaf costs sum(bt)); integers, first minimum in DFS leaf order wins (:340);
 //   * outputs: the maps of the best leaf's depth-1 and depth-2 ancestors and of the leaf itself (:341-363).
 // Where the reference has no answer (include/pmp.h: pmp_msbt_labels) a status bit is set and the kernel stays bounded.
+//
+// The same search also serves Map_to_SubMap(qt, bt, dire, cf).get_partition() (:262-312, map_to_parititon :377-382): the split flags
+// of the labels' own partition (label_partition_kernel below; include/pmp.h: pmp_label_partition).  The templates' PART argument
+// selects what a best leaf remembers: its CU list (PART) or the maps of its ancestors (!PART).
 #include "../../include/pmp.h"
 #include "pmp_kernels.h"
 
@@ -48,6 +52,7 @@ struct Sub {
     int rx, ry, rh, rw;
     int best_err, best_depth, have_best;
     int best[3][4];
+    int best_cu, best_ncu;   // PART: the best leaf's CU list (lane c holds CU c)
     int nleaf, stop;
 };
 
@@ -114,7 +119,7 @@ __device__ __forceinline__ int can_split(const Sub &s, int cu, int &n)
 
 // A leaf at depth D (get_leaf_nodes order = the order the DFS reaches it).  Budget: the (PMP_MSBT_LEAF_BUDGET + 1)-th leaf stops the
 // region's search; the best of the leaves scored so far stands.
-template <int D>
+template <int D, bool PART>
 __device__ __forceinline__ void score_leaf(Sub &s)
 {
     if (s.nleaf >= PMP_MSBT_LEAF_BUDGET) { s.stop = 1; return; }
@@ -137,6 +142,11 @@ __device__ __forceinline__ void score_leaf(Sub &s)
         s.have_best = 1;
         s.best_err = e;
         s.best_depth = D;
+        if constexpr (PART) {       // best_cus (:278); set_bt_partition_vector never walks parents, so any depth is legal
+            s.best_cu = s.cu[D];
+            s.best_ncu = s.ncu[D];
+            return;
+        }
         // sub_map[k] = map of the ancestor at depth min(k+1, D) (D = 3: the reference's :361-363; D < 3: the carry-down rule)
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -148,11 +158,11 @@ __device__ __forceinline__ void score_leaf(Sub &s)
 }
 
 // get_candidate_map_tree (:188-241) for a node at level L.
-template <int L>
+template <int L, bool PART>
 __device__ __forceinline__ void expand(Sub &s)
 {
     if constexpr (L == 3) {
-        score_leaf<3>(s);
+        score_leaf<3, PART>(s);
     } else {
         const int lane = threadIdx.x & 63;
         const int ncu = s.ncu[L];
@@ -160,7 +170,7 @@ __device__ __forceinline__ void expand(Sub &s)
         for (int c = 0; c < ncu; ++c) {
             int n;
             const int list = can_split<L>(s, rlane(s.cu[L], c), n);
-            if (n == 0) { score_leaf<L>(s); return; }    // a CU without a proper partition: the node has no children (:201-202)
+            if (n == 0) { score_leaf<L, PART>(s); return; }    // a CU without a proper partition: the node has no children (:201-202)
             if (lane == c) { my_list = list; my_n = n; }
         }
         // mixed-radix combination index, first CU slowest (Search, :45-79)
@@ -217,7 +227,7 @@ __device__ __forceinline__ void expand(Sub &s)
             for (int k = 0; k < 4; ++k) s.bt[L + 1][k] = nb[k];
             s.cu[L + 1] = child_cu;
             s.ncu[L + 1] = uni(nchild);
-            expand<L + 1>(s);
+            expand<L + 1, PART>(s);
         }
     }
 }
@@ -287,7 +297,7 @@ __global__ __launch_bounds__(256) void msbt_labels_kernel(const uint8_t *__restr
             s.best_depth = 0;
             s.nleaf = 0;
             s.stop = 0;
-            expand<0>(s);
+            expand<0, false>(s);
             if (s.best_depth < 3) st |= PMP_MSBT_INCONSISTENT;
             if (s.stop) st |= PMP_MSBT_BUDGET;
 #pragma unroll
@@ -313,6 +323,126 @@ __global__ __launch_bounds__(256) void msbt_labels_kernel(const uint8_t *__restr
     }
     __syncthreads();
     if (threadIdx.x == 0) status[b] = (uint8_t)(st_w[0] | st_w[1] | st_w[2] | st_w[3]);
+}
+
+// Map_to_SubMap.get_partition (:262-312) cropped as map_to_parititon does (:382): the split flags of the labels' own partition.
+// The same flattened QT walk and the same search as above; a region's best leaf hands over its CU list, whose edges are painted as
+// :285-292 do, and every QT node that splits further paints its cross (:300-304; sms = 8 >> d, at d = 3 as well, where nothing else
+// follows: status bit 2).  c < d paints nothing.  A best leaf above depth 3 is legal here, so bit 1 is never set.
+// Edges cross wave ownership (a CU's bottom edge on row 8 lies in the quadrant below), so every wave keeps its own 16-bit row masks in
+// registers - lane r: hor row r, lane 16 + r: ver row r; bit c = column c; row / column 16 of the reference's 17x17 par_vec has no
+// lane and no bit - and hands them over through one LDS slot per wave; they are OR-ed after the barrier.  No atomics.
+// Outputs: hor, ver u8[256] per block at `stride` bytes from block to block; qt_o / dire_o (records form, else null) receive byte
+// copies of the inputs at the same stride.
+__global__ __launch_bounds__(256) void label_partition_kernel(const uint8_t *__restrict__ qt, const uint8_t *__restrict__ bt,
+                                                              const int8_t *__restrict__ dire, int64_t N, int cf,
+                                                              uint8_t *__restrict__ hor_o, uint8_t *__restrict__ ver_o,
+                                                              uint8_t *__restrict__ qt_o, int8_t *__restrict__ dire_o, int stride,
+                                                              uint8_t *__restrict__ status)
+{
+    __shared__ int st_w[4];
+    __shared__ uint32_t msk[4][32];
+    const int64_t b = blockIdx.x;
+    if (b >= N) return;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+
+    Sub s;
+    s.row = lane >> 2;
+    s.col0 = (lane & 3) << 2;
+    s.cf = cf;
+    uint32_t vd[3];
+    {
+        const uint32_t vb = reinterpret_cast<const uint32_t *>(bt + b * 256)[lane];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s.lb[k] = (vb >> (8 * k)) & 255;
+#pragma unroll
+        for (int k3 = 0; k3 < 3; ++k3) {
+            vd[k3] = reinterpret_cast<const uint32_t *>(dire + (b * 3 + k3) * 256)[lane];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s.ld[k3][k] = (int)(int8_t)((vd[k3] >> (8 * k)) & 255);
+        }
+    }
+    const int q8 = qt[b * 64 + lane];            // lane l holds qt[l>>3][l&7]
+    const int j = lane & 15, part = lane >> 4;   // part 0: hor row j, part 1: ver row j
+    uint32_t em = 0;                             // a wave that paints nothing hands over zeros
+    int st = 0;
+
+    for (int d = 0; d < 4; ++d) {
+        const int sms = 8 >> d, nside = 1 << d;
+        for (int node = 0; node < nside * nside; ++node) {
+            const int qx = (node / nside) * sms, qy = (node % nside) * sms;
+            bool reached = true;
+            for (int a = 0; a < d; ++a) {
+                const int am = ~((8 >> a) - 1);
+                if (!(rlane(q8, (qx & am) * 8 + (qy & am)) > a)) reached = false;
+            }
+            if (!reached) continue;
+            if (wv != (d == 0 ? 0 : ((qx >= 4 ? 2 : 0) + (qy >= 4 ? 1 : 0)))) continue;   // another wave's quadrant
+            const int c = rlane(q8, qx * 8 + qy);
+            if (c > d) {
+                // the QT cross of [2qx, 2qy, 2sms, 2sms]: row 2qx + sms and column 2qy + sms (both <= 15)
+                if (part == 0 && j == 2 * qx + sms) em |= ((1u << (2 * sms)) - 1u) << (2 * qy);
+                if (part == 1 && j >= 2 * qx && j < 2 * qx + 2 * sms) em |= 1u << (2 * qy + sms);
+                if (d == 3) st |= PMP_MSBT_QT_DEEP;       // the reference recurses on empty regions from here: nothing more is painted
+                continue;
+            }
+            if (c < d) continue;                          // neither == nor >: nothing is painted
+            // ---- set_bt_partition_vector (:262-292) on [2qx, 2qy, 2sms, 2sms]
+            s.rx = 2 * qx; s.ry = 2 * qy; s.rh = 2 * sms; s.rw = 2 * sms;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s.bt[0][k] = 0;
+            s.cu[0] = pack_cu(s.rx, s.ry, s.rh, s.rw);
+            s.ncu[0] = 1;
+            s.have_best = 0;
+            s.best_err = 0;
+            s.best_depth = 0;
+            s.best_cu = 0;
+            s.best_ncu = 0;
+            s.nleaf = 0;
+            s.stop = 0;
+            expand<0, true>(s);
+            if (s.stop) st |= PMP_MSBT_BUDGET;
+            const int ncu = uni(s.best_ncu);
+            for (int ci = 0; ci < ncu; ++ci) {
+                const int cu = rlane(s.best_cu, ci);
+                const int x = cu & 15, y = (cu >> 4) & 15, h = ((cu >> 8) & 15) + 1, w = ((cu >> 12) & 15) + 1;
+                // rows x and x + h over columns y..y+w-1; columns y and y + w over rows x..x+h-1.  x + h = 16 matches no lane and
+                // bit y + w = 16 is masked off: the crop of :382
+                if (part == 0 && (j == x || j == x + h)) em |= ((1u << w) - 1u) << y;
+                if (part == 1 && j >= x && j < x + h) em |= (1u << y) | ((1u << (y + w)) & 0xFFFFu);
+            }
+        }
+    }
+    if (lane < 32) msk[wv][lane] = em;
+    if (lane == 0) st_w[wv] = st;
+    __syncthreads();
+    if (wv < 2) {                                 // wave 0 writes hor, wave 1 ver: lane l the cells of row l>>2, columns 4*(l&3)..+3
+        const int r = wv * 16 + s.row;
+        const uint32_t m = ((msk[0][r] | msk[1][r] | msk[2][r] | msk[3][r]) >> s.col0) & 15u;
+        const uint32_t pk = (m & 1u) | ((m & 2u) << 7) | ((m & 4u) << 14) | ((m & 8u) << 21);
+        reinterpret_cast<uint32_t *>((wv == 0 ? hor_o : ver_o) + b * stride)[lane] = pk;
+    } else if (wv == 2) {
+        if (qt_o && lane < 16) reinterpret_cast<uint32_t *>(qt_o + b * stride)[lane] = reinterpret_cast<const uint32_t *>(qt + b * 64)[lane];
+    } else if (dire_o) {
+#pragma unroll
+        for (int k3 = 0; k3 < 3; ++k3) reinterpret_cast<uint32_t *>(dire_o + b * stride + k3 * 256)[lane] = vd[k3];
+    }
+    if (threadIdx.x == 0) status[b] = (uint8_t)(st_w[0] | st_w[1] | st_w[2] | st_w[3]);
+}
+
+hipError_t launch_label_partition(hipStream_t st, const uint8_t *qt, const uint8_t *bt, const int8_t *dire, int64_t N, int chroma_factor,
+                                  uint8_t *hor, uint8_t *ver, uint8_t *rec, uint8_t *status)
+{
+    // rec: one packed PMP_RECORD_BYTES record per block (hor | ver | qt | dire) instead of the two dense arrays
+    const int stride = rec ? PMP_RECORD_BYTES : 256;
+    for (int64_t o = 0; o < N; o += (int64_t)1 << 20) {
+        const int64_t m = (N - o) < ((int64_t)1 << 20) ? (N - o) : ((int64_t)1 << 20);
+        uint8_t *h = rec ? rec + o * stride : hor + o * stride, *v = rec ? h + 256 : ver + o * stride;
+        hipLaunchKernelGGL(label_partition_kernel, dim3((unsigned)m), dim3(256), 0, st, qt + o * 64, bt + o * 256, dire + o * 768, m,
+                           chroma_factor, h, v, rec ? h + 512 : (uint8_t *)nullptr, rec ? (int8_t *)(h + 576) : (int8_t *)nullptr, stride,
+                           status + o);
+    }
+    return hipGetLastError();
 }
 
 hipError_t launch_msbt_labels(hipStream_t st, const uint8_t *qt, const uint8_t *bt, const int8_t *dire, int64_t N, int chroma_factor,

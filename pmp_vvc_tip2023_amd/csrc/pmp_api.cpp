@@ -917,6 +917,79 @@ int pmp_msbt_labels(pmp_ctx *c, int cf, const uint8_t *qt, const uint8_t *bt, co
     return PMP_OK;
 }
 
+// ---- the labels' own partition: Map_to_SubMap.get_partition (labels.hip) -------------------------------------------------
+static int lpart_args(pmp_ctx *c, int cf, const void *qt, const void *bt, const void *dire, int64_t n, const void *o0, const void *o1,
+                      const void *status)
+{
+    if (cf != 1 && cf != 2) return set_err(c, PMP_E_INVALID, "pmp_label_partition: cf must be 1 or 2");
+    if (n < 0) return set_err(c, PMP_E_INVALID, "pmp_label_partition: negative count");
+    if (n > 0 && (!qt || !bt || !dire || !o0 || !o1 || !status)) return set_err(c, PMP_E_INVALID, "pmp_label_partition: null buffer");
+    return PMP_OK;
+}
+
+int pmp_label_partition_device(pmp_ctx *c, int cf, const uint8_t *qt, const uint8_t *bt, const int8_t *dire, int64_t n, uint8_t *hor,
+                               uint8_t *ver, uint8_t *status)
+{
+    CHECK_CTX(c);
+    int rc;
+    if ((rc = lpart_args(c, cf, qt, bt, dire, n, hor, ver, status))) return rc;
+    if (n == 0) return PMP_OK;
+    if (((uintptr_t)qt | (uintptr_t)bt | (uintptr_t)dire | (uintptr_t)hor | (uintptr_t)ver) & 3)
+        return set_err(c, PMP_E_INVALID, "pmp_label_partition_device: qt, bt, dire, hor and ver must be 4-byte aligned");
+    const hipError_t e = launch_label_partition(c->stream, qt, bt, dire, n, cf, hor, ver, nullptr, status);
+    return e == hipSuccess ? PMP_OK : hip_fail(c, e, "label_partition");
+}
+
+int pmp_label_partition_records_device(pmp_ctx *c, int cf, const uint8_t *qt, const uint8_t *bt, const int8_t *dire, int64_t n,
+                                       uint8_t *rec, uint8_t *status)
+{
+    CHECK_CTX(c);
+    int rc;
+    if ((rc = lpart_args(c, cf, qt, bt, dire, n, rec, rec, status))) return rc;
+    if (n == 0) return PMP_OK;
+    if (((uintptr_t)qt | (uintptr_t)bt | (uintptr_t)dire | (uintptr_t)rec) & 3)
+        return set_err(c, PMP_E_INVALID, "pmp_label_partition_records_device: qt, bt, dire and rec must be 4-byte aligned");
+    const hipError_t e = launch_label_partition(c->stream, qt, bt, dire, n, cf, nullptr, nullptr, rec, status);
+    return e == hipSuccess ? PMP_OK : hip_fail(c, e, "label_partition");
+}
+
+int pmp_label_partition(pmp_ctx *c, int cf, const uint8_t *qt, const uint8_t *bt, const int8_t *dire, int64_t n, uint8_t *hor,
+                        uint8_t *ver, uint8_t *status)
+{
+    CHECK_CTX(c);
+    int rc;
+    if ((rc = lpart_args(c, cf, qt, bt, dire, n, hor, ver, status))) return rc;
+    if (n == 0) return PMP_OK;
+    if ((rc = settle_before_host_call(c))) return rc;
+    // passes of at most `chunk` blocks through the staging buffers of pmp_msbt_labels; hor and ver share its 768-byte-per-block output
+    const int64_t chunk = c->chunk;
+    const int64_t m0 = n < chunk ? n : chunk;
+    const size_t per[5] = {64, 256, 768, 768, 1};
+    for (int i = 0; i < 5; ++i)
+        if ((rc = ensure(c, c->d_lab[i], (size_t)m0 * per[i]))) return rc;
+    for (int64_t o = 0; o < n; o += chunk) {
+        const int64_t m = (n - o) < chunk ? (n - o) : chunk;
+        uint8_t *d_hor = (uint8_t *)c->d_lab[3].p, *d_ver = d_hor + (size_t)m * 256;
+        if (c->poison) {          // pmp_debug_poison_workspace: the kernel must write every output byte it hands back
+            for (int i = 3; i < 5; ++i) {
+                const hipError_t e = hipMemsetAsync(c->d_lab[i].p, poison_byte(c), (size_t)m * per[i], c->stream);
+                if (e != hipSuccess) return hip_fail(c, e, "poison label buffers");
+            }
+        }
+        if ((rc = h2d(c, c->d_lab[0], qt + o * 64, (size_t)m * 64)) || (rc = h2d(c, c->d_lab[1], bt + o * 256, (size_t)m * 256)) ||
+            (rc = h2d(c, c->d_lab[2], dire + o * 768, (size_t)m * 768)))
+            return rc;
+        const hipError_t e = launch_label_partition(c->stream, (const uint8_t *)c->d_lab[0].p, (const uint8_t *)c->d_lab[1].p,
+                                                    (const int8_t *)c->d_lab[2].p, m, cf, d_hor, d_ver, nullptr, (uint8_t *)c->d_lab[4].p);
+        if (e != hipSuccess) return hip_fail(c, e, "label_partition");
+        if ((rc = d2h(c, hor + o * 256, d_hor, (size_t)m * 256)) || (rc = d2h(c, ver + o * 256, d_ver, (size_t)m * 256)) ||
+            (rc = d2h(c, status + o, c->d_lab[4].p, (size_t)m)))
+            return rc;
+        if ((rc = sync(c))) return rc;   // the next pass reuses the staging buffers
+    }
+    return PMP_OK;
+}
+
 // ---- validation statistics (valstats.hip) and teacher-forced MTT inference ------------------------------------------------
 namespace {
 struct ValArgs {

@@ -178,7 +178,7 @@ struct pmp_ctx {
     int overlap = 0;                       // two chunks in flight on two streams (PMP_OVERLAP=1 in the environment at pmp_create)
     size_t ws_need = 0;                    // what the caller's largest pass so far needed of ws / ws2 (pmp_get_workspace_bytes)
     pmp::DevBuf d_in[3], d_logit[3], d_out[4], d_frames[3];  // staging for the host-pointer entry points
-    pmp::DevBuf d_lab[5];                  // staging of pmp_msbt_labels: qt, bt, dire in; msbt, status out
+    pmp::DevBuf d_lab[5];                  // staging of pmp_msbt_labels: qt, bt, dire in; msbt, status out (pmp_label_partition: hor | ver in msbt's)
     pmp::DevBuf d_val[6];                  // staging of pmp_val_stats: qt, bt, dire, qt8, msbt, msdire
     pmp::DevBuf d_valpart;                 // validation statistics: per-block partials f64[n][20] of a call that passes no d_block_stats
     pmp::DevBuf d_valout;                  // pmp_val_stats: f64[passes][20]

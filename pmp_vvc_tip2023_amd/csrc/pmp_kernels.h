@@ -184,6 +184,10 @@ hipError_t launch_postprocess(hipStream_t s, const float *qt, const float *bt, c
 // GenMSBtMap (labels.hip): qt u8[N][64], bt u8[N][256], dire i8[N][3][256] -> msbt u8[N][3][256], status u8[N] (include/pmp.h: pmp_msbt_labels).
 hipError_t launch_msbt_labels(hipStream_t s, const uint8_t *qt, const uint8_t *bt, const int8_t *dire, int64_t N, int chroma_factor,
                               uint8_t *msbt, uint8_t *status);
+// The labels' own partition (labels.hip; include/pmp.h: pmp_label_partition): the same inputs -> hor, ver u8[N][256] and status u8[N], or
+// with rec != null (hor, ver ignored) one packed record u8[N][PMP_RECORD_BYTES] = hor | ver | qt | dire per block.  All 4-byte aligned.
+hipError_t launch_label_partition(hipStream_t s, const uint8_t *qt, const uint8_t *bt, const int8_t *dire, int64_t N, int chroma_factor,
+                                  uint8_t *hor, uint8_t *ver, uint8_t *rec, uint8_t *status);
 
 // Validation statistics (valstats.hip; include/pmp.h: pmp_val_stats): logits against labels -> block_stats f64[N][20] (always written:
 // the caller's buffer or scratch) and their fixed-order sum stats f64[20].  qt/qt8 null: MTT only; bt/dire/msbt/msdire null: QT only.

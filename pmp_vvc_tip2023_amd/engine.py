@@ -8,6 +8,8 @@ Same names and argument meaning as the reference so callers (and the parity test
     Inference_QBD.output_block_yuv(...)                 Engine.output_block_yuv(y, u, v, bitdepth)
     Inference_QBD.load_pretrain_model(net, path)        Engine.load_pretrain_model(net_name, qp, weights)
     GenMSBtMap.gen_seq_sub_map(qt, bt, dire, is_luma)   Engine.gen_seq_sub_map(qt, bt, dire, is_luma)   (training labels)
+    GenMSBtMap.map_to_parititon(qt, bt, dire, cf)       Engine.label_partition(qt, bt, dire, cf)        (all blocks at once)
+    GenMSBtMap.get_sequence_partition_for_VTM(...)      Engine.label_partition_for_VTM(...)             (labels -> PartitionMat file)
     Metrics.validation_QBD(loader, Net_Q, Net_BD, qp)   Engine.validation_QBD(comp, qp, blocks, qt8, msbt, msdire, batch_size)
     Metrics.pre_validation(loader, Net, predID, qp)     Engine.pre_validation(comp, qp, pred_id, blocks, qt8[, msbt, msdire], batch_size)
     CreateDataSet.output_block_partition_map(...)       output_block_partition_map(...)                 (module level, host only)
@@ -296,6 +298,44 @@ class Engine:
     def msbt_labels_device(self, cf, d_qt, d_bt, d_dire, n, d_msbt, d_status):
         """pmp_msbt_labels_device: device pointers (u8 qt, u8 bt, i8 dire in; u8 msbt, u8 status out), stream-ordered."""
         self._ck(self.lib.pmp_msbt_labels_device(self.h, int(cf), d_qt, d_bt, d_dire, int(n), d_msbt, d_status))
+
+    # ------------------------------------------------------------------------------------------ the labels' own partition
+    def label_partition(self, qt_map, bt_map, dire_map, cf):
+        """GenMSBtMap.map_to_parititon (GenMSBtMap.py:377-382) on every block: qt_map [N,8,8] (qtDepth - 1), bt_map [N,16,16], dire_map
+        [N,3,16,16], chroma factor cf (1 or 2) -> hor, ver u8[N,16,16], status u8[N] (include/pmp.h: pmp_label_partition).  Values must
+        fit the reference's dtypes (u8, u8, i8): anything else is refused, not wrapped."""
+        if cf not in (1, 2):
+            raise ValueError("label_partition: cf must be 1 or 2")
+        qt = _fit(qt_map, np.uint8, "qt_map"); bt = _fit(bt_map, np.uint8, "bt_map"); dire = _fit(dire_map, np.int8, "dire_map")
+        n = qt.size // 64
+        if qt.size != n * 64 or bt.size != n * 256 or dire.size != n * 768:
+            raise ValueError("label_partition: expected qt_map[N,8,8], bt_map[N,16,16], dire_map[N,3,16,16]")
+        hor = np.empty((n, 16, 16), np.uint8); ver = np.empty((n, 16, 16), np.uint8); st = np.empty(n, np.uint8)
+        self._ck(self.lib.pmp_label_partition(self.h, int(cf), _ptr(qt), _ptr(bt), _ptr(dire), n, _ptr(hor), _ptr(ver), _ptr(st)))
+        return hor, ver, st
+
+    def label_partition_for_VTM(self, qt_map, bt_map, dire_map, is_luma, save_path, frm_num, frm_width, frm_height, binary=False):
+        """GenMSBtMap.get_sequence_partition_for_VTM (GenMSBtMap.py:384-432) without its plot: the labels of one sequence (blocks
+        frame-major, row-major; qt_map is qtDepth - 1) -> the PartitionMat file of a perfect predictor at save_path (None: no file).
+        Chroma factor 1 for luma, 2 otherwise, as there.  The file's qt and direction sections are the labels themselves (:407-408);
+        the text is what write_partition_file writes, so a direction of -1 is printed as -1 where the reference prints 255
+        (include/pmp.h: pmp_label_partition); binary=True writes the PMPB1 side channel instead.  Returns hor, ver, status."""
+        n_expected = int(frm_num) * (int(frm_height) // 64) * (int(frm_width) // 64)
+        hor, ver, st = self.label_partition(qt_map, bt_map, dire_map, 1 if is_luma else 2)
+        if hor.shape[0] != n_expected:
+            raise ValueError("label_partition_for_VTM: %d blocks given, geometry needs %d" % (hor.shape[0], n_expected))
+        if save_path is not None:
+            write = write_partition_binary if binary else write_partition_file
+            write(save_path, frm_num, frm_height, frm_width, hor, ver, _fit(qt_map, np.uint8, "qt_map"), _fit(dire_map, np.int8, "dire_map"))
+        return hor, ver, st
+
+    def label_partition_device(self, cf, d_qt, d_bt, d_dire, n, d_hor, d_ver, d_status):
+        """pmp_label_partition_device: device pointers (u8 qt, u8 bt, i8 dire in; u8 hor, u8 ver, u8 status out), stream-ordered."""
+        self._ck(self.lib.pmp_label_partition_device(self.h, int(cf), d_qt, d_bt, d_dire, int(n), d_hor, d_ver, d_status))
+
+    def label_partition_records_device(self, cf, d_qt, d_bt, d_dire, n, d_rec, d_status):
+        """pmp_label_partition_records_device: one packed 1344-byte record per block (hor | ver | qt | dire) and u8 status."""
+        self._ck(self.lib.pmp_label_partition_records_device(self.h, int(cf), d_qt, d_bt, d_dire, int(n), d_rec, d_status))
 
     # ------------------------------------------------------------------------------------------ validation
     def val_stats(self, qp, qt=None, bt=None, dire=None, qt8=None, msbt=None, msdire=None):

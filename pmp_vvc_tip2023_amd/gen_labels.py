@@ -54,11 +54,12 @@ def find_dump(depth_dir, seq, qp, comp):
     return None
 
 
-def plan(args):
+def plan(args, tool="gen_labels"):
     """Validates every flag and finds every dump -> (qps, comps, [(name, W, H, sub frames)], {(comp, qp, name): path}).
-    SystemExit(2) on the first problem: nothing has touched the GPU yet."""
+    SystemExit(2) on the first problem: nothing has touched the GPU yet.  Shared with label_partition (`tool`: the name in messages),
+    whose arguments have no dataType."""
     def fail(msg):
-        print("gen_labels: " + msg, file=sys.stderr)
+        print(tool + ": " + msg, file=sys.stderr)
         raise SystemExit(2)
     try:
         qps = [int(q) for q in str(args.qps).split(",") if q.strip()]
@@ -71,7 +72,7 @@ def plan(args):
         fail("--comps must be a subset of Luma,Chroma, got %r" % args.comps)
     if args.ssRatio < 1:
         fail("--ssRatio must be >= 1")
-    if not args.dataType or os.sep in args.dataType:
+    if hasattr(args, "dataType") and (not args.dataType or os.sep in args.dataType):
         fail("--dataType must be a plain name")
     if not os.path.isdir(args.depthDir):
         fail("--depthDir %s is not a directory" % args.depthDir)
