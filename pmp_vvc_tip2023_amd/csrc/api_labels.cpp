@@ -1,0 +1,273 @@
+// api_labels.cpp — the entry points that work on VTM's labels (include/pmp.h): MSBT training labels, the labels' own partition,
+// validation statistics and teacher-forced MTT inference.
+#include <algorithm>
+#include <initializer_list>
+
+#include "pmp_host.h"
+
+using namespace pmp;
+
+// ---- one staged pass loop for the host-pointer entry points below ----------------------------------------------------------
+namespace {
+struct StagedIn { const void *host; size_t per; DevBuf &buf; };          // per: bytes per block; host null: left out, nothing staged
+struct StagedOut { void *host; size_t per; DevBuf &buf; size_t off; };   // starts `off` bytes per block into buf (hor | ver share one)
+}  // namespace
+
+// n blocks in passes of at most `chunk` through the context's staging buffers, all on c->stream: H2D of every input, launch(blocks of
+// the pass, its index), D2H of every per-block output, and a synchronise per pass, because the next pass reuses the staging buffers.
+static int staged_passes(pmp_ctx *c, int64_t n, std::initializer_list<StagedIn> ins, std::initializer_list<StagedOut> outs,
+                         const std::function<int(int64_t, int64_t)> &launch)
+{
+    const int64_t chunk = c->chunk, m0 = n < chunk ? n : chunk;
+    int rc;
+    for (const StagedIn &i : ins)
+        if (i.host && (rc = ensure(c, i.buf, (size_t)m0 * i.per))) return rc;
+    for (const StagedOut &o : outs) {
+        size_t per = 0;                                // of the whole buffer: the outputs that share it lie plane behind plane
+        for (const StagedOut &q : outs) if (&q.buf == &o.buf) per = std::max(per, q.off + q.per);
+        if ((rc = ensure(c, o.buf, (size_t)m0 * per))) return rc;
+    }
+    for (int64_t at = 0, pass = 0; at < n; at += chunk, ++pass) {
+        const int64_t m = (n - at) < chunk ? (n - at) : chunk;
+        if (c->poison) {          // pmp_debug_poison_workspace: the kernel must write every output byte it hands back
+            for (const StagedOut &o : outs) {
+                const hipError_t e = hipMemsetAsync((char *)o.buf.p + (size_t)m * o.off, poison_byte(c), (size_t)m * o.per, c->stream);
+                if (e != hipSuccess) return hip_fail(c, e, "poison label buffers");
+            }
+        }
+        for (const StagedIn &i : ins)
+            if (i.host && (rc = h2d(c, i.buf, (const char *)i.host + (size_t)at * i.per, (size_t)m * i.per))) return rc;
+        if ((rc = launch(m, pass))) return rc;
+        for (const StagedOut &o : outs)
+            if ((rc = d2h(c, (char *)o.host + (size_t)at * o.per, (const char *)o.buf.p + (size_t)m * o.off, (size_t)m * o.per))) return rc;
+        if ((rc = sync(c))) return rc;
+    }
+    return PMP_OK;
+}
+
+// The argument checks that pmp_msbt_labels*, pmp_label_partition* share; fn: the entry point family the message names
+static int label_args(pmp_ctx *c, const char *fn, int cf, int64_t n, std::initializer_list<const void *> bufs)
+{
+    const std::string f(fn);
+    if (cf != 1 && cf != 2) return set_err(c, PMP_E_INVALID, f + ": cf must be 1 or 2");
+    if (n < 0) return set_err(c, PMP_E_INVALID, f + ": negative count");
+    if (n > 0 && std::find(bufs.begin(), bufs.end(), nullptr) != bufs.end()) return set_err(c, PMP_E_INVALID, f + ": null buffer");
+    return PMP_OK;
+}
+
+static bool misaligned(std::initializer_list<const void *> ps, uintptr_t mask)
+{
+    uintptr_t bits = 0;
+    for (const void *p : ps) bits |= (uintptr_t)p;
+    return (bits & mask) != 0;
+}
+
+extern "C" {
+
+// ---- training labels: GenMSBtMap (labels.hip) --------------------------------------------------------------------------
+int pmp_msbt_labels_device(pmp_ctx *c, int cf, const uint8_t *qt, const uint8_t *bt, const int8_t *dire, int64_t n, uint8_t *msbt,
+                           uint8_t *status)
+{
+    CHECK_CTX(c);
+    int rc;
+    if ((rc = label_args(c, "pmp_msbt_labels", cf, n, {qt, bt, dire, msbt, status}))) return rc;
+    if (n == 0) return PMP_OK;
+    if (misaligned({qt, bt, dire, msbt}, 3))
+        return set_err(c, PMP_E_INVALID, "pmp_msbt_labels_device: qt, bt, dire and msbt must be 4-byte aligned");
+    const hipError_t e = launch_msbt_labels(c->stream, qt, bt, dire, n, cf, msbt, status);
+    return e == hipSuccess ? PMP_OK : hip_fail(c, e, "msbt_labels");
+}
+
+int pmp_msbt_labels(pmp_ctx *c, int cf, const uint8_t *qt, const uint8_t *bt, const int8_t *dire, int64_t n, uint8_t *msbt,
+                    uint8_t *status)
+{
+    CHECK_CTX(c);
+    int rc;
+    if ((rc = label_args(c, "pmp_msbt_labels", cf, n, {qt, bt, dire, msbt, status}))) return rc;
+    if (n == 0) return PMP_OK;
+    if ((rc = settle_before_host_call(c))) return rc;
+    DevBuf *d = c->d_lab;                              // about 1.9 kB per block
+    return staged_passes(c, n, {{qt, 64, d[0]}, {bt, 256, d[1]}, {dire, 768, d[2]}}, {{msbt, 768, d[3], 0}, {status, 1, d[4], 0}},
+                         [&](int64_t m, int64_t) {
+                             const hipError_t e = launch_msbt_labels(c->stream, (const uint8_t *)d[0].p, (const uint8_t *)d[1].p,
+                                                                     (const int8_t *)d[2].p, m, cf, (uint8_t *)d[3].p, (uint8_t *)d[4].p);
+                             return e == hipSuccess ? PMP_OK : hip_fail(c, e, "msbt_labels");
+                         });
+}
+
+// ---- the labels' own partition: Map_to_SubMap.get_partition (labels.hip) -------------------------------------------------
+int pmp_label_partition_device(pmp_ctx *c, int cf, const uint8_t *qt, const uint8_t *bt, const int8_t *dire, int64_t n, uint8_t *hor,
+                               uint8_t *ver, uint8_t *status)
+{
+    CHECK_CTX(c);
+    int rc;
+    if ((rc = label_args(c, "pmp_label_partition", cf, n, {qt, bt, dire, hor, ver, status}))) return rc;
+    if (n == 0) return PMP_OK;
+    if (misaligned({qt, bt, dire, hor, ver}, 3))
+        return set_err(c, PMP_E_INVALID, "pmp_label_partition_device: qt, bt, dire, hor and ver must be 4-byte aligned");
+    const hipError_t e = launch_label_partition(c->stream, qt, bt, dire, n, cf, hor, ver, nullptr, status);
+    return e == hipSuccess ? PMP_OK : hip_fail(c, e, "label_partition");
+}
+
+int pmp_label_partition_records_device(pmp_ctx *c, int cf, const uint8_t *qt, const uint8_t *bt, const int8_t *dire, int64_t n,
+                                       uint8_t *rec, uint8_t *status)
+{
+    CHECK_CTX(c);
+    int rc;
+    if ((rc = label_args(c, "pmp_label_partition", cf, n, {qt, bt, dire, rec, status}))) return rc;
+    if (n == 0) return PMP_OK;
+    if (misaligned({qt, bt, dire, rec}, 3))
+        return set_err(c, PMP_E_INVALID, "pmp_label_partition_records_device: qt, bt, dire and rec must be 4-byte aligned");
+    const hipError_t e = launch_label_partition(c->stream, qt, bt, dire, n, cf, nullptr, nullptr, rec, status);
+    return e == hipSuccess ? PMP_OK : hip_fail(c, e, "label_partition");
+}
+
+int pmp_label_partition(pmp_ctx *c, int cf, const uint8_t *qt, const uint8_t *bt, const int8_t *dire, int64_t n, uint8_t *hor,
+                        uint8_t *ver, uint8_t *status)
+{
+    CHECK_CTX(c);
+    int rc;
+    if ((rc = label_args(c, "pmp_label_partition", cf, n, {qt, bt, dire, hor, ver, status}))) return rc;
+    if (n == 0) return PMP_OK;
+    if ((rc = settle_before_host_call(c))) return rc;
+    DevBuf *d = c->d_lab;                              // the staging buffers of pmp_msbt_labels; hor and ver share its msbt output
+    return staged_passes(c, n, {{qt, 64, d[0]}, {bt, 256, d[1]}, {dire, 768, d[2]}},
+                         {{hor, 256, d[3], 0}, {ver, 256, d[3], 256}, {status, 1, d[4], 0}}, [&](int64_t m, int64_t) {
+                             uint8_t *d_hor = (uint8_t *)d[3].p, *d_ver = d_hor + (size_t)m * 256;
+                             const hipError_t e = launch_label_partition(c->stream, (const uint8_t *)d[0].p, (const uint8_t *)d[1].p,
+                                                                         (const int8_t *)d[2].p, m, cf, d_hor, d_ver, nullptr, (uint8_t *)d[4].p);
+                             return e == hipSuccess ? PMP_OK : hip_fail(c, e, "label_partition");
+                         });
+}
+
+// ---- validation statistics (valstats.hip) and teacher-forced MTT inference ------------------------------------------------
+namespace {
+struct ValArgs {
+    const float *qt, *bt, *dire;
+    const uint8_t *qt8, *msbt;
+    const int8_t *msdire;
+    int64_t n;
+    float wm[3];
+    int w0_one;
+    double *stats, *block_stats;       // block_stats null: the context's scratch, looked up at launch (a replay may find it regrown)
+};
+}  // namespace
+
+static int val_check(pmp_ctx *c, int qp, const void *qt, const void *bt, const void *dire, const void *qt8, const void *msbt,
+                     const void *msdire, int64_t n, const void *stats, float wm[3], int *w0_one)
+{
+    // Metrics.py:148-151; the float64 entry becomes a float32 scalar when torch adds it to the float32 dl*dl
+    static const double weight_mat[4][3] = {{0.5 * 1.0, 0.5 * 0.73, 0.5 * 0.15}, {0.5 * 2.43, 0.5 * 0.35, 0.5 * 0.10},
+                                            {0.5 * 0.96, 0.5 * 0.23, 0.5 * 0.07}, {0.5 * 0.59, 0.5 * 0.16, 0.5 * 0.05}};
+    if (qp < 22 || qp > 41) return set_err(c, PMP_E_INVALID, "pmp_val_stats: qp must be in 22..41 (rows 0..3 of weight_mat)");
+    if (n < 0 || !stats) return set_err(c, PMP_E_INVALID, "pmp_val_stats: negative count or null stats");
+    const bool q = qt && qt8, noq = !qt && !qt8, m = bt && dire && msbt && msdire, nom = !bt && !dire && !msbt && !msdire;
+    if (n > 0 && !((q && m) || (q && nom) || (noq && m)))
+        return set_err(c, PMP_E_INVALID, "pmp_val_stats: pass (qt, qt8), (bt, dire, msbt, msdire) or both; no other NULL mix");
+    const int row = (qp - 22) / 5;
+    for (int k = 0; k < 3; ++k) wm[k] = (float)weight_mat[row][k];
+    *w0_one = qp == 22;
+    return PMP_OK;
+}
+
+static int val_launch(pmp_ctx *c, const ValArgs &a)
+{
+    double *part = a.block_stats;
+    if (!part) {
+        const int rc = ensure(c, c->d_valpart, (size_t)a.n * PMP_VAL_NSTATS * sizeof(double));
+        if (rc != PMP_OK) return rc;
+        part = (double *)c->d_valpart.p;
+    }
+    const hipError_t e = launch_val_stats(c->stream, a.qt, a.bt, a.dire, a.qt8, a.msbt, a.msdire, a.n, a.wm, a.w0_one, part, a.stats);
+    return e == hipSuccess ? PMP_OK : hip_fail(c, e, "val_stats");
+}
+
+static int val_device_impl(pmp_ctx *c, const ValArgs &a)
+{
+    if (a.n == 0) {
+        const hipError_t e = hipMemsetAsync(a.stats, 0, PMP_VAL_NSTATS * sizeof(double), c->stream);
+        return e == hipSuccess ? PMP_OK : hip_fail(c, e, "val_stats");
+    }
+    const int rc = val_launch(c, a);
+    // its logits may come from an inference call whose range flag has not been looked at yet: remember the call for the replay
+    if (rc == PMP_OK && !c->pending.empty())
+        c->pending.push_back(PendingCall{false, false, nullptr, nullptr, [=](bool) { return val_launch(c, a); }});
+    return rc;
+}
+
+int pmp_val_stats_device(pmp_ctx *c, int qp, const float *qt, const float *bt, const float *dire, const uint8_t *qt8,
+                         const uint8_t *msbt, const int8_t *msdire, int64_t n, double *stats, double *block_stats)
+{
+    CHECK_CTX(c);
+    ValArgs a{qt, bt, dire, qt8, msbt, msdire, n, {0.f, 0.f, 0.f}, 0, stats, block_stats};
+    int rc;
+    if ((rc = val_check(c, qp, qt, bt, dire, qt8, msbt, msdire, n, stats, a.wm, &a.w0_one))) return rc;
+    if (n > 0 && (misaligned({bt, dire}, 15) || misaligned({qt, msbt, msdire}, 3) || misaligned({stats, block_stats}, 7)))
+        return set_err(c, PMP_E_INVALID, "pmp_val_stats_device: bt, dire must be 16-byte aligned, qt, msbt, msdire 4-byte, the outputs 8-byte");
+    return val_device_impl(c, a);
+}
+
+int pmp_val_stats(pmp_ctx *c, int qp, const float *qt, const float *bt, const float *dire, const uint8_t *qt8, const uint8_t *msbt,
+                  const int8_t *msdire, int64_t n, double stats[PMP_VAL_NSTATS])
+{
+    CHECK_CTX(c);
+    ValArgs a{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, {0.f, 0.f, 0.f}, 0, nullptr, nullptr};
+    int rc;
+    if ((rc = val_check(c, qp, qt, bt, dire, qt8, msbt, msdire, n, stats, a.wm, &a.w0_one))) return rc;
+    for (int i = 0; i < PMP_VAL_NSTATS; ++i) stats[i] = 0.0;
+    if (n == 0) return PMP_OK;
+    if ((rc = settle_before_host_call(c))) return rc;
+    // about 6.9 kB per block through the context's own staging buffers; one result row per pass
+    const int64_t passes = (n + c->chunk - 1) / c->chunk;
+    if ((rc = ensure(c, c->d_valout, (size_t)passes * PMP_VAL_NSTATS * sizeof(double)))) return rc;
+    DevBuf *d = c->d_val;
+    rc = staged_passes(c, n, {{qt, 64 * 4, d[0]}, {bt, 768 * 4, d[1]}, {dire, 768 * 4, d[2]}, {qt8, 64, d[3]}, {msbt, 768, d[4]}, {msdire, 768, d[5]}},
+                       {}, [&](int64_t m, int64_t p) {
+                           a.qt = qt ? (const float *)d[0].p : nullptr;
+                           a.bt = bt ? (const float *)d[1].p : nullptr;
+                           a.dire = bt ? (const float *)d[2].p : nullptr;
+                           a.qt8 = qt ? (const uint8_t *)d[3].p : nullptr;
+                           a.msbt = bt ? (const uint8_t *)d[4].p : nullptr;
+                           a.msdire = bt ? (const int8_t *)d[5].p : nullptr;
+                           a.n = m;
+                           a.stats = (double *)c->d_valout.p + p * PMP_VAL_NSTATS;
+                           return val_launch(c, a);
+                       });
+    if (rc != PMP_OK) return rc;
+    std::vector<double> rows((size_t)passes * PMP_VAL_NSTATS);
+    if ((rc = d2h(c, rows.data(), c->d_valout.p, rows.size() * sizeof(double))) || (rc = sync(c))) return rc;
+    for (int64_t p = 0; p < passes; ++p)          // the whole call as one batch: pass results in pass order
+        for (int i = 0; i < PMP_VAL_NSTATS; ++i) stats[i] += rows[(size_t)p * PMP_VAL_NSTATS + i];
+    return PMP_OK;
+}
+
+int pmp_infer_msbd_device(pmp_ctx *c, int comp, int qp, const uint8_t *by, const uint8_t *bu, const uint8_t *bv, const float *qt_in,
+                          int64_t n, float *bt, float *dire)
+{
+    CHECK_CTX(c);
+    if (!qt_in) return set_err(c, PMP_E_INVALID, "pmp_infer_msbd: qt_in is null");
+    return infer_device_impl(c, comp, qp, by, bu, bv, n, nullptr, bt, dire, false, qt_in);
+}
+
+int pmp_infer_msbd(pmp_ctx *c, int comp, int qp, const uint8_t *by, const uint8_t *bu, const uint8_t *bv, const float *qt_in, int64_t n,
+                   float *bt, float *dire)
+{
+    CHECK_CTX(c);
+    if (n < 0 || !by || !qt_in || !bt || !dire || (comp == PMP_CHROMA && (!bu || !bv)))
+        return set_err(c, PMP_E_INVALID, "pmp_infer_msbd: null buffer or negative count");
+    if (n == 0) return PMP_OK;
+    int rc;
+    if ((rc = settle_before_host_call(c))) return rc;
+    if ((rc = stage_blocks(c, comp, by, bu, bv, n))) return rc;
+    if ((rc = ensure_logits(c, n))) return rc;
+    if ((rc = h2d(c, c->d_logit[0], qt_in, (size_t)n * 64 * 4))) return rc;
+    float *db = (float *)c->d_logit[1].p, *dd = (float *)c->d_logit[2].p;
+    if ((rc = infer_device_impl(c, comp, qp, (const uint8_t *)c->d_in[0].p, (const uint8_t *)c->d_in[1].p, (const uint8_t *)c->d_in[2].p,
+                                n, nullptr, db, dd, true, (const float *)c->d_logit[0].p)))
+        return rc;
+    if ((rc = resolve_pending(c, true))) return rc;      // range guard: a re-run is enqueued before the copies below
+    if ((rc = d2h(c, bt, db, (size_t)n * 768 * 4)) || (rc = d2h(c, dire, dd, (size_t)n * 768 * 4))) return rc;
+    return sync(c);
+}
+
+}  // extern "C"

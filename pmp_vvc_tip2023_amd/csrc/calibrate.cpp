@@ -85,8 +85,8 @@ int calibrate_mtt(pmp_ctx *c, bool luma, NetWeights &wq, NetWeights &wb)
     const size_t o_q = o_v + (((size_t)n * 34 * 34 + 255) & ~(size_t)255), o_bt = o_q + (size_t)n * 64 * 4, o_dr = o_bt + (size_t)n * 768 * 4;
     if ((rc = ensure(c, c->d_calbuf, o_dr + (size_t)n * 768 * 4)) != PMP_OK) return rc;
     hipError_t e = hipSuccess;
-    if (!c->d_cal) e = hipMalloc((void **)&c->d_cal, PMP_CAL_SLOTS * sizeof(unsigned));
-    if (e == hipSuccess && !c->cal_stream) e = hipStreamCreateWithFlags(&c->cal_stream, hipStreamNonBlocking);
+    if (!c->d_cal) e = hipMalloc((void **)&c->d_cal.h, PMP_CAL_SLOTS * sizeof(unsigned));
+    if (e == hipSuccess && !c->cal_stream) e = hipStreamCreateWithFlags(&c->cal_stream.h, hipStreamNonBlocking);
     if (e != hipSuccess) return hip_fail(c, e, "calibration: stream");
     // Its OWN stream and workspace: the calibration depends on nothing the context's stream is doing (weights are uploaded synchronously,
     // its blocks and logits are its own), so it runs beside the passes in flight instead of behind them - a driver that loads the next

@@ -295,7 +295,7 @@ struct Graph {
 
 }  // namespace
 
-// pmp_debug_run_resblock (pmp_api.cpp): block "rb" on an input that reaches it as a trunk tensor reaches a block of the nets - split on the
+// pmp_debug_run_resblock (api_debug.cpp): block "rb" on an input that reaches it as a trunk tensor reaches a block of the nets - split on the
 // split datapaths (the fp32 input goes through the graph's own conversion first), its bytes the block's to reuse.  A gated block is the
 // last of segment 1 and its gate a segment-0 tensor, as trunk_Att1.1 and x5 (forward_msbd); an ungated block stays in segment 0.
 int run_resblock(pmp_ctx *c, Pass &ps, const NetWeights &w, int n, int h, int wd, const float *x_host, const float *gate_host, bool pool, bool out_f32)

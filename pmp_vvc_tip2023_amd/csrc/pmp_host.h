@@ -18,9 +18,59 @@ namespace pmp {
 
 enum KClass { K_CONV3_64 = 0, K_CONV5_64, K_CONV_OTHER, K_STEM, K_SMALL, K_POST, K_NCLASS };
 
-struct DevBuf {  // grow-only device buffer
+struct DevBuf {  // grow-only device buffer, owned: freed with whatever holds it; ensure() is the only place that grows one
     void *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        if (this != &o) { reset(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    void reset() { if (p) hipFree(p); p = nullptr; cap = 0; }
+    void *release() { void *q = p; p = nullptr; cap = 0; return q; }   // the caller frees it
+};
+
+// The context's other owned handles: one stream, one allocation of device or pinned words.  Reads like the raw handle it holds.
+template <class T, auto Free>
+struct Owned {
+    T h = nullptr;
+    Owned() = default;
+    Owned(const Owned &) = delete;
+    Owned &operator=(const Owned &) = delete;
+    Owned(Owned &&o) noexcept : h(o.h) { o.h = nullptr; }
+    Owned &operator=(Owned &&o) noexcept
+    {
+        if (this != &o) { reset(); h = o.h; o.h = nullptr; }
+        return *this;
+    }
+    ~Owned() { reset(); }
+    void reset() { if (h) Free(h); h = nullptr; }
+    operator T() const { return h; }
+};
+using OwnedStream = Owned<hipStream_t, hipStreamDestroy>;
+using DevWords = Owned<unsigned *, hipFree>;
+using PinnedWords = Owned<unsigned *, hipHostFree>;
+
+// Events that are not in use: taken for a timing scope, a fork / join or a flag snapshot and handed back when that is over
+struct EventPool {
+    std::vector<hipEvent_t> idle;
+    EventPool() = default;
+    EventPool(const EventPool &) = delete;
+    EventPool &operator=(const EventPool &) = delete;
+    ~EventPool() { for (hipEvent_t e : idle) hipEventDestroy(e); }
+    hipEvent_t get()
+    {
+        hipEvent_t e = nullptr;
+        if (idle.empty()) hipEventCreate(&e);
+        else { e = idle.back(); idle.pop_back(); }
+        return e;
+    }
+    void put(hipEvent_t e) { idle.push_back(e); }
 };
 
 // ResidualBlock weights (Model_QBD.py:23-44), packed for the kernel that runs the block.
@@ -151,9 +201,23 @@ struct PendingCall {
 
 }  // namespace pmp
 
+namespace pmp {
+void free_net_weights(NetWeights &w);   // weights_pack.cpp
+constexpr int PMP_SAT_SLOTS = 64;             // flag snapshots in flight (pmp_ctx::h_sat)
+constexpr int PMP_TAP_MAX_BLOCKS = 64;        // pmp_debug_set_taps: tap memory is one copy of every tensor of the call
+}  // namespace pmp
+
+// Every device resource below is owned by its member (DevBuf, Owned, EventPool) and goes with the context: nothing is freed by name.
+// Members die in reverse order of declaration, so the streams, declared first, outlive every buffer and event.  That order only has to
+// be valid, not careful: pmp_destroy has synchronised the streams and drained the events before it deletes the context.
 struct pmp_ctx {
+    ~pmp_ctx() { for (auto &kv : nets) pmp::free_net_weights(kv.second); }   // NetWeights keeps its own list of allocations
     int device = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;   // stream: the caller's (pmp_set_stream); a pass runs on its Pass::stream
+    pmp::OwnedStream own_stream;
+    pmp::OwnedStream stream2;              // overlap mode: the passes of odd chunks; created on first use
+    pmp::OwnedStream cal_stream;           // calibration runs on its own stream and workspace: it neither waits for the passes in flight on the
+                                           // context's stream nor touches their workspace (created on first use)
+    hipStream_t stream = nullptr;          // the caller's (pmp_set_stream) or own_stream; a pass runs on its Pass::stream
     int chunk = 4096;   // blocks per pass: the 16x16-resolution layers need >= 4096 tiles to fill 256 CUs x 3 workgroups evenly (+2.5 % over 1024)
     int precision = 2;                     // 0: fp32 MFMA, 1: bf16x6 split, 2: f16x3 split (default; both splits fp32-equivalent) - the caller's setting; a pass runs on its Pass::precision
     int fuse16 = 1;                        // f16x3: run the 16x16-resolution tails LDS-resident (chain16.hip: two / three launches per net); 0 = launch per layer (pmp_debug_set_fusion: A/B and the bit-identity tests)
@@ -163,8 +227,8 @@ struct pmp_ctx {
     std::string err;
     // f16x3 range guard (include/pmp.h, pmp_set_saturation_policy): device word raised by every kernel that clamps a stored activation.
     // A 256-byte block: word 0 is the flag, bytes 64.. stay zero (the zero line of conv_f16x3_t32.hip's halo DMA)
-    unsigned *d_sat = nullptr;
-    unsigned *h_sat = nullptr;             // PMP_SAT_SLOTS pinned host words: flag snapshots of the calls still in flight
+    pmp::DevWords d_sat;
+    pmp::PinnedWords h_sat;                // PMP_SAT_SLOTS pinned host words: flag snapshots of the calls still in flight
     uint64_t sat_seq = 0;
     std::deque<pmp::PendingCall> pending;  // calls whose flag has not been looked at yet (+ the post-processing calls after them)
     pmp::AblCtx abl;                       // empty in the product library
@@ -174,7 +238,6 @@ struct pmp_ctx {
     std::map<int, pmp::NetWeights> nets;  // key = net_id * 100 + qp
     pmp::DevBuf ws;                        // activation workspace (its own, or a larger one parked by a destroyed context)
     pmp::DevBuf ws2;                       // second workspace: the passes of odd chunks on `stream2` (overlap mode)
-    hipStream_t stream2 = nullptr;         // created on first use
     int overlap = 0;                       // two chunks in flight on two streams (PMP_OVERLAP=1 in the environment at pmp_create)
     size_t ws_need = 0;                    // what the caller's largest pass so far needed of ws / ws2 (pmp_get_workspace_bytes)
     pmp::DevBuf d_in[3], d_logit[3], d_out[4], d_frames[3];  // staging for the host-pointer entry points
@@ -184,11 +247,10 @@ struct pmp_ctx {
     pmp::DevBuf d_valout;                  // pmp_val_stats: f64[passes][20]
     // calibration of the f16x3 activation scales (NetWeights::act_exp): in a Pass with `cal`, the graph (nets.cpp, running on the fp32
     // datapath) folds the largest |value| of every tensor it produces into d_cal[slot] and logs (name, segment) per slot
-    unsigned *d_cal = nullptr;             // PMP_CAL_SLOTS device words
+    pmp::DevWords d_cal;                   // PMP_CAL_SLOTS device words
     std::vector<std::pair<std::string, int>> cal_log;
     pmp::DevBuf d_calbuf;                  // calibration blocks and their logits
-    hipStream_t cal_stream = nullptr;      // calibration runs on its own stream and workspace: it neither waits for the passes in flight on the
-    pmp::DevBuf ws_cal;                    // context's stream nor touches their workspace (created on first use; 44 MB for 16-block fp32 passes)
+    pmp::DevBuf ws_cal;                    // the workspace of the passes on cal_stream (created on first use; 44 MB for 16-block fp32 passes)
     // test hooks (include/pmp.h): tensor taps and workspace poisoning
     int taps_on = 0;
     std::vector<pmp::TapRec> taps;         // slots, reused call after call; the first ntaps hold the last inference call's tensors in launch order
@@ -197,7 +259,7 @@ struct pmp_ctx {
     // kernel-class timing
     uint32_t kmask = 0;
     std::vector<pmp::KTimeRec> krec[pmp::K_NCLASS];
-    std::vector<hipEvent_t> event_pool;
+    pmp::EventPool event_pool;
     int64_t klaunch[pmp::K_NCLASS] = {0};
     double kms[pmp::K_NCLASS] = {0}, kflops[pmp::K_NCLASS] = {0};
 };
@@ -210,16 +272,36 @@ int hip_fail(pmp_ctx *c, hipError_t e, const char *what);
 // weights_pack.cpp
 int load_net_weights(pmp_ctx *c, int net_id, int qp, const float *blob, const pmp_tensor_desc *descs, int ndesc);
 int ensure_datapath(pmp_ctx *c, NetWeights &w, int precision);   // packs the formats of `precision` if the net does not hold them yet
-void free_net_weights(NetWeights &w);
 // f16x3 activation scales: stores exps in w.act_exp and (re)builds the scaled stem biases and head weights on the device
 int set_activation_scales(pmp_ctx *c, NetWeights &w, const int exps[5]);
 constexpr int PMP_CAL_SLOTS = 128;
 
-// pmp_api.cpp internals that calibrate.cpp shares
+// internals shared by the translation units of the C ABI (pmp_api.cpp, range_guard.cpp, api_labels.cpp, api_debug.cpp) and calibrate.cpp
+// pmp_api.cpp
 int ensure(pmp_ctx *c, DevBuf &b, size_t bytes);                    // grow-only device buffer
 NetWeights *find_net(pmp_ctx *c, int net_id, int qp);               // loaded weights of (net, qp) or nullptr
+int ensure_logits(pmp_ctx *c, int64_t n);                           // the context's own logit buffers, settled before one is regrown
+int stage_blocks(pmp_ctx *c, int comp, const uint8_t *by, const uint8_t *bu, const uint8_t *bv, int64_t n);   // host blocks -> c->d_in
+int h2d(pmp_ctx *c, DevBuf &b, const void *src, size_t bytes);      // ensure + copy on c->stream
+int d2h(pmp_ctx *c, void *dst, const void *src, size_t bytes);      // copy on c->stream; nothing for a null dst
+inline int poison_byte(const pmp_ctx *c) { return c->poison == 1 ? 0xFF : 0x3C; }   // pmp_debug_poison_workspace: NaN bytes or finite garbage
+// range_guard.cpp
 int run_graph(pmp_ctx *c, Pass &ps, const std::function<int()> &fwd);   // a forward graph twice: measuring pass, then the real one in ps.ws
+int infer_device_impl(pmp_ctx *c, int comp, int qp, const uint8_t *by, const uint8_t *bu, const uint8_t *bv, int64_t n, float *qt,
+                      float *bt, float *dire, bool ctx_logits = false, const float *qt_in = nullptr);
+int resolve_pending(pmp_ctx *c, bool wait);                         // looks at the flag snapshots in flight: re-runs and replays
+void drop_pending(pmp_ctx *c);
+int sat_fetch(pmp_ctx *c, unsigned *out);                           // reads and clears the device flag word (synchronises)
+int sync(pmp_ctx *c);                                               // hipStreamSynchronize(c->stream)
 int settle(pmp_ctx *c);                                             // everything asked of the context so far is done and final
+// Host-pointer entry points stage through the context's own buffers (d_in, d_logit, d_out) and return final results.  A *_device call
+// that is still in flight may re-run into those very buffers once its range flag is looked at (and a replayed post-processing call may
+// read them), so everything pending is made final BEFORE the host call stages anything: afterwards the queue holds this call only.
+inline int settle_before_host_call(pmp_ctx *c) { return c->pending.empty() ? PMP_OK : settle(c); }
+void park_workspace(int device, DevBuf &b);                         // pmp_destroy: hands a workspace to the next context on the device
+void trim_parked();                                                 // pmp_trim
+// api_debug.cpp
+void ktime_drain(pmp_ctx *c);                                       // folds the finished timing scopes into the class totals
 // pmp_debug_set_taps: copies a tensor just produced on `stream` into tap-owned memory (stream-ordered, before anything can overwrite it)
 int tap_record(pmp_ctx *c, hipStream_t stream, const std::string &name, const void *p, int n, int C, int H, int W, int c_real, int fmt, int exp);
 
@@ -239,7 +321,7 @@ int forward_q(pmp_ctx *c, Pass &ps, bool luma, const NetWeights &w, const uint8_
 int forward_msbd(pmp_ctx *c, Pass &ps, bool luma, const NetWeights &w, const uint8_t *by, const uint8_t *bu, const uint8_t *bv,
                  const float *qt, int n, float *bt, float *dire);
 
-// timing hooks used by nets.cpp
+// timing hooks used by nets.cpp (api_debug.cpp)
 struct KScope {
     pmp_ctx *c; hipStream_t stream; int cls; bool on; hipEvent_t a, b; double flops;
     KScope(pmp_ctx *c, hipStream_t stream, int cls, double flops);

@@ -1,4 +1,4 @@
-// Internal launch interface between the host-side graph (nets.cpp / pmp_api.cpp) and the HIP kernels.
+// Internal launch interface between the host-side graph (nets.cpp and the C ABI: pmp_api.cpp, range_guard.cpp, api_labels.cpp, api_debug.cpp) and the HIP kernels.
 //
 // Activation layout in HBM ("blocked channels-last"):  act[n][c/16][y][x][c%16]  float32, channels padded to a
 // multiple of 16 with zeros.  A 16-channel group of one tile row is contiguous (16 px * 64 B = 1 KiB), which is
@@ -12,7 +12,7 @@
 namespace pmp {
 
 // pmp_debug_run_resblock: the convolution launchers name the instantiation they launch ("kernel<a,b,...>", template arguments as integers,
-// -1 = absent) - host side, and a no-op unless that hook is collecting on this thread (pmp_api.cpp).
+// -1 = absent) - host side, and a no-op unless that hook is collecting on this thread (api_debug.cpp).
 void note_launch(const char *kernel, int t0, int t1, int t2, int t3 = -1, int t4 = -1);
 
 // ------------------------------------------------------------------------------------------------ conv (MFMA)
