@@ -392,6 +392,63 @@ int pmp_val_stats(pmp_ctx *ctx, int qp, const float *qt, const float *bt, const 
 int pmp_val_stats_device(pmp_ctx *ctx, int qp, const float *d_qt, const float *d_bt, const float *d_dire, const uint8_t *d_qt8,
                          const uint8_t *d_msbt, const int8_t *d_msdire, int64_t n, double *d_stats, double *d_block_stats);
 
+/* ---- training: the objective the nets are trained on and its gradient with respect to the logits, in one pass (trainloss.hip).
+ *      The arithmetic of Train_QBD.loss_func_QBD (Train_QBD.py:68-90), Train_QBD.loss_func_MSBD (:44-66) and the plain L1_Loss of
+ *      pre_train_Q (:161), and of torch's backward pass through them, for ONE batch of n blocks.  These are NOT the validation losses
+ *      above: they take ten weights (Train_QBD's --lambq, --lambb0..2, --lambd0..2, --lambresb0..2, :448-457) and chroma nets use a
+ *      second weight matrix.  Logits and labels in the layouts and dtypes of pmp_val_stats, converted the same way (ql = float(u8(qt8 - 1)):
+ *      a raw qtDepth of 0 becomes 255.0; bl = float(msbt); dl = float(msdire)).
+ *      WEIGHTS: w_k = dl_k*dl_k + float32(M[int((qp - 22) / 5)][k]), 22 <= qp <= 41, M = luma_weight_mat (= weight_mat above) for PMP_LUMA and
+ *      chroma_weight_mat = 0.5 * {{17.83, 0.49, 0.11}, {1.20, 0.25, 0.07}, {0.58, 0.17, 0.05}, {0.38, 0.12, 0.04}} for PMP_CHROMA
+ *      (Train_QBD.py:35-42); w_0 = 1.0 when qp == 22, for both components (:53-54, :76-77).
+ *      SUMS: T[0..12] are, term for term and in the same order of additions, S[0..12] of pmp_val_stats with the component's matrix in w -
+ *      for PMP_LUMA they equal pmp_val_stats_device's, bit for bit.  T[4..6], the unweighted direction L1 sums, are not part of the loss;
+ *      the training loops print them (Train_QBD.py:249-251).
+ *      LOSS, a float64 formed in this written order:
+ *        loss = lambq*T0/(64n) + (lambb0*T1 + lambb1*T2 + lambb2*T3 + lambd0*T7 + lambd1*T8 + lambd2*T9
+ *                                 + lambresb0*T10 + lambresb1*T11 + lambresb2*T12)/(256n)
+ *      GRADIENTS of that loss (optional).  sgn(x) is torch.sign, by which torch's backward of abs multiplies: +1, -1, and 0 for x == 0
+ *      AND for a NaN x (measured on the reference: a NaN term, an inf - inf layer difference included, gives a ZERO gradient, while the
+ *      loss is NaN; +-inf terms give -+1).  Every sign is taken of the float32 term exactly as the sums form it, so a term that is exactly
+ *      zero in float32 contributes zero:
+ *        a_k = sgn(bt_k - bl_k)      c_k = sgn(w_k*dire_k - w_k*dl_k)      e_0 = sgn(w_0*bt_0 - w_0*bl_0)
+ *        e_k = sgn(w_k*(bt_k - bt_{k-1}) - w_k*(bl_k - bl_{k-1})),  k = 1, 2
+ *        g_qt     = lambq*sgn(qt - ql) / (64n)
+ *        g_dire_k = lambd_k*w_k*c_k / (256n)
+ *        g_bt_k   = (lambb_k*a_k + lambresb_k*w_k*e_k - [k < 2] lambresb_{k+1}*w_{k+1}*e_{k+1}) / (256n)
+ *      each computed in float64 from the float32 w and the double weights, left to right as written, and rounded ONCE to float32.  Every
+ *      byte of a requested gradient tensor is written.  Against torch's float32 backward they differ by float32 rounding only
+ *      (tests/golden/g14_train_loss.npz records the measured distance); their zero pattern is torch's.
+ *      DETERMINISM: as pmp_val_stats - float64 sums in a fixed order that depends on n only, no atomics, the same bits on every run,
+ *      stream, context and chunk setting of pmp_train_loss_device.
+ *      FORMS (the NULL rules of pmp_val_stats): all inputs = loss_func_QBD; qt, qt8 NULL = loss_func_MSBD (T[0] = 0); bt, dire, msbt,
+ *      msdire NULL = pre_train_Q's L1 (T[1..12] = 0; pass lambq = 1).  p NULL = Train_QBD's defaults.  terms and loss are required.
+ *      Gradient pointers: all NULL (value only, nothing else is written) or exactly those of the form's logits.  PMP_E_INVALID before
+ *      any launch, nothing written: any other mix, comp not PMP_LUMA / PMP_CHROMA, n < 0, qp outside 22..41, a weight that is not
+ *      finite, NULL terms or loss, a gradient tensor that overlaps an input.  n = 0: thirteen zeros, loss 0, no launch.
+ *      pmp_train_loss_device: device pointers - bt, dire, g_bt, g_dire 16-byte aligned, the other inputs and g_qt 4-byte, terms and loss
+ *      8-byte (PMP_E_INVALID otherwise) - stream-ordered on the context's stream; the host does not wait for the kernel.  RANGE GUARD:
+ *      unlike a statistics call it is never queued for a replay: it first SETTLES the context's calls in flight, as the pmp_debug_set_*
+ *      calls do, so a caller whose logits come from a pending pmp_infer*_device call gets the loss of the FINAL logits (and waits for
+ *      them).  Logits that come from elsewhere (a torch forward pass) find nothing in flight and pay nothing.
+ *      pmp_train_loss: host pointers; runs in passes of at most pmp_set_chunk blocks through staging buffers.  The sums are the pass
+ *      sums added in pass order (so their bits depend on the chunk setting), the loss is formed from them on the host in the same
+ *      float64 order, and every pass divides by the WHOLE call's n: the gradients do not depend on the chunk setting.
+ *      pmp_parse_loss_params is host-only (no context, no GPU): it reads "lambb0=0.8,lambresb2=0" (keys lambq, lambb0..2, lambd0..2,
+ *      lambresb0..2, comma-separated, any subset, the last of a repeated key wins) on top of *inout and writes *inout only if the
+ *      whole text parses to finite numbers; "" leaves *inout as it is. ---- */
+typedef struct {
+    double lambq, lambb[3], lambd[3], lambresb[3];   /* defaults 1.0 | 0.8, 1.0, 1.2 | 1, 1, 1 | 0.5, 0.5, 0.5 (Train_QBD.py:448-457) */
+} pmp_loss_params;
+#define PMP_LOSS_NTERMS 13
+int pmp_parse_loss_params(const char *spec, pmp_loss_params *inout);
+int pmp_train_loss(pmp_ctx *ctx, int comp, int qp, const pmp_loss_params *p, const float *qt, const float *bt, const float *dire,
+                   const uint8_t *qt8, const uint8_t *msbt, const int8_t *msdire, int64_t n, double terms[PMP_LOSS_NTERMS], double *loss,
+                   float *g_qt, float *g_bt, float *g_dire);
+int pmp_train_loss_device(pmp_ctx *ctx, int comp, int qp, const pmp_loss_params *p, const float *d_qt, const float *d_bt,
+                          const float *d_dire, const uint8_t *d_qt8, const uint8_t *d_msbt, const int8_t *d_msdire, int64_t n,
+                          double *d_terms, double *d_loss, float *d_g_qt, float *d_g_bt, float *d_g_dire);
+
 /* ---- teacher-forced MTT inference: the MTT net of (comp, qp) on the blocks with a GIVEN QT map instead of the QT net's output, what
  *      pre_validation predID 1 runs (Net(input_batch, qt_label_batch), Metrics.py:226).  qt_in f32[n][8][8] is read, never written
  *      (for the reference's validation: float(qt8 - 1) with the u8 wrap above).  Everything else is pmp_infer's: the context's datapath,

@@ -11,6 +11,7 @@ PMP_LUMA, PMP_CHROMA = 0, 1
 PMP_RECORD_BYTES = 1344
 PMP_MSBT_LEAF_BUDGET = 4096
 PMP_VAL_NSTATS = 20
+PMP_LOSS_NTERMS = 13
 PMP_MSBT_INCONSISTENT, PMP_MSBT_QT_DEEP, PMP_MSBT_BUDGET = 1, 2, 4
 NET_IDS = {"Luma_Q": 0, "Luma_MSBD": 1, "Chroma_Q": 2, "Chroma_MSBD": 3}
 ERRORS = {-1: "PMP_E_INVALID", -2: "PMP_E_HIP", -3: "PMP_E_NOWEIGHTS", -4: "PMP_E_IO", -5: "PMP_E_NOMEM", -6: "PMP_E_NODEVICE", -7: "PMP_E_RANGE"}
@@ -29,6 +30,11 @@ class TensorDesc(C.Structure):
 class PartitionParams(C.Structure):
     """pmp_partition_params: Map_to_Partition's lamb1..lamb5 (Map2Partition.py:100) and th_round's thd (:105)."""
     _fields_ = [("lamb", C.c_double * 5), ("thd", C.c_float)]
+
+
+class LossParams(C.Structure):
+    """pmp_loss_params: Train_QBD's --lambq, --lambb0..2, --lambd0..2, --lambresb0..2 (Train_QBD.py:448-457)."""
+    _fields_ = [("lambq", C.c_double), ("lambb", C.c_double * 3), ("lambd", C.c_double * 3), ("lambresb", C.c_double * 3)]
 
 
 # name -> (restype, argtypes); every symbol declared in include/pmp.h
@@ -76,6 +82,9 @@ SIGNATURES = {
     "pmp_label_partition_records_device": (_I, [_VP, _I, _VP, _VP, _VP, _I64, _VP, _VP]),
     "pmp_val_stats": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
     "pmp_val_stats_device": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
+    "pmp_parse_loss_params": (_I, [C.c_char_p, C.POINTER(LossParams)]),
+    "pmp_train_loss": (_I, [_VP, _I, _I, C.POINTER(LossParams), _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP]),
+    "pmp_train_loss_device": (_I, [_VP, _I, _I, C.POINTER(LossParams), _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP]),
     "pmp_infer_msbd": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
     "pmp_infer_msbd_device": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
     "pmp_read_depth_dump": (_I, [C.c_char_p, _I, _I, _I, _I, _VP, _VP, _VP, C.POINTER(_I64)]),

@@ -1,6 +1,7 @@
 // api_labels.cpp — the entry points that work on VTM's labels (include/pmp.h): MSBT training labels, the labels' own partition,
-// validation statistics and teacher-forced MTT inference.
+// validation statistics, teacher-forced MTT inference and the training losses.
 #include <algorithm>
+#include <cmath>
 #include <initializer_list>
 
 #include "pmp_host.h"
@@ -153,12 +154,16 @@ struct ValArgs {
 };
 }  // namespace
 
+// Metrics.py:148-151 = Train_QBD.py:35-38 (luma) and Train_QBD.py:39-42 (chroma, training only); the float64 entry becomes a float32
+// scalar when torch adds it to the float32 dl*dl
+static const double weight_mat[4][3] = {{0.5 * 1.0, 0.5 * 0.73, 0.5 * 0.15}, {0.5 * 2.43, 0.5 * 0.35, 0.5 * 0.10},
+                                        {0.5 * 0.96, 0.5 * 0.23, 0.5 * 0.07}, {0.5 * 0.59, 0.5 * 0.16, 0.5 * 0.05}};
+static const double chroma_weight_mat[4][3] = {{0.5 * 17.83, 0.5 * 0.49, 0.5 * 0.11}, {0.5 * 1.20, 0.5 * 0.25, 0.5 * 0.07},
+                                               {0.5 * 0.58, 0.5 * 0.17, 0.5 * 0.05}, {0.5 * 0.38, 0.5 * 0.12, 0.5 * 0.04}};
+
 static int val_check(pmp_ctx *c, int qp, const void *qt, const void *bt, const void *dire, const void *qt8, const void *msbt,
                      const void *msdire, int64_t n, const void *stats, float wm[3], int *w0_one)
 {
-    // Metrics.py:148-151; the float64 entry becomes a float32 scalar when torch adds it to the float32 dl*dl
-    static const double weight_mat[4][3] = {{0.5 * 1.0, 0.5 * 0.73, 0.5 * 0.15}, {0.5 * 2.43, 0.5 * 0.35, 0.5 * 0.10},
-                                            {0.5 * 0.96, 0.5 * 0.23, 0.5 * 0.07}, {0.5 * 0.59, 0.5 * 0.16, 0.5 * 0.05}};
     if (qp < 22 || qp > 41) return set_err(c, PMP_E_INVALID, "pmp_val_stats: qp must be in 22..41 (rows 0..3 of weight_mat)");
     if (n < 0 || !stats) return set_err(c, PMP_E_INVALID, "pmp_val_stats: negative count or null stats");
     const bool q = qt && qt8, noq = !qt && !qt8, m = bt && dire && msbt && msdire, nom = !bt && !dire && !msbt && !msdire;
@@ -238,6 +243,132 @@ int pmp_val_stats(pmp_ctx *c, int qp, const float *qt, const float *bt, const fl
     if ((rc = d2h(c, rows.data(), c->d_valout.p, rows.size() * sizeof(double))) || (rc = sync(c))) return rc;
     for (int64_t p = 0; p < passes; ++p)          // the whole call as one batch: pass results in pass order
         for (int i = 0; i < PMP_VAL_NSTATS; ++i) stats[i] += rows[(size_t)p * PMP_VAL_NSTATS + i];
+    return PMP_OK;
+}
+
+// ---- training losses and their logit gradients (trainloss.hip) ------------------------------------------------------------
+namespace {
+struct TrainArgs {
+    const float *qt, *bt, *dire;
+    const uint8_t *qt8, *msbt;
+    const int8_t *msdire;
+    float *g_qt, *g_bt, *g_dire;
+    pmp_loss_params L;
+    float wm[3];
+    int w0_one;
+};
+const pmp_loss_params LOSS_DEFAULT = {1.0, {0.8, 1.0, 1.2}, {1.0, 1.0, 1.0}, {0.5, 0.5, 0.5}};   // Train_QBD.py:448-457
+
+bool overlaps(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return a && b && x < y + nb && y < x + na;
+}
+}  // namespace
+
+// Every check of pmp_train_loss* that does not depend on where the pointers live; fills a.L, a.wm, a.w0_one.  Nothing is written before it passes.
+static int train_check(pmp_ctx *c, int comp, int qp, const pmp_loss_params *p, int64_t n, const void *terms, const void *loss, TrainArgs &a)
+{
+    if (comp != PMP_LUMA && comp != PMP_CHROMA) return set_err(c, PMP_E_INVALID, "pmp_train_loss: comp must be PMP_LUMA or PMP_CHROMA");
+    if (qp < 22 || qp > 41) return set_err(c, PMP_E_INVALID, "pmp_train_loss: qp must be in 22..41 (rows 0..3 of the weight matrices)");
+    if (n < 0 || !terms || !loss) return set_err(c, PMP_E_INVALID, "pmp_train_loss: negative count, null terms or null loss");
+    a.L = p ? *p : LOSS_DEFAULT;
+    const double *lam = &a.L.lambq;
+    for (int i = 0; i < 10; ++i)
+        if (!std::isfinite(lam[i])) return set_err(c, PMP_E_INVALID, "pmp_train_loss: a loss weight is not finite");
+    if (n > 0) {
+        const bool q = a.qt && a.qt8, noq = !a.qt && !a.qt8, m = a.bt && a.dire && a.msbt && a.msdire,
+                   nom = !a.bt && !a.dire && !a.msbt && !a.msdire;
+        if (!((q && m) || (q && nom) || (noq && m)))
+            return set_err(c, PMP_E_INVALID, "pmp_train_loss: pass (qt, qt8), (bt, dire, msbt, msdire) or both; no other NULL mix");
+        const bool none = !a.g_qt && !a.g_bt && !a.g_dire;
+        if (!none && ((a.g_qt != nullptr) != q || (a.g_bt != nullptr) != m || (a.g_dire != nullptr) != m))
+            return set_err(c, PMP_E_INVALID, "pmp_train_loss: gradient pointers are all NULL or exactly those of the logits given");
+        const struct { const void *p; size_t per; } in[6] = {{a.qt, 256}, {a.bt, 3072}, {a.dire, 3072}, {a.qt8, 64}, {a.msbt, 768}, {a.msdire, 768}},
+                                                    g[3] = {{a.g_qt, 256}, {a.g_bt, 3072}, {a.g_dire, 3072}};
+        for (const auto &o : g)
+            for (const auto &i : in)
+                if (overlaps(o.p, (size_t)n * o.per, i.p, (size_t)n * i.per))
+                    return set_err(c, PMP_E_INVALID, "pmp_train_loss: a gradient tensor overlaps an input");
+    }
+    const double(*M)[3] = comp == PMP_LUMA ? weight_mat : chroma_weight_mat;
+    for (int k = 0; k < 3; ++k) a.wm[k] = (float)M[(qp - 22) / 5][k];
+    a.w0_one = qp == 22;
+    return PMP_OK;
+}
+
+// m blocks at the pointers of `a`, gradient divisors of an n_div-block call; block partials in the context's scratch
+static int train_launch(pmp_ctx *c, const TrainArgs &a, int64_t m, int64_t n_div, double *terms, double *loss)
+{
+    const int rc = ensure(c, c->d_trainpart, (size_t)m * PMP_LOSS_NTERMS * sizeof(double));
+    if (rc != PMP_OK) return rc;
+    const hipError_t e = launch_train_loss(c->stream, a.qt, a.bt, a.dire, a.qt8, a.msbt, a.msdire, m, n_div, a.wm, a.w0_one, a.L,
+                                           (double *)c->d_trainpart.p, terms, loss, a.g_qt, a.g_bt, a.g_dire);
+    return e == hipSuccess ? PMP_OK : hip_fail(c, e, "train_loss");
+}
+
+int pmp_train_loss_device(pmp_ctx *c, int comp, int qp, const pmp_loss_params *p, const float *qt, const float *bt, const float *dire,
+                          const uint8_t *qt8, const uint8_t *msbt, const int8_t *msdire, int64_t n, double *terms, double *loss,
+                          float *g_qt, float *g_bt, float *g_dire)
+{
+    CHECK_CTX(c);
+    TrainArgs a{qt, bt, dire, qt8, msbt, msdire, g_qt, g_bt, g_dire, LOSS_DEFAULT, {0.f, 0.f, 0.f}, 0};
+    int rc;
+    if ((rc = train_check(c, comp, qp, p, n, terms, loss, a))) return rc;
+    if (misaligned({terms, loss}, 7) || (n > 0 && (misaligned({bt, dire, g_bt, g_dire}, 15) || misaligned({qt, qt8, msbt, msdire, g_qt}, 3))))
+        return set_err(c, PMP_E_INVALID, "pmp_train_loss_device: bt, dire, g_bt, g_dire must be 16-byte aligned, the other inputs and g_qt 4-byte, terms and loss 8-byte");
+    // never queued for a range-guard replay: whatever is in flight on the context is made final first (nothing, for logits from elsewhere)
+    if ((rc = settle_before_host_call(c))) return rc;
+    if (n == 0) {
+        hipError_t e = hipMemsetAsync(terms, 0, PMP_LOSS_NTERMS * sizeof(double), c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(loss, 0, sizeof(double), c->stream);
+        return e == hipSuccess ? PMP_OK : hip_fail(c, e, "train_loss");
+    }
+    return train_launch(c, a, n, n, terms, loss);
+}
+
+int pmp_train_loss(pmp_ctx *c, int comp, int qp, const pmp_loss_params *p, const float *qt, const float *bt, const float *dire,
+                   const uint8_t *qt8, const uint8_t *msbt, const int8_t *msdire, int64_t n, double terms[PMP_LOSS_NTERMS], double *loss,
+                   float *g_qt, float *g_bt, float *g_dire)
+{
+    CHECK_CTX(c);
+    TrainArgs a{qt, bt, dire, qt8, msbt, msdire, g_qt, g_bt, g_dire, LOSS_DEFAULT, {0.f, 0.f, 0.f}, 0};
+    int rc;
+    if ((rc = train_check(c, comp, qp, p, n, terms, loss, a))) return rc;
+    for (int i = 0; i < PMP_LOSS_NTERMS; ++i) terms[i] = 0.0;
+    *loss = 0.0;
+    if (n == 0) return PMP_OK;
+    if ((rc = settle_before_host_call(c))) return rc;
+    // about 6.9 kB in and, with gradients, 6.4 kB out per block through the context's own staging buffers; one row of sums per pass
+    const int64_t passes = (n + c->chunk - 1) / c->chunk;
+    if ((rc = ensure(c, c->d_trainout, (size_t)passes * PMP_LOSS_NTERMS * sizeof(double)))) return rc;
+    DevBuf *d = c->d_val, *g = c->d_train;
+    TrainArgs s = a;                                   // the same call on the staging buffers
+    const auto run = [&](std::initializer_list<StagedOut> outs) {
+        return staged_passes(c, n, {{qt, 64 * 4, d[0]}, {bt, 768 * 4, d[1]}, {dire, 768 * 4, d[2]}, {qt8, 64, d[3]}, {msbt, 768, d[4]}, {msdire, 768, d[5]}},
+                             outs, [&](int64_t m, int64_t pass) {
+                                 s.qt = qt ? (const float *)d[0].p : nullptr;
+                                 s.bt = bt ? (const float *)d[1].p : nullptr;
+                                 s.dire = bt ? (const float *)d[2].p : nullptr;
+                                 s.qt8 = qt ? (const uint8_t *)d[3].p : nullptr;
+                                 s.msbt = bt ? (const uint8_t *)d[4].p : nullptr;
+                                 s.msdire = bt ? (const int8_t *)d[5].p : nullptr;
+                                 s.g_qt = g_qt ? (float *)g[0].p : nullptr;
+                                 s.g_bt = g_bt ? (float *)g[1].p : nullptr;
+                                 s.g_dire = g_dire ? (float *)g[2].p : nullptr;
+                                 return train_launch(c, s, m, n, (double *)c->d_trainout.p + pass * PMP_LOSS_NTERMS, nullptr);
+                             });
+    };
+    if (g_qt && g_bt) rc = run({{g_qt, 64 * 4, g[0], 0}, {g_bt, 768 * 4, g[1], 0}, {g_dire, 768 * 4, g[2], 0}});
+    else if (g_qt) rc = run({{g_qt, 64 * 4, g[0], 0}});
+    else if (g_bt) rc = run({{g_bt, 768 * 4, g[1], 0}, {g_dire, 768 * 4, g[2], 0}});
+    else rc = run({});
+    if (rc != PMP_OK) return rc;
+    std::vector<double> rows((size_t)passes * PMP_LOSS_NTERMS);
+    if ((rc = d2h(c, rows.data(), c->d_trainout.p, rows.size() * sizeof(double))) || (rc = sync(c))) return rc;
+    for (int64_t q = 0; q < passes; ++q)              // the whole call as one batch: pass sums in pass order
+        for (int i = 0; i < PMP_LOSS_NTERMS; ++i) terms[i] += rows[(size_t)q * PMP_LOSS_NTERMS + i];
+    *loss = train_loss_value(terms, a.L, n);
     return PMP_OK;
 }
 

@@ -374,4 +374,47 @@ int pmp_parse_partition_params(const char *spec, pmp_partition_params *inout)
     return PMP_OK;
 }
 
+// ---- Train_QBD's ten loss weights (include/pmp.h: pmp_loss_params), the same grammar as above ------------------------------
+int pmp_parse_loss_params(const char *spec, pmp_loss_params *inout)
+{
+    if (!spec || !inout) return set_err_global(PMP_E_INVALID, "pmp_parse_loss_params: null argument");
+    pmp_loss_params p = *inout;
+    const char *s = spec;
+    while (*s) {
+        while (*s == ' ' || *s == '\t') ++s;
+        const char *k0 = s;
+        while (*s && *s != '=' && *s != ',' && *s != ' ' && *s != '\t') ++s;
+        const std::string key(k0, s);
+        while (*s == ' ' || *s == '\t') ++s;
+        if (key.empty() && !*s) break;                    // "" or blanks only
+        if (key.empty() || *s != '=')                     // an empty item (",,", a trailing comma) is an error here
+            return set_err_global(PMP_E_INVALID, "pmp_parse_loss_params: expected key=value at '" + std::string(k0) + "'");
+        ++s;
+        while (*s == ' ' || *s == '\t') ++s;
+        const char *v0 = s;
+        while (*s && *s != ',') ++s;
+        std::string val(v0, s);
+        while (!val.empty() && (val.back() == ' ' || val.back() == '\t')) val.pop_back();
+        char *end = nullptr;
+        const double d = val.empty() ? 0.0 : std::strtod(val.c_str(), &end);
+        if (val.empty() || end != val.c_str() + val.size() || !std::isfinite(d))
+            return set_err_global(PMP_E_INVALID, "pmp_parse_loss_params: '" + val + "' is not a finite number (key " + key + ")");
+        const int i = key.empty() ? -1 : key.back() - '0';
+        const std::string stem = key.substr(0, key.size() - 1);
+        if (key == "lambq") p.lambq = d;
+        else if (i >= 0 && i <= 2 && stem == "lambb") p.lambb[i] = d;
+        else if (i >= 0 && i <= 2 && stem == "lambd") p.lambd[i] = d;
+        else if (i >= 0 && i <= 2 && stem == "lambresb") p.lambresb[i] = d;
+        else
+            return set_err_global(PMP_E_INVALID, "pmp_parse_loss_params: unknown key '" + key + "' (lambq, lambb0..2, lambd0..2, lambresb0..2)");
+        if (*s == ',') {
+            ++s;
+            while (*s == ' ' || *s == '\t') ++s;
+            if (!*s) return set_err_global(PMP_E_INVALID, "pmp_parse_loss_params: trailing comma");
+        }
+    }
+    *inout = p;
+    return PMP_OK;
+}
+
 }  // extern "C"

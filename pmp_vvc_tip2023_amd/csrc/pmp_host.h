@@ -245,6 +245,9 @@ struct pmp_ctx {
     pmp::DevBuf d_val[6];                  // staging of pmp_val_stats: qt, bt, dire, qt8, msbt, msdire
     pmp::DevBuf d_valpart;                 // validation statistics: per-block partials f64[n][20] of a call that passes no d_block_stats
     pmp::DevBuf d_valout;                  // pmp_val_stats: f64[passes][20]
+    pmp::DevBuf d_train[3];                // staging of pmp_train_loss's gradients: g_qt, g_bt, g_dire (its inputs go through d_val)
+    pmp::DevBuf d_trainpart;               // training losses: per-block partials f64[n][13]
+    pmp::DevBuf d_trainout;                // pmp_train_loss: f64[passes][13]
     // calibration of the f16x3 activation scales (NetWeights::act_exp): in a Pass with `cal`, the graph (nets.cpp, running on the fp32
     // datapath) folds the largest |value| of every tensor it produces into d_cal[slot] and logs (name, segment) per slot
     pmp::DevWords d_cal;                   // PMP_CAL_SLOTS device words

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pmp.h"         // pmp_loss_params (include/)
 #include "abl_types.h"   // hooks/ in the product build (empty structs), abl/ in the measurement library
 
 namespace pmp {
@@ -194,6 +195,17 @@ hipError_t launch_label_partition(hipStream_t s, const uint8_t *qt, const uint8_
 // wm: float32(weight_mat[row][0..2]); w0_one: qp == 22 (weight_d0 = 1.0).  bt, dire 16-byte aligned, msbt, msdire 4-byte aligned.  N >= 1.
 hipError_t launch_val_stats(hipStream_t s, const float *qt, const float *bt, const float *dire, const uint8_t *qt8, const uint8_t *msbt,
                             const int8_t *msdire, int64_t N, const float wm[3], int w0_one, double *block_stats, double *stats);
+
+// Training losses and their logit gradients (trainloss.hip; include/pmp.h: pmp_train_loss): the same inputs, alignments and NULL forms
+// as launch_val_stats, wm from the component's matrix -> block_terms f64[N][13] (scratch, always written), their fixed-order sum
+// terms f64[13] and, if loss != null, train_loss_value(terms, L, n_div).  g_qt f32[N][64], g_bt, g_dire f32[N][3][256] (16-byte
+// aligned): all null = value only, else those of the logits given; every cell is written.  n_div: the block count in the gradients'
+// divisors 64 n and 256 n (the whole call's, where N is one pass of it).  N >= 1.
+hipError_t launch_train_loss(hipStream_t s, const float *qt, const float *bt, const float *dire, const uint8_t *qt8, const uint8_t *msbt,
+                             const int8_t *msdire, int64_t N, int64_t n_div, const float wm[3], int w0_one, const pmp_loss_params &L,
+                             double *block_terms, double *terms, double *loss, float *g_qt, float *g_bt, float *g_dire);
+// lambq T0 / (64 n) + (lambb0 T1 + .. + lambresb2 T12) / (256 n) in float64, in that order, on either side (no FMA)
+__host__ __device__ double train_loss_value(const double T[PMP_LOSS_NTERMS], const pmp_loss_params &L, int64_t n);
 
 // Block cutter (Inference_QBD.py:104-149).
 hipError_t launch_cut_blocks(hipStream_t s, const void *y, const void *u, const void *v, int F, int H, int W,

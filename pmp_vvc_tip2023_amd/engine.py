@@ -12,6 +12,7 @@ Same names and argument meaning as the reference so callers (and the parity test
     GenMSBtMap.get_sequence_partition_for_VTM(...)      Engine.label_partition_for_VTM(...)             (labels -> PartitionMat file)
     Metrics.validation_QBD(loader, Net_Q, Net_BD, qp)   Engine.validation_QBD(comp, qp, blocks, qt8, msbt, msdire, batch_size)
     Metrics.pre_validation(loader, Net, predID, qp)     Engine.pre_validation(comp, qp, pred_id, blocks, qt8[, msbt, msdire], batch_size)
+    Train_QBD.loss_func_QBD / loss_func_MSBD / L1_Loss  Engine.train_loss(comp, qp, ...)  (+ gradients; torch: train_loss.py)
     CreateDataSet.output_block_partition_map(...)       output_block_partition_map(...)                 (module level, host only)
 
 numpy arrays in/out for the host API; the *_device methods take raw device pointers (ints), e.g. torch
@@ -357,6 +358,40 @@ class Engine:
         partials f64[n,20] -> d_block_stats; stream-ordered, final after synchronize() (include/pmp.h: range guard)."""
         self._ck(self.lib.pmp_val_stats_device(self.h, int(qp), d_qt, d_bt, d_dire, d_qt8, d_msbt, d_msdire, int(n), d_stats, d_block_stats))
 
+    # ------------------------------------------------------------------------------------------ training losses
+    def train_loss(self, comp, qp, qt=None, bt=None, dire=None, qt8=None, msbt=None, msdire=None, params=None, want_grads=True):
+        """pmp_train_loss (include/pmp.h): Train_QBD.loss_func_QBD (all six given), loss_func_MSBD (no qt, qt8) or pre_train_Q's L1 (qt, qt8
+        only) of one batch, and the gradient of that loss with respect to the logits.  Arrays as val_stats takes them; params: a dict with
+        any of LOSS_KEYS, a "lambb0=0.8,..." text or a LossParams (None: Train_QBD's defaults).
+        -> (terms float64[13], loss float, grads): grads is None without want_grads, else {"qt": f32[N,8,8], "bt": f32[N,3,16,16],
+        "dire": f32[N,3,16,16]} with the entries of the logits given."""
+        f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+        qt, bt, dire = f(qt), f(bt), f(dire)
+        qt8 = None if qt8 is None else _fit(qt8, np.uint8, "qt8")
+        msbt = None if msbt is None else _fit(msbt, np.uint8, "msbt")
+        msdire = None if msdire is None else _fit(msdire, np.int8, "msdire")
+        n = _val_count(qt, bt, dire, qt8, msbt, msdire)
+        terms = np.zeros(_lib.PMP_LOSS_NTERMS, np.float64)
+        loss = np.zeros(1, np.float64)
+        grads = None
+        if want_grads:
+            grads = {}
+            if qt is not None:
+                grads["qt"] = np.empty((n, 8, 8), np.float32)
+            if bt is not None:
+                grads["bt"] = np.empty((n, 3, 16, 16), np.float32); grads["dire"] = np.empty((n, 3, 16, 16), np.float32)
+        g = grads or {}
+        self._ck(self.lib.pmp_train_loss(self.h, COMP_ID[comp], int(qp), loss_params(params), _ptr(qt), _ptr(bt), _ptr(dire), _ptr(qt8), _ptr(msbt),
+                                         _ptr(msdire), n, _ptr(terms), _ptr(loss), _ptr(g.get("qt")), _ptr(g.get("bt")), _ptr(g.get("dire"))))
+        return terms, float(loss[0]), grads
+
+    def train_loss_device(self, comp, qp, d_qt, d_bt, d_dire, d_qt8, d_msbt, d_msdire, n, d_terms, d_loss, d_g_qt=None, d_g_bt=None,
+                          d_g_dire=None, params=None):
+        """pmp_train_loss_device: device pointers (None for the pair / the four left out; gradients all None or those of the logits given),
+        f64[13] -> d_terms, f64 -> d_loss; stream-ordered on the engine's stream, the host does not wait."""
+        self._ck(self.lib.pmp_train_loss_device(self.h, COMP_ID[comp], int(qp), loss_params(params), d_qt, d_bt, d_dire, d_qt8, d_msbt, d_msdire,
+                                                int(n), d_terms, d_loss, d_g_qt, d_g_bt, d_g_dire))
+
     def infer_msbd(self, comp, qp, qt_in, block_y, block_u=None, block_v=None):
         """Teacher-forced MTT inference (pmp_infer_msbd; Net(input_batch, qt_label_batch), Metrics.py:226): the MTT net of (comp, qp) on
         the blocks with the GIVEN QT map qt_in f32[N,(1,)8,8] -> bt f32[N,3,16,16], dire f32[N,3,16,16]."""
@@ -534,6 +569,27 @@ def _fit(a, dtype, name):
                    or a.min() < info.min or a.max() > info.max):
         raise ValueError("%s: values outside %s (the reference's dtype); refusing to wrap them" % (name, np.dtype(dtype).name))
     return np.ascontiguousarray(a.astype(dtype))
+
+
+LOSS_KEYS = ("lambq", "lambb0", "lambb1", "lambb2", "lambd0", "lambd1", "lambd2", "lambresb0", "lambresb1", "lambresb2")
+
+
+def loss_params(params=None):
+    """-> _lib.LossParams from None (Train_QBD's defaults, Train_QBD.py:448-457), a dict with any of LOSS_KEYS, a text such as
+    "lambb0=0.8,lambresb2=0" (pmp_parse_loss_params) or a LossParams.  An unknown key or a value that is not finite: ValueError."""
+    if isinstance(params, _lib.LossParams):
+        return params
+    p = _lib.LossParams(1.0, (0.8, 1.0, 1.2), (1.0, 1.0, 1.0), (0.5, 0.5, 0.5))
+    if params is None:
+        return p
+    if isinstance(params, dict):
+        bad = [k for k in params if k not in LOSS_KEYS]
+        if bad:
+            raise ValueError("loss_params: unknown key %s (one of %s)" % (bad[0], ", ".join(LOSS_KEYS)))
+        params = ",".join("%s=%r" % (k, float(v)) for k, v in params.items())
+    if _lib.load().pmp_parse_loss_params(str(params).encode(), C.byref(p)) != 0:
+        raise ValueError(_lib.load().pmp_last_error(None).decode())
+    return p
 
 
 VAL_ELEMS = np.array([64] + [256] * 12 + [64] + [256] * 6, np.float64)      # elements per block behind each of the twenty statistics
