@@ -11,7 +11,7 @@ using namespace pmp;
 // ---- one staged pass loop for the host-pointer entry points below ----------------------------------------------------------
 namespace {
 struct StagedIn { const void *host; size_t per; DevBuf &buf; };          // per: bytes per block; host null: left out, nothing staged
-struct StagedOut { void *host; size_t per; DevBuf &buf; size_t off; };   // starts `off` bytes per block into buf (hor | ver share one)
+struct StagedOut { void *host; size_t per; DevBuf &buf; size_t off; };   // starts `off` bytes per block into buf (hor | ver share one); host null: left out
 }  // namespace
 
 // n blocks in passes of at most `chunk` through the context's staging buffers, all on c->stream: H2D of every input, launch(blocks of
@@ -24,14 +24,16 @@ static int staged_passes(pmp_ctx *c, int64_t n, std::initializer_list<StagedIn> 
     for (const StagedIn &i : ins)
         if (i.host && (rc = ensure(c, i.buf, (size_t)m0 * i.per))) return rc;
     for (const StagedOut &o : outs) {
+        if (!o.host) continue;
         size_t per = 0;                                // of the whole buffer: the outputs that share it lie plane behind plane
-        for (const StagedOut &q : outs) if (&q.buf == &o.buf) per = std::max(per, q.off + q.per);
+        for (const StagedOut &q : outs) if (q.host && &q.buf == &o.buf) per = std::max(per, q.off + q.per);
         if ((rc = ensure(c, o.buf, (size_t)m0 * per))) return rc;
     }
     for (int64_t at = 0, pass = 0; at < n; at += chunk, ++pass) {
         const int64_t m = (n - at) < chunk ? (n - at) : chunk;
         if (c->poison) {          // pmp_debug_poison_workspace: the kernel must write every output byte it hands back
             for (const StagedOut &o : outs) {
+                if (!o.host) continue;
                 const hipError_t e = hipMemsetAsync((char *)o.buf.p + (size_t)m * o.off, poison_byte(c), (size_t)m * o.per, c->stream);
                 if (e != hipSuccess) return hip_fail(c, e, "poison label buffers");
             }
@@ -40,7 +42,7 @@ static int staged_passes(pmp_ctx *c, int64_t n, std::initializer_list<StagedIn> 
             if (i.host && (rc = h2d(c, i.buf, (const char *)i.host + (size_t)at * i.per, (size_t)m * i.per))) return rc;
         if ((rc = launch(m, pass))) return rc;
         for (const StagedOut &o : outs)
-            if ((rc = d2h(c, (char *)o.host + (size_t)at * o.per, (const char *)o.buf.p + (size_t)m * o.off, (size_t)m * o.per))) return rc;
+            if (o.host && (rc = d2h(c, (char *)o.host + (size_t)at * o.per, (const char *)o.buf.p + (size_t)m * o.off, (size_t)m * o.per))) return rc;
         if ((rc = sync(c))) return rc;
     }
     return PMP_OK;
@@ -55,6 +57,8 @@ static int label_args(pmp_ctx *c, const char *fn, int cf, int64_t n, std::initia
     if (n > 0 && std::find(bufs.begin(), bufs.end(), nullptr) != bufs.end()) return set_err(c, PMP_E_INVALID, f + ": null buffer");
     return PMP_OK;
 }
+
+static int hip_rc(pmp_ctx *c, hipError_t e, const char *what) { return e == hipSuccess ? PMP_OK : hip_fail(c, e, what); }
 
 static bool misaligned(std::initializer_list<const void *> ps, uintptr_t mask)
 {
@@ -75,8 +79,7 @@ int pmp_msbt_labels_device(pmp_ctx *c, int cf, const uint8_t *qt, const uint8_t 
     if (n == 0) return PMP_OK;
     if (misaligned({qt, bt, dire, msbt}, 3))
         return set_err(c, PMP_E_INVALID, "pmp_msbt_labels_device: qt, bt, dire and msbt must be 4-byte aligned");
-    const hipError_t e = launch_msbt_labels(c->stream, qt, bt, dire, n, cf, msbt, status);
-    return e == hipSuccess ? PMP_OK : hip_fail(c, e, "msbt_labels");
+    return hip_rc(c, launch_msbt_labels(c->stream, qt, bt, dire, n, cf, msbt, status), "msbt_labels");
 }
 
 int pmp_msbt_labels(pmp_ctx *c, int cf, const uint8_t *qt, const uint8_t *bt, const int8_t *dire, int64_t n, uint8_t *msbt,
@@ -90,9 +93,8 @@ int pmp_msbt_labels(pmp_ctx *c, int cf, const uint8_t *qt, const uint8_t *bt, co
     DevBuf *d = c->d_lab;                              // about 1.9 kB per block
     return staged_passes(c, n, {{qt, 64, d[0]}, {bt, 256, d[1]}, {dire, 768, d[2]}}, {{msbt, 768, d[3], 0}, {status, 1, d[4], 0}},
                          [&](int64_t m, int64_t) {
-                             const hipError_t e = launch_msbt_labels(c->stream, (const uint8_t *)d[0].p, (const uint8_t *)d[1].p,
-                                                                     (const int8_t *)d[2].p, m, cf, (uint8_t *)d[3].p, (uint8_t *)d[4].p);
-                             return e == hipSuccess ? PMP_OK : hip_fail(c, e, "msbt_labels");
+                             return hip_rc(c, launch_msbt_labels(c->stream, (const uint8_t *)d[0].p, (const uint8_t *)d[1].p, (const int8_t *)d[2].p,
+                                                                 m, cf, (uint8_t *)d[3].p, (uint8_t *)d[4].p), "msbt_labels");
                          });
 }
 
@@ -106,8 +108,7 @@ int pmp_label_partition_device(pmp_ctx *c, int cf, const uint8_t *qt, const uint
     if (n == 0) return PMP_OK;
     if (misaligned({qt, bt, dire, hor, ver}, 3))
         return set_err(c, PMP_E_INVALID, "pmp_label_partition_device: qt, bt, dire, hor and ver must be 4-byte aligned");
-    const hipError_t e = launch_label_partition(c->stream, qt, bt, dire, n, cf, hor, ver, nullptr, status);
-    return e == hipSuccess ? PMP_OK : hip_fail(c, e, "label_partition");
+    return hip_rc(c, launch_label_partition(c->stream, qt, bt, dire, n, cf, hor, ver, nullptr, status), "label_partition");
 }
 
 int pmp_label_partition_records_device(pmp_ctx *c, int cf, const uint8_t *qt, const uint8_t *bt, const int8_t *dire, int64_t n,
@@ -119,8 +120,7 @@ int pmp_label_partition_records_device(pmp_ctx *c, int cf, const uint8_t *qt, co
     if (n == 0) return PMP_OK;
     if (misaligned({qt, bt, dire, rec}, 3))
         return set_err(c, PMP_E_INVALID, "pmp_label_partition_records_device: qt, bt, dire and rec must be 4-byte aligned");
-    const hipError_t e = launch_label_partition(c->stream, qt, bt, dire, n, cf, nullptr, nullptr, rec, status);
-    return e == hipSuccess ? PMP_OK : hip_fail(c, e, "label_partition");
+    return hip_rc(c, launch_label_partition(c->stream, qt, bt, dire, n, cf, nullptr, nullptr, rec, status), "label_partition");
 }
 
 int pmp_label_partition(pmp_ctx *c, int cf, const uint8_t *qt, const uint8_t *bt, const int8_t *dire, int64_t n, uint8_t *hor,
@@ -135,43 +135,76 @@ int pmp_label_partition(pmp_ctx *c, int cf, const uint8_t *qt, const uint8_t *bt
     return staged_passes(c, n, {{qt, 64, d[0]}, {bt, 256, d[1]}, {dire, 768, d[2]}},
                          {{hor, 256, d[3], 0}, {ver, 256, d[3], 256}, {status, 1, d[4], 0}}, [&](int64_t m, int64_t) {
                              uint8_t *d_hor = (uint8_t *)d[3].p, *d_ver = d_hor + (size_t)m * 256;
-                             const hipError_t e = launch_label_partition(c->stream, (const uint8_t *)d[0].p, (const uint8_t *)d[1].p,
-                                                                         (const int8_t *)d[2].p, m, cf, d_hor, d_ver, nullptr, (uint8_t *)d[4].p);
-                             return e == hipSuccess ? PMP_OK : hip_fail(c, e, "label_partition");
+                             return hip_rc(c, launch_label_partition(c->stream, (const uint8_t *)d[0].p, (const uint8_t *)d[1].p, (const int8_t *)d[2].p,
+                                                                     m, cf, d_hor, d_ver, nullptr, (uint8_t *)d[4].p), "label_partition");
                          });
 }
 
-// ---- validation statistics (valstats.hip) and teacher-forced MTT inference ------------------------------------------------
-namespace {
-struct ValArgs {
-    const float *qt, *bt, *dire;
-    const uint8_t *qt8, *msbt;
-    const int8_t *msdire;
-    int64_t n;
-    float wm[3];
-    int w0_one;
-    double *stats, *block_stats;       // block_stats null: the context's scratch, looked up at launch (a replay may find it regrown)
-};
-}  // namespace
-
-// Metrics.py:148-151 = Train_QBD.py:35-38 (luma) and Train_QBD.py:39-42 (chroma, training only); the float64 entry becomes a float32
-// scalar when torch adds it to the float32 dl*dl
+// ---- validation statistics, training losses (logitstats.hip) and teacher-forced MTT inference -----------------------------
+// Metrics.py:148-151 = Train_QBD.py:35-38 (luma; validation is always luma) and Train_QBD.py:39-42 (chroma, training only); the float64
+// entry becomes a float32 scalar when torch adds it to the float32 dl*dl
 static const double weight_mat[4][3] = {{0.5 * 1.0, 0.5 * 0.73, 0.5 * 0.15}, {0.5 * 2.43, 0.5 * 0.35, 0.5 * 0.10},
                                         {0.5 * 0.96, 0.5 * 0.23, 0.5 * 0.07}, {0.5 * 0.59, 0.5 * 0.16, 0.5 * 0.05}};
 static const double chroma_weight_mat[4][3] = {{0.5 * 17.83, 0.5 * 0.49, 0.5 * 0.11}, {0.5 * 1.20, 0.5 * 0.25, 0.5 * 0.07},
                                                {0.5 * 0.58, 0.5 * 0.17, 0.5 * 0.05}, {0.5 * 0.38, 0.5 * 0.12, 0.5 * 0.04}};
 
-static int val_check(pmp_ctx *c, int qp, const void *qt, const void *bt, const void *dire, const void *qt8, const void *msbt,
-                     const void *msdire, int64_t n, const void *stats, float wm[3], int *w0_one)
+static LogitWeights logit_weights(int comp, int qp)     // qp in 22..41
+{
+    const double *row = (comp == PMP_LUMA ? weight_mat : chroma_weight_mat)[(qp - 22) / 5];
+    return {{(float)row[0], (float)row[1], (float)row[2]}, qp == 22};
+}
+
+// The NULL forms that pmp_val_stats* and pmp_train_loss* take; fn: the entry point family the message names
+static int logit_label_args(pmp_ctx *c, const char *fn, const LogitLabels &a, int64_t n)
+{
+    const bool q = a.qt && a.qt8, noq = !a.qt && !a.qt8, m = a.bt && a.dire && a.msbt && a.msdire,
+               nom = !a.bt && !a.dire && !a.msbt && !a.msdire;
+    if (n > 0 && !((q && m) || (q && nom) || (noq && m)))
+        return set_err(c, PMP_E_INVALID, std::string(fn) + ": pass (qt, qt8), (bt, dire, msbt, msdire) or both; no other NULL mix");
+    return PMP_OK;
+}
+
+// The host forms of pmp_val_stats and pmp_train_loss, the whole call as one batch: the six inputs go through c->d_val in passes (about
+// 6.9 kB per block), launch(the pass's inputs on the device, its blocks, its row of `rows` f64[passes][ncols]) per pass, then the rows
+// are copied back and added to sums[ncols] in pass order.
+static int staged_logit_sums(pmp_ctx *c, const LogitLabels &h, int64_t n, std::initializer_list<StagedOut> outs, DevBuf &rows, int ncols,
+                             double *sums, const std::function<int(const LogitLabels &, int64_t, double *)> &launch)
+{
+    const int64_t passes = (n + c->chunk - 1) / c->chunk;
+    int rc;
+    if ((rc = ensure(c, rows, (size_t)passes * ncols * sizeof(double)))) return rc;
+    DevBuf *d = c->d_val;
+    rc = staged_passes(c, n, {{h.qt, 64 * 4, d[0]}, {h.bt, 768 * 4, d[1]}, {h.dire, 768 * 4, d[2]}, {h.qt8, 64, d[3]}, {h.msbt, 768, d[4]}, {h.msdire, 768, d[5]}},
+                       outs, [&](int64_t m, int64_t pass) {
+                           const auto on = [&](const void *host, int i) { return host ? d[i].p : nullptr; };   // left out stays left out
+                           return launch(LogitLabels{(const float *)on(h.qt, 0), (const float *)on(h.bt, 1), (const float *)on(h.dire, 2),
+                                                     (const uint8_t *)on(h.qt8, 3), (const uint8_t *)on(h.msbt, 4), (const int8_t *)on(h.msdire, 5)},
+                                         m, (double *)rows.p + pass * ncols);
+                       });
+    if (rc != PMP_OK) return rc;
+    std::vector<double> r((size_t)passes * ncols);
+    if ((rc = d2h(c, r.data(), rows.p, r.size() * sizeof(double))) || (rc = sync(c))) return rc;
+    for (int64_t p = 0; p < passes; ++p)
+        for (int i = 0; i < ncols; ++i) sums[i] += r[(size_t)p * ncols + i];
+    return PMP_OK;
+}
+
+namespace {
+struct ValArgs {
+    LogitLabels in;
+    int64_t n;
+    LogitWeights w;
+    double *stats, *block_stats;       // block_stats null: the context's scratch, looked up at launch (a replay may find it regrown)
+};
+}  // namespace
+
+static int val_check(pmp_ctx *c, int qp, const void *stats, ValArgs &a)      // fills a.w
 {
     if (qp < 22 || qp > 41) return set_err(c, PMP_E_INVALID, "pmp_val_stats: qp must be in 22..41 (rows 0..3 of weight_mat)");
-    if (n < 0 || !stats) return set_err(c, PMP_E_INVALID, "pmp_val_stats: negative count or null stats");
-    const bool q = qt && qt8, noq = !qt && !qt8, m = bt && dire && msbt && msdire, nom = !bt && !dire && !msbt && !msdire;
-    if (n > 0 && !((q && m) || (q && nom) || (noq && m)))
-        return set_err(c, PMP_E_INVALID, "pmp_val_stats: pass (qt, qt8), (bt, dire, msbt, msdire) or both; no other NULL mix");
-    const int row = (qp - 22) / 5;
-    for (int k = 0; k < 3; ++k) wm[k] = (float)weight_mat[row][k];
-    *w0_one = qp == 22;
+    if (a.n < 0 || !stats) return set_err(c, PMP_E_INVALID, "pmp_val_stats: negative count or null stats");
+    const int rc = logit_label_args(c, "pmp_val_stats", a.in, a.n);
+    if (rc != PMP_OK) return rc;
+    a.w = logit_weights(PMP_LUMA, qp);
     return PMP_OK;
 }
 
@@ -183,16 +216,12 @@ static int val_launch(pmp_ctx *c, const ValArgs &a)
         if (rc != PMP_OK) return rc;
         part = (double *)c->d_valpart.p;
     }
-    const hipError_t e = launch_val_stats(c->stream, a.qt, a.bt, a.dire, a.qt8, a.msbt, a.msdire, a.n, a.wm, a.w0_one, part, a.stats);
-    return e == hipSuccess ? PMP_OK : hip_fail(c, e, "val_stats");
+    return hip_rc(c, launch_val_stats(c->stream, a.in, a.n, a.w, part, a.stats), "val_stats");
 }
 
 static int val_device_impl(pmp_ctx *c, const ValArgs &a)
 {
-    if (a.n == 0) {
-        const hipError_t e = hipMemsetAsync(a.stats, 0, PMP_VAL_NSTATS * sizeof(double), c->stream);
-        return e == hipSuccess ? PMP_OK : hip_fail(c, e, "val_stats");
-    }
+    if (a.n == 0) return hip_rc(c, hipMemsetAsync(a.stats, 0, PMP_VAL_NSTATS * sizeof(double), c->stream), "val_stats");
     const int rc = val_launch(c, a);
     // its logits may come from an inference call whose range flag has not been looked at yet: remember the call for the replay
     if (rc == PMP_OK && !c->pending.empty())
@@ -204,9 +233,9 @@ int pmp_val_stats_device(pmp_ctx *c, int qp, const float *qt, const float *bt, c
                          const uint8_t *msbt, const int8_t *msdire, int64_t n, double *stats, double *block_stats)
 {
     CHECK_CTX(c);
-    ValArgs a{qt, bt, dire, qt8, msbt, msdire, n, {0.f, 0.f, 0.f}, 0, stats, block_stats};
+    ValArgs a{{qt, bt, dire, qt8, msbt, msdire}, n, {}, stats, block_stats};
     int rc;
-    if ((rc = val_check(c, qp, qt, bt, dire, qt8, msbt, msdire, n, stats, a.wm, &a.w0_one))) return rc;
+    if ((rc = val_check(c, qp, stats, a))) return rc;
     if (n > 0 && (misaligned({bt, dire}, 15) || misaligned({qt, msbt, msdire}, 3) || misaligned({stats, block_stats}, 7)))
         return set_err(c, PMP_E_INVALID, "pmp_val_stats_device: bt, dire must be 16-byte aligned, qt, msbt, msdire 4-byte, the outputs 8-byte");
     return val_device_impl(c, a);
@@ -216,46 +245,23 @@ int pmp_val_stats(pmp_ctx *c, int qp, const float *qt, const float *bt, const fl
                   const int8_t *msdire, int64_t n, double stats[PMP_VAL_NSTATS])
 {
     CHECK_CTX(c);
-    ValArgs a{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, {0.f, 0.f, 0.f}, 0, nullptr, nullptr};
+    ValArgs a{{qt, bt, dire, qt8, msbt, msdire}, n, {}, stats, nullptr};
     int rc;
-    if ((rc = val_check(c, qp, qt, bt, dire, qt8, msbt, msdire, n, stats, a.wm, &a.w0_one))) return rc;
+    if ((rc = val_check(c, qp, stats, a))) return rc;
     for (int i = 0; i < PMP_VAL_NSTATS; ++i) stats[i] = 0.0;
     if (n == 0) return PMP_OK;
     if ((rc = settle_before_host_call(c))) return rc;
-    // about 6.9 kB per block through the context's own staging buffers; one result row per pass
-    const int64_t passes = (n + c->chunk - 1) / c->chunk;
-    if ((rc = ensure(c, c->d_valout, (size_t)passes * PMP_VAL_NSTATS * sizeof(double)))) return rc;
-    DevBuf *d = c->d_val;
-    rc = staged_passes(c, n, {{qt, 64 * 4, d[0]}, {bt, 768 * 4, d[1]}, {dire, 768 * 4, d[2]}, {qt8, 64, d[3]}, {msbt, 768, d[4]}, {msdire, 768, d[5]}},
-                       {}, [&](int64_t m, int64_t p) {
-                           a.qt = qt ? (const float *)d[0].p : nullptr;
-                           a.bt = bt ? (const float *)d[1].p : nullptr;
-                           a.dire = bt ? (const float *)d[2].p : nullptr;
-                           a.qt8 = qt ? (const uint8_t *)d[3].p : nullptr;
-                           a.msbt = bt ? (const uint8_t *)d[4].p : nullptr;
-                           a.msdire = bt ? (const int8_t *)d[5].p : nullptr;
-                           a.n = m;
-                           a.stats = (double *)c->d_valout.p + p * PMP_VAL_NSTATS;
-                           return val_launch(c, a);
-                       });
-    if (rc != PMP_OK) return rc;
-    std::vector<double> rows((size_t)passes * PMP_VAL_NSTATS);
-    if ((rc = d2h(c, rows.data(), c->d_valout.p, rows.size() * sizeof(double))) || (rc = sync(c))) return rc;
-    for (int64_t p = 0; p < passes; ++p)          // the whole call as one batch: pass results in pass order
-        for (int i = 0; i < PMP_VAL_NSTATS; ++i) stats[i] += rows[(size_t)p * PMP_VAL_NSTATS + i];
-    return PMP_OK;
+    return staged_logit_sums(c, a.in, n, {}, c->d_valout, PMP_VAL_NSTATS, stats, [&](const LogitLabels &dev, int64_t m, double *row) {
+        return val_launch(c, ValArgs{dev, m, a.w, row, nullptr});
+    });
 }
 
-// ---- training losses and their logit gradients (trainloss.hip) ------------------------------------------------------------
 namespace {
 struct TrainArgs {
-    const float *qt, *bt, *dire;
-    const uint8_t *qt8, *msbt;
-    const int8_t *msdire;
-    float *g_qt, *g_bt, *g_dire;
+    LogitLabels in;
+    LogitGrads g;
     pmp_loss_params L;
-    float wm[3];
-    int w0_one;
+    LogitWeights w;
 };
 const pmp_loss_params LOSS_DEFAULT = {1.0, {0.8, 1.0, 1.2}, {1.0, 1.0, 1.0}, {0.5, 0.5, 0.5}};   // Train_QBD.py:448-457
 
@@ -266,7 +272,7 @@ bool overlaps(const void *a, size_t na, const void *b, size_t nb)
 }
 }  // namespace
 
-// Every check of pmp_train_loss* that does not depend on where the pointers live; fills a.L, a.wm, a.w0_one.  Nothing is written before it passes.
+// Every check of pmp_train_loss* that does not depend on where the pointers live; fills a.L, a.w.  Nothing is written before it passes.
 static int train_check(pmp_ctx *c, int comp, int qp, const pmp_loss_params *p, int64_t n, const void *terms, const void *loss, TrainArgs &a)
 {
     if (comp != PMP_LUMA && comp != PMP_CHROMA) return set_err(c, PMP_E_INVALID, "pmp_train_loss: comp must be PMP_LUMA or PMP_CHROMA");
@@ -276,24 +282,20 @@ static int train_check(pmp_ctx *c, int comp, int qp, const pmp_loss_params *p, i
     const double *lam = &a.L.lambq;
     for (int i = 0; i < 10; ++i)
         if (!std::isfinite(lam[i])) return set_err(c, PMP_E_INVALID, "pmp_train_loss: a loss weight is not finite");
+    const int rc = logit_label_args(c, "pmp_train_loss", a.in, n);
+    if (rc != PMP_OK) return rc;
     if (n > 0) {
-        const bool q = a.qt && a.qt8, noq = !a.qt && !a.qt8, m = a.bt && a.dire && a.msbt && a.msdire,
-                   nom = !a.bt && !a.dire && !a.msbt && !a.msdire;
-        if (!((q && m) || (q && nom) || (noq && m)))
-            return set_err(c, PMP_E_INVALID, "pmp_train_loss: pass (qt, qt8), (bt, dire, msbt, msdire) or both; no other NULL mix");
-        const bool none = !a.g_qt && !a.g_bt && !a.g_dire;
-        if (!none && ((a.g_qt != nullptr) != q || (a.g_bt != nullptr) != m || (a.g_dire != nullptr) != m))
+        const bool none = !a.g.qt && !a.g.bt && !a.g.dire;
+        if (!none && ((a.g.qt != nullptr) != a.in.has_q() || (a.g.bt != nullptr) != a.in.has_m() || (a.g.dire != nullptr) != a.in.has_m()))
             return set_err(c, PMP_E_INVALID, "pmp_train_loss: gradient pointers are all NULL or exactly those of the logits given");
-        const struct { const void *p; size_t per; } in[6] = {{a.qt, 256}, {a.bt, 3072}, {a.dire, 3072}, {a.qt8, 64}, {a.msbt, 768}, {a.msdire, 768}},
-                                                    g[3] = {{a.g_qt, 256}, {a.g_bt, 3072}, {a.g_dire, 3072}};
+        const struct { const void *p; size_t per; } in[6] = {{a.in.qt, 256}, {a.in.bt, 3072}, {a.in.dire, 3072}, {a.in.qt8, 64}, {a.in.msbt, 768}, {a.in.msdire, 768}},
+                                                    g[3] = {{a.g.qt, 256}, {a.g.bt, 3072}, {a.g.dire, 3072}};
         for (const auto &o : g)
             for (const auto &i : in)
                 if (overlaps(o.p, (size_t)n * o.per, i.p, (size_t)n * i.per))
                     return set_err(c, PMP_E_INVALID, "pmp_train_loss: a gradient tensor overlaps an input");
     }
-    const double(*M)[3] = comp == PMP_LUMA ? weight_mat : chroma_weight_mat;
-    for (int k = 0; k < 3; ++k) a.wm[k] = (float)M[(qp - 22) / 5][k];
-    a.w0_one = qp == 22;
+    a.w = logit_weights(comp, qp);
     return PMP_OK;
 }
 
@@ -302,9 +304,7 @@ static int train_launch(pmp_ctx *c, const TrainArgs &a, int64_t m, int64_t n_div
 {
     const int rc = ensure(c, c->d_trainpart, (size_t)m * PMP_LOSS_NTERMS * sizeof(double));
     if (rc != PMP_OK) return rc;
-    const hipError_t e = launch_train_loss(c->stream, a.qt, a.bt, a.dire, a.qt8, a.msbt, a.msdire, m, n_div, a.wm, a.w0_one, a.L,
-                                           (double *)c->d_trainpart.p, terms, loss, a.g_qt, a.g_bt, a.g_dire);
-    return e == hipSuccess ? PMP_OK : hip_fail(c, e, "train_loss");
+    return hip_rc(c, launch_train_loss(c->stream, a.in, m, n_div, a.w, a.L, (double *)c->d_trainpart.p, terms, loss, a.g), "train_loss");
 }
 
 int pmp_train_loss_device(pmp_ctx *c, int comp, int qp, const pmp_loss_params *p, const float *qt, const float *bt, const float *dire,
@@ -312,7 +312,7 @@ int pmp_train_loss_device(pmp_ctx *c, int comp, int qp, const pmp_loss_params *p
                           float *g_qt, float *g_bt, float *g_dire)
 {
     CHECK_CTX(c);
-    TrainArgs a{qt, bt, dire, qt8, msbt, msdire, g_qt, g_bt, g_dire, LOSS_DEFAULT, {0.f, 0.f, 0.f}, 0};
+    TrainArgs a{{qt, bt, dire, qt8, msbt, msdire}, {g_qt, g_bt, g_dire}, LOSS_DEFAULT, {}};
     int rc;
     if ((rc = train_check(c, comp, qp, p, n, terms, loss, a))) return rc;
     if (misaligned({terms, loss}, 7) || (n > 0 && (misaligned({bt, dire, g_bt, g_dire}, 15) || misaligned({qt, qt8, msbt, msdire, g_qt}, 3))))
@@ -322,7 +322,7 @@ int pmp_train_loss_device(pmp_ctx *c, int comp, int qp, const pmp_loss_params *p
     if (n == 0) {
         hipError_t e = hipMemsetAsync(terms, 0, PMP_LOSS_NTERMS * sizeof(double), c->stream);
         if (e == hipSuccess) e = hipMemsetAsync(loss, 0, sizeof(double), c->stream);
-        return e == hipSuccess ? PMP_OK : hip_fail(c, e, "train_loss");
+        return hip_rc(c, e, "train_loss");
     }
     return train_launch(c, a, n, n, terms, loss);
 }
@@ -332,42 +332,21 @@ int pmp_train_loss(pmp_ctx *c, int comp, int qp, const pmp_loss_params *p, const
                    float *g_qt, float *g_bt, float *g_dire)
 {
     CHECK_CTX(c);
-    TrainArgs a{qt, bt, dire, qt8, msbt, msdire, g_qt, g_bt, g_dire, LOSS_DEFAULT, {0.f, 0.f, 0.f}, 0};
+    TrainArgs a{{qt, bt, dire, qt8, msbt, msdire}, {g_qt, g_bt, g_dire}, LOSS_DEFAULT, {}};
     int rc;
     if ((rc = train_check(c, comp, qp, p, n, terms, loss, a))) return rc;
     for (int i = 0; i < PMP_LOSS_NTERMS; ++i) terms[i] = 0.0;
     *loss = 0.0;
     if (n == 0) return PMP_OK;
     if ((rc = settle_before_host_call(c))) return rc;
-    // about 6.9 kB in and, with gradients, 6.4 kB out per block through the context's own staging buffers; one row of sums per pass
-    const int64_t passes = (n + c->chunk - 1) / c->chunk;
-    if ((rc = ensure(c, c->d_trainout, (size_t)passes * PMP_LOSS_NTERMS * sizeof(double)))) return rc;
-    DevBuf *d = c->d_val, *g = c->d_train;
-    TrainArgs s = a;                                   // the same call on the staging buffers
-    const auto run = [&](std::initializer_list<StagedOut> outs) {
-        return staged_passes(c, n, {{qt, 64 * 4, d[0]}, {bt, 768 * 4, d[1]}, {dire, 768 * 4, d[2]}, {qt8, 64, d[3]}, {msbt, 768, d[4]}, {msdire, 768, d[5]}},
-                             outs, [&](int64_t m, int64_t pass) {
-                                 s.qt = qt ? (const float *)d[0].p : nullptr;
-                                 s.bt = bt ? (const float *)d[1].p : nullptr;
-                                 s.dire = bt ? (const float *)d[2].p : nullptr;
-                                 s.qt8 = qt ? (const uint8_t *)d[3].p : nullptr;
-                                 s.msbt = bt ? (const uint8_t *)d[4].p : nullptr;
-                                 s.msdire = bt ? (const int8_t *)d[5].p : nullptr;
-                                 s.g_qt = g_qt ? (float *)g[0].p : nullptr;
-                                 s.g_bt = g_bt ? (float *)g[1].p : nullptr;
-                                 s.g_dire = g_dire ? (float *)g[2].p : nullptr;
-                                 return train_launch(c, s, m, n, (double *)c->d_trainout.p + pass * PMP_LOSS_NTERMS, nullptr);
-                             });
-    };
-    if (g_qt && g_bt) rc = run({{g_qt, 64 * 4, g[0], 0}, {g_bt, 768 * 4, g[1], 0}, {g_dire, 768 * 4, g[2], 0}});
-    else if (g_qt) rc = run({{g_qt, 64 * 4, g[0], 0}});
-    else if (g_bt) rc = run({{g_bt, 768 * 4, g[1], 0}, {g_dire, 768 * 4, g[2], 0}});
-    else rc = run({});
+    DevBuf *g = c->d_train;                            // with gradients, 6.4 kB out per block
+    rc = staged_logit_sums(c, a.in, n, {{g_qt, 64 * 4, g[0], 0}, {g_bt, 768 * 4, g[1], 0}, {g_dire, 768 * 4, g[2], 0}}, c->d_trainout,
+                           PMP_LOSS_NTERMS, terms, [&](const LogitLabels &dev, int64_t m, double *row) {
+                               const LogitGrads dg = {g_qt ? (float *)g[0].p : nullptr, g_bt ? (float *)g[1].p : nullptr,
+                                                      g_dire ? (float *)g[2].p : nullptr};
+                               return train_launch(c, TrainArgs{dev, dg, a.L, a.w}, m, n, row, nullptr);
+                           });
     if (rc != PMP_OK) return rc;
-    std::vector<double> rows((size_t)passes * PMP_LOSS_NTERMS);
-    if ((rc = d2h(c, rows.data(), c->d_trainout.p, rows.size() * sizeof(double))) || (rc = sync(c))) return rc;
-    for (int64_t q = 0; q < passes; ++q)              // the whole call as one batch: pass sums in pass order
-        for (int i = 0; i < PMP_LOSS_NTERMS; ++i) terms[i] += rows[(size_t)q * PMP_LOSS_NTERMS + i];
     *loss = train_loss_value(terms, a.L, n);
     return PMP_OK;
 }

@@ -190,20 +190,42 @@ hipError_t launch_msbt_labels(hipStream_t s, const uint8_t *qt, const uint8_t *b
 hipError_t launch_label_partition(hipStream_t s, const uint8_t *qt, const uint8_t *bt, const int8_t *dire, int64_t N, int chroma_factor,
                                   uint8_t *hor, uint8_t *ver, uint8_t *rec, uint8_t *status);
 
-// Validation statistics (valstats.hip; include/pmp.h: pmp_val_stats): logits against labels -> block_stats f64[N][20] (always written:
-// the caller's buffer or scratch) and their fixed-order sum stats f64[20].  qt/qt8 null: MTT only; bt/dire/msbt/msdire null: QT only.
-// wm: float32(weight_mat[row][0..2]); w0_one: qp == 22 (weight_d0 = 1.0).  bt, dire 16-byte aligned, msbt, msdire 4-byte aligned.  N >= 1.
-hipError_t launch_val_stats(hipStream_t s, const float *qt, const float *bt, const float *dire, const uint8_t *qt8, const uint8_t *msbt,
-                            const int8_t *msdire, int64_t N, const float wm[3], int w0_one, double *block_stats, double *stats);
+// Logits against labels (logitstats.hip): what pmp_val_stats and pmp_train_loss read.  qt f32[N][64] with qt8 u8[N][64] (RAW qtDepth),
+// bt, dire f32[N][3][256] with msbt u8 / msdire i8 [N][3][256].  qt/qt8 null: MTT only; bt/dire/msbt/msdire null: QT only.
+// bt, dire 16-byte aligned, the others 4-byte aligned.
+struct LogitLabels {
+    const float *qt, *bt, *dire;
+    const uint8_t *qt8, *msbt;
+    const int8_t *msdire;
+    __host__ __device__ bool has_q() const { return qt != nullptr; }
+    __host__ __device__ bool has_m() const { return bt != nullptr; }
+    LogitLabels from(int64_t o) const                   // the same arrays from block o on; what is left out stays left out
+    {
+        return {qt ? qt + o * 64 : nullptr,    bt ? bt + o * 768 : nullptr,     dire ? dire + o * 768 : nullptr,
+                qt8 ? qt8 + o * 64 : nullptr,  msbt ? msbt + o * 768 : nullptr, msdire ? msdire + o * 768 : nullptr};
+    }
+};
+// The gradients of pmp_train_loss: qt f32[N][64], bt, dire f32[N][3][256] (16-byte aligned); all null = value only, else those of
+// the logits given.
+struct LogitGrads {
+    float *qt, *bt, *dire;
+    LogitGrads from(int64_t o) const { return {qt ? qt + o * 64 : nullptr, bt ? bt + o * 768 : nullptr, dire ? dire + o * 768 : nullptr}; }
+};
+// w_k = dl_k * dl_k + wm[k], wm = float32(weight matrix[row][0..2]) of the component; w0_one: qp == 22 (weight_d0 = 1.0)
+struct LogitWeights {
+    float wm[3];
+    int w0_one;
+};
 
-// Training losses and their logit gradients (trainloss.hip; include/pmp.h: pmp_train_loss): the same inputs, alignments and NULL forms
-// as launch_val_stats, wm from the component's matrix -> block_terms f64[N][13] (scratch, always written), their fixed-order sum
-// terms f64[13] and, if loss != null, train_loss_value(terms, L, n_div).  g_qt f32[N][64], g_bt, g_dire f32[N][3][256] (16-byte
-// aligned): all null = value only, else those of the logits given; every cell is written.  n_div: the block count in the gradients'
-// divisors 64 n and 256 n (the whole call's, where N is one pass of it).  N >= 1.
-hipError_t launch_train_loss(hipStream_t s, const float *qt, const float *bt, const float *dire, const uint8_t *qt8, const uint8_t *msbt,
-                             const int8_t *msdire, int64_t N, int64_t n_div, const float wm[3], int w0_one, const pmp_loss_params &L,
-                             double *block_terms, double *terms, double *loss, float *g_qt, float *g_bt, float *g_dire);
+// Validation statistics (include/pmp.h: pmp_val_stats): block_stats f64[N][20] (always written: the caller's buffer or scratch) and
+// their fixed-order sum stats f64[20].  lw: the luma matrix.  N >= 1.
+hipError_t launch_val_stats(hipStream_t s, const LogitLabels &in, int64_t N, const LogitWeights &lw, double *block_stats, double *stats);
+
+// Training losses and their logit gradients (include/pmp.h: pmp_train_loss): block_terms f64[N][13] (scratch, always written), their
+// fixed-order sum terms f64[13] and, if loss != null, train_loss_value(terms, L, n_div).  Every cell of the gradients given is
+// written.  n_div: the block count in the gradients' divisors 64 n and 256 n (the whole call's, where N is one pass of it).  N >= 1.
+hipError_t launch_train_loss(hipStream_t s, const LogitLabels &in, int64_t N, int64_t n_div, const LogitWeights &lw, const pmp_loss_params &L,
+                             double *block_terms, double *terms, double *loss, const LogitGrads &g);
 // lambq T0 / (64 n) + (lambb0 T1 + .. + lambresb2 T12) / (256 n) in float64, in that order, on either side (no FMA)
 __host__ __device__ double train_loss_value(const double T[PMP_LOSS_NTERMS], const pmp_loss_params &L, int64_t n);
 

@@ -343,12 +343,7 @@ class Engine:
         """pmp_val_stats (include/pmp.h): the twenty per-batch numbers S[0..19] of logits against labels, the whole call as one batch.
         qt f32[N,(1,)8,8] with qt8 u8[N,8,8] (RAW qtDepth), bt / dire f32[N,3,16,16] with msbt u8 / msdire i8 [N,3,16,16]; leave the
         QT pair or the MTT four out for the MTT-only / QT-only forms.  -> float64[20]."""
-        f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
-        qt, bt, dire = f(qt), f(bt), f(dire)
-        qt8 = None if qt8 is None else _fit(qt8, np.uint8, "qt8")
-        msbt = None if msbt is None else _fit(msbt, np.uint8, "msbt")
-        msdire = None if msdire is None else _fit(msdire, np.int8, "msdire")
-        n = _val_count(qt, bt, dire, qt8, msbt, msdire)
+        (qt, bt, dire, qt8, msbt, msdire), n = _logit_label_arrays(qt, bt, dire, qt8, msbt, msdire)
         out = np.zeros(_lib.PMP_VAL_NSTATS, np.float64)
         self._ck(self.lib.pmp_val_stats(self.h, int(qp), _ptr(qt), _ptr(bt), _ptr(dire), _ptr(qt8), _ptr(msbt), _ptr(msdire), n, _ptr(out)))
         return out
@@ -365,12 +360,7 @@ class Engine:
         any of LOSS_KEYS, a "lambb0=0.8,..." text or a LossParams (None: Train_QBD's defaults).
         -> (terms float64[13], loss float, grads): grads is None without want_grads, else {"qt": f32[N,8,8], "bt": f32[N,3,16,16],
         "dire": f32[N,3,16,16]} with the entries of the logits given."""
-        f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
-        qt, bt, dire = f(qt), f(bt), f(dire)
-        qt8 = None if qt8 is None else _fit(qt8, np.uint8, "qt8")
-        msbt = None if msbt is None else _fit(msbt, np.uint8, "msbt")
-        msdire = None if msdire is None else _fit(msdire, np.int8, "msdire")
-        n = _val_count(qt, bt, dire, qt8, msbt, msdire)
+        (qt, bt, dire, qt8, msbt, msdire), n = _logit_label_arrays(qt, bt, dire, qt8, msbt, msdire)
         terms = np.zeros(_lib.PMP_LOSS_NTERMS, np.float64)
         loss = np.zeros(1, np.float64)
         grads = None
@@ -593,6 +583,15 @@ def loss_params(params=None):
 
 
 VAL_ELEMS = np.array([64] + [256] * 12 + [64] + [256] * 6, np.float64)      # elements per block behind each of the twenty statistics
+
+
+def _logit_label_arrays(qt, bt, dire, qt8, msbt, msdire):
+    """The six optional arrays of val_stats / train_loss as the ABI takes them: contiguous float32 logits, labels in the reference's
+    dtypes (u8, u8, i8) if every value fits exactly.  -> ((qt, bt, dire, qt8, msbt, msdire), block count)."""
+    f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+    fit = lambda a, dtype, name: None if a is None else _fit(a, dtype, name)
+    arrays = (f(qt), f(bt), f(dire), fit(qt8, np.uint8, "qt8"), fit(msbt, np.uint8, "msbt"), fit(msdire, np.int8, "msdire"))
+    return arrays, _val_count(*arrays)
 
 
 def _val_count(qt, bt, dire, qt8, msbt, msdire):

@@ -1,4 +1,4 @@
-"""Train_QBD's losses as torch autograd functions over pmp_train_loss_device (include/pmp.h; trainloss.hip).
+"""Train_QBD's losses as torch autograd functions over pmp_train_loss_device (include/pmp.h; logitstats.hip).
 
 Drop-in for the loss calls of the reference's training loops:
 

@@ -1,4 +1,4 @@
-"""GPU: Train_QBD's losses and their logit gradients (include/pmp.h: pmp_train_loss, trainloss.hip; pmp_vvc_tip2023_amd/train_loss.py).
+"""GPU: Train_QBD's losses and their logit gradients (include/pmp.h: pmp_train_loss, logitstats.hip; pmp_vvc_tip2023_amd/train_loss.py).
 
 Bounds.  The order of every addition is fixed by the header and the numpy restatement (tests/train_loss_cases.py) follows it, so sums,
 loss and gradients are compared BIT FOR BIT (a NaN equals a NaN).  Against the reference's numbers (tests/golden/g14_train_loss.npz)
@@ -157,6 +157,16 @@ def test_host_form_passes(eng):
     # a pass of its own is not a call of its own: blocks 0..4 as a call divide by 5, as a pass by 12
     alone = eng.train_loss(c["comp"], c["qp"], params=c["lam"], **K.kw_of(c, "qbd", slice(0, 5)))
     assert not np.array_equal(alone[2]["qt"], one[2]["qt"][:5])
+    # value only through poisoned staging: the three gradient outputs are left out of every pass, the sums are the same bits
+    eng.lib.pmp_debug_poison_workspace(eng.h, 1)
+    eng.set_chunk(5)
+    try:
+        T, loss, g = eng.train_loss(c["comp"], c["qp"], params=c["lam"], want_grads=False, **K.kw_of(c))
+    finally:
+        eng.set_chunk(4096)
+        eng.lib.pmp_debug_poison_workspace(eng.h, 0)
+    assert g is None
+    check_bits("value only, 5 + 5 + 2, poisoned", (T, loss, None), want_of(c, "qbd", passes=c["passes"]))
 
 
 # ---- 4. every byte of a requested gradient is written; value only writes none

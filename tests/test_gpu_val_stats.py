@@ -1,4 +1,4 @@
-"""GPU: validation statistics (include/pmp.h: pmp_val_stats, valstats.hip) and teacher-forced MTT inference (pmp_infer_msbd).
+"""GPU: validation statistics (include/pmp.h: pmp_val_stats, logitstats.hip) and teacher-forced MTT inference (pmp_infer_msbd).
 
 Bounds.  The seven hit counts are integers: EXACT.  The thirteen sums: the kernel and the numpy restatement (tests/val_cases.py) add the
 SAME float32 terms in float64, at most 2e5 of them, in different orders - 1e-12 relative covers any order (n * 2^-53 = 2.2e-11 is the

@@ -144,7 +144,7 @@ def block_terms(comp, qp, **kw):
 
 
 def reduce_blocks(P):
-    """train_reduce_kernel's order: row group g adds rows g, g + 16, .. in order, then the 16 group partials are added in order."""
+    """sum_rows_kernel's order (logitstats.hip): row group g adds rows g, g + 16, .. in order, then the 16 group partials are added in order."""
     acc = np.zeros((16, NTERMS), np.float64)
     with np.errstate(invalid="ignore"):
         for r in range(len(P)):
