@@ -449,6 +449,49 @@ int pmp_train_loss_device(pmp_ctx *ctx, int comp, int qp, const pmp_loss_params 
                           const float *d_dire, const uint8_t *d_qt8, const uint8_t *d_msbt, const int8_t *d_msdire, int64_t n,
                           double *d_terms, double *d_loss, float *d_g_qt, float *d_g_bt, float *d_g_dire);
 
+/* ---- training: ONE Model_QBD.ResidualBlock (Model_QBD.py:23-44), forward and backward, on this library's kernels - about 97 % of the
+ *      nets' FLOPs in training as in inference.  t = relu(conv0(x)), out = relu(conv2(t) + sc(x)); both convolutions k x k, stride 1,
+ *      zero padding k/2, no bias; sc is the identity when cin == cout and a 1x1 convolution otherwise.  Backward, from the saved x, t,
+ *      out and the upstream gradient g_out, in this order:
+ *        gu    = g_out where out > 0, else 0
+ *        g_w2  = wgrad(t, gu)                         wgrad(a, g)[co][ci][dy][dx] = sum over (n, y, x) of g[n][co][y][x] *
+ *        g_wsc = wgrad_1x1(x, gu)   (cin != cout)                                    a[n][ci][y + dy - k/2][x + dx - k/2]
+ *        gt    = conv(gu, flipT(w2)) where t > 0, else 0        flipT: taps mirrored, cin and cout swapped
+ *        g_w0  = wgrad(x, gt)
+ *        g_x   = conv(gt, flipT(w0)) + gu             (cin == cout)
+ *              = conv(gt, flipT(w0)) + conv1x1(gu, wsc transposed)   (cin != cout)
+ *      The masks are exactly `> 0` of the t and out the CALLER passes (torch's ReLU backward for finite values), so a trainer may hand
+ *      in the tensors the forward call returned or its own.
+ *      ARITHMETIC: always the fp32 MFMA datapath (v_mfma_f32_16x16x4_f32, a chain of fused multiply-adds in float32), whatever
+ *      pmp_set_precision says.  The forward is the launches of the inference graph on PMP_PRECISION_F32, bit for bit.  The weight
+ *      gradients are reduced over (n, 16x16 tile) in two stages in an order that depends on the shape only, without atomics: the same
+ *      bits on every run, stream, context and device.  On values whose every product and sum is exactly representable in float32 every
+ *      result is exact.  Behaviour on non-finite values (NaN, +-inf in any tensor) is NOT specified.
+ *      TENSORS: dense fp32 in torch's layouts at true scale - x, g_x [n][cin][h][w]; t, out, g_out [n][cout][h][w]; w0, g_w0
+ *      [cout][cin][k][k]; w2, g_w2 [cout][cout][k][k]; wsc, g_wsc [cout][cin].  wsc (and, backward, g_wsc) are passed exactly when
+ *      cin != cout and NULL otherwise.  g_x may be NULL: it is then not computed and nothing is written for it (a first block whose
+ *      input needs no gradient).  Every byte of every requested output is written.
+ *      SHAPES: n in 1..256; h and w multiples of 16 in 16..256; cin and cout in 1..64 (padded to 16, 32 or 64 internally); k 3 or 5.
+ *      PMP_E_INVALID before any launch, nothing written: a NULL shape, any other shape, a missing tensor or a shortcut tensor that
+ *      should not be there, an output that overlaps an input or another output, and for the _device forms a pointer that is not
+ *      4-byte aligned.
+ *      pmp_resblock_*_device: device pointers, stream-ordered on the context's stream; the host does not wait and the weights - which
+ *      change every optimiser step - are packed on the device, never copied to the host.  Like pmp_train_loss_device the call first
+ *      SETTLES the context's calls in flight.  Intermediates live in the context's activation workspace (pmp_get_workspace_bytes).
+ *      pmp_resblock_forward / _backward: host pointers, staged through the context's buffers; they return final results. ---- */
+typedef struct pmp_rb_shape {
+    int n, h, w, cin, cout, k;
+} pmp_rb_shape;
+int pmp_resblock_forward(pmp_ctx *ctx, const pmp_rb_shape *shape, const float *x, const float *w0, const float *w2, const float *wsc,
+                         float *t, float *out);
+int pmp_resblock_forward_device(pmp_ctx *ctx, const pmp_rb_shape *shape, const float *d_x, const float *d_w0, const float *d_w2,
+                                const float *d_wsc, float *d_t, float *d_out);
+int pmp_resblock_backward(pmp_ctx *ctx, const pmp_rb_shape *shape, const float *x, const float *t, const float *out, const float *w0,
+                          const float *w2, const float *wsc, const float *g_out, float *g_x, float *g_w0, float *g_w2, float *g_wsc);
+int pmp_resblock_backward_device(pmp_ctx *ctx, const pmp_rb_shape *shape, const float *d_x, const float *d_t, const float *d_out,
+                                 const float *d_w0, const float *d_w2, const float *d_wsc, const float *d_g_out, float *d_g_x,
+                                 float *d_g_w0, float *d_g_w2, float *d_g_wsc);
+
 /* ---- teacher-forced MTT inference: the MTT net of (comp, qp) on the blocks with a GIVEN QT map instead of the QT net's output, what
  *      pre_validation predID 1 runs (Net(input_batch, qt_label_batch), Metrics.py:226).  qt_in f32[n][8][8] is read, never written
  *      (for the reference's validation: float(qt8 - 1) with the u8 wrap above).  Everything else is pmp_infer's: the context's datapath,

@@ -37,6 +37,11 @@ class LossParams(C.Structure):
     _fields_ = [("lambq", C.c_double), ("lambb", C.c_double * 3), ("lambd", C.c_double * 3), ("lambresb", C.c_double * 3)]
 
 
+class RbShape(C.Structure):
+    """pmp_rb_shape: one ResidualBlock of pmp_resblock_forward / _backward."""
+    _fields_ = [("n", C.c_int), ("h", C.c_int), ("w", C.c_int), ("cin", C.c_int), ("cout", C.c_int), ("k", C.c_int)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/pmp.h
 _VP, _I, _I64, _U32 = C.c_void_p, C.c_int, C.c_int64, C.c_uint32
 SIGNATURES = {
@@ -85,6 +90,10 @@ SIGNATURES = {
     "pmp_parse_loss_params": (_I, [C.c_char_p, C.POINTER(LossParams)]),
     "pmp_train_loss": (_I, [_VP, _I, _I, C.POINTER(LossParams), _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP]),
     "pmp_train_loss_device": (_I, [_VP, _I, _I, C.POINTER(LossParams), _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP]),
+    "pmp_resblock_forward": (_I, [_VP, C.POINTER(RbShape)] + [_VP] * 6),
+    "pmp_resblock_forward_device": (_I, [_VP, C.POINTER(RbShape)] + [_VP] * 6),
+    "pmp_resblock_backward": (_I, [_VP, C.POINTER(RbShape)] + [_VP] * 11),
+    "pmp_resblock_backward_device": (_I, [_VP, C.POINTER(RbShape)] + [_VP] * 11),
     "pmp_infer_msbd": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
     "pmp_infer_msbd_device": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
     "pmp_read_depth_dump": (_I, [C.c_char_p, _I, _I, _I, _I, _VP, _VP, _VP, C.POINTER(_I64)]),

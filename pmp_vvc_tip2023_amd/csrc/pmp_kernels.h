@@ -1,4 +1,4 @@
-// Internal launch interface between the host-side graph (nets.cpp and the C ABI: pmp_api.cpp, range_guard.cpp, api_labels.cpp, api_debug.cpp) and the HIP kernels.
+// Internal launch interface between the host-side graph (nets.cpp and the C ABI: pmp_api.cpp, range_guard.cpp, api_labels.cpp, api_train.cpp, api_debug.cpp) and the HIP kernels.
 //
 // Activation layout in HBM ("blocked channels-last"):  act[n][c/16][y][x][c%16]  float32, channels padded to a
 // multiple of 16 with zeros.  A 16-channel group of one tile row is contiguous (16 px * 64 B = 1 KiB), which is
@@ -228,6 +228,22 @@ hipError_t launch_train_loss(hipStream_t s, const LogitLabels &in, int64_t N, in
                              double *block_terms, double *terms, double *loss, const LogitGrads &g);
 // lambq T0 / (64 n) + (lambb0 T1 + .. + lambresb2 T12) / (256 n) in float64, in that order, on either side (no FMA)
 __host__ __device__ double train_loss_value(const double T[PMP_LOSS_NTERMS], const pmp_loss_params &L, int64_t n);
+
+// ------------------------------------------------------------------------------------------------ training (conv_wgrad.hip)
+// Weight gradient of a stride-1 KxK convolution (K = 1, 3, 5): dw[cout][cin][K][K] (torch's dense layout, real channels only) =
+// sum over (n, y, x) of g[n][co][y][x] * a[n][ci][y + dy - K/2][x + dx - K/2].  a [N][Ca/16][H][W][16] and g [N][Cg/16][H][W][16] are
+// blocked, Ca, Cg = 16, 32 or 64; cin <= Ca, cout <= Cg.  part: scratch of wgrad_partial_floats() floats, every one written.  Two
+// launches, a fixed order of additions that depends on the shape only, no atomics.
+size_t wgrad_partial_floats(int N, int H, int W, int Ca, int Cg, int K);
+hipError_t launch_wgrad(hipStream_t s, const float *a, const float *g, int N, int H, int W, int Ca, int Cg, int K, float *part,
+                        float *dw, int cout, int cin);
+// torch's dense [N][C][H][W] <-> blocked [N][Cp/16][H][W][16] (channels C .. Cp-1 zero / dropped).  mode 0: the values; 1: src where
+// m > 0, else 0 (m dense, src's shape); 2: 1.0 where src > 0, else 0.0 - a ReLU's backward, and its mask as the conv kernel's `gate`.
+hipError_t launch_dense_to_blocked(hipStream_t s, const float *src, const float *m, int mode, float *dst, int N, int C, int Cp, int H, int W);
+hipError_t launch_blocked_to_dense(hipStream_t s, const float *src, float *dst, int N, int C, int Cp, int H, int W);
+// pack_mfma() on the device, from w [cout][cin][K][K] into [CB][K*K][NT][64][4].  flip_t = 0: as is (16 NT >= cout, 16 CB >= cin);
+// flip_t = 1: taps mirrored, cin and cout swapped - the data gradient's weights (16 NT >= cin, 16 CB >= cout).
+hipError_t launch_pack_mfma(hipStream_t s, const float *w, float *out, int cout, int cin, int K, int NT, int CB, int flip_t);
 
 // Block cutter (Inference_QBD.py:104-149).
 hipError_t launch_cut_blocks(hipStream_t s, const void *y, const void *u, const void *v, int F, int H, int W,

@@ -50,6 +50,7 @@ class Engine:
         self.device = device
         self.weight_dir = weight_dir
         self.provenance = {}
+        self.stream_ptr = 0
         if chunk:
             self.set_chunk(chunk)
 
@@ -70,6 +71,7 @@ class Engine:
 
     def set_stream(self, hip_stream_ptr):
         self._ck(self.lib.pmp_set_stream(self.h, C.c_void_p(hip_stream_ptr or 0)))
+        self.stream_ptr = hip_stream_ptr or 0           # what the engine runs on now (0: the context's own stream)
 
     def set_chunk(self, blocks):
         self._ck(self.lib.pmp_set_chunk(self.h, int(blocks)))
@@ -381,6 +383,59 @@ class Engine:
         f64[13] -> d_terms, f64 -> d_loss; stream-ordered on the engine's stream, the host does not wait."""
         self._ck(self.lib.pmp_train_loss_device(self.h, COMP_ID[comp], int(qp), loss_params(params), d_qt, d_bt, d_dire, d_qt8, d_msbt, d_msdire,
                                                 int(n), d_terms, d_loss, d_g_qt, d_g_bt, d_g_dire))
+
+    # ------------------------------------------------------------------------------------------ one ResidualBlock, forward and backward
+    @staticmethod
+    def _rb_arrays(**arrays):
+        """float32 C-contiguous copies of the arrays of one ResidualBlock call and its RbShape, derived from x and w0; every other array
+        given must have exactly the shape that follows (the C call reads that many floats)."""
+        a = {k: None if v is None else np.ascontiguousarray(v, np.float32) for k, v in arrays.items()}
+        if a["x"].ndim != 4 or a["w0"].ndim != 4:
+            raise ValueError("resblock: x must be [n, cin, h, w] and w0 [cout, cin, k, k]")
+        n, cin, h, w = a["x"].shape
+        cout, cin_w, k, k2 = a["w0"].shape
+        if cin_w != cin or k != k2:
+            raise ValueError("resblock: w0 must be [cout, cin, k, k] for x [n, cin, h, w]")
+        want = {"w2": [(cout, cout, k, k)], "wsc": [(cout, cin), (cout, cin, 1, 1)], "t": [(n, cout, h, w)], "out": [(n, cout, h, w)],
+                "g_out": [(n, cout, h, w)]}
+        for key, v in a.items():
+            if key in want and v is not None and v.shape not in want[key]:
+                raise ValueError("resblock: %s has shape %s, expected %s" % (key, v.shape, want[key][0]))
+        if (a.get("wsc") is not None) != (cin != cout):
+            raise ValueError("resblock: wsc is passed exactly when cin != cout")
+        return a, _lib.RbShape(n, h, w, cin, cout, k)
+
+    def resblock_forward(self, x, w0, w2, wsc=None):
+        """pmp_resblock_forward (include/pmp.h): Model_QBD.ResidualBlock on the fp32 MFMA datapath.  x f32[n,cin,h,w], w0 [cout,cin,k,k],
+        w2 [cout,cout,k,k], wsc [cout,cin(,1,1)] exactly when cin != cout.  -> (t, out) f32[n,cout,h,w]: the activation between the two
+        convolutions, which the backward pass needs, and the block's output."""
+        a, s = self._rb_arrays(x=x, w0=w0, w2=w2, wsc=wsc)
+        t = np.empty((s.n, s.cout, s.h, s.w), np.float32); out = np.empty_like(t)
+        self._ck(self.lib.pmp_resblock_forward(self.h, C.byref(s), _ptr(a["x"]), _ptr(a["w0"]), _ptr(a["w2"]), _ptr(a["wsc"]), _ptr(t), _ptr(out)))
+        return t, out
+
+    def resblock_backward(self, x, t, out, w0, w2, wsc, g_out, want_g_x=True):
+        """pmp_resblock_backward: the gradients of the block from its saved x, t, out and the upstream gradient g_out f32[n,cout,h,w].
+        -> (g_x or None without want_g_x, g_w0, g_w2, g_wsc or None for an identity shortcut), shaped like x, w0, w2, wsc."""
+        a, s = self._rb_arrays(x=x, t=t, out=out, w0=w0, w2=w2, wsc=wsc, g_out=g_out)
+        g_x = np.empty_like(a["x"]) if want_g_x else None
+        g_w0, g_w2 = np.empty_like(a["w0"]), np.empty_like(a["w2"])
+        g_wsc = None if a["wsc"] is None else np.empty_like(a["wsc"])
+        self._ck(self.lib.pmp_resblock_backward(self.h, C.byref(s), *[_ptr(a[k]) for k in ("x", "t", "out", "w0", "w2", "wsc", "g_out")],
+                                                _ptr(g_x), _ptr(g_w0), _ptr(g_w2), _ptr(g_wsc)))
+        return g_x, g_w0, g_w2, g_wsc
+
+    def resblock_forward_device(self, shape, d_x, d_w0, d_w2, d_wsc, d_t, d_out):
+        """pmp_resblock_forward_device: shape = (n, h, w, cin, cout, k), device pointers (d_wsc None for an identity shortcut);
+        stream-ordered on the engine's stream, the host does not wait."""
+        s = _lib.RbShape(*(int(v) for v in shape))
+        self._ck(self.lib.pmp_resblock_forward_device(self.h, C.byref(s), d_x, d_w0, d_w2, d_wsc, d_t, d_out))
+
+    def resblock_backward_device(self, shape, d_x, d_t, d_out, d_w0, d_w2, d_wsc, d_g_out, d_g_x, d_g_w0, d_g_w2, d_g_wsc):
+        """pmp_resblock_backward_device: as above; d_g_x None = not computed, d_wsc and d_g_wsc None for an identity shortcut."""
+        s = _lib.RbShape(*(int(v) for v in shape))
+        self._ck(self.lib.pmp_resblock_backward_device(self.h, C.byref(s), d_x, d_t, d_out, d_w0, d_w2, d_wsc, d_g_out, d_g_x, d_g_w0, d_g_w2,
+                                                       d_g_wsc))
 
     def infer_msbd(self, comp, qp, qt_in, block_y, block_u=None, block_v=None):
         """Teacher-forced MTT inference (pmp_infer_msbd; Net(input_batch, qt_label_batch), Metrics.py:226): the MTT net of (comp, qp) on

@@ -1,0 +1,97 @@
+"""Model_QBD.ResidualBlock as a torch autograd function over pmp_resblock_forward_device / pmp_resblock_backward_device
+(include/pmp.h; conv_mfma.hip, conv_wgrad.hip).
+
+Drop-in for the body of the reference's ResidualBlock.forward:
+
+    reference (Model_QBD.py:40-44)                  here
+    out = self.left(x); out += self.shortcut(x)     return residual_block_of(engine, self, x)
+    return F.relu(out)
+
+    residual_block(engine, x, w0, w2, wsc=None)     the same on bare tensors: w0 [cout,cin,k,k], w2 [cout,cout,k,k], wsc [cout,cin,1,1]
+                                                    (or [cout,cin]) exactly when cin != cout
+
+Forward saves x, the activation t between the two convolutions and the output; backward hands them to one library call that returns
+the gradients of x and of the weights.  Everything runs on torch's current stream, float32 on the exact fp32 MFMA datapath; nothing
+synchronises with the host.  One Engine serves ONE stream at a time: its context has a single activation workspace, so calls from
+two torch streams that are not ordered with each other need an Engine each.  The gradient of x is skipped when x does not require one (the first block of a net).  torch is imported
+on use, so the package stays importable without it.
+"""
+
+_FUNCTION = None
+
+
+def _function():
+    """The autograd.Function, built on first use (torch is not imported before)."""
+    global _FUNCTION
+    if _FUNCTION is not None:
+        return _FUNCTION
+    import torch
+
+    side = {}
+
+    def run(engine, dev, call):
+        """call() with the engine on torch's current stream, and back on the stream it was on afterwards.  The legacy default stream
+        has no handle the library could adopt (a null stream selects the context's OWN non-blocking stream, which torch's work is not
+        ordered with): the call then runs on a side stream fenced against the current one on both ends, still without a host
+        synchronisation."""
+        cur = torch.cuda.current_stream(dev)
+        before = engine.stream_ptr
+        try:
+            if cur.cuda_stream:
+                engine.set_stream(cur.cuda_stream)
+                call()
+                return
+            s = side.setdefault(dev, torch.cuda.Stream(dev))
+            s.wait_stream(cur)
+            engine.set_stream(s.cuda_stream)
+            call()
+            cur.wait_stream(s)
+        finally:
+            engine.set_stream(before)
+
+    def shape_of(x, w0):
+        n, cin, h, w = x.shape
+        return (n, h, w, cin, w0.shape[0], w0.shape[2])
+
+    class ResidualBlockFn(torch.autograd.Function):
+        """(engine, x, w0, w2, wsc or None) -> out f32[n,cout,h,w]"""
+
+        @staticmethod
+        def forward(ctx, engine, x, w0, w2, wsc):
+            c = lambda t: None if t is None else t.detach().to(device=x.device, dtype=torch.float32).contiguous()
+            x_, w0_, w2_, wsc_ = c(x), c(w0), c(w2), c(wsc)
+            shape = shape_of(x_, w0_)
+            t = torch.empty((shape[0], shape[4], shape[1], shape[2]), dtype=torch.float32, device=x.device)
+            out = torch.empty_like(t)
+            P = lambda a: None if a is None else a.data_ptr()
+            run(engine, x.device, lambda: engine.resblock_forward_device(shape, P(x_), P(w0_), P(w2_), P(wsc_), P(t), P(out)))
+            ctx.engine, ctx.has_sc = engine, wsc is not None
+            ctx.save_for_backward(x_, t, out, w0_, w2_, *(() if wsc_ is None else (wsc_,)))
+            return out
+
+        @staticmethod
+        def backward(ctx, g_out):
+            x, t, out, w0, w2 = ctx.saved_tensors[:5]
+            wsc = ctx.saved_tensors[5] if ctx.has_sc else None
+            g = g_out.detach().to(dtype=torch.float32).contiguous()
+            g_x = torch.empty_like(x) if ctx.needs_input_grad[1] else None
+            g_w0, g_w2 = torch.empty_like(w0), torch.empty_like(w2)
+            g_wsc = None if wsc is None else torch.empty_like(wsc)
+            P = lambda a: None if a is None else a.data_ptr()
+            run(ctx.engine, x.device, lambda: ctx.engine.resblock_backward_device(shape_of(x, w0), P(x), P(t), P(out), P(w0), P(w2), P(wsc), P(g),
+                                                                                  P(g_x), P(g_w0), P(g_w2), P(g_wsc)))
+            return None, g_x, g_w0, g_w2, g_wsc
+
+    _FUNCTION = ResidualBlockFn
+    return ResidualBlockFn
+
+
+def residual_block(engine, x, w0, w2, wsc=None):
+    """relu(conv(relu(conv(x, w0)), w2) + shortcut(x)): shortcut the identity (wsc None, cin == cout) or the 1x1 convolution wsc."""
+    return _function().apply(engine, x, w0, w2, wsc)
+
+
+def residual_block_of(engine, module, x):
+    """The same with the weights of a Model_QBD.ResidualBlock: module.left[0], module.left[2] and, if it has one, module.shortcut[0]."""
+    sc = module.shortcut[0].weight if len(module.shortcut) else None
+    return residual_block(engine, x, module.left[0].weight, module.left[2].weight, sc)
