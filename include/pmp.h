@@ -492,6 +492,48 @@ int pmp_resblock_backward_device(pmp_ctx *ctx, const pmp_rb_shape *shape, const 
                                  const float *d_w0, const float *d_w2, const float *d_wsc, const float *d_g_out, float *d_g_x,
                                  float *d_g_w0, float *d_g_w2, float *d_g_wsc);
 
+/* ---- training: a TRUNK - an nn.Sequential of 1..8 ResidualBlocks, optionally followed by F.max_pool2d(., 2) (Model_QBD.py:112-125,
+ *      :136-137, :151: trunk_M1 = 6 blocks + pool, trunk_M2 = 4 + pool, trunk_B1..B3 = 3, trunk_Att1/2 = 2, resblock_q1/q2 = 1 + pool):
+ *        y = [max_pool2d(., 2)] (block_{L-1} o ... o block_0)(x)
+ *      Every block is exactly pmp_resblock_forward's block - the same formulas, the same fp32 MFMA datapath, the same bits - but the
+ *      activations stay in the kernels' blocked layout between the blocks and between forward and backward: x goes dense -> blocked
+ *      once, y (and g_x) blocked -> dense once, where a chain of pmp_resblock_* calls converts eight tensors per block.
+ *      SHAPE: block i is cin_i -> cout[i] with k[i] (3 or 5), cin_0 = cin and cin_i = cout[i-1]; n 1..256; h and w multiples of 16 in
+ *      16..256; every channel count 1..64; nblocks 1..PMP_TRUNK_MAX_BLOCKS; pool 0 or 1.
+ *      TENSORS (device pointers, dense fp32 in torch's layouts): x, g_x [n][cin][h][w]; y, g_y [n][cout_last][h][w], with pool
+ *      [n][cout_last][h/2][w/2]; d_w and d_g_w are HOST arrays of 3 * nblocks device pointers - w0, w2, wsc of block 0, then of block
+ *      1, ... - in pmp_resblock_*'s layouts, the wsc entry NULL exactly where cin_i == cout[i], and d_g_w NULL exactly where d_w is.
+ *      d_saved: pmp_trunk_saved_bytes(shape) bytes the caller owns, 16-byte aligned, OPAQUE: the blocked x, every t_i and every out_i
+ *      (the last one un-pooled).  Forward writes every byte of it that backward or unpack reads; backward and unpack only read it.
+ *      pmp_trunk_unpack_device copies one saved tensor out in torch's dense layout: index 0 = x, 2i + 1 = t_i, 2i + 2 = out_i.
+ *      BACKWARD walks the blocks from the last to the first with pmp_resblock_backward's six steps per block, in that order; the g_x of
+ *      block i + 1 becomes the g_out of block i without leaving the blocked layout.  d_g_x may be NULL: the first block's data gradient
+ *      is then not computed and nothing is written for it.  Every byte of every requested output is written.
+ *      POOL BACKWARD: the gradient of a 2x2 window goes to its FIRST maximum in the order (0,0), (0,1), (1,0), (1,1) - torch's
+ *      max_pool2d rule (`val > maxval` replaces, so ties keep the earlier element) - recomputed from the saved un-pooled out; no index
+ *      tensor is stored.  As in pmp_resblock_*, behaviour on non-finite values is NOT specified.
+ *      PMP_E_INVALID before any launch, nothing written: a NULL or unsupported shape; a missing tensor; a shortcut pointer present
+ *      where cin_i == cout[i] or absent where they differ; a d_g_w whose NULL pattern differs from d_w's; an output that overlaps an
+ *      input or another output (d_saved is an output of forward and an input of backward and unpack); a pointer that is not 4-byte
+ *      aligned (d_saved: 16-byte); an index out of range.  pmp_trunk_saved_bytes returns PMP_E_INVALID (< 0) for such a shape; it
+ *      needs no context and no GPU.
+ *      Like pmp_resblock_*_device the calls first SETTLE the context's calls in flight and run stream-ordered on its stream; the
+ *      intermediates (one block's working set and the running gradient) live in the activation workspace.
+ *      There are NO host-pointer forms: the saved activations are device-resident by design (trunk_M1 at n = 200 saves 2.6 GB), and a
+ *      host form would copy them out and back between the two calls. ---- */
+#define PMP_TRUNK_MAX_BLOCKS 8
+typedef struct pmp_trunk_shape {
+    int n, h, w, cin, nblocks;
+    int cout[PMP_TRUNK_MAX_BLOCKS], k[PMP_TRUNK_MAX_BLOCKS];
+    int pool;
+} pmp_trunk_shape;
+int64_t pmp_trunk_saved_bytes(const pmp_trunk_shape *shape);
+int pmp_trunk_forward_device(pmp_ctx *ctx, const pmp_trunk_shape *shape, const float *d_x, const float *const *d_w, void *d_saved,
+                             float *d_y);
+int pmp_trunk_backward_device(pmp_ctx *ctx, const pmp_trunk_shape *shape, const void *d_saved, const float *const *d_w,
+                              const float *d_g_y, float *d_g_x, float *const *d_g_w);
+int pmp_trunk_unpack_device(pmp_ctx *ctx, const pmp_trunk_shape *shape, const void *d_saved, int index, float *d_dense);
+
 /* ---- teacher-forced MTT inference: the MTT net of (comp, qp) on the blocks with a GIVEN QT map instead of the QT net's output, what
  *      pre_validation predID 1 runs (Net(input_batch, qt_label_batch), Metrics.py:226).  qt_in f32[n][8][8] is read, never written
  *      (for the reference's validation: float(qt8 - 1) with the u8 wrap above).  Everything else is pmp_infer's: the context's datapath,

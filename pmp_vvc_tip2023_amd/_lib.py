@@ -42,6 +42,38 @@ class RbShape(C.Structure):
     _fields_ = [("n", C.c_int), ("h", C.c_int), ("w", C.c_int), ("cin", C.c_int), ("cout", C.c_int), ("k", C.c_int)]
 
 
+PMP_TRUNK_MAX_BLOCKS = 8
+
+
+class TrunkShape(C.Structure):
+    """pmp_trunk_shape: a chain of ResidualBlocks (block i: cout[i-1] or cin -> cout[i], k[i]) and an optional 2x2 max-pool."""
+    _fields_ = [("n", C.c_int), ("h", C.c_int), ("w", C.c_int), ("cin", C.c_int), ("nblocks", C.c_int),
+                ("cout", C.c_int * PMP_TRUNK_MAX_BLOCKS), ("k", C.c_int * PMP_TRUNK_MAX_BLOCKS), ("pool", C.c_int)]
+
+
+def trunk_shape(shape):
+    """(n, h, w, cin, [(cout, k), ...], pool) -> TrunkShape (a TrunkShape passes through).  More blocks than the struct holds keep
+    their count, so that the library refuses the shape; their channels have no place to go."""
+    if isinstance(shape, TrunkShape):
+        return shape
+    n, h, w, cin, blocks, pool = shape
+    s = TrunkShape(int(n), int(h), int(w), int(cin), len(blocks))
+    for i, (cout, k) in enumerate(blocks[:PMP_TRUNK_MAX_BLOCKS]):
+        s.cout[i], s.k[i] = int(cout), int(k)
+    s.pool = int(pool)
+    return s
+
+
+def pointer_array(ptrs, count):
+    """A host array of `count` device pointers (None = NULL) for the C ABI; None stays None."""
+    if ptrs is None:
+        return None
+    ptrs = list(ptrs)
+    if len(ptrs) != count:
+        raise ValueError("expected %d pointers, got %d" % (count, len(ptrs)))
+    return (C.c_void_p * count)(*ptrs)
+
+
 # name -> (restype, argtypes); every symbol declared in include/pmp.h
 _VP, _I, _I64, _U32 = C.c_void_p, C.c_int, C.c_int64, C.c_uint32
 SIGNATURES = {
@@ -94,6 +126,10 @@ SIGNATURES = {
     "pmp_resblock_forward_device": (_I, [_VP, C.POINTER(RbShape)] + [_VP] * 6),
     "pmp_resblock_backward": (_I, [_VP, C.POINTER(RbShape)] + [_VP] * 11),
     "pmp_resblock_backward_device": (_I, [_VP, C.POINTER(RbShape)] + [_VP] * 11),
+    "pmp_trunk_saved_bytes": (_I64, [C.POINTER(TrunkShape)]),
+    "pmp_trunk_forward_device": (_I, [_VP, C.POINTER(TrunkShape), _VP, _VP, _VP, _VP]),
+    "pmp_trunk_backward_device": (_I, [_VP, C.POINTER(TrunkShape), _VP, _VP, _VP, _VP, _VP]),
+    "pmp_trunk_unpack_device": (_I, [_VP, C.POINTER(TrunkShape), _VP, _I, _VP]),
     "pmp_infer_msbd": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
     "pmp_infer_msbd_device": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
     "pmp_read_depth_dump": (_I, [C.c_char_p, _I, _I, _I, _I, _VP, _VP, _VP, C.POINTER(_I64)]),

@@ -245,6 +245,18 @@ hipError_t launch_blocked_to_dense(hipStream_t s, const float *src, float *dst, 
 // flip_t = 1: taps mirrored, cin and cout swapped - the data gradient's weights (16 NT >= cin, 16 CB >= cout).
 hipError_t launch_pack_mfma(hipStream_t s, const float *w, float *out, int cout, int cin, int K, int NT, int CB, int flip_t);
 
+// ------------------------------------------------------------------------------------------------ training, blocked in and out (trunk_glue.hip)
+// A trunk of ResidualBlocks keeps its activations blocked [N][Cp/16][H][W][16] (H, W multiples of 16): these are the steps between
+// its convolutions.  Padded channels are zero on the way in and on the way out.
+// mode 1: dst = a where m > 0, else 0 (dst may be a);  2: dst = 1.0 where a > 0, else 0.0 (m unused) - launch_dense_to_blocked's modes
+hipError_t launch_blocked_relu(hipStream_t s, int mode, const float *a, const float *m, float *dst, int N, int Cp, int H, int W);
+// 2x2 max-pool of blocked src into dense dst [N][C][H/2][W/2]: the bits of conv_mfma's `pool` epilogue
+hipError_t launch_pool_to_dense(hipStream_t s, const float *src, float *dst, int N, int C, int Cp, int H, int W);
+// dense upstream gradient g -> blocked dst, behind the ReLU of blocked `out` (un-pooled).  pool = 0: g [N][C][H][W], dst = g where
+// out > 0.  pool = 1: g [N][C][H/2][W/2], dst[y][x] = g[y/2][x/2] where out[y][x] > 0 and is the FIRST maximum of its 2x2 window in
+// the order (0,0), (0,1), (1,0), (1,1).  Everything else, the padded channels included, is written as +0.
+hipError_t launch_grad_to_blocked(hipStream_t s, int pool, const float *g, const float *out, float *dst, int N, int C, int Cp, int H, int W);
+
 // Block cutter (Inference_QBD.py:104-149).
 hipError_t launch_cut_blocks(hipStream_t s, const void *y, const void *u, const void *v, int F, int H, int W,
                              int bitdepth, uint8_t *by, uint8_t *bu, uint8_t *bv);

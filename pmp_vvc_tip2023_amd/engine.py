@@ -437,6 +437,32 @@ class Engine:
         self._ck(self.lib.pmp_resblock_backward_device(self.h, C.byref(s), d_x, d_t, d_out, d_w0, d_w2, d_wsc, d_g_out, d_g_x, d_g_w0, d_g_w2,
                                                        d_g_wsc))
 
+    # ------------------------------------------------------------------------------------------ a trunk of ResidualBlocks, kept blocked
+    @staticmethod
+    def trunk_saved_bytes(shape):
+        """pmp_trunk_saved_bytes: the size of the saved-activation buffer of shape = (n, h, w, cin, [(cout, k), ...], pool)."""
+        size = _lib.load().pmp_trunk_saved_bytes(C.byref(_lib.trunk_shape(shape)))
+        if size < 0:                                   # no context, so no pmp_last_error
+            raise _lib.PmpError(int(size), "pmp_trunk_saved_bytes: unsupported shape %s" % (tuple(shape),))
+        return size
+
+    def trunk_forward_device(self, shape, d_x, d_w, d_saved, d_y):
+        """pmp_trunk_forward_device: d_w = 3 device pointers per block (w0, w2, wsc or None); d_saved trunk_saved_bytes(shape) bytes,
+        16-byte aligned; stream-ordered on the engine's stream, the host does not wait."""
+        s = _lib.trunk_shape(shape)
+        self._ck(self.lib.pmp_trunk_forward_device(self.h, C.byref(s), d_x, _lib.pointer_array(d_w, 3 * s.nblocks), d_saved, d_y))
+
+    def trunk_backward_device(self, shape, d_saved, d_w, d_g_y, d_g_x, d_g_w):
+        """pmp_trunk_backward_device: d_g_x None = not computed; d_g_w None exactly where d_w is."""
+        s = _lib.trunk_shape(shape)
+        self._ck(self.lib.pmp_trunk_backward_device(self.h, C.byref(s), d_saved, _lib.pointer_array(d_w, 3 * s.nblocks), d_g_y, d_g_x,
+                                                    _lib.pointer_array(d_g_w, 3 * s.nblocks)))
+
+    def trunk_unpack_device(self, shape, d_saved, index, d_dense):
+        """pmp_trunk_unpack_device: saved tensor `index` (0: x; 2i + 1: t_i; 2i + 2: out_i, un-pooled) -> torch's dense layout."""
+        s = _lib.trunk_shape(shape)
+        self._ck(self.lib.pmp_trunk_unpack_device(self.h, C.byref(s), d_saved, int(index), d_dense))
+
     def infer_msbd(self, comp, qp, qt_in, block_y, block_u=None, block_v=None):
         """Teacher-forced MTT inference (pmp_infer_msbd; Net(input_batch, qt_label_batch), Metrics.py:226): the MTT net of (comp, qp) on
         the blocks with the GIVEN QT map qt_in f32[N,(1,)8,8] -> bt f32[N,3,16,16], dire f32[N,3,16,16]."""

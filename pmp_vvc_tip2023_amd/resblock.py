@@ -18,6 +18,29 @@ on use, so the package stays importable without it.
 """
 
 _FUNCTION = None
+_SIDE = {}          # device -> the side stream that stands in for the legacy default stream
+
+
+def run(engine, dev, call):
+    """call() with the engine on torch's current stream, and back on the stream it was on afterwards.  The legacy default stream
+    has no handle the library could adopt (a null stream selects the context's OWN non-blocking stream, which torch's work is not
+    ordered with): the call then runs on a side stream fenced against the current one on both ends, still without a host
+    synchronisation.  Shared with trunk.py."""
+    import torch
+    cur = torch.cuda.current_stream(dev)
+    before = engine.stream_ptr
+    try:
+        if cur.cuda_stream:
+            engine.set_stream(cur.cuda_stream)
+            call()
+            return
+        s = _SIDE.setdefault(dev, torch.cuda.Stream(dev))
+        s.wait_stream(cur)
+        engine.set_stream(s.cuda_stream)
+        call()
+        cur.wait_stream(s)
+    finally:
+        engine.set_stream(before)
 
 
 def _function():
@@ -26,28 +49,6 @@ def _function():
     if _FUNCTION is not None:
         return _FUNCTION
     import torch
-
-    side = {}
-
-    def run(engine, dev, call):
-        """call() with the engine on torch's current stream, and back on the stream it was on afterwards.  The legacy default stream
-        has no handle the library could adopt (a null stream selects the context's OWN non-blocking stream, which torch's work is not
-        ordered with): the call then runs on a side stream fenced against the current one on both ends, still without a host
-        synchronisation."""
-        cur = torch.cuda.current_stream(dev)
-        before = engine.stream_ptr
-        try:
-            if cur.cuda_stream:
-                engine.set_stream(cur.cuda_stream)
-                call()
-                return
-            s = side.setdefault(dev, torch.cuda.Stream(dev))
-            s.wait_stream(cur)
-            engine.set_stream(s.cuda_stream)
-            call()
-            cur.wait_stream(s)
-        finally:
-            engine.set_stream(before)
 
     def shape_of(x, w0):
         n, cin, h, w = x.shape
