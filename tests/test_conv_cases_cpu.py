@@ -17,8 +17,9 @@ LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 
 _SYM = re.compile(r"_ZN3pmp\d+(conv_h2_kernel|conv_x6_kernel|conv_mfma_kernel)I((?:L[ib]\d+E)+)E")
 
 
-def kernel_symbols(lib):
-    """{"conv_h2_kernel<3,3,4,0,1>", ...}: the kernel symbols of the gfx950 code objects bundled in `lib`."""
+def kernel_symbols(lib, pattern=_SYM):
+    """{"conv_h2_kernel<3,3,4,0,1>", ...}: the kernel symbols of the gfx950 code objects bundled in `lib` that match `pattern` (group 1:
+    the kernel's name, group 2: its mangled template arguments, absent for a kernel that is no template)."""
     objdump, readelf = os.path.join(ROCM_LLVM, "llvm-objdump"), os.path.join(ROCM_LLVM, "llvm-readelf")
     if not (os.path.exists(objdump) and os.path.exists(readelf)):
         pytest.skip("ROCm's llvm-objdump / llvm-readelf are not installed")
@@ -32,8 +33,8 @@ def kernel_symbols(lib):
             if "amdgcn" not in f:
                 continue
             syms = subprocess.run([readelf, "-W", "--syms", os.path.join(d, f)], check=True, capture_output=True, text=True).stdout
-            for m in _SYM.finditer(syms):
-                out.add("%s<%s>" % (m.group(1), ",".join(re.findall(r"L[ib](\d+)E", m.group(2)))))
+            for m in pattern.finditer(syms):
+                out.add("%s<%s>" % (m.group(1), ",".join(re.findall(r"L[ib](\d+)E", m.group(2)))) if m.group(2) else m.group(1))
     finally:
         shutil.rmtree(d)
     return out

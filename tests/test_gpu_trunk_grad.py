@@ -78,6 +78,7 @@ class Dev:
         for i, (cout, _) in enumerate(self.shape[4]):
             ts.append(nan(n, cout, h, w))
             outs.append(nan(n, cout, h, w))
+            torch.cuda.synchronize()                 # torch fills them on ITS stream: done before the engine's stream writes them
             e.trunk_unpack_device(self.shape, P(self.saved), 2 * i + 1, P(ts[-1]))
             e.trunk_unpack_device(self.shape, P(self.saved), 2 * i + 2, P(outs[-1]))
         return ts, outs
@@ -87,6 +88,7 @@ class Dev:
         if ts is None:
             ts, outs = self.unpack(e)
         x0 = nan(*self.x.shape)
+        torch.cuda.synchronize()
         e.trunk_unpack_device(self.shape, P(self.saved), 0, P(x0))
         e.synchronize()
         num = lambda a: None if a is None else a.cpu().numpy()
@@ -133,6 +135,7 @@ def chain(e, c, ts_in, outs_in):
     ts, outs, xs = [], [], [x]
     for (ci, co, k), (w0, w2, wsc) in zip(T.block_shapes(c["shape"]), ws):
         t, out = nan(n, co, h, w), nan(n, co, h, w)
+        torch.cuda.synchronize()                     # (as in Dev.unpack: the NaN fills must not overtake the engine's kernels)
         e.resblock_forward_device((n, h, w, ci, co, k), P(xs[-1]), P(w0), P(w2), P(wsc), P(t), P(out))
         ts.append(t); outs.append(out); xs.append(out)
     e.synchronize()
@@ -149,6 +152,7 @@ def chain(e, c, ts_in, outs_in):
         w0, w2, wsc = ws[i]
         x_i = x if i == 0 else outs_in[i - 1]
         g_x, gw = nan(n, ci, h, w), tuple(None if a is None else nan(*a.shape) for a in ws[i])
+        torch.cuda.synchronize()
         e.resblock_backward_device((n, h, w, ci, co, k), P(x_i), P(ts_in[i]), P(outs_in[i]), P(w0), P(w2), P(wsc), P(g), P(g_x), P(gw[0]), P(gw[1]),
                                    P(gw[2]))
         g_w[i], g = gw, g_x

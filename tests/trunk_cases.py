@@ -51,37 +51,38 @@ def y_shape(shape):
     return (n, blocks[-1][0], h // 2, w // 2) if pool else (n, blocks[-1][0], h, w)
 
 
-def make_exact(name):
-    """-> dict(shape, x, blocks [(w0, w2, wsc or None), ...], g_y) as float32 numpy arrays of small integers."""
-    shape = EXACT[name]
+def make_case(shape, seed, exact=True):
+    """A trunk of `shape` from `seed` -> dict(shape, x, blocks [(w0, w2, wsc or None), ...], g_y) as float32 numpy arrays: the EXACT scheme
+    (small integers, sparse +-1 weights) or, with exact=False, the FLOAT one (normal values, weights scaled by 1 / sqrt(fan-in))."""
     n, h, w, cin = shape[:4]
-    g = torch.Generator().manual_seed(_seed(name))
+    g = torch.Generator().manual_seed(seed)
     ri = lambda lo, hi, *s: torch.randint(lo, hi + 1, s, generator=g).to(torch.float32).numpy()
+    rn = lambda scale, *s: (torch.randn(s, generator=g, dtype=torch.float64) * scale).to(torch.float32).numpy()
 
     def sparse(p, *s):                              # +-1 with probability p (capped at 1), else 0
         on = (torch.rand(s, generator=g) < p).to(torch.float32).numpy()
         return on * (2 * ri(0, 1, *s) - 1)
 
-    c = {"shape": shape, "x": ri(-2, 2, n, cin, h, w), "blocks": []}
+    c = {"shape": shape, "x": ri(-2, 2, n, cin, h, w) if exact else rn(1.0, n, cin, h, w), "blocks": []}
     for ci, co, k in block_shapes(shape):
-        c["blocks"].append((sparse(5.0 / (ci * k * k), co, ci, k, k), sparse(5.0 / (co * k * k), co, co, k, k),
-                            sparse(2.0 / ci, co, ci) if ci != co else None))
-    c["g_y"] = ri(-1, 1, *y_shape(shape))
+        if exact:
+            c["blocks"].append((sparse(5.0 / (ci * k * k), co, ci, k, k), sparse(5.0 / (co * k * k), co, co, k, k),
+                                sparse(2.0 / ci, co, ci) if ci != co else None))
+        else:
+            c["blocks"].append((rn((ci * k * k) ** -0.5, co, ci, k, k), rn((co * k * k) ** -0.5, co, co, k, k),
+                                rn(ci ** -0.5, co, ci) if ci != co else None))
+    c["g_y"] = ri(-1, 1, *y_shape(shape)) if exact else rn(1.0, *y_shape(shape))
     return c
+
+
+def make_exact(name):
+    """-> dict(shape, x, blocks [(w0, w2, wsc or None), ...], g_y) as float32 numpy arrays of small integers."""
+    return make_case(EXACT[name], _seed(name), True)
 
 
 def make_float(name):
     """-> the same with normal values; weights scaled by 1 / sqrt(fan-in)."""
-    shape = FLOAT[name]
-    n, h, w, cin = shape[:4]
-    g = torch.Generator().manual_seed(_seed(name))
-    rn = lambda scale, *s: (torch.randn(s, generator=g, dtype=torch.float64) * scale).to(torch.float32).numpy()
-    c = {"shape": shape, "x": rn(1.0, n, cin, h, w), "blocks": []}
-    for ci, co, k in block_shapes(shape):
-        c["blocks"].append((rn((ci * k * k) ** -0.5, co, ci, k, k), rn((co * k * k) ** -0.5, co, co, k, k),
-                            rn(ci ** -0.5, co, ci) if ci != co else None))
-    c["g_y"] = rn(1.0, *y_shape(shape))
-    return c
+    return make_case(FLOAT[name], _seed(name), False)
 
 
 def _windows(a):
