@@ -153,7 +153,7 @@ hipError_t launch_wgrad(hipStream_t s, const float *a, const float *g, int N, in
 
 // ---- dense NCHW <-> blocked.  One workgroup per (block, channel group, row, 16 columns): 16 channels x 16 pixels through LDS, so both
 // sides move whole 64-byte pieces.  Channels C .. Cp-1 of the blocked side are written as zeros and dropped on the way back.
-// mode 0: v = src;  1: v = m > 0 ? src : 0 (the upstream gradient behind a ReLU);  2: v = src > 0 ? 1 : 0 (the ReLU mask itself)
+// mode 0: v = src;  1: v = m > 0 ? src : 0 (the upstream gradient behind a ReLU)
 __global__ __launch_bounds__(256) void dense_to_blocked_kernel(const float *__restrict__ src, const float *__restrict__ m, int mode,
                                                                float *__restrict__ dst, int C, int G, int H, int W)
 {
@@ -169,7 +169,6 @@ __global__ __launch_bounds__(256) void dense_to_blocked_kernel(const float *__re
         const size_t i = (((size_t)n * C + c) * H + y) * W + x;
         v = src[i];
         if (mode == 1) v = m[i] > 0.f ? v : 0.f;
-        else if (mode == 2) v = v > 0.f ? 1.f : 0.f;
     }
     tile[tid >> 4][tid & 15] = v;
     __syncthreads();
@@ -192,7 +191,7 @@ __global__ __launch_bounds__(256) void blocked_to_dense_kernel(const float *__re
 
 hipError_t launch_dense_to_blocked(hipStream_t s, const float *src, const float *m, int mode, float *dst, int N, int C, int Cp, int H, int W)
 {
-    if (N <= 0 || C < 1 || C > Cp || (Cp & 15) || (W & 15) || H <= 0 || W <= 0 || mode < 0 || mode > 2 || (mode == 1 && !m))
+    if (N <= 0 || C < 1 || C > Cp || (Cp & 15) || (W & 15) || H <= 0 || W <= 0 || mode < 0 || mode > 1 || (mode == 1 && !m))
         return hipErrorInvalidValue;
     const size_t blocks = (size_t)N * (Cp >> 4) * H * (W >> 4);
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;

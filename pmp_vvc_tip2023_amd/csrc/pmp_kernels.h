@@ -238,7 +238,7 @@ size_t wgrad_partial_floats(int N, int H, int W, int Ca, int Cg, int K);
 hipError_t launch_wgrad(hipStream_t s, const float *a, const float *g, int N, int H, int W, int Ca, int Cg, int K, float *part,
                         float *dw, int cout, int cin);
 // torch's dense [N][C][H][W] <-> blocked [N][Cp/16][H][W][16] (channels C .. Cp-1 zero / dropped).  mode 0: the values; 1: src where
-// m > 0, else 0 (m dense, src's shape); 2: 1.0 where src > 0, else 0.0 - a ReLU's backward, and its mask as the conv kernel's `gate`.
+// m > 0, else 0 (m dense, src's shape) - a ReLU's backward.
 hipError_t launch_dense_to_blocked(hipStream_t s, const float *src, const float *m, int mode, float *dst, int N, int C, int Cp, int H, int W);
 hipError_t launch_blocked_to_dense(hipStream_t s, const float *src, float *dst, int N, int C, int Cp, int H, int W);
 // pack_mfma() on the device, from w [cout][cin][K][K] into [CB][K*K][NT][64][4].  flip_t = 0: as is (16 NT >= cout, 16 CB >= cin);
@@ -248,7 +248,8 @@ hipError_t launch_pack_mfma(hipStream_t s, const float *w, float *out, int cout,
 // ------------------------------------------------------------------------------------------------ training, blocked in and out (trunk_glue.hip)
 // A trunk of ResidualBlocks keeps its activations blocked [N][Cp/16][H][W][16] (H, W multiples of 16): these are the steps between
 // its convolutions.  Padded channels are zero on the way in and on the way out.
-// mode 1: dst = a where m > 0, else 0 (dst may be a);  2: dst = 1.0 where a > 0, else 0.0 (m unused) - launch_dense_to_blocked's modes
+// mode 1: dst = a where m > 0, else 0 - launch_dense_to_blocked's mode 1;  2: dst = 1.0 where a > 0, else 0.0 (m unused) - a ReLU's mask
+// as the conv kernel's `gate`.  In both dst may be a.
 hipError_t launch_blocked_relu(hipStream_t s, int mode, const float *a, const float *m, float *dst, int N, int Cp, int H, int W);
 // 2x2 max-pool of blocked src into dense dst [N][C][H/2][W/2]: the bits of conv_mfma's `pool` epilogue
 hipError_t launch_pool_to_dense(hipStream_t s, const float *src, float *dst, int N, int C, int Cp, int H, int W);

@@ -1,0 +1,110 @@
+// train_check.h — what pmp_resblock_* and pmp_trunk_* (api_train.cpp) accept: the shape rule, a trunk's blocks and its d_saved layout,
+// and the rules on a call's tensors.  A single block is checked as the one-block trunk it is.  Pure host code without the HIP runtime,
+// so that it also builds, with a main of its own, for the CPU under a sanitizer (train_check_main.cpp, `make traincheck`).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <initializer_list>
+#include <vector>
+
+#include "../../include/pmp.h"
+
+namespace pmp {
+
+inline int pad_channels(int c) { return c <= 16 ? 16 : c <= 32 ? 32 : 64; }      // the channel counts the convolution kernels have
+
+constexpr const char *TRAIN_SHAPE_RULE =
+    "null or unsupported shape (n 1..256, h and w multiples of 16 in 16..256, channels 1..64, k 3 or 5, 1..8 blocks, pool 0 or 1)";
+
+inline bool train_shape_ok(const pmp_trunk_shape *s)
+{
+    auto side = [](int v) { return v >= 16 && v <= 256 && !(v & 15); };
+    if (!s || s->n < 1 || s->n > 256 || !side(s->h) || !side(s->w) || s->cin < 1 || s->cin > 64 || s->nblocks < 1 ||
+        s->nblocks > PMP_TRUNK_MAX_BLOCKS || (s->pool != 0 && s->pool != 1))
+        return false;
+    for (int i = 0; i < s->nblocks; ++i)
+        if (s->cout[i] < 1 || s->cout[i] > 64 || (s->k[i] != 3 && s->k[i] != 5)) return false;
+    return true;
+}
+
+inline pmp_trunk_shape one_block(const pmp_rb_shape &s) { return pmp_trunk_shape{s.n, s.h, s.w, s.cin, 1, {s.cout}, {s.k}, 0}; }
+
+struct BlockShape {
+    int cin, cout, k;
+    int cip() const { return pad_channels(cin); }
+    int cop() const { return pad_channels(cout); }
+};
+
+inline BlockShape block_shape(const pmp_trunk_shape &s, int i) { return BlockShape{i ? s.cout[i - 1] : s.cin, s.cout[i], s.k[i]}; }
+
+// d_saved: blocked x, then t_i and out_i of every block, each [n][pad_channels(c)/16][h][w][16]
+struct TrunkLayout {
+    int nt;
+    int c[2 * PMP_TRUNK_MAX_BLOCKS + 1];         // the real channels of saved tensor 0 .. nt-1 (pmp_trunk_unpack_device's index)
+    size_t off[2 * PMP_TRUNK_MAX_BLOCKS + 2];    // bytes; off[nt] = the size
+    explicit TrunkLayout(const pmp_trunk_shape &s) : nt(2 * s.nblocks + 1)
+    {
+        const size_t px = (size_t)s.n * s.h * s.w * sizeof(float);
+        off[0] = 0;
+        for (int i = 0; i < nt; ++i) {
+            c[i] = i == 0 ? s.cin : s.cout[(i - 1) / 2];
+            off[i + 1] = off[i] + px * pad_channels(c[i]);
+        }
+    }
+};
+
+// A tensor of a call.  optional: may be NULL (a g_x that is not asked for, the shortcut's weights of a block that has none)
+struct Span { const void *p; size_t bytes; bool optional = false; unsigned align = 4; };
+
+inline bool overlaps(const Span &a, const Span &b)
+{
+    const uintptr_t x = (uintptr_t)a.p, y = (uintptr_t)b.p;
+    return a.p && b.p && x < y + b.bytes && y < x + a.bytes;
+}
+
+// The weights of every block of s, w0, w2, wsc per block as in pmp_trunk_*'s d_w and d_g_w (a single block's: three pointers), go IN
+// FRONT of the call's other tensors in ins / outs (the gradients only backward).  -> why the call is refused, or NULL
+inline const char *weights_refused(const pmp_trunk_shape &s, const float *const *w, float *const *g_w, bool backward, std::vector<Span> &ins,
+                                   std::vector<Span> &outs)
+{
+    if (!w || (backward && !g_w)) return "null tensor";
+    std::vector<Span> wi, wo;
+    for (int i = 0; i < s.nblocks; ++i) {
+        const BlockShape b = block_shape(s, i);
+        const size_t kk = (size_t)b.k * b.k * 4, bytes[3] = {kk * b.cout * b.cin, kk * b.cout * b.cout, (size_t)4 * b.cout * b.cin};
+        for (int j = 0; j < 3; ++j) {
+            const bool need = j < 2 || b.cin != b.cout;                 // w0, w2 required; wsc and g_wsc exactly when cin != cout
+            const float *p = w[3 * i + j];
+            if (j < 2 && !p) return "null tensor";
+            if ((p != nullptr) != need) return "a shortcut's tensors are passed exactly when its cin != cout";
+            if (backward && (g_w[3 * i + j] != nullptr) != need) return "a weight gradient must be NULL exactly where its weight is";
+            wi.push_back({p, bytes[j], true});
+            if (backward) wo.push_back({g_w[3 * i + j], bytes[j], true});
+        }
+    }
+    ins.insert(ins.begin(), wi.begin(), wi.end());
+    outs.insert(outs.begin(), wo.begin(), wo.end());
+    return nullptr;
+}
+
+// Every tensor that is not optional present, no output over an input or another output and, for device pointers, every one aligned.
+// -> why the call is refused, or NULL
+inline const char *spans_refused(const std::vector<Span> &ins, const std::vector<Span> &outs, bool device)
+{
+    for (const std::vector<Span> *v : {&ins, &outs})
+        for (const Span &t : *v)
+            if (!t.p && !t.optional) return "null tensor";
+    for (size_t i = 0; i < outs.size(); ++i) {
+        for (const Span &in : ins)
+            if (overlaps(outs[i], in)) return "an output tensor overlaps an input";
+        for (size_t j = 0; j < i; ++j)
+            if (overlaps(outs[i], outs[j])) return "two output tensors overlap";
+    }
+    for (const std::vector<Span> *v : {&ins, &outs})
+        for (const Span &t : *v)
+            if (device && ((uintptr_t)t.p & (t.align - 1))) return "every tensor must be 4-byte aligned, d_saved 16-byte";
+    return nullptr;
+}
+
+}  // namespace pmp

@@ -1,0 +1,100 @@
+// train_check_main.cpp — train_check.h on the CPU, with a main of its own, for `make traincheck` (-fsanitize=address,undefined): the
+// shapes of the refusal matrices of tests/test_gpu_resblock_grad.py and tests/test_gpu_trunk_grad.py, the weight rule per block, and
+// spans that overlap, are missing or are misaligned.  No pointer is dereferenced; exit status 0 and "train_check: ok" when all hold.
+#include <stdio.h>
+#include <string.h>
+
+#include "train_check.h"
+
+using namespace pmp;
+
+static int failures = 0;
+
+static void expect(bool ok, const char *what)
+{
+    if (!ok) { ++failures; fprintf(stderr, "train_check: FAILED: %s\n", what); }
+}
+
+static bool says(const char *why, const char *word) { return why && strstr(why, word); }
+
+int main()
+{
+    // ---- shapes: a single block as a one-block trunk
+    const int n = 2, h = 16, w = 16, ci = 16, co = 16, k = 3;
+    const pmp_rb_shape bad[] = {{0, h, w, ci, co, k}, {257, h, w, ci, co, k}, {n, 8, w, ci, co, k}, {n, 24, w, ci, co, k}, {n, 272, w, ci, co, k},
+                                {n, h, 0, ci, co, k}, {n, h, 40, ci, co, k}, {n, h, 272, ci, co, k}, {n, h, w, 0, co, k}, {n, h, w, 65, co, k},
+                                {n, h, w, ci, 0, k}, {n, h, w, ci, 65, k}, {n, h, w, ci, co, 1}, {n, h, w, ci, co, 4}, {n, h, w, ci, co, 7},
+                                {-1, h, w, ci, co, k}, {n, -16, w, ci, co, k}, {n, h, w, ci, co, -3}};
+    for (const pmp_rb_shape &s : bad) {
+        const pmp_trunk_shape t = one_block(s);
+        expect(!train_shape_ok(&t), "a shape of the refusal matrix is refused");
+    }
+    const pmp_rb_shape good[] = {{n, h, w, ci, co, k}, {1, 16, 16, 1, 1, 3}, {256, 256, 256, 64, 64, 5}, {3, 32, 48, 17, 33, 5}};
+    for (const pmp_rb_shape &s : good) {
+        const pmp_trunk_shape t = one_block(s);
+        expect(train_shape_ok(&t) && t.nblocks == 1 && t.pool == 0 && block_shape(t, 0).cin == s.cin && block_shape(t, 0).cout == s.cout &&
+                   block_shape(t, 0).k == s.k,
+               "an accepted shape is a one-block trunk");
+    }
+    // ---- shapes: trunks
+    pmp_trunk_shape m1{200, 64, 64, 32, 6, {64, 64, 64, 64, 64, 64}, {5, 3, 3, 3, 3, 3}, 1};
+    expect(train_shape_ok(&m1), "trunk_M1's shape");
+    expect(!train_shape_ok(nullptr), "a null shape");
+    for (int v : {0, -1, PMP_TRUNK_MAX_BLOCKS + 1}) { pmp_trunk_shape t = m1; t.nblocks = v; expect(!train_shape_ok(&t), "nblocks out of range"); }
+    for (int v : {-1, 2}) { pmp_trunk_shape t = m1; t.pool = v; expect(!train_shape_ok(&t), "pool out of range"); }
+    { pmp_trunk_shape t = m1; t.cout[5] = 65; expect(!train_shape_ok(&t), "a late block's channels"); }
+    { pmp_trunk_shape t = m1; t.k[3] = 4; expect(!train_shape_ok(&t), "a late block's k"); }
+    { pmp_trunk_shape t = m1; t.cout[7] = 1000; t.k[7] = 9; expect(train_shape_ok(&t), "entries behind nblocks are not read"); }
+    // ---- d_saved of the largest trunk: 17 tensors, offsets that add up, every one a multiple of 16 bytes
+    pmp_trunk_shape big{256, 256, 256, 64, 8, {64, 33, 17, 1, 64, 16, 32, 48}, {3, 5, 3, 5, 3, 5, 3, 5}, 0};
+    expect(train_shape_ok(&big), "the largest trunk");
+    const TrunkLayout lay(big);
+    size_t sum = 0;
+    for (int i = 0; i < lay.nt; ++i) {
+        expect(lay.off[i] == sum && !(lay.off[i] & 15), "d_saved offsets");
+        sum += (size_t)256 * 256 * 256 * 4 * pad_channels(lay.c[i]);
+    }
+    expect(lay.nt == 17 && lay.off[17] == sum && lay.c[0] == 64 && lay.c[1] == 64 && lay.c[2] == 64 && lay.c[3] == 33 && lay.c[16] == 48, "d_saved layout");
+    expect(block_shape(big, 0).cin == 64 && block_shape(big, 1).cin == 64 && block_shape(big, 7).cin == 32 && block_shape(big, 7).cout == 48, "block_shape");
+    // ---- the weights of every block
+    alignas(16) static float mem[16 * 2560];                                   // 2560 floats apart: the largest tensor here has 9 * 16 * 16
+    auto at = [&](int i) { return mem + i * 2560; };
+    const pmp_trunk_shape two{n, h, w, 16, 2, {16, 8}, {3, 3}, 0};             // block 0 identity, block 1 with a 1x1 shortcut
+    const float *wt[6] = {at(0), at(1), nullptr, at(2), at(3), at(4)};
+    float *gw[6] = {at(5), at(6), nullptr, at(7), at(8), at(9)};
+    std::vector<Span> ins = {{at(10), 64}}, outs = {{at(11), 64}};
+    expect(!weights_refused(two, wt, gw, true, ins, outs) && ins.size() == 7 && outs.size() == 7 && ins[6].p == at(10) && ins[0].p == mem &&
+               outs[5].p == at(9) && ins[5].bytes == (size_t)4 * 8 * 16 && ins[4].bytes == (size_t)4 * 9 * 8 * 8 && ins[0].bytes == (size_t)4 * 9 * 256,
+           "weights go in front, with their sizes");
+    expect(!spans_refused(ins, outs, true), "the spans of an accepted call");
+    std::vector<Span> a, b;
+    expect(!weights_refused(two, wt, nullptr, false, a, b) && a.size() == 6 && b.empty(), "forward: no gradients");
+    expect(says(weights_refused(two, nullptr, gw, true, a, b), "null") && says(weights_refused(two, wt, nullptr, true, a, b), "null"), "no weight array");
+    for (int j : {0, 1, 3, 4}) {
+        const float *v[6]; memcpy(v, wt, sizeof v); v[j] = nullptr;
+        expect(says(weights_refused(two, v, gw, true, a, b), "null tensor"), "a missing w0 or w2");
+    }
+    { const float *v[6]; memcpy(v, wt, sizeof v); v[2] = at(12); expect(says(weights_refused(two, v, gw, true, a, b), "shortcut"), "wsc with an identity shortcut"); }
+    { const float *v[6]; memcpy(v, wt, sizeof v); v[5] = nullptr; expect(says(weights_refused(two, v, gw, true, a, b), "shortcut"), "no wsc with a conv shortcut"); }
+    for (int j = 0; j < 6; ++j) {
+        float *v[6]; memcpy(v, gw, sizeof v); v[j] = v[j] ? nullptr : at(12);
+        expect(says(weights_refused(two, wt, v, true, a, b), "NULL exactly"), "a gradient's NULL pattern differs from its weight's");
+        expect(!weights_refused(two, wt, v, false, a, b), "... which forward does not look at");
+    }
+    expect(a.size() == 6 * 7 && b.empty(), "a refused call appends nothing");
+    // ---- spans
+    auto refused = [](std::vector<Span> i, std::vector<Span> o, bool device = true) { return spans_refused(i, o, device); };
+    const Span x{mem, 256}, y{mem + 64, 256}, y2{mem + 128, 256};
+    expect(!refused({x}, {y, y2}), "adjacent spans do not overlap");
+    expect(says(refused({x}, {{mem + 63, 8}}), "overlaps an input"), "an output's first byte range in an input's last word");
+    expect(says(refused({x}, {{mem, 4}}), "overlaps an input") && says(refused({{mem + 1, 4}}, {x}), "overlaps an input"), "containment both ways");
+    expect(says(refused({x}, {y, {mem + 127, 256}}), "two output") && says(refused({x}, {y, y}), "two output"), "two outputs");
+    expect(!refused({x, x}, {y}), "inputs may alias");
+    expect(says(refused({{nullptr, 4}}, {y}), "null") && says(refused({x}, {{nullptr, 4}}), "null"), "a missing tensor");
+    expect(!refused({x, {nullptr, 1 << 20, true}}, {y, {nullptr, 1 << 20, true}}), "an optional tensor may be NULL and overlaps nothing");
+    expect(says(refused({{(char *)mem + 2, 16}}, {y}), "aligned") && says(refused({x}, {{(char *)(mem + 64) + 1, 16}}), "aligned"), "4-byte alignment");
+    expect(!refused({{(char *)mem + 2, 16}}, {y}, false), "host pointers need no alignment");
+    expect(says(refused({{mem + 1, 64, false, 16}}, {y}), "aligned") && !refused({{mem + 4, 64, false, 16}}, {y}), "d_saved's 16 bytes");
+    if (!failures) printf("train_check: ok\n");
+    return failures ? 1 : 0;
+}

@@ -10,7 +10,8 @@ namespace pmp {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// mode 1: dst = a where m > 0, else +0 (dst may be a: every thread reads its own words before it writes them);  2: dst = [a > 0]
+// mode 1: dst = a where m > 0, else +0;  2: dst = [a > 0], the ReLU mask itself.  In both dst may be a: every thread reads its own
+// words before it writes them, and no other thread touches them (mode 2 in place: a single block's backward, api_train.cpp).
 // A workgroup moves 1024 consecutive 16-byte pieces, four per thread; n4 (a whole number of 16x16 tiles of 16 channels) is a multiple
 // of 1024, and the guard is there for a caller that breaks that.
 template <int MODE>

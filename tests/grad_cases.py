@@ -235,7 +235,7 @@ SYMBOL_PATTERN = (r"_ZN3pmp\d+(wgrad_partial_kernel|blocked_relu_kernel|grad_to_
 
 def block_kernels(shape):
     """The kernels of INSTANTIATIONS a pmp_resblock_forward + _backward of this shape launches."""
-    ks = {"dense_to_blocked_kernel", "blocked_to_dense_kernel", "pack_mfma_kernel", "wgrad_reduce_kernel"}
+    ks = {"dense_to_blocked_kernel", "blocked_to_dense_kernel", "pack_mfma_kernel", "wgrad_reduce_kernel", "blocked_relu_kernel<2>"}
     return ks | {"wgrad_partial_kernel<%d,%d>" % (k, nco) for _, k, nco, _, _, _ in wgrads(shape)}
 
 

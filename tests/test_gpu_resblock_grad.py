@@ -233,6 +233,31 @@ def test_refusals_write_nothing(eng):
     check_bits("after the refusals", dev_backward(eng, c), exact("identity")[1], GRADS)
 
 
+# ---- 4b. the workspace a block call needs: what it needed before the block calls shared the trunk's block path, to the byte, at
+# a trainer's sizes.  The bounds are pmp_get_workspace_bytes() of these same lines at the commit before that change (a pure host
+# function of the shape and the arena's take/give order); a mask or a copy of t kept beside gt would add n * pad(cout) * h * w * 4.
+WORKSPACE_NEED = {(64, 64, 64, 32, 64, 3): 235028480, (64, 64, 64, 64, 64, 3): 268582912, (64, 32, 32, 64, 32, 3): 41979904,
+                  (48, 32, 32, 32, 64, 5): 64110592}
+
+
+@pytest.mark.parametrize("shape", list(WORKSPACE_NEED), ids=lambda s: "x".join(map(str, s)))
+def test_workspace_need_of_block_calls(shape):
+    from pmp_vvc_tip2023_amd import engine
+    c = {"shape": shape}
+    sc = shape[3] != shape[4]
+    d = {k: torch.zeros(shape_of(c, k), device="cuda") if sc or k not in ("wsc", "g_wsc") else None for k in BWD_IN + GRADS}
+    e = engine.Engine(0)
+    try:
+        e.resblock_forward_device(shape, *[P(d[k]) for k in FWD_IN], P(d["t"]), P(d["out"]))
+        e.resblock_backward_device(shape, *[P(d[k]) for k in BWD_IN], *[P(d[k]) for k in GRADS])
+        e.synchronize()
+        need = e.workspace_bytes()
+    finally:
+        e.close()
+    print("workspace need of %s: %d bytes (bound %d)" % (shape, need, WORKSPACE_NEED[shape]))
+    assert 0 < need <= WORKSPACE_NEED[shape], (shape, need)
+
+
 # ---- 5. determinism: twice, on a second stream, on a second context
 def test_same_bits_on_every_run_stream_and_context(eng):
     from pmp_vvc_tip2023_amd import engine
