@@ -534,6 +534,34 @@ int pmp_trunk_backward_device(pmp_ctx *ctx, const pmp_trunk_shape *shape, const 
                               const float *d_g_y, float *d_g_x, float *const *d_g_w);
 int pmp_trunk_unpack_device(pmp_ctx *ctx, const pmp_trunk_shape *shape, const void *d_saved, int index, float *d_dense);
 
+/* ---- training: a net's STEM - its first layer, a bias convolution with 1..4 input channels, 32 outputs and a ReLU, at full resolution
+ *      (Model_QBD.py:79-80, :132-135, :177-178, :230-233).  With p = k / 2, x is f32 [n][cin][h + p][w + p], dense; everything to the
+ *      right of and below x is zero (the nets' padding_rb, padding_r and padding_b, folded into index arithmetic), and
+ *        split = 0 (QT nets):   y = relu(conv_kxk(x, w[0]) + b[0]),                       w[0] [32][cin][k][k], b[0] [32]
+ *        split = 1 (MTT nets):  y = relu(cat[conv(x, w[0]) + b[0], conv(x, w[1]) + b[1], conv(x, w[2]) + b[2]]),
+ *                               w[0] [16][cin][k][k], w[1] [8][cin][p+1][k] (rows 0..p of the k x k window), w[2] [8][cin][k][p+1]
+ *                               (columns 0..p), b of 16, 8 and 8 values
+ *      In both forms y[n][co][yy][xx] reads x[n][ci][yy + dy][xx + dx]; y and g_y are f32 [n][32][h][w], dense.  The split form is
+ *      ONE k x k convolution with 32 outputs whose smaller kernels are zero-padded (stem_train.hip); taps outside a kernel's support
+ *      are not part of g_w.
+ *      BACKWARD: gm = g_y where y > 0, else 0 (torch's mask rule); g_w[j], g_b[j] have the shapes of w[j], b[j]; g_x [n][cin][h+p][w+p]
+ *      is optional: NULL = not computed, nothing written.  Every element of every requested output is written.  The weight and bias
+ *      gradients are a two-stage reduction whose order depends on the shape only, the input gradient a fixed chain per element: no
+ *      atomics, the same bits on every run, stream and context.  Behaviour on non-finite values is NOT specified.
+ *      SHAPES: n 1..256; h and w multiples of 16 in 16..256; cin 1..4; k 5 or 9; split 0 or 1.  d_w, d_b, d_g_w, d_g_b are HOST arrays
+ *      of three device pointers; entries 1 and 2 are non-NULL exactly when split = 1.
+ *      PMP_E_INVALID before any launch, nothing written: a NULL or unsupported shape, a missing tensor or array, entries 1 and 2
+ *      against the rule, an output that overlaps an input or another output, a pointer that is not 4-byte aligned.
+ *      Like pmp_trunk_*_device the calls first SETTLE the context's calls in flight and run stream-ordered on its stream, always on
+ *      the exact fp32 MFMA datapath; packed weights and partial sums live in the activation workspace. ---- */
+typedef struct pmp_stem_shape {
+    int n, h, w, cin, k, split;
+} pmp_stem_shape;
+int pmp_stem_forward_device(pmp_ctx *ctx, const pmp_stem_shape *shape, const float *d_x, const float *const d_w[3],
+                            const float *const d_b[3], float *d_y);
+int pmp_stem_backward_device(pmp_ctx *ctx, const pmp_stem_shape *shape, const float *d_x, const float *d_y, const float *const d_w[3],
+                             const float *d_g_y, float *d_g_x /* may be NULL */, float *const d_g_w[3], float *const d_g_b[3]);
+
 /* ---- teacher-forced MTT inference: the MTT net of (comp, qp) on the blocks with a GIVEN QT map instead of the QT net's output, what
  *      pre_validation predID 1 runs (Net(input_batch, qt_label_batch), Metrics.py:226).  qt_in f32[n][8][8] is read, never written
  *      (for the reference's validation: float(qt8 - 1) with the u8 wrap above).  Everything else is pmp_infer's: the context's datapath,

@@ -64,6 +64,16 @@ def trunk_shape(shape):
     return s
 
 
+class StemShape(C.Structure):
+    """pmp_stem_shape: a net's first layer, x [n][cin][h + k/2][w + k/2] -> y [n][32][h][w]; split 1: the MTT nets' three convolutions."""
+    _fields_ = [("n", C.c_int), ("h", C.c_int), ("w", C.c_int), ("cin", C.c_int), ("k", C.c_int), ("split", C.c_int)]
+
+
+def stem_shape(shape):
+    """(n, h, w, cin, k, split) -> StemShape (a StemShape passes through)."""
+    return shape if isinstance(shape, StemShape) else StemShape(*(int(v) for v in shape))
+
+
 def pointer_array(ptrs, count):
     """A host array of `count` device pointers (None = NULL) for the C ABI; None stays None."""
     if ptrs is None:
@@ -130,6 +140,8 @@ SIGNATURES = {
     "pmp_trunk_forward_device": (_I, [_VP, C.POINTER(TrunkShape), _VP, _VP, _VP, _VP]),
     "pmp_trunk_backward_device": (_I, [_VP, C.POINTER(TrunkShape), _VP, _VP, _VP, _VP, _VP]),
     "pmp_trunk_unpack_device": (_I, [_VP, C.POINTER(TrunkShape), _VP, _I, _VP]),
+    "pmp_stem_forward_device": (_I, [_VP, C.POINTER(StemShape), _VP, _VP, _VP, _VP]),
+    "pmp_stem_backward_device": (_I, [_VP, C.POINTER(StemShape)] + [_VP] * 7),
     "pmp_infer_msbd": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
     "pmp_infer_msbd_device": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
     "pmp_read_depth_dump": (_I, [C.c_char_p, _I, _I, _I, _I, _VP, _VP, _VP, C.POINTER(_I64)]),

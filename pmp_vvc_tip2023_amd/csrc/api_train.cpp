@@ -1,6 +1,7 @@
 // api_train.cpp — a trunk of Model_QBD.ResidualBlocks, forward and backward, for a trainer (include/pmp.h: pmp_trunk_*), its activations
-// blocked between the blocks and between the two directions (trunk_glue.hip), and ONE block (pmp_resblock_forward / _backward): a shell
-// around the trunk's block that takes the caller's dense tensors through the blocked layout in the context's workspace arena.  There is
+// blocked between the blocks and between the two directions (trunk_glue.hip), ONE block (pmp_resblock_forward / _backward): a shell
+// around the trunk's block that takes the caller's dense tensors through the blocked layout in the context's workspace arena, and a
+// net's stem (pmp_stem_*, stem_train.hip), dense in and out.  There is
 // one statement of the block, TrainGraph::block_forward / block_backward, and one of what a call must satisfy (train_check.h).  The
 // convolutions are conv_mfma.hip's (the data gradients are ordinary convolutions with mirrored, transposed weights), the weight
 // gradients conv_wgrad.hip's.  Always the exact fp32 MFMA datapath: the Pass says so, whatever pmp_set_precision chose for inference.
@@ -217,17 +218,28 @@ struct TrainGraph {
         if (q.g_x) dense(gu, q.g_x, s.cin);
         release(gu);
     }
+
+    // ---- pmp_stem_*: dense in and out (stem_train.hip); the arena holds the packed weights, or the partial sums of g_w and g_b
+    void stem(const StemTrainArgs &q, bool backward)
+    {
+        Tensor scratch = floats(backward ? stem_partial_floats(q.N, q.H, q.W, q.cin, q.K) : stem_packed_floats(q.cin, q.K));
+        if (live()) check(backward ? launch_stem_wgrad(ps.stream, q, scratch.p) : launch_stem_forward(ps.stream, q, scratch.p), "stem");
+        release(scratch);
+        if (backward && q.g_x && live()) check(launch_stem_dgrad(ps.stream, q), "stem_dgrad");
+    }
 };
 
-int run_train(pmp_ctx *c, const pmp_trunk_shape &s, const std::function<void(TrainGraph &)> &body)
+int run_train(pmp_ctx *c, int n, int h, int w, const std::function<void(TrainGraph &)> &body)
 {
     Pass ps{c->stream, c->ws, PMP_PRECISION_F32, /*taps*/ false, /*cal*/ false, /*caller*/ true};
     return run_graph(c, ps, [&] {
-        TrainGraph g{c, ps, s.n, s.h, s.w};
+        TrainGraph g{c, ps, n, h, w};
         body(g);
         return g.rc;
     });
 }
+
+int run_train(pmp_ctx *c, const pmp_trunk_shape &s, const std::function<void(TrainGraph &)> &body) { return run_train(c, s.n, s.h, s.w, body); }
 
 int refuse(pmp_ctx *c, const char *fn, const char *why) { return set_err(c, PMP_E_INVALID, std::string(fn) + ": " + why); }
 
@@ -318,9 +330,52 @@ int trunk_entry(pmp_ctx *c, const char *fn, const pmp_trunk_shape *s, const Trun
     return run_train(c, *s, [&](TrainGraph &g) { dir ? g.trunk_backward(*s, q) : g.trunk_forward(*s, q); });
 }
 
+// pmp_stem_forward_device (backward = false) and pmp_stem_backward_device
+int stem_entry(pmp_ctx *c, const char *fn, const pmp_stem_shape *s, bool backward, const float *x, const float *y, const float *const *w,
+               const float *const *b, const float *g_y, float *y_out, float *g_x, float *const *g_w, float *const *g_b)
+{
+    CHECK_CTX(c);
+    if (!stem_shape_ok(s)) return refuse(c, fn, STEM_SHAPE_RULE);
+    const StemSizes z(*s);
+    std::vector<Span> ins, outs;
+    ins.push_back({x, z.x});
+    if (backward) {
+        ins.push_back({y, z.y});
+        ins.push_back({g_y, z.y});
+    }
+    outs.push_back(backward ? Span{g_x, z.x, true} : Span{y_out, z.y});
+    const char *why = stem_array_refused(*s, w, z.w, ins);
+    if (!why && !backward) why = stem_array_refused(*s, b, z.b, ins);
+    if (!why && backward) why = stem_array_refused(*s, g_w, z.w, outs);
+    if (!why && backward) why = stem_array_refused(*s, g_b, z.b, outs);
+    if (why || (why = spans_refused(ins, outs, true))) return refuse(c, fn, why);
+    int rc;
+    if ((rc = settle_before_host_call(c))) return rc;
+    StemTrainArgs q{};
+    q.N = s->n; q.H = s->h; q.W = s->w; q.cin = s->cin; q.K = s->k; q.split = s->split;
+    q.x = x; q.y = y; q.g_y = g_y; q.y_out = y_out; q.g_x = g_x;
+    for (int j = 0; j < (s->split ? 3 : 1); ++j) {
+        q.w[j] = w[j];
+        if (!backward) q.b[j] = b[j];
+        else { q.g_w[j] = g_w[j]; q.g_b[j] = g_b[j]; }
+    }
+    return run_train(c, s->n, s->h, s->w, [&](TrainGraph &g) { g.stem(q, backward); });
+}
+
 }  // namespace
 
 extern "C" {
+
+int pmp_stem_forward_device(pmp_ctx *c, const pmp_stem_shape *s, const float *x, const float *const w[3], const float *const b[3], float *y)
+{
+    return stem_entry(c, "pmp_stem_forward_device", s, false, x, nullptr, w, b, nullptr, y, nullptr, nullptr, nullptr);
+}
+
+int pmp_stem_backward_device(pmp_ctx *c, const pmp_stem_shape *s, const float *x, const float *y, const float *const w[3], const float *g_y,
+                             float *g_x, float *const g_w[3], float *const g_b[3])
+{
+    return stem_entry(c, "pmp_stem_backward_device", s, true, x, y, w, nullptr, g_y, nullptr, g_x, g_w, g_b);
+}
 
 int64_t pmp_trunk_saved_bytes(const pmp_trunk_shape *s)
 {

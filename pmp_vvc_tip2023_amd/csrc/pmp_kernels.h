@@ -258,6 +258,22 @@ hipError_t launch_pool_to_dense(hipStream_t s, const float *src, float *dst, int
 // the order (0,0), (0,1), (1,0), (1,1).  Everything else, the padded channels included, is written as +0.
 hipError_t launch_grad_to_blocked(hipStream_t s, int pool, const float *g, const float *out, float *dst, int N, int C, int Cp, int H, int W);
 
+// ------------------------------------------------------------------------------------------------ training, a net's stem (stem_train.hip)
+// pmp_stem_*'s convolution: x [N][cin][H+K/2][W+K/2], zeros to its right and below; y, g_y [N][32][H][W]; w, b and their gradients the
+// caller's one (split 0) or three (split 1) dense tensors, read and written through the unified K x K kernel.  cin 1..4, K 5 or 9.
+struct StemTrainArgs {
+    int N, H, W, cin, K, split;
+    const float *x, *y, *g_y;          // y: the forward's output, read by the gradients
+    const float *w[3], *b[3];
+    float *y_out;                      // forward
+    float *g_x, *g_w[3], *g_b[3];      // backward; g_x only for launch_stem_dgrad
+};
+size_t stem_packed_floats(int cin, int K);                            // launch_stem_forward's scratch, every word written
+size_t stem_partial_floats(int N, int H, int W, int cin, int K);      // launch_stem_wgrad's
+hipError_t launch_stem_forward(hipStream_t s, const StemTrainArgs &a, float *packed);     // y_out = relu(conv(x, w) + b)
+hipError_t launch_stem_wgrad(hipStream_t s, const StemTrainArgs &a, float *part);         // g_w, g_b: two launches, a fixed order
+hipError_t launch_stem_dgrad(hipStream_t s, const StemTrainArgs &a);                      // g_x, every element
+
 // Block cutter (Inference_QBD.py:104-149).
 hipError_t launch_cut_blocks(hipStream_t s, const void *y, const void *u, const void *v, int F, int H, int W,
                              int bitdepth, uint8_t *by, uint8_t *bu, uint8_t *bv);

@@ -1,6 +1,7 @@
-// train_check.h — what pmp_resblock_* and pmp_trunk_* (api_train.cpp) accept: the shape rule, a trunk's blocks and its d_saved layout,
-// and the rules on a call's tensors.  A single block is checked as the one-block trunk it is.  Pure host code without the HIP runtime,
-// so that it also builds, with a main of its own, for the CPU under a sanitizer (train_check_main.cpp, `make traincheck`).
+// train_check.h — what pmp_resblock_*, pmp_trunk_* and pmp_stem_* (api_train.cpp) accept: the shape rules, a trunk's blocks and its
+// d_saved layout, a stem's sizes, and the rules on a call's tensors.  A single block is checked as the one-block trunk it is.  Pure
+// host code without the HIP runtime, so that it also builds, with a main of its own, for the CPU under a sanitizer
+// (train_check_main.cpp, `make traincheck`).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -104,6 +105,41 @@ inline const char *spans_refused(const std::vector<Span> &ins, const std::vector
     for (const std::vector<Span> *v : {&ins, &outs})
         for (const Span &t : *v)
             if (device && ((uintptr_t)t.p & (t.align - 1))) return "every tensor must be 4-byte aligned, d_saved 16-byte";
+    return nullptr;
+}
+
+// ---- a stem (pmp_stem_*): the shape rule, the sizes of its three convolutions and the rule on its pointer arrays
+constexpr const char *STEM_SHAPE_RULE =
+    "null or unsupported shape (n 1..256, h and w multiples of 16 in 16..256, cin 1..4, k 5 or 9, split 0 or 1)";
+
+inline bool stem_shape_ok(const pmp_stem_shape *s)
+{
+    auto side = [](int v) { return v >= 16 && v <= 256 && !(v & 15); };
+    return s && s->n >= 1 && s->n <= 256 && side(s->h) && side(s->w) && s->cin >= 1 && s->cin <= 4 && (s->k == 5 || s->k == 9) &&
+           (s->split == 0 || s->split == 1);
+}
+
+// bytes of x and g_x [n][cin][h + p][w + p], of y and g_y [n][32][h][w], and of w[j] and b[j] (0 for the entries a QT stem lacks)
+struct StemSizes {
+    size_t x, y, w[3], b[3];
+    explicit StemSizes(const pmp_stem_shape &s)
+    {
+        const size_t p = s.k / 2, k = s.k, c = s.cin;
+        x = (size_t)s.n * c * (s.h + p) * (s.w + p) * 4;
+        y = (size_t)s.n * 32 * s.h * s.w * 4;
+        const size_t ws[3] = {(s.split ? 16 : 32) * c * k * k, 8 * c * (p + 1) * k, 8 * c * k * (p + 1)}, bs[3] = {s.split ? 16u : 32u, 8, 8};
+        for (int j = 0; j < 3; ++j) { w[j] = j && !s.split ? 0 : ws[j] * 4; b[j] = j && !s.split ? 0 : bs[j] * 4; }
+    }
+};
+
+// One of a stem call's arrays of three pointers (d_w, d_b, d_g_w, d_g_b), its tensors appended to v.  -> why refused, or NULL
+// (one copy for the call's four uses, not four inlined ones: the product library is held to a size)
+__attribute__((noinline)) inline const char *stem_array_refused(const pmp_stem_shape &s, const float *const *arr, const size_t bytes[3], std::vector<Span> &v)
+{
+    if (!arr || !arr[0]) return "null tensor";
+    for (int j = 1; j < 3; ++j)
+        if ((arr[j] != nullptr) != (s.split == 1)) return "entries 1 and 2 of a stem's pointer arrays are passed exactly when split = 1";
+    for (int j = 0; j < (s.split ? 3 : 1); ++j) v.push_back({arr[j], bytes[j]});
     return nullptr;
 }
 

@@ -1,6 +1,7 @@
 // train_check_main.cpp — train_check.h on the CPU, with a main of its own, for `make traincheck` (-fsanitize=address,undefined): the
 // shapes of the refusal matrices of tests/test_gpu_resblock_grad.py and tests/test_gpu_trunk_grad.py, the weight rule per block, and
-// spans that overlap, are missing or are misaligned.  No pointer is dereferenced; exit status 0 and "train_check: ok" when all hold.
+// spans that overlap, are missing or are misaligned, and a stem's shapes, sizes and pointer arrays (tests/test_gpu_stem_grad.py).  No
+// pointer is dereferenced; exit status 0 and "train_check: ok" when all hold.
 #include <stdio.h>
 #include <string.h>
 
@@ -95,6 +96,41 @@ int main()
     expect(says(refused({{(char *)mem + 2, 16}}, {y}), "aligned") && says(refused({x}, {{(char *)(mem + 64) + 1, 16}}), "aligned"), "4-byte alignment");
     expect(!refused({{(char *)mem + 2, 16}}, {y}, false), "host pointers need no alignment");
     expect(says(refused({{mem + 1, 64, false, 16}}, {y}), "aligned") && !refused({{mem + 4, 64, false, 16}}, {y}), "d_saved's 16 bytes");
+    // ---- a stem: the shapes of the refusal matrix of tests/test_gpu_stem_grad.py, the sizes, and the rule on the pointer arrays
+    const pmp_stem_shape sbad[] = {{0, 16, 16, 1, 9, 0}, {257, 16, 16, 1, 9, 0}, {-1, 16, 16, 1, 9, 0}, {2, 8, 16, 1, 9, 0}, {2, 24, 16, 1, 9, 0},
+                                   {2, 272, 16, 1, 9, 0}, {2, -16, 16, 1, 9, 0}, {2, 16, 0, 1, 9, 0}, {2, 16, 40, 1, 9, 0}, {2, 16, 272, 1, 9, 0},
+                                   {2, 16, 16, 0, 9, 0}, {2, 16, 16, 5, 9, 0}, {2, 16, 16, -1, 9, 0}, {2, 16, 16, 1, 3, 0}, {2, 16, 16, 1, 7, 0},
+                                   {2, 16, 16, 1, 4, 0}, {2, 16, 16, 1, 11, 0}, {2, 16, 16, 1, -9, 0}, {2, 16, 16, 1, 9, 2}, {2, 16, 16, 1, 9, -1}};
+    for (const pmp_stem_shape &t : sbad) expect(!stem_shape_ok(&t), "a stem shape of the refusal matrix is refused");
+    const pmp_stem_shape sgood[] = {{1, 16, 16, 1, 9, 0}, {200, 64, 64, 2, 9, 1}, {200, 32, 32, 3, 5, 0}, {200, 32, 32, 4, 5, 1}, {256, 256, 256, 4, 9, 1},
+                                    {3, 48, 16, 2, 5, 1}};
+    for (const pmp_stem_shape &t : sgood) expect(stem_shape_ok(&t), "an accepted stem shape");
+    expect(!stem_shape_ok(nullptr), "a null stem shape");
+    {
+        const StemSizes q(pmp_stem_shape{2, 16, 32, 3, 5, 0}), m(pmp_stem_shape{3, 48, 16, 2, 9, 1});
+        expect(q.x == (size_t)4 * 2 * 3 * 18 * 34 && q.y == (size_t)4 * 2 * 32 * 16 * 32 && q.w[0] == (size_t)4 * 32 * 3 * 25 && q.b[0] == 128 &&
+                   !q.w[1] && !q.w[2] && !q.b[1] && !q.b[2],
+               "the sizes of a QT stem");
+        expect(m.x == (size_t)4 * 3 * 2 * 52 * 20 && m.y == (size_t)4 * 3 * 32 * 48 * 16 && m.w[0] == (size_t)4 * 16 * 2 * 81 &&
+                   m.w[1] == (size_t)4 * 8 * 2 * 45 && m.w[2] == m.w[1] && m.b[0] == 64 && m.b[1] == 32 && m.b[2] == 32,
+               "the sizes of an MTT stem");
+        const pmp_stem_shape qs{2, 16, 32, 3, 5, 0}, ms{3, 48, 16, 2, 9, 1};
+        const float *w1[3] = {at(0), nullptr, nullptr}, *w3[3] = {at(0), at(1), at(2)};
+        float *g3[3] = {at(3), at(4), at(5)};
+        std::vector<Span> v;
+        expect(!stem_array_refused(qs, w1, q.w, v) && v.size() == 1 && v[0].p == at(0) && v[0].bytes == q.w[0], "a QT stem's array: one tensor");
+        expect(!stem_array_refused(ms, w3, m.w, v) && v.size() == 4 && v[3].p == at(2) && v[3].bytes == m.w[2], "an MTT stem's array: three");
+        expect(!stem_array_refused(ms, g3, m.b, v) && v.size() == 7 && v[4].bytes == 64, "an array of outputs");
+        const size_t before = v.size();
+        expect(says(stem_array_refused(qs, nullptr, q.w, v), "null"), "no array");
+        { const float *u[3] = {nullptr, nullptr, nullptr}; expect(says(stem_array_refused(qs, u, q.w, v), "null"), "no entry 0"); }
+        { const float *u[3] = {nullptr, at(1), at(2)}; expect(says(stem_array_refused(ms, u, m.w, v), "null"), "no entry 0, split"); }
+        expect(says(stem_array_refused(qs, w3, q.w, v), "exactly when split"), "three tensors without split");
+        expect(says(stem_array_refused(ms, w1, m.w, v), "exactly when split"), "one tensor with split");
+        { const float *u[3] = {at(0), at(1), nullptr}; expect(says(stem_array_refused(ms, u, m.w, v), "exactly when split") && says(stem_array_refused(qs, u, q.w, v), "exactly when split"), "two tensors"); }
+        { const float *u[3] = {at(0), nullptr, at(2)}; expect(says(stem_array_refused(ms, u, m.w, v), "exactly when split") && says(stem_array_refused(qs, u, q.w, v), "exactly when split"), "entries 0 and 2"); }
+        expect(v.size() == before, "a refused array appends nothing");
+    }
     if (!failures) printf("train_check: ok\n");
     return failures ? 1 : 0;
 }

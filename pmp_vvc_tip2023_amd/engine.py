@@ -463,6 +463,29 @@ class Engine:
         s = _lib.trunk_shape(shape)
         self._ck(self.lib.pmp_trunk_unpack_device(self.h, C.byref(s), d_saved, int(index), d_dense))
 
+    # ------------------------------------------------------------------------------------------ a net's stem, forward and backward
+    @staticmethod
+    def _stem_arrays(*arrays):
+        """d_w, d_b, ...: one pointer or a sequence of one (split 0) or three -> host arrays of three pointers, the missing ones NULL."""
+        out = []
+        for a in arrays:
+            a = list(a) if isinstance(a, (list, tuple)) else [a]
+            out.append(_lib.pointer_array(a + [None] * (3 - len(a)), 3))
+        return out
+
+    def stem_forward_device(self, shape, d_x, d_w, d_b, d_y):
+        """pmp_stem_forward_device: shape = (n, h, w, cin, k, split); d_w and d_b one device pointer (split 0) or three (split 1);
+        stream-ordered on the engine's stream, the host does not wait."""
+        s = _lib.stem_shape(shape)
+        w, b = self._stem_arrays(d_w, d_b)
+        self._ck(self.lib.pmp_stem_forward_device(self.h, C.byref(s), d_x, w, b, d_y))
+
+    def stem_backward_device(self, shape, d_x, d_y, d_w, d_g_y, d_g_x, d_g_w, d_g_b):
+        """pmp_stem_backward_device: as above; d_g_x None = not computed."""
+        s = _lib.stem_shape(shape)
+        w, g_w, g_b = self._stem_arrays(d_w, d_g_w, d_g_b)
+        self._ck(self.lib.pmp_stem_backward_device(self.h, C.byref(s), d_x, d_y, w, d_g_y, d_g_x, g_w, g_b))
+
     def infer_msbd(self, comp, qp, qt_in, block_y, block_u=None, block_v=None):
         """Teacher-forced MTT inference (pmp_infer_msbd; Net(input_batch, qt_label_batch), Metrics.py:226): the MTT net of (comp, qp) on
         the blocks with the GIVEN QT map qt_in f32[N,(1,)8,8] -> bt f32[N,3,16,16], dire f32[N,3,16,16]."""
