@@ -39,6 +39,10 @@ Largest |gpu - ref64| / bound on an MI355X (tests/test_gpu_stem_grad.py prints t
     stem_forward_kernel 0.46 (f_luma_pixels; 0.26-0.40 on the others)     stem_wgrad_kernel + stem_reduce_kernel 0.46
     (f_luma_positive; 0.34 on f_chroma_positive, 0.06-0.07 on randn and pixels)     stem_dgrad_kernel 0.46 (f_chroma_positive; 0.44
     on f_luma_positive, 0.16-0.22 on the others): the GPU stays below half of each bound, as the emulation does by construction.
+
+THE SWEEP over every shape the header accepts - all sixteen (cin, k, split), sides and n of 256, the cap of the partition with the wide
+accumulator sets, masks on the edge of `> 0`, subnormals, float cases with a real second-stage chain - is tests/stem_sweep_cases.py,
+built on this module's machinery, with constants of its own; the cases and constants here stay as they are.
 """
 import functools
 import os
@@ -100,9 +104,13 @@ def stem_np(shape):
     return items, min((items + 1) // 2, NP_CAP)
 
 
-def make_case(name, kind="exact"):
-    """-> dict(shape, x, w [list], b [list], g_y) of float32 numpy arrays."""
-    shape = EXACT[name] if name in EXACT else FLOAT_SHAPES[name]
+def make_case(name, kind="exact", shape=None, sparse=None):
+    """-> dict(shape, x, w [list], b [list], g_y) of float32 numpy arrays.  shape, sparse: of a case that is not in this module's
+    tables (tests/stem_sweep_cases.py); the name still seeds the values."""
+    if shape is None:
+        shape = EXACT[name] if name in EXACT else FLOAT_SHAPES[name]
+    if sparse is None:
+        sparse = name in SPARSE
     n, h, w, cin, k, split = shape
     p = k // 2
     g = torch.Generator().manual_seed(_seed(name + "/" + kind))
@@ -120,7 +128,7 @@ def make_case(name, kind="exact"):
     shapes = conv_shapes(shape)
     if kind == "exact":
         c = {"x": pixels(), "w": [2 * ri(0, 1, *s) - 1 for s in shapes], "b": [ri(-3, 3, s[0]) for s in shapes], "g_y": ri(-1, 1, *sy)}
-        if name in SPARSE:
+        if sparse:
             c["g_y"] = np.where(ri(0, 15, *sy) == 0, c["g_y"], np.float32(0))
     else:
         c = {"w": [rn((s[1] * s[2] * s[3]) ** -0.5, *s) for s in shapes], "b": [rn(1.0, s[0]) for s in shapes]}
