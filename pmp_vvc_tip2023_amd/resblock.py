@@ -17,37 +17,13 @@ two torch streams that are not ordered with each other need an Engine each.  The
 on use, so the package stays importable without it.
 """
 
-_FUNCTION = None
-_SIDE = {}          # device -> the side stream that stands in for the legacy default stream
+from . import torch_call
+from .torch_call import P, f32, lazy
 
 
-def run(engine, dev, call):
-    """call() with the engine on torch's current stream, and back on the stream it was on afterwards.  The legacy default stream
-    has no handle the library could adopt (a null stream selects the context's OWN non-blocking stream, which torch's work is not
-    ordered with): the call then runs on a side stream fenced against the current one on both ends, still without a host
-    synchronisation.  Shared with trunk.py."""
-    import torch
-    cur = torch.cuda.current_stream(dev)
-    before = engine.stream_ptr
-    try:
-        if cur.cuda_stream:
-            engine.set_stream(cur.cuda_stream)
-            call()
-            return
-        s = _SIDE.setdefault(dev, torch.cuda.Stream(dev))
-        s.wait_stream(cur)
-        engine.set_stream(s.cuda_stream)
-        call()
-        cur.wait_stream(s)
-    finally:
-        engine.set_stream(before)
-
-
+@lazy
 def _function():
     """The autograd.Function, built on first use (torch is not imported before)."""
-    global _FUNCTION
-    if _FUNCTION is not None:
-        return _FUNCTION
     import torch
 
     def shape_of(x, w0):
@@ -59,13 +35,11 @@ def _function():
 
         @staticmethod
         def forward(ctx, engine, x, w0, w2, wsc):
-            c = lambda t: None if t is None else t.detach().to(device=x.device, dtype=torch.float32).contiguous()
-            x_, w0_, w2_, wsc_ = c(x), c(w0), c(w2), c(wsc)
+            x_, w0_, w2_, wsc_ = (f32(t, x.device) for t in (x, w0, w2, wsc))
             shape = shape_of(x_, w0_)
             t = torch.empty((shape[0], shape[4], shape[1], shape[2]), dtype=torch.float32, device=x.device)
             out = torch.empty_like(t)
-            P = lambda a: None if a is None else a.data_ptr()
-            run(engine, x.device, lambda: engine.resblock_forward_device(shape, P(x_), P(w0_), P(w2_), P(wsc_), P(t), P(out)))
+            torch_call.run(engine, x.device, lambda: engine.resblock_forward_device(shape, P(x_), P(w0_), P(w2_), P(wsc_), P(t), P(out)))
             ctx.engine, ctx.has_sc = engine, wsc is not None
             ctx.save_for_backward(x_, t, out, w0_, w2_, *(() if wsc_ is None else (wsc_,)))
             return out
@@ -74,16 +48,14 @@ def _function():
         def backward(ctx, g_out):
             x, t, out, w0, w2 = ctx.saved_tensors[:5]
             wsc = ctx.saved_tensors[5] if ctx.has_sc else None
-            g = g_out.detach().to(dtype=torch.float32).contiguous()
+            g = f32(g_out, g_out.device)
             g_x = torch.empty_like(x) if ctx.needs_input_grad[1] else None
             g_w0, g_w2 = torch.empty_like(w0), torch.empty_like(w2)
             g_wsc = None if wsc is None else torch.empty_like(wsc)
-            P = lambda a: None if a is None else a.data_ptr()
-            run(ctx.engine, x.device, lambda: ctx.engine.resblock_backward_device(shape_of(x, w0), P(x), P(t), P(out), P(w0), P(w2), P(wsc), P(g),
-                                                                                  P(g_x), P(g_w0), P(g_w2), P(g_wsc)))
+            torch_call.run(ctx.engine, x.device, lambda: ctx.engine.resblock_backward_device(
+                shape_of(x, w0), P(x), P(t), P(out), P(w0), P(w2), P(wsc), P(g), P(g_x), P(g_w0), P(g_w2), P(g_wsc)))
             return None, g_x, g_w0, g_w2, g_wsc
 
-    _FUNCTION = ResidualBlockFn
     return ResidualBlockFn
 
 

@@ -20,11 +20,10 @@ x is f32[n, cin, h + k//2, w + k//2] - the nets' own input, before their right a
 arithmetic - and the result f32[n, 32, h, w].  k (5 or 9) and the form are read from the weights' shapes; anything that is not a stem
 raises ValueError.  Backward masks the upstream gradient where the output is zero (torch's rule for relu) and returns the gradients of
 every weight and bias, and of x only when x requires one (the MTT net's qt channel in train_QBD).  The modules keep their parameters:
-.grad arrives through autograd.  Streams are handled as in resblock.py (its run()); torch is imported on use.
+.grad arrives through autograd.  Streams are handled by torch_call.run(); torch is imported on use.
 """
-from . import resblock
-
-_FUNCTION = None
+from . import torch_call
+from .torch_call import P, f32, lazy
 
 
 def shape_of(x, convs):
@@ -48,26 +47,21 @@ def shape_of(x, convs):
     return (n, h, w_, cin, k, 1 if len(convs) == 3 else 0)
 
 
+@lazy
 def _function():
     """The autograd.Function, built on first use (torch is not imported before)."""
-    global _FUNCTION
-    if _FUNCTION is not None:
-        return _FUNCTION
     import torch
-
-    P = lambda a: None if a is None else a.data_ptr()
 
     class StemFn(torch.autograd.Function):
         """(engine, x, w, b [, w, b, w, b]) -> y f32[n, 32, h, w]"""
 
         @staticmethod
         def forward(ctx, engine, x, *wb):
-            c = lambda t: t.detach().to(device=x.device, dtype=torch.float32).contiguous()
-            x_, ws, bs = c(x), [c(t) for t in wb[0::2]], [c(t) for t in wb[1::2]]
+            x_, ws, bs = f32(x, x.device), [f32(t, x.device) for t in wb[0::2]], [f32(t, x.device) for t in wb[1::2]]
             shape = shape_of(x_, list(zip(ws, bs)))
             n, h, w = shape[:3]
             y = torch.empty((n, 32, h, w), dtype=torch.float32, device=x.device)
-            resblock.run(engine, x.device, lambda: engine.stem_forward_device(shape, P(x_), [P(t) for t in ws], [P(t) for t in bs], P(y)))
+            torch_call.run(engine, x.device, lambda: engine.stem_forward_device(shape, P(x_), [P(t) for t in ws], [P(t) for t in bs], P(y)))
             ctx.engine, ctx.shape, ctx.nconv = engine, shape, len(ws)
             ctx.save_for_backward(x_, y, *ws)
             return y
@@ -76,18 +70,17 @@ def _function():
         def backward(ctx, g_y):
             x, y = ctx.saved_tensors[:2]
             ws = ctx.saved_tensors[2:]
-            g = g_y.detach().to(dtype=torch.float32).contiguous()
+            g = f32(g_y, g_y.device)
             g_x = torch.empty_like(x) if ctx.needs_input_grad[1] else None
             g_ws = [torch.empty_like(t) for t in ws]
             g_bs = [torch.empty(t.shape[0], dtype=torch.float32, device=t.device) for t in ws]
-            resblock.run(ctx.engine, x.device, lambda: ctx.engine.stem_backward_device(ctx.shape, P(x), P(y), [P(t) for t in ws], P(g), P(g_x),
-                                                                                       [P(t) for t in g_ws], [P(t) for t in g_bs]))
+            torch_call.run(ctx.engine, x.device, lambda: ctx.engine.stem_backward_device(
+                ctx.shape, P(x), P(y), [P(t) for t in ws], P(g), P(g_x), [P(t) for t in g_ws], [P(t) for t in g_bs]))
             out = [None, g_x]
             for gw, gb in zip(g_ws, g_bs):
                 out += [gw, gb]
             return tuple(out)
 
-    _FUNCTION = StemFn
     return StemFn
 
 

@@ -14,48 +14,41 @@ Where a chain of resblock.residual_block calls converts between torch's dense la
 the trunk converts x once on the way in and y once on the way out (and g_y, g_x on the way back).  Everything between - x, every
 block's intermediate t and output - stays blocked in one opaque uint8 tensor that lives on the autograd context from forward to
 backward; the pool's backward is recomputed from it (first maximum of a window, torch's rule).  The results are those of the chain,
-bit for bit.  Streams are handled as in resblock.py (its run()); one Engine serves one stream at a time.  torch is imported on use.
+bit for bit.  Streams are handled by torch_call.run(); one Engine serves one stream at a time.  torch is imported on use.
 """
-from . import resblock
+from . import torch_call
+from .torch_call import P, f32, lazy
 
-_FUNCTION = None
 
-
+@lazy
 def _function():
     """The autograd.Function, built on first use (torch is not imported before)."""
-    global _FUNCTION
-    if _FUNCTION is not None:
-        return _FUNCTION
     import torch
-
-    P = lambda a: None if a is None else a.data_ptr()
 
     class TrunkFn(torch.autograd.Function):
         """(engine, pool, x, w0, w2, wsc-or-None of block 0, of block 1, ...) -> y f32[n, cout_last, h(/2), w(/2)]"""
 
         @staticmethod
         def forward(ctx, engine, pool, x, *ws):
-            c = lambda t: None if t is None else t.detach().to(device=x.device, dtype=torch.float32).contiguous()
-            x_, ws_ = c(x), [c(t) for t in ws]
+            x_, ws_ = f32(x, x.device), [f32(t, x.device) for t in ws]
             n, cin, h, w = x_.shape
             shape = (n, h, w, cin, [(w0.shape[0], w0.shape[2]) for w0 in ws_[0::3]], 1 if pool else 0)
             saved = torch.empty(engine.trunk_saved_bytes(shape), dtype=torch.uint8, device=x.device)
             y = torch.empty((n, shape[4][-1][0], h // 2 if pool else h, w // 2 if pool else w), dtype=torch.float32, device=x.device)
-            resblock.run(engine, x.device, lambda: engine.trunk_forward_device(shape, P(x_), [P(t) for t in ws_], P(saved), P(y)))
+            torch_call.run(engine, x.device, lambda: engine.trunk_forward_device(shape, P(x_), [P(t) for t in ws_], P(saved), P(y)))
             ctx.engine, ctx.shape, ctx.saved, ctx.ws = engine, shape, saved, ws_
             return y
 
         @staticmethod
         def backward(ctx, g_y):
-            g = g_y.detach().to(dtype=torch.float32).contiguous()
+            g = f32(g_y, g_y.device)
             n, h, w, cin = ctx.shape[:4]
             g_x = torch.empty((n, cin, h, w), dtype=torch.float32, device=g.device) if ctx.needs_input_grad[2] else None
             g_ws = [None if t is None else torch.empty_like(t) for t in ctx.ws]
-            resblock.run(ctx.engine, g.device, lambda: ctx.engine.trunk_backward_device(ctx.shape, P(ctx.saved), [P(t) for t in ctx.ws], P(g),
-                                                                                        P(g_x), [P(t) for t in g_ws]))
+            torch_call.run(ctx.engine, g.device, lambda: ctx.engine.trunk_backward_device(
+                ctx.shape, P(ctx.saved), [P(t) for t in ctx.ws], P(g), P(g_x), [P(t) for t in g_ws]))
             return (None, None, g_x) + tuple(g_ws)
 
-    _FUNCTION = TrunkFn
     return TrunkFn
 
 

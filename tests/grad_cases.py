@@ -50,6 +50,7 @@ import torch.nn.functional as F
 
 import resblock_cases as K
 import trunk_cases as T
+from cases_common import ratio  # noqa: F401 (G.ratio)
 from oracle import layers64 as L
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g17_grad_sweep.npz")
@@ -337,13 +338,6 @@ def emulate_wgrad(a, g, k):
     for q in range(1, NP):
         s = s + acc[q]
     return s.numpy()
-
-
-def ratio(got, ref, bound):
-    """max |got - ref| / bound over a tensor (0 / 0 = 0; a difference where the bound is 0 is inf)."""
-    d = np.abs(np.asarray(got, np.float64) - ref)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return float(np.where(d == 0, 0.0, d / bound).max())
 
 
 # ---- the mask-edge cases: backward only, from the caller's t and out

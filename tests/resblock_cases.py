@@ -18,6 +18,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from cases_common import as_f32, same_bits  # noqa: F401 (K.as_f32, K.same_bits)
+
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g15_resblock_grad.npz")
 OUTPUTS = ("t", "out", "g_x", "g_w0", "g_w2", "g_wsc")
 
@@ -128,16 +130,6 @@ def worst_partial_sum(c):
     if wsc is not None:
         sums.append(torch.nn.grad.conv2d_weight(x, wsc4.shape, gu))
     return max(float(v.max()) for v in sums)
-
-
-def as_f32(a):
-    """A float64 result as the float32 a kernel must produce: rounded once, zeros positive (a kernel's sums start from +0)."""
-    return None if a is None else (np.asarray(a, np.float64) + 0.0).astype(np.float32)
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 def rel_err(a, ref64):

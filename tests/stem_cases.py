@@ -51,6 +51,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from cases_common import as_f32, ratio, same_bits  # noqa: F401 (S.as_f32, S.ratio, S.same_bits)
+
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g18_stem_grad.npz")
 EPS = 2.0 ** -24
 R_STORE = 2.0 ** -23
@@ -225,16 +227,6 @@ def worst_partial_sum(c):
     return max([float(forward(c, absolute=True).max()), float(a["g_x"].max())] + [float(v.max()) for v in a["g_w"] + a["g_b"]])
 
 
-def as_f32(a):
-    """A float64 result as the float32 a kernel must produce: rounded once, zeros positive (a kernel's sums start from +0)."""
-    return (np.asarray(a, np.float64) + 0.0).astype(np.float32)
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
 @functools.lru_cache(maxsize=None)
 def exact(name):
     """-> (case, the float64 restatement, flat, as the float32 a kernel must produce); computed once, never changed."""
@@ -331,10 +323,3 @@ def emulate(c, y32):
     """flat() of the three emulations."""
     g_w, g_b = emulate_wgrad(c, y32)
     return flat({"y": emulate_forward(c), "g_x": emulate_dgrad(c, y32), "g_w": g_w, "g_b": g_b})
-
-
-def ratio(got, ref, bound):
-    """max |got - ref| / bound over a tensor (0 / 0 = 0; a difference where the bound is 0 is inf)."""
-    d = np.abs(np.asarray(got, np.float64) - ref)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return float(np.where(d == 0, 0.0, d / bound).max())

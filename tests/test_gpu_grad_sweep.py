@@ -9,30 +9,17 @@ bound, |gpu - ref64| <= c * 2^-24 * A + 2^-23 * |ref64| + P; `pytest -s` prints 
 grad_cases' docstring.  Float trunks equal the chain of pmp_resblock_*_device calls bit for bit."""
 import numpy as np
 import pytest
-import torch
 
 import grad_cases as G
 import resblock_cases as K
-import test_gpu_resblock_grad as RG
-import test_gpu_trunk_grad as TG
+import train_rig as R
 
 pytestmark = pytest.mark.gpu
 
-GRADS = RG.GRADS
+GRADS, Off4 = R.GRADS, R.Off4
 NGROUPS = G.NGROUPS
 WORST = {}                 # kernel class -> (largest ratio, case): printed as it grows
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from pmp_vvc_tip2023_amd import engine
-    assert torch.cuda.is_available()
-    torch.set_num_threads(16)
-    e = engine.Engine(0)
-    e._ck(e.lib.pmp_debug_poison_workspace(e.h, 2))
-    yield e
-    e._ck(e.lib.pmp_debug_poison_workspace(e.h, 0))
-    e.close()
+eng = R.engine_fixture(poison=2)
 
 
 def block_exact(name):
@@ -50,8 +37,8 @@ def test_exact_block_cases_bit_equal(eng, group):
     assert names
     for name in names:
         c, want = block_exact(name)
-        RG.check_bits(name + " forward", RG.dev_forward(eng, c), want, ("t", "out"))
-        RG.check_bits(name + " backward", RG.dev_backward(eng, c), want, GRADS)
+        R.check_bits(name + " forward", R.dev_forward(eng, c), want, ("t", "out"))
+        R.check_bits(name + " backward", R.dev_backward(eng, c), want, GRADS)
 
 
 # ---- 2. masks on the edge of `> 0`, and subnormal results
@@ -60,16 +47,16 @@ def test_mask_edges_bit_equal(eng, name):
     c = G.make_block(name)
     want = {k: K.as_f32(v) for k, v in G.mask_edges_reference(c)[0].items()}
     assert np.abs(want["g_w2"]).max() < 2.0 ** -126 and (want["g_w2"] != 0).mean() > 0.9
-    RG.check_bits(name, RG.dev_backward(eng, c), want, GRADS)
+    R.check_bits(name, R.dev_backward(eng, c), want, GRADS)
 
 
 def test_subnormal_trunk_bit_equal(eng):
     base, flat = G.trunk_exact(G.SUBNORMAL_TRUNK)
     c = G.scaled_trunk(base)
     want = {k: K.as_f32(v) for k, v in G.scaled_restatement(flat).items()}
-    got = TG.run(eng, c)
+    got = R.run_trunk(eng, c)
     assert sorted(k for k in got if k != "x") == sorted(want)
-    TG.check_bits("subnormal trunk", got, want)
+    R.check_bits("subnormal trunk", got, want)
     assert K.same_bits(got["x"], c["x"]) and np.abs(got["y"]).max() > 0
 
 
@@ -86,7 +73,7 @@ def test_float_case_within_its_bound_per_element(eng, name):
     c = G.make_block(*G.FLOAT[name])
     t32, out32, ref, bnd, _ = G.float_reference(c)
     c["t"], c["out"] = t32, out32
-    got = dict(RG.dev_forward(eng, c), **RG.dev_backward(eng, c))
+    got = R.run_block(eng, c)
     cls = _classes(c["shape"])
     ratios = {}
     for key in K.OUTPUTS:
@@ -107,43 +94,29 @@ def test_float_case_within_its_bound_per_element(eng, name):
 def test_exact_trunk_cases_bit_equal(eng, name):
     c, flat = G.trunk_exact(name)
     want = {k: K.as_f32(v) for k, v in flat.items()}
-    got = TG.run(eng, c)
+    got = R.run_trunk(eng, c)
     assert sorted(k for k in got if k != "x") == sorted(want)
-    TG.check_bits(name, got, want)
+    R.check_bits(name, got, want)
     assert K.same_bits(got["x"], c["x"]), "unpack of x"
 
 
 @pytest.mark.parametrize("name", G.TRUNK_FLOAT)
 def test_float_trunk_equals_chain_of_block_calls(eng, name):
     c = G.make_trunk(name, "float")
-    d = TG.Dev(eng, c)
+    d = R.TrunkDev(eng, c)
     d.forward(eng)
     d.backward(eng)
     ts, outs = d.unpack(eng)
     eng.synchronize()
     got = d.results(eng, ts, outs)
-    want = TG.chain(eng, c, ts, outs)
+    want = R.chain(eng, c, ts, outs)
     assert sorted(k for k in got if k != "x") == sorted(want)
     for k, v in want.items():
         assert np.isfinite(v).all() and np.abs(v).max() > 0, (name, k)
-    TG.check_bits(name, got, want)
+    R.check_bits(name, got, want)
 
 
 # ---- 5. caller tensors that are 4-byte but not 16-byte aligned
-class Off4:
-    """A device tensor whose first element lies 4 bytes behind a 16-byte boundary, inside a NaN-filled buffer."""
-
-    def __init__(self, t):
-        n = t.numel()
-        self.buf = torch.full((n + 8,), float("nan"), device="cuda")
-        self.view = self.buf[1:1 + n].view(t.shape)
-        self.view.copy_(t)
-        assert self.buf.data_ptr() % 16 == 0 and self.view.data_ptr() % 16 == 4 and self.view.is_contiguous()
-
-    def guards_intact(self):
-        return bool(torch.isnan(self.buf[0])) and bool(torch.isnan(self.buf[1 + self.view.numel():]).all())
-
-
 @pytest.mark.parametrize("name", ["r_k5_1to17", "p_k3_64to64", "r_k3_31to17"])
 def test_block_on_tensors_4_bytes_off(eng, name):
     if name == "r_k3_31to17":                                                # one on float values: the same bits, not only the same integers
@@ -151,14 +124,14 @@ def test_block_on_tensors_4_bytes_off(eng, name):
         c["t"], c["out"] = (K.as_f32(v) for v in K.forward(c["x"], c["w0"], c["w2"], c["wsc"]))
     else:
         c, _ = block_exact(name)
-    want = dict(RG.dev_forward(eng, c), **RG.dev_backward(eng, c))           # the aligned run
+    want = R.run_block(eng, c)                                               # the aligned run
     sc = c["wsc"] is not None
-    d = {k: Off4(RG.up(c[k])) for k in RG.BWD_IN if c[k] is not None}
-    o = {k: Off4(v) for k, v in RG.nan_dev(c, [k for k in ("t", "out") + GRADS if sc or k != "g_wsc"]).items()}
+    d = {k: Off4(R.up(c[k])) for k in R.BWD_IN if c[k] is not None}
+    o = {k: Off4(v) for k, v in R.nan_dev(c, [k for k in ("t", "out") + GRADS if sc or k != "g_wsc"]).items()}
     p = lambda m, k: m[k].view.data_ptr() if k in m else None
-    torch.cuda.synchronize()
-    eng.resblock_forward_device(c["shape"], *[p(d, k) for k in RG.FWD_IN], p(o, "t"), p(o, "out"))
-    eng.resblock_backward_device(c["shape"], *[p(d, k) for k in RG.BWD_IN], *[p(o, k) for k in GRADS])
+    R.torch_done()
+    eng.resblock_forward_device(c["shape"], *[p(d, k) for k in R.FWD_IN], p(o, "t"), p(o, "out"))
+    eng.resblock_backward_device(c["shape"], *[p(d, k) for k in R.BWD_IN], *[p(o, k) for k in GRADS])
     eng.synchronize()
     for k, v in o.items():
         got = v.view.cpu().numpy()
@@ -171,8 +144,8 @@ def test_block_on_tensors_4_bytes_off(eng, name):
 @pytest.mark.parametrize("name", ["wide_pool63", "mixed5"])
 def test_trunk_on_tensors_4_bytes_off(eng, name):
     c, _ = G.trunk_exact(name)
-    want = TG.run(eng, c)                                                    # the aligned run
-    d = TG.Dev(eng, c)
+    want = R.run_trunk(eng, c)                                                    # the aligned run
+    d = R.TrunkDev(eng, c)
     held = []
 
     def off(t):
@@ -184,17 +157,17 @@ def test_trunk_on_tensors_4_bytes_off(eng, name):
     d.x, d.g_y, d.y, d.g_x = off(d.x), off(d.g_y), off(d.y), off(d.g_x)
     d.w, d.g_w = [off(a) for a in d.w], [off(a) for a in d.g_w]
     assert d.saved.data_ptr() % 16 == 0                                      # d_saved keeps its 16 bytes
-    torch.cuda.synchronize()
+    R.torch_done()
     d.forward(eng)
     d.backward(eng)
     n, h, w = d.shape[:3]
     ts, outs = [], []
     for i, (cout, _) in enumerate(d.shape[4]):                               # unpack into tensors 4 bytes off, too
-        ts.append(off(TG.nan(n, cout, h, w)))
-        outs.append(off(TG.nan(n, cout, h, w)))
-        torch.cuda.synchronize()
-        eng.trunk_unpack_device(d.shape, TG.P(d.saved), 2 * i + 1, TG.P(ts[-1]))
-        eng.trunk_unpack_device(d.shape, TG.P(d.saved), 2 * i + 2, TG.P(outs[-1]))
+        ts.append(off(R.nan(n, cout, h, w)))
+        outs.append(off(R.nan(n, cout, h, w)))
+        R.torch_done()
+        eng.trunk_unpack_device(d.shape, R.P(d.saved), 2 * i + 1, R.P(ts[-1]))
+        eng.trunk_unpack_device(d.shape, R.P(d.saved), 2 * i + 2, R.P(outs[-1]))
     got = d.results(eng, ts, outs)
     assert sorted(got) == sorted(want)
     for k, v in want.items():

@@ -14,22 +14,14 @@ import pytest
 import torch
 
 import resblock_cases as K
+import train_rig as R
 
 pytestmark = pytest.mark.gpu
 
-FWD_IN, BWD_IN = ("x", "w0", "w2", "wsc"), ("x", "t", "out", "w0", "w2", "wsc", "g_out")
-GRADS = ("g_x", "g_w0", "g_w2", "g_wsc")
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from pmp_vvc_tip2023_amd import engine
-    assert torch.cuda.is_available()
-    torch.set_num_threads(16)
-    e = engine.Engine(0)
-    yield e
-    e._ck(e.lib.pmp_debug_poison_workspace(e.h, 0))
-    e.close()
+FWD_IN, BWD_IN, GRADS = R.FWD_IN, R.BWD_IN, R.GRADS
+P, up, nan_dev, shape_of, check_bits = R.P, R.up, R.nan_dev, R.shape_of, R.check_bits
+dev_forward, dev_backward, host_calls, _np = R.dev_forward, R.dev_backward, R.host_calls, R._np
+eng = R.engine_fixture()
 
 
 @functools.lru_cache(maxsize=None)
@@ -39,69 +31,6 @@ def exact(name):
     want = {k: K.as_f32(v) for k, v in K.restate(c).items()}
     c["t"], c["out"] = want["t"], want["out"]
     return c, want
-
-
-def shape_of(c, key):
-    n, h, w, cin, cout, k = c["shape"]
-    return {"x": (n, cin, h, w), "g_x": (n, cin, h, w), "t": (n, cout, h, w), "out": (n, cout, h, w), "g_out": (n, cout, h, w),
-            "w0": (cout, cin, k, k), "g_w0": (cout, cin, k, k), "w2": (cout, cout, k, k), "g_w2": (cout, cout, k, k),
-            "wsc": (cout, cin), "g_wsc": (cout, cin)}[key]
-
-
-def P(t):
-    return None if t is None else t.data_ptr()
-
-
-def up(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-
-
-def nan_dev(c, keys):
-    return {k: torch.full(shape_of(c, k), float("nan"), device="cuda") for k in keys}
-
-
-def dev_forward(e, c):
-    d = {k: up(c[k]) for k in FWD_IN}
-    o = nan_dev(c, ("t", "out"))
-    torch.cuda.synchronize()
-    e.resblock_forward_device(c["shape"], *[P(d[k]) for k in FWD_IN], P(o["t"]), P(o["out"]))
-    e.synchronize()
-    return {k: v.cpu().numpy() for k, v in o.items()}
-
-
-def dev_backward(e, c, want_g_x=True):
-    """-> the gradients; g_x comes back as the untouched NaN buffer when it is not asked for (it is not passed)."""
-    d = {k: up(c[k]) for k in BWD_IN}
-    sc = c["wsc"] is not None
-    o = nan_dev(c, [k for k in GRADS if sc or k != "g_wsc"])
-    torch.cuda.synchronize()
-    e.resblock_backward_device(c["shape"], *[P(d[k]) for k in BWD_IN], P(o["g_x"]) if want_g_x else None, P(o["g_w0"]), P(o["g_w2"]), P(o.get("g_wsc")))
-    e.synchronize()
-    return {k: v.cpu().numpy() for k, v in o.items()}
-
-
-def _np(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-def host_calls(e, c):
-    """The host forms through the library itself, into NaN-filled numpy buffers -> (rc forward, rc backward, outputs)."""
-    from pmp_vvc_tip2023_amd import _lib
-    s = _lib.RbShape(*c["shape"])
-    a = {k: None if c[k] is None else np.ascontiguousarray(c[k], np.float32) for k in BWD_IN}
-    sc = c["wsc"] is not None
-    o = {k: np.full(shape_of(c, k), np.nan, np.float32) for k in ("t", "out") + GRADS if sc or k != "g_wsc"}
-    rf = e.lib.pmp_resblock_forward(e.h, C.byref(s), *[_np(a[k]) for k in FWD_IN], _np(o["t"]), _np(o["out"]))
-    rb = e.lib.pmp_resblock_backward(e.h, C.byref(s), *[_np(a[k]) for k in BWD_IN], *[_np(o.get(k)) for k in GRADS])
-    return rf, rb, o
-
-
-def check_bits(what, got, want, keys):
-    for k in keys:
-        if want[k] is None:
-            assert k not in got or got[k] is None, (what, k)
-            continue
-        assert got[k].dtype == np.float32 and K.same_bits(got[k], want[k]), (what, k, np.argwhere(~(got[k] == want[k]))[:4])
 
 
 # ---- 1. every exact case, device and host form, in poisoned workspaces, into NaN-filled buffers
@@ -167,10 +96,10 @@ def test_refusals_write_nothing(eng):
     base = {"identity": exact("identity")[0], "padded_cout": exact("padded_cout")[0]}
     dev = {nm: dict({k: up(c[k]) for k in BWD_IN}, **nan_dev(c, GRADS)) for nm, c in base.items()}
     for nm, c in base.items():
-        dev[nm]["t_o"], dev[nm]["out_o"] = (torch.full(shape_of(c, "t"), float("nan"), device="cuda") for _ in range(2))
-    torch.cuda.synchronize()
+        dev[nm].update(t_o=R.nan(*shape_of(c, "t")), out_o=R.nan(*shape_of(c, "out")))
+    R.torch_done()
 
-    def call(nm, fwd, shape=None, null_shape=False, **swap):
+    def call(nm, which, shape=None, null_shape=False, **swap):
         """The device form of case nm with some pointers swapped (name -> pointer or None) -> return code."""
         d = dev[nm]
         p = {k: P(d[k]) for k in d}
@@ -179,7 +108,7 @@ def test_refusals_write_nothing(eng):
         p.update(swap)
         s = _lib.RbShape(*(shape or base[nm]["shape"]))
         sp = None if null_shape else C.byref(s)
-        if fwd:
+        if which == "forward":
             return eng.lib.pmp_resblock_forward_device(eng.h, sp, p["x"], p["w0"], p["w2"], p["wsc"], p["t_o"], p["out_o"])
         return eng.lib.pmp_resblock_backward_device(eng.h, sp, p["x"], p["t"], p["out"], p["w0"], p["w2"], p["wsc"], p["g_out"], p["g_x"], p["g_w0"],
                                                     p["g_w2"], p["g_wsc"])
@@ -191,33 +120,31 @@ def test_refusals_write_nothing(eng):
                   (n, h, w, cin, 8, k)]                                   # the last: cin != cout without the shortcut's tensors
     idn, pc = dev["identity"], dev["padded_cout"]
     tries = []
-    for fwd in (True, False):
-        tries += [("shape %s" % (s,), "identity", fwd, dict(shape=s)) for s in bad_shapes]
-        tries += [("null shape", "identity", fwd, dict(null_shape=True)), ("null x", "identity", fwd, dict(x=None)),
-                  ("null w0", "identity", fwd, dict(w0=None)), ("null w2", "identity", fwd, dict(w2=None)),
-                  ("wsc with an identity shortcut", "identity", fwd, dict(wsc=P(pc["wsc"]))),
-                  ("no wsc with a conv shortcut", "padded_cout", fwd, dict(wsc=None)),
-                  ("misaligned x", "identity", fwd, dict(x=P(idn["x"]) + 2))]
-    tries += [("null t out", "identity", True, dict(t_o=None)), ("null out out", "identity", True, dict(out_o=None)),
-              ("t overlaps x", "identity", True, dict(t_o=P(idn["x"]) + 64)), ("t is out", "identity", True, dict(out_o=P(idn["t_o"]))),
-              ("out overlaps w2", "identity", True, dict(out_o=P(idn["w2"]))), ("misaligned out", "identity", True, dict(out_o=P(idn["out_o"]) + 1)),
-              ("null t", "identity", False, dict(t=None)), ("null out", "identity", False, dict(out=None)), ("null g_out", "identity", False, dict(g_out=None)),
-              ("null g_w0", "identity", False, dict(g_w0=None)), ("null g_w2", "identity", False, dict(g_w2=None)),
-              ("g_wsc with an identity shortcut", "identity", False, dict(g_wsc=P(pc["g_wsc"]))),
-              ("no g_wsc with a conv shortcut", "padded_cout", False, dict(g_wsc=None)),
-              ("g_x overlaps g_out", "identity", False, dict(g_x=P(idn["g_out"]))), ("g_w0 is g_w2", "identity", False, dict(g_w0=P(idn["g_w2"]))),
-              ("g_w2 overlaps t", "identity", False, dict(g_w2=P(idn["t"]) + 4)), ("misaligned g_w0", "identity", False, dict(g_w0=P(idn["g_w0"]) + 2))]
-    for what, nm, fwd, kw in tries:
-        assert call(nm, fwd, **kw) == -1, (what, "forward" if fwd else "backward")
-        assert eng.lib.pmp_last_error(eng.h), what
-    eng.synchronize()
-    torch.cuda.synchronize()
-    for nm, c in base.items():
-        for k in ("t_o", "out_o") + GRADS:
-            assert torch.isnan(dev[nm][k]).all(), (nm, k, "written by a refused call")
-        for k in BWD_IN:                                                   # ... and the inputs are what they were
-            if c[k] is not None:
-                assert K.same_bits(dev[nm][k].cpu().numpy(), c[k]), (nm, k)
+    for which in ("forward", "backward"):
+        tries += [("shape %s" % (s,), "identity", which, dict(shape=s)) for s in bad_shapes]
+        tries += [("null shape", "identity", which, dict(null_shape=True)), ("null x", "identity", which, dict(x=None)),
+                  ("null w0", "identity", which, dict(w0=None)), ("null w2", "identity", which, dict(w2=None)),
+                  ("wsc with an identity shortcut", "identity", which, dict(wsc=P(pc["wsc"]))),
+                  ("no wsc with a conv shortcut", "padded_cout", which, dict(wsc=None)),
+                  ("misaligned x", "identity", which, dict(x=P(idn["x"]) + 2))]
+    tries += [("null t out", "identity", "forward", dict(t_o=None)), ("null out out", "identity", "forward", dict(out_o=None)),
+              ("t overlaps x", "identity", "forward", dict(t_o=P(idn["x"]) + 64)),
+              ("t is out", "identity", "forward", dict(out_o=P(idn["t_o"]))),
+              ("out overlaps w2", "identity", "forward", dict(out_o=P(idn["w2"]))),
+              ("misaligned out", "identity", "forward", dict(out_o=P(idn["out_o"]) + 1)),
+              ("null t", "identity", "backward", dict(t=None)), ("null out", "identity", "backward", dict(out=None)),
+              ("null g_out", "identity", "backward", dict(g_out=None)),
+              ("null g_w0", "identity", "backward", dict(g_w0=None)), ("null g_w2", "identity", "backward", dict(g_w2=None)),
+              ("g_wsc with an identity shortcut", "identity", "backward", dict(g_wsc=P(pc["g_wsc"]))),
+              ("no g_wsc with a conv shortcut", "padded_cout", "backward", dict(g_wsc=None)),
+              ("g_x overlaps g_out", "identity", "backward", dict(g_x=P(idn["g_out"]))),
+              ("g_w0 is g_w2", "identity", "backward", dict(g_w0=P(idn["g_w2"]))),
+              ("g_w2 overlaps t", "identity", "backward", dict(g_w2=P(idn["t"]) + 4)),
+              ("misaligned g_w0", "identity", "backward", dict(g_w0=P(idn["g_w0"]) + 2))]
+    R.refuse_all(eng, tries, call)
+    for nm, c in base.items():                                             # ... and the inputs are what they were
+        R.check_untouched(nm, [(k, dev[nm][k]) for k in ("t_o", "out_o") + GRADS],
+                          [(k, dev[nm][k], c[k]) for k in BWD_IN if c[k] is not None])
     # the host forms refuse the same way
     c = base["identity"]
     s = _lib.RbShape(n, h, w, cin, cout, 4)
@@ -260,30 +187,10 @@ def test_workspace_need_of_block_calls(shape):
 
 # ---- 5. determinism: twice, on a second stream, on a second context
 def test_same_bits_on_every_run_stream_and_context(eng):
-    from pmp_vvc_tip2023_amd import engine
     c = K.make_float("f_sc_5x5")
     t64, out64 = K.forward(c["x"], c["w0"], c["w2"], c["wsc"])
     c["t"], c["out"] = K.as_f32(t64), K.as_f32(out64)
-
-    def run(e):
-        return dict(dev_forward(e, c), **dev_backward(e, c))
-
-    first = run(eng)
-    runs = {"again": run(eng)}
-    side = torch.cuda.Stream()
-    eng.set_stream(side.cuda_stream)
-    try:
-        runs["second stream"] = run(eng)
-    finally:
-        eng.set_stream(0)
-    e2 = engine.Engine(0)
-    try:
-        runs["second context"] = run(e2)
-    finally:
-        e2.close()
-    for what, r in runs.items():
-        for k, v in first.items():
-            assert not np.isnan(v).any() and K.same_bits(r[k], v), (what, k)
+    R.same_bits_on_every_run_stream_and_context(eng, R.run_block, c, context_stream=False)
 
 
 # ---- 6. float values: no further from float64 than 4 x torch's own float32 ops
@@ -295,7 +202,7 @@ def test_float_case_within_4x_of_torch_float32(eng, name):
     ref = dict(K.backward(c["x"], c["t"], c["out"], c["w0"], c["w2"], c["wsc"], c["g_out"]), t=t64, out=out64)
     t32, out32 = K.forward(c["x"], c["w0"], c["w2"], c["wsc"], torch.float32)
     cpu = dict(K.backward(c["x"], c["t"], c["out"], c["w0"], c["w2"], c["wsc"], c["g_out"], torch.float32), t=t32, out=out32)
-    got = dict(dev_forward(eng, c), **dev_backward(eng, c))
+    got = R.run_block(eng, c)
     worst = []
     for k in K.OUTPUTS:
         if ref[k] is None:
@@ -309,29 +216,13 @@ def test_float_case_within_4x_of_torch_float32(eng, name):
 
 
 # ---- 7. under torch.autograd, on CUDA tensors
-class _Block(torch.nn.Module):
-    """The attributes residual_block_of reads of a Model_QBD.ResidualBlock."""
-
-    def __init__(self, c):
-        super().__init__()
-        n, h, w, cin, cout, k = c["shape"]
-        conv = lambda i, o, kk: torch.nn.Conv2d(i, o, kk, padding=kk // 2, bias=False)
-        self.left = torch.nn.Sequential(conv(cin, cout, k), torch.nn.ReLU(inplace=True), conv(cout, cout, k))
-        self.shortcut = torch.nn.Sequential() if c["wsc"] is None else torch.nn.Sequential(conv(cin, cout, 1))
-        with torch.no_grad():
-            self.left[0].weight.copy_(torch.from_numpy(c["w0"]))
-            self.left[2].weight.copy_(torch.from_numpy(c["w2"]))
-            if c["wsc"] is not None:
-                self.shortcut[0].weight.copy_(torch.from_numpy(c["wsc"]).reshape(cout, cin, 1, 1))
-
-
 @pytest.mark.parametrize("name", ["padded_cin", "identity"])
 def test_autograd_function(eng, name):
     from pmp_vvc_tip2023_amd import resblock
     c, want = exact(name)
     try:
         for x_grad in (True, False):
-            m = _Block(c).cuda()
+            m = R.reference_block(c["w0"], c["w2"], c["wsc"]).cuda()
             x = up(c["x"]).requires_grad_(x_grad)
             out = resblock.residual_block_of(eng, m, x)
             out.backward(up(c["g_out"]))

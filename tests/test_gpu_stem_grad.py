@@ -17,79 +17,13 @@ import torch
 import torch.nn.functional as F
 
 import stem_cases as S
+import train_rig as R
 
 pytestmark = pytest.mark.gpu
 RATIOS = {}
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from pmp_vvc_tip2023_amd import engine
-    assert torch.cuda.is_available()
-    torch.set_num_threads(16)
-    e = engine.Engine(0)
-    yield e
-    e._ck(e.lib.pmp_debug_poison_workspace(e.h, 0))
-    e.close()
-
-
-def P(t):
-    return None if t is None else t.data_ptr()
-
-
-def up(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-
-
-def nan(*shape):
-    return torch.full(shape, float("nan"), device="cuda")
-
-
-class Dev:
-    """A case on the device: x inside a NaN-filled allocation, 37 words from its start; NaN-filled outputs."""
-    GUARD = 37
-
-    def __init__(self, c, y=None):
-        self.shape = c["shape"]
-        n, h, w, cin, k, split = self.shape
-        size = c["x"].size
-        self.buf = nan(size + 2 * self.GUARD)
-        self.x = self.buf[self.GUARD:self.GUARD + size].view(c["x"].shape)
-        self.x.copy_(up(c["x"]))
-        self.w, self.b, self.g_y = [up(a) for a in c["w"]], [up(a) for a in c["b"]], up(c["g_y"])
-        self.y = nan(n, 32, h, w) if y is None else up(y)
-        self.g_x = nan(*c["x"].shape)
-        self.g_w, self.g_b = [nan(*a.shape) for a in c["w"]], [nan(*a.shape) for a in c["b"]]
-        torch.cuda.synchronize()
-
-    def forward(self, e):
-        e.stem_forward_device(self.shape, P(self.x), [P(a) for a in self.w], [P(a) for a in self.b], P(self.y))
-
-    def backward(self, e, want_g_x=True):
-        e.stem_backward_device(self.shape, P(self.x), P(self.y), [P(a) for a in self.w], P(self.g_y), P(self.g_x) if want_g_x else None,
-                               [P(a) for a in self.g_w], [P(a) for a in self.g_b])
-
-    def results(self, e):
-        e.synchronize()
-        num = lambda a: a.cpu().numpy()
-        assert torch.isnan(self.buf[:self.GUARD]).all() and torch.isnan(self.buf[-self.GUARD:]).all()
-        return S.flat({"y": num(self.y), "g_x": num(self.g_x), "g_w": [num(a) for a in self.g_w], "g_b": [num(a) for a in self.g_b]})
-
-
-def run(e, c, want_g_x=True, y=None):
-    """forward (unless the backward pass is GIVEN y) and backward -> flat results."""
-    d = Dev(c, y)
-    if y is None:
-        d.forward(e)
-    d.backward(e, want_g_x)
-    return d.results(e)
-
-
-def check_bits(what, got, want, skip=()):
-    assert sorted(got) == sorted(want)
-    for k, v in want.items():
-        if k not in skip:
-            assert got[k].dtype == np.float32 and S.same_bits(got[k], v), (what, k, np.argwhere(~(got[k] == v))[:4])
+P, nan, check_bits = R.P, R.nan, R.check_bits_same_keys
+Dev, run = R.StemDev, R.run_stem
+eng = R.engine_fixture()
 
 
 # ---- 1. every exact case equals the restatement, in poisoned workspaces, into NaN-filled outputs; without g_x its buffer stays NaN
@@ -109,26 +43,7 @@ def test_exact_cases_bit_equal(eng, name):
 
 # ---- 2. determinism: twice, on a second stream, on a second context
 def test_same_bits_on_every_run_stream_and_context(eng):
-    from pmp_vvc_tip2023_amd import engine
-    c = S.make_case("f_luma", "randn")
-    first = run(eng, c)
-    runs = {"again": run(eng, c)}
-    side = torch.cuda.Stream()
-    eng.set_stream(side.cuda_stream)
-    try:
-        runs["second stream"] = run(eng, c)
-    finally:
-        eng.set_stream(0)
-    e2 = engine.Engine(0)
-    try:
-        side2 = torch.cuda.Stream()
-        e2.set_stream(side2.cuda_stream)
-        runs["second context on another stream"] = run(e2, c)
-    finally:
-        e2.close()
-    for what, r in runs.items():
-        for k, v in first.items():
-            assert not np.isnan(v).any() and np.abs(v).max() > 0 and S.same_bits(r[k], v), (what, k)
+    R.same_bits_on_every_run_stream_and_context(eng, run, S.make_case("f_luma", "randn"), nonzero=True)
 
 
 # ---- 3. float values within the bound, every element
@@ -277,18 +192,10 @@ def test_refusals_write_nothing(eng):
               ("misaligned g_x", "q_luma_one", "backward", dict(g_x=P(ok.g_x) + 2)), ("misaligned g_y", "q_luma_one", "backward", dict(g_y=P(ok.g_y) + 1)),
               ("misaligned y", "q_luma_one", "backward", dict(y=P(ok.y) + 2)), ("misaligned g_w[0]", "q_luma_one", "backward", dict(g_w={0: P(ok.g_w[0]) + 2})),
               ("misaligned g_b[2]", "parts1", "backward", dict(g_b={2: P(m.g_b[2]) + 2}))]
-    for what, nm, which, kw in tries:
-        assert call(nm, which, **kw) == -1, (what, which)
-        assert eng.lib.pmp_last_error(eng.h), what
-    eng.synchronize()
-    torch.cuda.synchronize()
-    for nm, d in list(dev.items()) + [("ok", ok)]:
-        for k, a in [("y", d.y), ("g_x", d.g_x)] + [("g_w%d" % i, a) for i, a in enumerate(d.g_w)] + [("g_b%d" % i, a) for i, a in enumerate(d.g_b)]:
-            assert nm == "ok" and k == "y" or torch.isnan(a).all(), (nm, k, "written by a refused call")
-        c = cs["q_luma_one" if nm == "ok" else nm]
-        assert S.same_bits(d.x.cpu().numpy(), c["x"]) and S.same_bits(d.g_y.cpu().numpy(), c["g_y"])
-        for a, src in zip(d.w + d.b, c["w"] + c["b"]):
-            assert S.same_bits(a.cpu().numpy(), src), nm
+    R.refuse_all(eng, tries, call)
+    for nm, d in dev.items():
+        R.check_untouched(nm, d.outputs(), d.inputs(cs[nm]))
+    R.check_untouched("ok", ok.outputs(), ok.inputs(cs["q_luma_one"]), skip=("y",))                # its forward ran
     assert torch.isnan(spare).all() and torch.equal(ok.y, y_ok)
     # and the calls after a refusal still work
     ok.backward(eng)

@@ -15,24 +15,13 @@ import torch
 
 import stem_cases as S
 import stem_sweep_cases as W
-import test_gpu_stem_grad as SG
+import train_rig as R
 
 pytestmark = pytest.mark.gpu
-Dev, run, check_bits = SG.Dev, SG.run, SG.check_bits
+Dev, run, check_bits = R.StemDev, R.run_stem, R.check_bits_same_keys
 RATIOS = {}
 PATTERN = 0x7FC5A5A5                               # a quiet NaN with a payload nothing computes
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from pmp_vvc_tip2023_amd import engine
-    assert torch.cuda.is_available()
-    torch.set_num_threads(16)
-    e = engine.Engine(0)
-    e._ck(e.lib.pmp_debug_poison_workspace(e.h, 2))
-    yield e
-    e._ck(e.lib.pmp_debug_poison_workspace(e.h, 0))
-    e.close()
+eng = R.engine_fixture(poison=2)
 
 
 # ---- 1. every exact case of the table
@@ -97,10 +86,10 @@ class Arena(Dev):
         self.sources = dict([("x", c["x"]), ("g_y", c["g_y"])] + [("w%d" % j, a) for j, a in enumerate(c["w"])] +
                             [("b%d" % j, a) for j, a in enumerate(c["b"])])
         for nm, a in self.sources.items():
-            view(nm).copy_(SG.up(a))
+            view(nm).copy_(R.up(a))
         for t in [self.x, self.y, self.g_y, self.g_x] + self.w + self.b + self.g_w + self.g_b:
             assert t.data_ptr() % 4 == 0 and (guard is None or t.data_ptr() % 16 == 4 * first)
-        torch.cuda.synchronize()
+        R.torch_done()
 
     def outputs(self):
         return [nm for nm in self.at if nm not in self.sources]
@@ -150,7 +139,7 @@ def test_touching_tensors_are_accepted_and_one_shared_word_is_refused(eng, name)
     order = list(d.at)
     for a, b in zip(order, order[1:]):
         assert d.at[a][0] + d.at[a][1] == d.at[b][0], "back to back"
-    P = SG.P
+    P = R.P
     ptr = {nm: d.buf.data_ptr() + 4 * v[0] for nm, v in d.at.items()}
     nc = len(c["w"])
     arr = lambda key, p: [p["%s%d" % (key, j)] for j in range(nc)]

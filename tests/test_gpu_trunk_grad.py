@@ -15,20 +15,14 @@ import torch
 import torch.nn.functional as F
 
 import resblock_cases as K
+import train_rig as R
 import trunk_cases as T
 
 pytestmark = pytest.mark.gpu
 
-
-@pytest.fixture(scope="module")
-def eng():
-    from pmp_vvc_tip2023_amd import engine
-    assert torch.cuda.is_available()
-    torch.set_num_threads(16)
-    e = engine.Engine(0)
-    yield e
-    e._ck(e.lib.pmp_debug_poison_workspace(e.h, 0))
-    e.close()
+P, up, nan, check_bits = R.P, R.up, R.nan, R.check_bits
+Dev, run, chain = R.TrunkDev, R.run_trunk, R.chain
+eng = R.engine_fixture()
 
 
 @functools.lru_cache(maxsize=None)
@@ -36,80 +30,6 @@ def exact(name):
     """-> (case, the float64 restatement as the float32 a kernel must produce, flat); computed once, never changed."""
     c = T.make_exact(name)
     return c, {k: K.as_f32(v) for k, v in T.flat(T.restate(c)).items()}
-
-
-def P(t):
-    return None if t is None else t.data_ptr()
-
-
-def up(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-
-
-def nan(*shape):
-    return torch.full(shape, float("nan"), device="cuda")
-
-
-class Dev:
-    """A case on the device: inputs, NaN-filled outputs and a NaN-filled saved buffer (0xFF bytes)."""
-
-    def __init__(self, e, c, pool=None):
-        n, h, w, cin, blocks, p = c["shape"]
-        self.shape = (n, h, w, cin, blocks, p if pool is None else pool)
-        self.x, self.g_y = up(c["x"]), up(c["g_y"])
-        self.w = [up(a) for blk in c["blocks"] for a in blk]
-        self.saved = torch.full((e.trunk_saved_bytes(self.shape),), 0xFF, dtype=torch.uint8, device="cuda")
-        self.y = nan(*T.y_shape(self.shape))
-        self.g_x = nan(n, cin, h, w)
-        self.g_w = [None if a is None else nan(*a.shape) for a in self.w]
-        torch.cuda.synchronize()
-
-    def forward(self, e):
-        e.trunk_forward_device(self.shape, P(self.x), [P(a) for a in self.w], P(self.saved), P(self.y))
-
-    def backward(self, e, want_g_x=True):
-        e.trunk_backward_device(self.shape, P(self.saved), [P(a) for a in self.w], P(self.g_y), P(self.g_x) if want_g_x else None,
-                                [P(a) for a in self.g_w])
-
-    def unpack(self, e):
-        """-> (t, out): lists of dense device tensors, through pmp_trunk_unpack_device into NaN-filled buffers."""
-        n, h, w = self.shape[:3]
-        ts, outs = [], []
-        for i, (cout, _) in enumerate(self.shape[4]):
-            ts.append(nan(n, cout, h, w))
-            outs.append(nan(n, cout, h, w))
-            torch.cuda.synchronize()                 # torch fills them on ITS stream: done before the engine's stream writes them
-            e.trunk_unpack_device(self.shape, P(self.saved), 2 * i + 1, P(ts[-1]))
-            e.trunk_unpack_device(self.shape, P(self.saved), 2 * i + 2, P(outs[-1]))
-        return ts, outs
-
-    def results(self, e, ts=None, outs=None):
-        """Everything the calls produced, flat like trunk_cases.flat (g_x the untouched NaN buffer if it was not asked for)."""
-        if ts is None:
-            ts, outs = self.unpack(e)
-        x0 = nan(*self.x.shape)
-        torch.cuda.synchronize()
-        e.trunk_unpack_device(self.shape, P(self.saved), 0, P(x0))
-        e.synchronize()
-        num = lambda a: None if a is None else a.cpu().numpy()
-        r = T.flat({"y": num(self.y), "g_x": num(self.g_x), "t": [num(a) for a in ts], "out": [num(a) for a in outs],
-                    "g_w": [tuple(num(a) for a in self.g_w[3 * i:3 * i + 3]) for i in range(len(ts))]})
-        r["x"] = num(x0)
-        return r
-
-
-def run(e, c, want_g_x=True, pool=None):
-    d = Dev(e, c, pool)
-    d.forward(e)
-    d.backward(e, want_g_x)
-    return d.results(e)
-
-
-def check_bits(what, got, want, skip=()):
-    for k, v in want.items():
-        if k in skip:
-            continue
-        assert got[k].dtype == np.float32 and K.same_bits(got[k], v), (what, k, np.argwhere(~(got[k] == v))[:4])
 
 
 # ---- 1. every exact case equals the restatement, in poisoned workspaces, into NaN-filled outputs and a NaN-filled d_saved
@@ -126,42 +46,6 @@ def test_exact_cases_bit_equal(eng, name):
 
 
 # ---- 2. float values: the trunk is the chain of pmp_resblock_*_device calls through dense tensors, plus torch's max_pool2d
-def chain(e, c, ts_in, outs_in):
-    """The parent's API: forward block by block, y by torch; backward block by block on the GIVEN t_i and out_i -> flat results."""
-    n, h, w = c["shape"][:3]
-    pool = c["shape"][5]
-    x = up(c["x"])
-    ws = [tuple(up(a) for a in blk) for blk in c["blocks"]]
-    ts, outs, xs = [], [], [x]
-    for (ci, co, k), (w0, w2, wsc) in zip(T.block_shapes(c["shape"]), ws):
-        t, out = nan(n, co, h, w), nan(n, co, h, w)
-        torch.cuda.synchronize()                     # (as in Dev.unpack: the NaN fills must not overtake the engine's kernels)
-        e.resblock_forward_device((n, h, w, ci, co, k), P(xs[-1]), P(w0), P(w2), P(wsc), P(t), P(out))
-        ts.append(t); outs.append(out); xs.append(out)
-    e.synchronize()
-    y = F.max_pool2d(outs[-1], 2) if pool else outs[-1]
-    g = up(c["g_y"])
-    if pool:
-        o = outs_in[-1].detach().clone().requires_grad_()
-        g, = torch.autograd.grad(F.max_pool2d(o, 2), o, g)
-        g = g.contiguous()
-    torch.cuda.synchronize()
-    g_w = [None] * len(ws)
-    for i in range(len(ws) - 1, -1, -1):
-        ci, co, k = T.block_shapes(c["shape"])[i]
-        w0, w2, wsc = ws[i]
-        x_i = x if i == 0 else outs_in[i - 1]
-        g_x, gw = nan(n, ci, h, w), tuple(None if a is None else nan(*a.shape) for a in ws[i])
-        torch.cuda.synchronize()
-        e.resblock_backward_device((n, h, w, ci, co, k), P(x_i), P(ts_in[i]), P(outs_in[i]), P(w0), P(w2), P(wsc), P(g), P(g_x), P(gw[0]), P(gw[1]),
-                                   P(gw[2]))
-        g_w[i], g = gw, g_x
-    e.synchronize()
-    num = lambda a: None if a is None else a.cpu().numpy()
-    return T.flat({"y": num(y), "g_x": num(g), "t": [num(a) for a in ts], "out": [num(a) for a in outs],
-                   "g_w": [tuple(num(a) for a in gw) for gw in g_w]})
-
-
 @pytest.mark.parametrize("name", ["f_m1_like", "f_b3_like"])
 def test_trunk_equals_chain_of_block_calls(eng, name):
     c = T.make_float(name)
@@ -203,26 +87,7 @@ def test_pool_and_no_pool_agree_on_the_saved_tensors(eng):
 
 # ---- 4. determinism: twice, on a second stream, on a second context
 def test_same_bits_on_every_run_stream_and_context(eng):
-    from pmp_vvc_tip2023_amd import engine
-    c = T.make_float("f_m1_like")
-    first = run(eng, c)
-    runs = {"again": run(eng, c)}
-    side = torch.cuda.Stream()
-    eng.set_stream(side.cuda_stream)
-    try:
-        runs["second stream"] = run(eng, c)
-    finally:
-        eng.set_stream(0)
-    e2 = engine.Engine(0)
-    try:
-        side2 = torch.cuda.Stream()
-        e2.set_stream(side2.cuda_stream)
-        runs["second context on another stream"] = run(e2, c)
-    finally:
-        e2.close()
-    for what, r in runs.items():
-        for k, v in first.items():
-            assert not np.isnan(v).any() and K.same_bits(r[k], v), (what, k)
+    R.same_bits_on_every_run_stream_and_context(eng, run, T.make_float("f_m1_like"))
 
 
 # ---- 5. refusals: PMP_E_INVALID before any launch, nothing written
@@ -292,20 +157,10 @@ def test_refusals_write_nothing(eng):
               ("null dense", "one_pool", "unpack", dict(dense=None)), ("index -1", "one_pool", "unpack", dict(index=-1)),
               ("index 3 of one block", "one_pool", "unpack", dict(index=3)), ("dense inside d_saved", "one_pool", "unpack", dict(dense=P(ok.saved) + 512)),
               ("misaligned dense", "one_pool", "unpack", dict(dense=P(dense) + 2))]
-    for what, nm, which, kw in tries:
-        assert call(nm, which, **kw) == -1, (what, which)
-        assert eng.lib.pmp_last_error(eng.h), what
-    eng.synchronize()
-    torch.cuda.synchronize()
-    for nm, d in list(dev.items()) + [("ok", ok)]:
-        for k, a in [("y", d.y), ("g_x", d.g_x)] + [("g_w%d" % i, a) for i, a in enumerate(d.g_w) if a is not None]:
-            assert nm == "ok" and k == "y" or torch.isnan(a).all(), (nm, k, "written by a refused call")
-        if nm != "ok":
-            assert (d.saved == 0xFF).all(), (nm, "d_saved written by a refused call")
-        c = cs["one_pool" if nm == "ok" else nm]
-        assert K.same_bits(d.x.cpu().numpy(), c["x"]) and K.same_bits(d.g_y.cpu().numpy(), c["g_y"])
-        for a, src in zip(d.w, [a for blk in c["blocks"] for a in blk]):
-            assert a is None or K.same_bits(a.cpu().numpy(), src), nm
+    R.refuse_all(eng, tries, call)
+    for nm, d in dev.items():
+        R.check_untouched(nm, d.outputs(), d.inputs(cs[nm]))
+    R.check_untouched("ok", ok.outputs(), ok.inputs(cs["one_pool"]), skip=("y", "d_saved"))     # its forward ran
     assert torch.isnan(dense).all() and torch.isnan(other_g).all() and torch.equal(ok.saved, saved_ok)
     # and the calls after a refusal still work
     ok.backward(eng)
@@ -354,25 +209,9 @@ def test_autograd_function_equals_chain_of_block_functions(eng, side_stream):
         assert K.same_bits(a, b), i
 
 
-class _Block(torch.nn.Module):
-    """The attributes trunk_of reads of a Model_QBD.ResidualBlock."""
-
-    def __init__(self, w0, w2, wsc):
-        super().__init__()
-        par = lambda a: torch.nn.Parameter(torch.from_numpy(a))
-        conv = lambda a: torch.nn.Conv2d(a.shape[1], a.shape[0], a.shape[2], padding=a.shape[2] // 2, bias=False)
-        self.left = torch.nn.Sequential(conv(w0), torch.nn.ReLU(inplace=True), conv(w2))
-        self.left[0].weight, self.left[2].weight = par(w0), par(w2)
-        self.shortcut = torch.nn.Sequential()
-        if wsc is not None:
-            wsc4 = wsc.reshape(wsc.shape[0], wsc.shape[1], 1, 1)
-            self.shortcut = torch.nn.Sequential(conv(wsc4))
-            self.shortcut[0].weight = par(wsc4)
-
-
 def test_trunk_of_a_sequential(eng):
     c, want = exact("b3_like")
-    seq = torch.nn.Sequential(*[_Block(*blk) for blk in c["blocks"]]).cuda()
+    seq = torch.nn.Sequential(*[R.reference_block(*blk) for blk in c["blocks"]]).cuda()
     from pmp_vvc_tip2023_amd import trunk
     try:
         x = up(c["x"]).requires_grad_()
