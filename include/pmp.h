@@ -562,6 +562,55 @@ int pmp_stem_forward_device(pmp_ctx *ctx, const pmp_stem_shape *shape, const flo
 int pmp_stem_backward_device(pmp_ctx *ctx, const pmp_stem_shape *shape, const float *d_x, const float *d_y, const float *const d_w[3],
                              const float *d_g_y, float *d_g_x /* may be NULL */, float *const d_g_w[3], float *const d_g_b[3]);
 
+/* ---- training: an MTT net's HEAD - conv_B1..3 (8 -> 2, 3x3, padding 1, bias), the carry out_k[:,0] += out_{k-1}[:,0] and the next
+ *      attention trunk's input cat[interpolate(x1), interpolate(out)] (Model_QBD.py:139-153, :237-251) - forward and backward
+ *      (head_train.hip).  All tensors dense NCHW f32.
+ *      FORWARD.  x [n][cin][h][w], w [cout][cin][3][3], b [cout]; one element of y [n][cout][h][w]:
+ *        acc = +0; acc = fma(w[co][ci][dy][dx], x[n][ci][yy+dy-1][xx+dx-1], acc) for ci = 0..cin-1, inside that dy = 0..2, inside that
+ *        dx = 0..2 (an x outside the map enters as +0); y = acc + b[co]; then, if d_prev [n][cout][h][w] is given and co = 0,
+ *        y = y + prev[n][0][yy][xx] - the carry, added behind the bias as the reference adds it.  Channels 1.. of prev are not read.
+ *        If up_y != 0, att [n][1+cout][up_y h][up_y w] is written in the same pass from the CARRIED y:
+ *        att[n][0][Y][X] = q[n][0][Y / up_q][X / up_q], att[n][1+co][Y][X] = y[n][co][Y / up_y][X / up_y]  (nearest, the reference's
+ *        F.interpolate), q [n][1][up_y h / up_q][up_y w / up_q].  d_q and d_att are passed exactly when up_y != 0.
+ *      BACKWARD.  g_y [n][cout][h][w] is the gradient that reaches the carried y from everywhere but att (the loss, and the next
+ *        head's carry); g_att [n][1+cout][up_y h][up_y w] is passed exactly when up_y != 0.  The effective gradient of the carried y:
+ *        gy = g_y, then gy = gy + g_att[n][1+co][up_y yy + i][up_y xx + j] for (i, j) = (0,0), (0,1), (1,0), (1,1) in that order
+ *        (up_y = 1: the one element).
+ *        g_x [n][cin][h][w] (optional): acc = +0; acc = fma(w[co][ci][dy][dx], gy[n][co][yy+1-dy][xx+1-dx], acc) for co, inside that
+ *        dy, inside that dx (a gy outside the map enters as +0).
+ *        g_w [cout][cin][3][3] and g_b [cout], two stages: the ITEMS are the 8x8 tiles of the maps, item = (n * h/8 + ty) * w/8 + tx;
+ *        NP = min(ceil(items / 2), 128) partitions, a function of the shape only; partition p starts from +0 and adds the items p,
+ *        p + NP, ... in that order, each pixel by pixel in row order, acc = fma(gy, x, acc) (g_b: acc = acc + gy); then
+ *        s = partial 0, s = s + partial p for p = 1 .. NP-1.  No atomics: the same bits on every run, stream and context.
+ *        g_q [n][1][up_y h / up_q][up_y w / up_q] (optional, only with g_att): s = +0, then s = s + g_att[n][0][up_q Y + i][up_q X + j]
+ *        over the window in row-major order.
+ *        g_prev [n][cout][h][w] (optional): the carry's gradient, g_prev[:,0] = gy[:,0] and +0 in the other channels.  Where up_y = 0
+ *        that is g_y[:,0] and a caller needs no copy of it; with an attention input (conv_B2) the window sums of g_att belong to it.
+ *      SHAPES: n 1..256; h and w multiples of 8 in 8..256; cin 1..16; cout 1 or 2 (conv_q2 has 1); (up_q, up_y) = (0,0): no attention
+ *      input, or (2,1) or (4,2), the two pairs the nets use.
+ *      PMP_E_INVALID before any launch, nothing written: a NULL or unsupported shape, a missing tensor, q / att / g_att against the
+ *      rule, g_q without g_att, an output that overlaps an input or another output, a pointer that is not 4-byte aligned.  Every
+ *      element of every requested output is written.  Settles the context's calls in flight, then runs stream-ordered on its stream;
+ *      the partial sums live in the activation workspace.  Behaviour on non-finite values is NOT specified. ---- */
+typedef struct pmp_head_shape {
+    int n, h, w, cin, cout, up_q, up_y;
+} pmp_head_shape;
+int pmp_head_forward_device(pmp_ctx *ctx, const pmp_head_shape *shape, const float *d_x, const float *d_w, const float *d_b,
+                            const float *d_prev /* may be NULL */, const float *d_q, float *d_y, float *d_att);
+int pmp_head_backward_device(pmp_ctx *ctx, const pmp_head_shape *shape, const float *d_x, const float *d_w, const float *d_g_y,
+                             const float *d_g_att, float *d_g_x /* may be NULL */, float *d_g_w, float *d_g_b,
+                             float *d_g_q /* may be NULL */, float *d_g_prev /* may be NULL */);
+
+/* ---- training: the GATE product of an attention trunk, xb = x * a (Model_QBD.py:143, :150), over count floats (1 .. 2^31 - 1).
+ *      forward:  y = x * a
+ *      backward: g_a = g_y * x;  g_x = g_y * a, or with d_g_acc (the gradient x already has from its other reader, trunk_M2 or
+ *                trunk_B1) g_x = g_acc + g_y * a: the product rounded, then the sum rounded - torch's mul and add, bit for bit.
+ *      16-byte accesses when every pointer of the call is 16-byte aligned, scalar ones otherwise.  PMP_E_INVALID before any launch
+ *      as above (count out of range, a missing tensor, an output over an input or another output, a misaligned pointer). ---- */
+int pmp_gate_forward_device(pmp_ctx *ctx, int64_t count, const float *d_x, const float *d_a, float *d_y);
+int pmp_gate_backward_device(pmp_ctx *ctx, int64_t count, const float *d_x, const float *d_a, const float *d_g_y,
+                             const float *d_g_acc /* may be NULL */, float *d_g_x, float *d_g_a);
+
 /* ---- teacher-forced MTT inference: the MTT net of (comp, qp) on the blocks with a GIVEN QT map instead of the QT net's output, what
  *      pre_validation predID 1 runs (Net(input_batch, qt_label_batch), Metrics.py:226).  qt_in f32[n][8][8] is read, never written
  *      (for the reference's validation: float(qt8 - 1) with the u8 wrap above).  Everything else is pmp_infer's: the context's datapath,

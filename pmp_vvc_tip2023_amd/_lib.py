@@ -74,6 +74,16 @@ def stem_shape(shape):
     return shape if isinstance(shape, StemShape) else StemShape(*(int(v) for v in shape))
 
 
+class HeadShape(C.Structure):
+    """pmp_head_shape: an MTT net's head, x [n][cin][h][w] -> y [n][cout][h][w] and, with up_y, att [n][1+cout][up_y h][up_y w]."""
+    _fields_ = [("n", C.c_int), ("h", C.c_int), ("w", C.c_int), ("cin", C.c_int), ("cout", C.c_int), ("up_q", C.c_int), ("up_y", C.c_int)]
+
+
+def head_shape(shape):
+    """(n, h, w, cin, cout, up_q, up_y) -> HeadShape (a HeadShape passes through)."""
+    return shape if isinstance(shape, HeadShape) else HeadShape(*(int(v) for v in shape))
+
+
 def pointer_array(ptrs, count):
     """A host array of `count` device pointers (None = NULL) for the C ABI; None stays None."""
     if ptrs is None:
@@ -142,6 +152,10 @@ SIGNATURES = {
     "pmp_trunk_unpack_device": (_I, [_VP, C.POINTER(TrunkShape), _VP, _I, _VP]),
     "pmp_stem_forward_device": (_I, [_VP, C.POINTER(StemShape), _VP, _VP, _VP, _VP]),
     "pmp_stem_backward_device": (_I, [_VP, C.POINTER(StemShape)] + [_VP] * 7),
+    "pmp_head_forward_device": (_I, [_VP, C.POINTER(HeadShape)] + [_VP] * 7),
+    "pmp_head_backward_device": (_I, [_VP, C.POINTER(HeadShape)] + [_VP] * 9),
+    "pmp_gate_forward_device": (_I, [_VP, _I64, _VP, _VP, _VP]),
+    "pmp_gate_backward_device": (_I, [_VP, _I64] + [_VP] * 6),
     "pmp_infer_msbd": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
     "pmp_infer_msbd_device": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
     "pmp_read_depth_dump": (_I, [C.c_char_p, _I, _I, _I, _I, _VP, _VP, _VP, C.POINTER(_I64)]),

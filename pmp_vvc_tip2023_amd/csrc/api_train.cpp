@@ -1,10 +1,11 @@
-// api_train.cpp — a trunk of Model_QBD.ResidualBlocks, forward and backward, for a trainer (include/pmp.h: pmp_trunk_*), its activations
-// blocked between the blocks and between the two directions (trunk_glue.hip), ONE block (pmp_resblock_forward / _backward): a shell
-// around the trunk's block that takes the caller's dense tensors through the blocked layout in the context's workspace arena, and a
-// net's stem (pmp_stem_*, stem_train.hip), dense in and out.  There is
-// one statement of the block, TrainGraph::block_forward / block_backward, and one of what a call must satisfy (train_check.h).  The
-// convolutions are conv_mfma.hip's (the data gradients are ordinary convolutions with mirrored, transposed weights), the weight
-// gradients conv_wgrad.hip's.  Always the exact fp32 MFMA datapath: the Pass says so, whatever pmp_set_precision chose for inference.
+// api_train.cpp — a trunk of Model_QBD.ResidualBlocks, forward and backward, for a trainer (include/pmp.h: pmp_trunk_*), its
+// activations blocked between the blocks and between the two directions (trunk_glue.hip), ONE block (pmp_resblock_forward /
+// _backward): a shell around the trunk's block that takes the caller's dense tensors through the blocked layout in the context's
+// workspace arena, and a net's stem (pmp_stem_*, stem_train.hip), dense in and out, and an MTT net's heads and gate products
+// (pmp_head_*, pmp_gate_*, head_train.hip), dense too.  There is one statement of the block, TrainGraph::block_forward /
+// block_backward, and one of what a call must satisfy (train_check.h).  The convolutions are conv_mfma.hip's (the data gradients are
+// ordinary convolutions with mirrored, transposed weights), the weight gradients conv_wgrad.hip's.  Always the exact fp32 MFMA
+// datapath: the Pass says so, whatever pmp_set_precision chose for inference.
 #include <initializer_list>
 
 #include "pmp_host.h"
@@ -227,6 +228,18 @@ struct TrainGraph {
         release(scratch);
         if (backward && q.g_x && live()) check(launch_stem_dgrad(ps.stream, q), "stem_dgrad");
     }
+
+    // ---- pmp_head_*: dense in and out (head_train.hip); the arena holds the partial sums of g_w and g_b
+    void head(const HeadTrainArgs &q, bool backward)
+    {
+        if (!backward) {
+            if (live()) check(launch_head_forward(ps.stream, q), "head_forward");
+            return;
+        }
+        Tensor part = floats(head_partial_floats(q.N, q.H, q.W, q.cin, q.cout));
+        if (live()) check(launch_head_backward(ps.stream, q, part.p), "head_backward");
+        release(part);
+    }
 };
 
 int run_train(pmp_ctx *c, int n, int h, int w, const std::function<void(TrainGraph &)> &body)
@@ -362,9 +375,82 @@ int stem_entry(pmp_ctx *c, const char *fn, const pmp_stem_shape *s, bool backwar
     return run_train(c, s->n, s->h, s->w, [&](TrainGraph &g) { g.stem(q, backward); });
 }
 
+// pmp_head_forward_device (backward = false) and pmp_head_backward_device
+int head_entry(pmp_ctx *c, const char *fn, const pmp_head_shape *s, bool backward, const HeadTrainArgs &t)
+{
+    CHECK_CTX(c);
+    if (!head_shape_ok(s)) return refuse(c, fn, HEAD_SHAPE_RULE);
+    const HeadSizes z(*s);
+    std::vector<Span> ins = {{t.x, z.x}, {t.w, z.w}}, outs;
+    const char *why;
+    if (!backward) {
+        why = head_att_refused(*s, {t.q, t.att}, nullptr);
+        ins.insert(ins.end(), {{t.b, z.b}, {t.prev, z.y, true}, {t.q, z.q, true}});
+        outs = {{t.y, z.y}, {t.att, z.att, true}};
+    } else {
+        why = head_att_refused(*s, {t.g_att}, t.g_q);
+        ins.insert(ins.end(), {{t.g_y, z.y}, {t.g_att, z.att, true}});
+        outs = {{t.g_x, z.x, true}, {t.g_w, z.w}, {t.g_b, z.b}, {t.g_q, z.q, true}, {t.g_prev, z.y, true}};
+    }
+    if (why || (why = spans_refused(ins, outs, true))) return refuse(c, fn, why);
+    int rc;
+    if ((rc = settle_before_host_call(c))) return rc;
+    HeadTrainArgs q = t;
+    q.N = s->n; q.H = s->h; q.W = s->w; q.cin = s->cin; q.cout = s->cout; q.up_q = s->up_q; q.up_y = s->up_y;
+    return run_train(c, s->n, s->h, s->w, [&](TrainGraph &g) { g.head(q, backward); });
+}
+
+// pmp_gate_forward_device (g_y = null) and pmp_gate_backward_device
+int gate_entry(pmp_ctx *c, const char *fn, int64_t count, const float *x, const float *a, const float *g_y, const float *g_acc, float *o0,
+               float *o1)
+{
+    CHECK_CTX(c);
+    if (!gate_count_ok(count)) return refuse(c, fn, GATE_COUNT_RULE);
+    const size_t bytes = (size_t)count * 4;
+    std::vector<Span> ins = {{x, bytes}, {a, bytes}}, outs = {{o0, bytes}};
+    if (g_y) {
+        ins.insert(ins.end(), {{g_y, bytes}, {g_acc, bytes, true}});
+        outs.push_back({o1, bytes});
+    }
+    if (const char *why = spans_refused(ins, outs, true)) return refuse(c, fn, why);
+    int rc;
+    if ((rc = settle_before_host_call(c))) return rc;
+    const hipError_t e = g_y ? launch_gate_backward(c->stream, (size_t)count, x, a, g_y, g_acc, o0, o1)
+                             : launch_gate_forward(c->stream, (size_t)count, x, a, o0);
+    return e == hipSuccess ? PMP_OK : hip_fail(c, e, "gate");
+}
+
 }  // namespace
 
 extern "C" {
+
+int pmp_head_forward_device(pmp_ctx *c, const pmp_head_shape *s, const float *x, const float *w, const float *b, const float *prev,
+                            const float *q, float *y, float *att)
+{
+    HeadTrainArgs t{};
+    t.x = x; t.w = w; t.b = b; t.prev = prev; t.q = q; t.y = y; t.att = att;
+    return head_entry(c, "pmp_head_forward_device", s, false, t);
+}
+
+int pmp_head_backward_device(pmp_ctx *c, const pmp_head_shape *s, const float *x, const float *w, const float *g_y, const float *g_att,
+                             float *g_x, float *g_w, float *g_b, float *g_q, float *g_prev)
+{
+    HeadTrainArgs t{};
+    t.x = x; t.w = w; t.g_y = g_y; t.g_att = g_att; t.g_x = g_x; t.g_w = g_w; t.g_b = g_b; t.g_q = g_q; t.g_prev = g_prev;
+    return head_entry(c, "pmp_head_backward_device", s, true, t);
+}
+
+int pmp_gate_forward_device(pmp_ctx *c, int64_t count, const float *x, const float *a, float *y)
+{
+    return gate_entry(c, "pmp_gate_forward_device", count, x, a, nullptr, nullptr, y, nullptr);
+}
+
+int pmp_gate_backward_device(pmp_ctx *c, int64_t count, const float *x, const float *a, const float *g_y, const float *g_acc, float *g_x,
+                             float *g_a)
+{
+    if (c && !g_y) return refuse(c, "pmp_gate_backward_device", "null tensor");
+    return gate_entry(c, "pmp_gate_backward_device", count, x, a, g_y, g_acc, g_x, g_a);
+}
 
 int pmp_stem_forward_device(pmp_ctx *c, const pmp_stem_shape *s, const float *x, const float *const w[3], const float *const b[3], float *y)
 {

@@ -274,6 +274,24 @@ hipError_t launch_stem_forward(hipStream_t s, const StemTrainArgs &a, float *pac
 hipError_t launch_stem_wgrad(hipStream_t s, const StemTrainArgs &a, float *part);         // g_w, g_b: two launches, a fixed order
 hipError_t launch_stem_dgrad(hipStream_t s, const StemTrainArgs &a);                      // g_x, every element
 
+// ------------------------------------------------------------------------------------------------ training, a head and the gate (head_train.hip)
+// pmp_head_*'s 3x3 bias convolution with cin 1..16 inputs and cout 1..2 outputs on dense NCHW, its carry and its attention input;
+// the formulas and the orders of summation are include/pmp.h's.  H, W multiples of 8.
+struct HeadTrainArgs {
+    int N, H, W, cin, cout, up_q, up_y;
+    const float *x, *w, *b, *prev, *q;           // forward; x and w backward too
+    float *y, *att;
+    const float *g_y, *g_att;                    // backward
+    float *g_x, *g_w, *g_b, *g_q, *g_prev;       // g_x, g_q, g_prev may be null
+};
+size_t head_partial_floats(int N, int H, int W, int cin, int cout);       // launch_head_backward's scratch, every word written
+hipError_t launch_head_forward(hipStream_t s, const HeadTrainArgs &a);
+hipError_t launch_head_backward(hipStream_t s, const HeadTrainArgs &a, float *part);
+// y = x * a;  g_a = g_y * x, g_x = (g_acc ? g_acc + : ) g_y * a: product and sum each rounded once.  count >= 1
+hipError_t launch_gate_forward(hipStream_t s, size_t count, const float *x, const float *a, float *y);
+hipError_t launch_gate_backward(hipStream_t s, size_t count, const float *x, const float *a, const float *g_y, const float *g_acc, float *g_x,
+                                float *g_a);
+
 // Block cutter (Inference_QBD.py:104-149).
 hipError_t launch_cut_blocks(hipStream_t s, const void *y, const void *u, const void *v, int F, int H, int W,
                              int bitdepth, uint8_t *by, uint8_t *bu, uint8_t *bv);

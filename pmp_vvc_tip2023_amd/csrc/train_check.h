@@ -1,7 +1,7 @@
-// train_check.h — what pmp_resblock_*, pmp_trunk_* and pmp_stem_* (api_train.cpp) accept: the shape rules, a trunk's blocks and its
-// d_saved layout, a stem's sizes, and the rules on a call's tensors.  A single block is checked as the one-block trunk it is.  Pure
-// host code without the HIP runtime, so that it also builds, with a main of its own, for the CPU under a sanitizer
-// (train_check_main.cpp, `make traincheck`).
+// train_check.h — what pmp_resblock_*, pmp_trunk_*, pmp_stem_*, pmp_head_* and pmp_gate_* (api_train.cpp) accept: the shape rules, a
+// trunk's blocks and its d_saved layout, a stem's and a head's sizes, and the rules on a call's tensors.  A single block is checked as
+// the one-block trunk it is.  Pure host code without the HIP runtime, so that it also builds, with a main of its own, for the CPU
+// under a sanitizer (train_check_main.cpp, `make traincheck`).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -142,5 +142,47 @@ __attribute__((noinline)) inline const char *stem_array_refused(const pmp_stem_s
     for (int j = 0; j < (s.split ? 3 : 1); ++j) v.push_back({arr[j], bytes[j]});
     return nullptr;
 }
+
+// ---- a head (pmp_head_*): the shape rule, its sizes, and which of its tensors go with an attention input
+constexpr const char *HEAD_SHAPE_RULE =
+    "null or unsupported shape (n 1..256, h and w multiples of 8 in 8..256, cin 1..16, cout 1 or 2, (up_q, up_y) (0,0), (2,1) or (4,2))";
+
+inline bool head_shape_ok(const pmp_head_shape *s)
+{
+    auto side = [](int v) { return v >= 8 && v <= 256 && !(v & 7); };
+    return s && s->n >= 1 && s->n <= 256 && side(s->h) && side(s->w) && s->cin >= 1 && s->cin <= 16 && (s->cout == 1 || s->cout == 2) &&
+           ((s->up_q == 0 && s->up_y == 0) || (s->up_q == 2 && s->up_y == 1) || (s->up_q == 4 && s->up_y == 2));
+}
+
+// bytes of x and g_x [n][cin][h][w], of y, prev, g_y and g_prev [n][cout][h][w], of w [cout][cin][3][3] and b [cout], and with an
+// attention input of att and g_att [n][1+cout][up_y h][up_y w] and of q and g_q [n][1][up_y h / up_q][up_y w / up_q] (0 without)
+struct HeadSizes {
+    size_t x, y, w, b, att, q;
+    explicit HeadSizes(const pmp_head_shape &s)
+    {
+        const size_t px = (size_t)s.n * s.h * s.w * 4, u = s.up_y;
+        x = px * s.cin;
+        y = px * s.cout;
+        w = (size_t)4 * 9 * s.cout * s.cin;
+        b = (size_t)4 * s.cout;
+        att = px * u * u * (1 + s.cout);
+        q = u ? px * u * u / ((size_t)s.up_q * s.up_q) : 0;
+    }
+};
+
+// The tensors of a head call that exist exactly when the head has an attention input (forward: q, att; backward: g_att), and g_q,
+// which may be asked for only then.  -> why refused, or NULL  (out of line, one copy for both directions)
+__attribute__((noinline)) inline const char *head_att_refused(const pmp_head_shape &s, std::initializer_list<const void *> tied, const void *g_q)
+{
+    for (const void *p : tied)
+        if ((p != nullptr) != (s.up_y != 0)) return "q, att and g_att are passed exactly when up_y != 0";
+    if (g_q && !s.up_y) return "g_q may be asked for only with g_att";
+    return nullptr;
+}
+
+// ---- the gate (pmp_gate_*)
+constexpr const char *GATE_COUNT_RULE = "count must be in 1 .. 2^31 - 1";
+
+inline bool gate_count_ok(int64_t count) { return count >= 1 && count <= INT32_MAX; }
 
 }  // namespace pmp

@@ -1,7 +1,8 @@
 // train_check_main.cpp — train_check.h on the CPU, with a main of its own, for `make traincheck` (-fsanitize=address,undefined): the
 // shapes of the refusal matrices of tests/test_gpu_resblock_grad.py and tests/test_gpu_trunk_grad.py, the weight rule per block, and
-// spans that overlap, are missing or are misaligned, and a stem's shapes, sizes and pointer arrays (tests/test_gpu_stem_grad.py).  No
-// pointer is dereferenced; exit status 0 and "train_check: ok" when all hold.
+// spans that overlap, are missing or are misaligned, a stem's shapes, sizes and pointer arrays (tests/test_gpu_stem_grad.py), and a
+// head's shapes, sizes and the tensors tied to its attention input (tests/test_gpu_head_grad.py).  No pointer is dereferenced; exit
+// status 0 and "train_check: ok" when all hold.
 #include <stdio.h>
 #include <string.h>
 
@@ -131,6 +132,49 @@ int main()
         { const float *u[3] = {at(0), nullptr, at(2)}; expect(says(stem_array_refused(ms, u, m.w, v), "exactly when split") && says(stem_array_refused(qs, u, q.w, v), "exactly when split"), "entries 0 and 2"); }
         expect(v.size() == before, "a refused array appends nothing");
     }
+    // ---- a head: the shapes of the refusal matrix of tests/test_gpu_head_grad.py, the sizes, and the tensors tied to up_y
+    const pmp_head_shape hbad[] = {{0, 16, 16, 8, 2, 0, 0}, {257, 16, 16, 8, 2, 0, 0}, {-1, 16, 16, 8, 2, 0, 0}, {2, 0, 16, 8, 2, 0, 0},
+                                   {2, 4, 16, 8, 2, 0, 0}, {2, 12, 16, 8, 2, 0, 0}, {2, 264, 16, 8, 2, 0, 0}, {2, -8, 16, 8, 2, 0, 0},
+                                   {2, 16, 0, 8, 2, 0, 0}, {2, 16, 20, 8, 2, 0, 0}, {2, 16, 264, 8, 2, 0, 0}, {2, 16, 16, 0, 2, 0, 0},
+                                   {2, 16, 16, 17, 2, 0, 0}, {2, 16, 16, -1, 2, 0, 0}, {2, 16, 16, 8, 0, 0, 0}, {2, 16, 16, 8, 3, 0, 0},
+                                   {2, 16, 16, 8, -1, 0, 0}, {2, 16, 16, 8, 2, 2, 2}, {2, 16, 16, 8, 2, 4, 1}, {2, 16, 16, 8, 2, 0, 1},
+                                   {2, 16, 16, 8, 2, 2, 0}, {2, 16, 16, 8, 2, 1, 1}, {2, 16, 16, 8, 2, 8, 4}, {2, 16, 16, 8, 2, -2, -1}};
+    for (const pmp_head_shape &t : hbad) expect(!head_shape_ok(&t), "a head shape of the refusal matrix is refused");
+    const pmp_head_shape hgood[] = {{1, 8, 8, 8, 1, 0, 0}, {200, 16, 16, 8, 2, 2, 1}, {200, 16, 16, 8, 2, 4, 2}, {200, 16, 16, 8, 2, 0, 0},
+                                    {256, 256, 256, 16, 2, 4, 2}, {3, 24, 16, 5, 1, 2, 1}, {1, 256, 8, 1, 2, 0, 0}};
+    for (const pmp_head_shape &t : hgood) expect(head_shape_ok(&t), "an accepted head shape");
+    expect(!head_shape_ok(nullptr), "a null head shape");
+    {
+        const pmp_head_shape plain{3, 24, 16, 5, 1, 0, 0}, a1{2, 16, 16, 8, 2, 2, 1}, a2{2, 16, 24, 8, 2, 4, 2};
+        const HeadSizes p(plain), u(a1), v(a2);
+        expect(p.x == (size_t)4 * 3 * 5 * 24 * 16 && p.y == (size_t)4 * 3 * 24 * 16 && p.w == (size_t)4 * 45 && p.b == 4 && !p.att && !p.q,
+               "the sizes of a head without an attention input");
+        expect(u.x == (size_t)4 * 2 * 8 * 256 && u.y == (size_t)4 * 2 * 2 * 256 && u.w == (size_t)4 * 144 && u.b == 8 &&
+                   u.att == (size_t)4 * 2 * 3 * 256 && u.q == (size_t)4 * 2 * 64,
+               "the sizes of conv_B1's head");
+        expect(v.att == (size_t)4 * 2 * 3 * 32 * 48 && v.q == (size_t)4 * 2 * 8 * 12, "the sizes of conv_B2's head");
+        expect(!head_att_refused(plain, {nullptr, nullptr}, nullptr) && !head_att_refused(a1, {at(0), at(1)}, nullptr) &&
+                   !head_att_refused(a2, {at(0)}, at(1)) && !head_att_refused(a2, {at(0)}, nullptr),
+               "the accepted patterns");
+        expect(says(head_att_refused(plain, {at(0), nullptr}, nullptr), "exactly when up_y") &&
+                   says(head_att_refused(plain, {nullptr, at(0)}, nullptr), "exactly when up_y") &&
+                   says(head_att_refused(plain, {at(0)}, nullptr), "exactly when up_y"),
+               "q, att or g_att without up_y");
+        expect(says(head_att_refused(a1, {nullptr, at(0)}, nullptr), "exactly when up_y") &&
+                   says(head_att_refused(a1, {at(0), nullptr}, nullptr), "exactly when up_y") && says(head_att_refused(a2, {nullptr}, nullptr), "exactly when up_y"),
+               "up_y without q, att or g_att");
+        expect(says(head_att_refused(plain, {nullptr}, at(0)), "only with g_att"), "g_q without g_att");
+        // a backward call's spans: prev-like optional tensors may be absent, an output over an input is refused
+        std::vector<Span> hi = {{at(0), u.x}, {at(4), u.w}, {at(5), u.y}, {at(6), u.att, true}};
+        std::vector<Span> ho = {{nullptr, u.x, true}, {at(8), u.w}, {at(9), u.b}, {nullptr, u.q, true}, {nullptr, u.y, true}};
+        expect(!spans_refused(hi, ho, true), "a head's backward call without its optional outputs");
+        ho[0].p = at(5);
+        expect(says(spans_refused(hi, ho, true), "overlaps an input"), "g_x over g_y");
+        ho[0].p = nullptr; ho[1].p = nullptr;
+        expect(says(spans_refused(hi, ho, true), "null"), "no g_w");
+    }
+    expect(gate_count_ok(1) && gate_count_ok(INT32_MAX) && !gate_count_ok(0) && !gate_count_ok(-5) && !gate_count_ok((int64_t)INT32_MAX + 1),
+           "the gate's count");
     if (!failures) printf("train_check: ok\n");
     return failures ? 1 : 0;
 }

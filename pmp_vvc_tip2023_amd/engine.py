@@ -486,6 +486,25 @@ class Engine:
         w, g_w, g_b = self._stem_arrays(d_w, d_g_w, d_g_b)
         self._ck(self.lib.pmp_stem_backward_device(self.h, C.byref(s), d_x, d_y, w, d_g_y, d_g_x, g_w, g_b))
 
+    # ------------------------------------------------------------------------------------------ an MTT net's heads and gate products
+    def head_forward_device(self, shape, d_x, d_w, d_b, d_prev, d_q, d_y, d_att):
+        """pmp_head_forward_device: shape = (n, h, w, cin, cout, up_q, up_y); d_prev None = no carry; d_q and d_att exactly when
+        up_y != 0; stream-ordered on the engine's stream, the host does not wait."""
+        self._ck(self.lib.pmp_head_forward_device(self.h, C.byref(_lib.head_shape(shape)), d_x, d_w, d_b, d_prev, d_q, d_y, d_att))
+
+    def head_backward_device(self, shape, d_x, d_w, d_g_y, d_g_att, d_g_x, d_g_w, d_g_b, d_g_q=None, d_g_prev=None):
+        """pmp_head_backward_device: d_g_att exactly when up_y != 0; d_g_x, d_g_q, d_g_prev None = not computed."""
+        self._ck(self.lib.pmp_head_backward_device(self.h, C.byref(_lib.head_shape(shape)), d_x, d_w, d_g_y, d_g_att, d_g_x, d_g_w, d_g_b,
+                                                   d_g_q, d_g_prev))
+
+    def gate_forward_device(self, count, d_x, d_a, d_y):
+        """pmp_gate_forward_device: y = x * a over count floats."""
+        self._ck(self.lib.pmp_gate_forward_device(self.h, int(count), d_x, d_a, d_y))
+
+    def gate_backward_device(self, count, d_x, d_a, d_g_y, d_g_acc, d_g_x, d_g_a):
+        """pmp_gate_backward_device: g_a = g_y * x, g_x = g_y * a, or d_g_acc + g_y * a when d_g_acc is given."""
+        self._ck(self.lib.pmp_gate_backward_device(self.h, int(count), d_x, d_a, d_g_y, d_g_acc, d_g_x, d_g_a))
+
     def infer_msbd(self, comp, qp, qt_in, block_y, block_u=None, block_v=None):
         """Teacher-forced MTT inference (pmp_infer_msbd; Net(input_batch, qt_label_batch), Metrics.py:226): the MTT net of (comp, qp) on
         the blocks with the GIVEN QT map qt_in f32[N,(1,)8,8] -> bt f32[N,3,16,16], dire f32[N,3,16,16]."""
