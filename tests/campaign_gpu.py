@@ -11,8 +11,11 @@ import numpy as np
 import pytest
 
 import conftest  # noqa: F401 - puts tools/ on sys.path
+import gpu_rig
 import trained_like  # tools/trained_like.py: test-weight data (round 6: out of the product package)
 import torch
+
+from oracle import parity as Y
 
 TOL = 1e-3
 N = int(os.environ.get("PMP_CAMPAIGN_BLOCKS", "4096"))
@@ -22,11 +25,8 @@ MTT_WEIGHTS = os.environ.get("PMP_CAMPAIGN_MTT", "synthetic")      # synthetic (
 
 @pytest.fixture(scope="module")
 def eng():
-    from pmp_vvc_tip2023_amd import engine
-    e = engine.Engine(0, allow_synthetic_mtt=True)
-    e.set_precision(PRECISION)
-    yield e
-    e.close()
+    with gpu_rig.engine(PRECISION, synthetic_mtt=True) as e:
+        yield e
 
 
 @pytest.mark.gpu
@@ -36,7 +36,6 @@ def test_full_size_parity(eng, comp, qp):
     from oracle import nets_torch as O, postproc as P
     from pmp_vvc_tip2023_amd import synth, weights as W
     P.build()
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
     luma = comp == "Luma"
     y, u, v = synth.recipe_r_blocks(N, 5000 + qp + (11 if not luma else 0))
     wq, _ = W.load_net_weights(comp + "_Q", qp)
@@ -47,27 +46,23 @@ def test_full_size_parity(eng, comp, qp):
     else:
         wbd, src = W.load_net_weights(comp + "_MSBD", qp, allow_synthetic=True)
     x = O.luma_input(y) if luma else O.chroma_input(y, u, v)
-    oq, obt, od = O.infer_qbd(wq, wbd, x, luma, batch=64)
+    oq, obt, od = Y.oracle_logits(comp, qp, y, u, v, wbd, wq=wq)
     hor, ver, q8, d8, qt, bt, dire = eng.infer_postprocess(comp, qp, y, u, v, want_logits=True)
     assert not eng.saturated() and eng.saturation_reruns() == 0
     err = (float(np.abs(qt - oq).max()), float(np.abs(bt - obt).max()), float(np.abs(dire - od).max()))
     strict = os.environ.get("PMP_CAMPAIGN_REPORT_ONLY", "0") != "1"       # report-only: print every figure below before judging (profiles/)
     assert max(err) < TOL or not strict, "%s QP%d logits off by %s" % (comp, qp, err)
     # (i) post-processing on identical inputs: the device logits through the C oracle - bit-exact, every block
-    dh, dv, dq8, dd8 = P.seq_post_process(qt, bt, dire, comp, 1, 64 * N, 64, None)
-    exact = np.array_equal(hor, dh) and np.array_equal(ver, dv) and np.array_equal(q8, dq8.astype(np.uint8)) and np.array_equal(d8, dd8)
+    exact = Y.flags_equal((hor, ver, q8, d8), Y.oracle_flags(comp, qt, bt, dire))
     assert exact, "%s QP%d: HIP post-processing differs from the oracle's on the same logits" % (comp, qp)
     # (ii) end to end against the oracle's own logits: only near-boundary blocks may differ
-    oh, ov, oq8, od8 = P.seq_post_process(oq, obt, od, comp, 1, 64 * N, 64, None)
+    oh, ov, oq8, od8 = Y.oracle_flags(comp, oq, obt, od)
     margin = max(2e-4, 2 * max(err))
-    pooled = oq.reshape(-1, 4, 2, 4, 2).max(axis=(2, 4))
-    risky = ((np.abs(pooled - np.floor(pooled) - 0.5) < margin).any(axis=(1, 2)) | (np.abs(obt - np.floor(obt) - 0.5) < margin).any(axis=(1, 2, 3)) |
-             (np.abs(np.abs(od) - 0.5) < margin).any(axis=(1, 2, 3)))
-    bad = ((hor != oh).any(axis=(1, 2)) | (ver != ov).any(axis=(1, 2)) | (q8 != oq8.astype(np.uint8)).any(axis=(1, 2)) | (d8 != od8).any(axis=(1, 2, 3)))
+    bad, risky = Y.boundary_audit(oq, obt, od, (hor, ver, q8, d8), (oh, ov, oq8, od8), margin)
     assert not (bad & ~risky).any()
     cells = int((hor != oh).sum() + (ver != ov).sum())
-    worst = int(np.argmax(np.maximum(np.abs(qt - oq).reshape(N, -1).max(1), np.maximum(np.abs(bt - obt).reshape(N, -1).max(1), np.abs(dire - od).reshape(N, -1).max(1)))))
-    per_block = np.maximum(np.abs(qt - oq).reshape(N, -1).max(1), np.maximum(np.abs(bt - obt).reshape(N, -1).max(1), np.abs(dire - od).reshape(N, -1).max(1)))
+    per_block = Y.per_block_error((qt, bt, dire), (oq, obt, od))
+    worst = int(np.argmax(per_block))
     print("\n       [%s] per-block max error: median %.2e, p99 %.2e, p99.9 %.2e, max %.2e at block %d (max |logit| there %.1f, of the batch %.1f)"
           % (PRECISION, float(np.median(per_block)), float(np.quantile(per_block, 0.99)), float(np.quantile(per_block, 0.999)), float(per_block.max()), worst,
              float(max(np.abs(oq[worst]).max(), np.abs(obt[worst]).max(), np.abs(od[worst]).max())), float(max(np.abs(oq).max(), np.abs(obt).max(), np.abs(od).max()))), flush=True)
@@ -87,7 +82,7 @@ def test_full_size_parity(eng, comp, qp):
         for prec in ("fp32", "bf16x6"):
             eng.set_precision(prec)
             q2, b2, d2 = eng.inference_pre_QBD(comp, qp, y, u, v)
-            pb2 = np.maximum(np.abs(q2 - oq).reshape(N, -1).max(1), np.maximum(np.abs(b2 - obt).reshape(N, -1).max(1), np.abs(d2 - od).reshape(N, -1).max(1)))
+            pb2 = Y.per_block_error((q2, b2, d2), (oq, obt, od))
             e2 = max(np.abs(q2[si] - rq).max(), np.abs(b2[si] - rbt).max(), np.abs(d2[si] - rd).max())
             print("       [%s] vs the torch oracle: max %.2e (block %d), p99.9 %.2e, blocks over 1e-3: %d; the same 32 blocks against fp64 accumulation: %.2e"
                   % (prec, float(pb2.max()), int(np.argmax(pb2)), float(np.quantile(pb2, 0.999)), int((pb2 >= TOL).sum()), e2), flush=True)

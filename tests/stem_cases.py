@@ -193,6 +193,18 @@ def flat(r):
     return out
 
 
+def autograd(c):
+    """The stem as float64 torch ops under autograd, the way the nets' forward writes it -> flat results (the CPU tests' yardstick
+    of the restatement, here and in the sweep)."""
+    d = lambda a: torch.from_numpy(np.asarray(a, np.float64).copy())
+    x = d(c["x"]).requires_grad_()
+    ws, bs = [d(w).requires_grad_() for w in c["w"]], [d(b).requires_grad_() for b in c["b"]]
+    y = torch.cat([F.relu(F.conv2d(F.pad(x, pd), w, b)) for w, b, pd in zip(ws, bs, pads(c["shape"]))], 1)
+    (y * d(c["g_y"])).sum().backward()
+    num = lambda v: v.detach().numpy()
+    return flat({"y": num(y), "g_x": num(x.grad), "g_w": [num(w.grad) for w in ws], "g_b": [num(b.grad) for b in bs]})
+
+
 def unified(shape, ws, bs):
     """The one k x k convolution: -> (wu [32, cin, k, k], bu [32]) with the smaller kernels zero-padded (csrc/stem_train.hip)."""
     n, h, w, cin, k, split = shape

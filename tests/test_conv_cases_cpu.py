@@ -2,46 +2,16 @@
 conv_h2 / conv_x6 / conv_mfma kernel symbol in the device code of libpmp_hip.so is in INSTANTIATIONS and every entry is a symbol, so a new
 or removed instantiation fails here until the table says which cases reach it or why none can.  The case table's predicted dispatch
 (expected_kernels, checked against the launches on the GPU by tests/test_gpu_conv_sweep.py) reaches exactly the entries marked reachable."""
-import os
 import re
-import shutil
-import subprocess
-import tempfile
 
-import pytest
-
+from cases_common import LIB, kernel_symbols
 from oracle import conv_cases as CC
 
-ROCM_LLVM = "/opt/rocm/llvm/bin"
-LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pmp_vvc_tip2023_amd", "libpmp_hip.so")
 _SYM = re.compile(r"_ZN3pmp\d+(conv_h2_kernel|conv_x6_kernel|conv_mfma_kernel)I((?:L[ib]\d+E)+)E")
 
 
-def kernel_symbols(lib, pattern=_SYM):
-    """{"conv_h2_kernel<3,3,4,0,1>", ...}: the kernel symbols of the gfx950 code objects bundled in `lib` that match `pattern` (group 1:
-    the kernel's name, group 2: its mangled template arguments, absent for a kernel that is no template)."""
-    objdump, readelf = os.path.join(ROCM_LLVM, "llvm-objdump"), os.path.join(ROCM_LLVM, "llvm-readelf")
-    if not (os.path.exists(objdump) and os.path.exists(readelf)):
-        pytest.skip("ROCm's llvm-objdump / llvm-readelf are not installed")
-    out = set()
-    d = tempfile.mkdtemp()
-    try:
-        copy = os.path.join(d, "lib.so")
-        shutil.copy(lib, copy)                  # --offloading writes the extracted bundles next to its input
-        subprocess.run([objdump, "--offloading", copy], cwd=d, check=True, capture_output=True)
-        for f in os.listdir(d):
-            if "amdgcn" not in f:
-                continue
-            syms = subprocess.run([readelf, "-W", "--syms", os.path.join(d, f)], check=True, capture_output=True, text=True).stdout
-            for m in pattern.finditer(syms):
-                out.add("%s<%s>" % (m.group(1), ",".join(re.findall(r"L[ib](\d+)E", m.group(2)))) if m.group(2) else m.group(1))
-    finally:
-        shutil.rmtree(d)
-    return out
-
-
 def test_instantiation_table_matches_the_library():
-    syms = kernel_symbols(LIB)
+    syms = kernel_symbols(LIB, _SYM)
     assert syms, "no convolution kernel symbols found in " + LIB
     table = set(CC.INSTANTIATIONS)
     assert syms == table, "in the library, not in the table: %s; in the table, not in the library: %s" % (

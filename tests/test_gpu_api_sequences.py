@@ -11,6 +11,7 @@ import trained_like  # tools/trained_like.py: test-weight data (round 6: out of 
 import torch
 
 from conftest import golden
+from oracle.parity import range_stress_weights
 
 pytestmark = pytest.mark.gpu
 
@@ -23,15 +24,7 @@ def _weights(kind):
         return trained_like.msbd_weights("Luma", 22)
     if kind == "trained_k":
         return trained_like.msbd_weights("Luma", 22, trunk_gain=1024.0, gate_gain=64.0)
-    w = dict(synth.synth_msbd_weights("Luma", 22))             # "stress": tests/test_gpu_parity.py's range-stress construction
-    K = np.float32(2.0 ** 17)
-    for k in ("conv_b1_1", "conv_b1_2", "conv_b1_3"):
-        w[k + ".weight"] = (w[k + ".weight"] * K).astype(np.float32)
-        w[k + ".bias"] = (w[k + ".bias"] * K).astype(np.float32)
-    for t in ("trunk_B1.0", "trunk_B2.0", "trunk_B3.0"):
-        for k in (".left.0.weight", ".shortcut.0.weight"):
-            w[t + k] = (w[t + k] / K).astype(np.float32)
-    return w
+    return range_stress_weights()                              # "stress"
 
 
 @pytest.mark.parametrize("seed", [20250, 7, 424242])

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import gpu_rig
 from oracle import conv_cases as CC
 from oracle import layers64 as L
 from oracle import taps as T
@@ -38,15 +39,8 @@ def run_block(e, c, x, w0, w2, wsc, gate):
     return rc, sat.value, buf.value.decode().split()
 
 
-@pytest.fixture(scope="module")
-def eng():
-    from pmp_vvc_tip2023_amd import engine
-    torch.set_num_threads(16)
-    e = engine.Engine(0)
-    e._ck(e.lib.pmp_debug_set_taps(e.h, 1))
-    e._ck(e.lib.pmp_debug_poison_workspace(e.h, 2))     # finite garbage (0x3C bytes) before every pass
-    yield e
-    e.close()
+# taps on; poison 2: finite garbage (0x3C bytes) before every pass
+eng = gpu_rig.engine_fixture(threads=16, setup=lambda e: T.taps_on(e, True), poison=2)
 
 
 def _t(a):

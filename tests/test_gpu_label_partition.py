@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import golden
+import gpu_rig
 import label_partition_cases as LP
 import msbt_cases as K
 
@@ -14,15 +15,7 @@ pytestmark = pytest.mark.gpu
 
 ORDER = ("valid_cf1", "valid_cf2", "noisy", "ties", "ties_cf2", "qtdeep", "bigtree_cf1", "bigtree_cf2", "overbudget")
 
-
-@pytest.fixture(scope="module")
-def eng():
-    import torch
-    from pmp_vvc_tip2023_amd import engine
-    assert torch.cuda.is_available()
-    e = engine.Engine(0)
-    yield e
-    e.close()
+eng = gpu_rig.engine_fixture()
 
 
 @pytest.fixture(scope="module")

@@ -3,14 +3,14 @@ tensor by tensor, poisoned workspaces, and block-order independence of the persi
 
 Taps (pmp_debug_get_tap, include/pmp.h) give each intermediate tensor exactly as its consumer read it; oracle/layers64.py recomputes
 each launch in float64 with the bound its datapath's arithmetic allows (tests/test_layer_bound_cpu.py shows the bound is sharp)."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
+import gpu_rig
 import trained_like  # tools/trained_like.py: test-weight data
 from oracle import layers64 as L, range_cases as RC, taps as T
+from oracle.parity import range_stress_weights
 
 pytestmark = pytest.mark.gpu
 
@@ -53,17 +53,16 @@ def _all_names():
 _MAXR = {}    # (datapath, layer class) -> largest ratio seen in this session
 
 
-@pytest.fixture(scope="module", params=["f16x3", "bf16x6", "fp32"])
-def eng(request):
-    from pmp_vvc_tip2023_amd import engine
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-    e = engine.Engine(0, allow_synthetic_mtt=True)
-    e.set_precision(request.param)
+def _per_layer(e):
     e.set_fusion(False)                  # every tensor of the graph exists (the fused kernels keep some in LDS); fused: test below
     e.set_saturation_policy("ignore")    # taps skip a range-guard re-run: nothing may saturate, checked below
-    _poison(e, 2)                        # finite garbage (0x3C bytes) in every workspace before each pass: an unwritten pad channel shows
-    yield e
-    e.close()
+
+
+@pytest.fixture(scope="module", params=gpu_rig.DATAPATHS)
+def eng(request):
+    # poison 2: finite garbage (0x3C bytes) in every workspace before each pass: an unwritten pad channel shows
+    with gpu_rig.engine(request.param, synthetic_mtt=True, threads=16, setup=_per_layer, poison=2) as e:
+        yield e
     print("\nlayer-local max |gpu - ref64| / bound on %s (c_dp %g):" % (request.param, L.C_DP[request.param]))
     for (dp, cls), r in sorted(_MAXR.items()):
         if dp == request.param:
@@ -372,9 +371,8 @@ def test_taps_are_those_of_the_first_run_not_of_the_rerun():
     """A call whose range flag fired is run again on the fp32 datapath: its logits are the fp32 datapath's, bit for bit, while its taps stay
     those of the f16x3 run that fired - what a context that ignores the flag records, bit for bit.  Set-up of test_f16x3_range_guard
     (tests/test_gpu_parity.py): the range-stress MTT weights with activation scales off."""
-    from test_gpu_parity import _range_stress_weights
     from pmp_vvc_tip2023_amd import engine
-    y, w = _g1_luma4(), _range_stress_weights()
+    y, w = _g1_luma4(), range_stress_weights()
 
     def run(precision, policy):
         e = engine.Engine(0, allow_synthetic_mtt=True)

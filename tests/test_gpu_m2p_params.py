@@ -8,21 +8,15 @@ import numpy as np
 import pytest
 
 from conftest import golden
+import gpu_rig
 import m2p_params_cases as K
+from oracle import parity as Y
 
 pytestmark = pytest.mark.gpu
 
 COMPS = {1: "Luma", 2: "Chroma"}
 
-
-@pytest.fixture(scope="module")
-def eng():
-    import torch
-    from pmp_vvc_tip2023_amd import engine
-    assert torch.cuda.is_available()
-    e = engine.Engine(0, allow_synthetic_mtt=True)
-    yield e
-    e.close()
+eng = gpu_rig.engine_fixture(synthetic_mtt=True)
 
 
 @pytest.fixture
@@ -187,7 +181,6 @@ def test_range_guard_replay_uses_the_set_captured_at_enqueue(g10):
     """A saturated f16x3 inference call is re-run at pmp_synchronize and the post-processing enqueued behind it is replayed
     (include/pmp.h).  The set is changed between enqueue and pmp_synchronize: the replay still runs with the set of its enqueue."""
     import torch
-    from test_gpu_parity import _range_stress_weights
     from pmp_vvc_tip2023_amd import engine
     dev = torch.device("cuda", 0)
     y = np.ascontiguousarray(golden("g1_qt.npz")["block_y"][:6])
@@ -195,7 +188,7 @@ def test_range_guard_replay_uses_the_set_captured_at_enqueue(g10):
     try:
         e2.set_precision("f16x3")
         e2.load("Luma", 22)
-        e2.load_pretrain_model("Luma_MSBD", 22, _range_stress_weights())
+        e2.load_pretrain_model("Luma_MSBD", 22, Y.range_stress_weights())
         e2.set_activation_scales(False)                  # activations leave the fp16 range: the guard fires (test_f16x3_range_guard)
         n = len(y)
         ty = torch.from_numpy(y).to(dev)

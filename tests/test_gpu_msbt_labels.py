@@ -8,21 +8,14 @@ import numpy as np
 import pytest
 
 from conftest import golden
+import gpu_rig
 import msbt_cases as K
 
 pytestmark = pytest.mark.gpu
 
 WORST_BATCH_BOUND_S = 1.0       # a 1024-block launch of worst-case blocks (profiles/msbt_labels.txt)
 
-
-@pytest.fixture(scope="module")
-def eng():
-    import torch
-    from pmp_vvc_tip2023_amd import engine
-    assert torch.cuda.is_available()
-    e = engine.Engine(0)
-    yield e
-    e.close()
+eng = gpu_rig.engine_fixture()
 
 
 @pytest.fixture(scope="module")

@@ -43,7 +43,7 @@ def model_dir(tmp_path_factory):
 
 @pytest.mark.parametrize("bitdepth,width,height,frames,qp", [(8, 200, 136, 2, 22), (10, 136, 72, 3, 37)])
 def test_hook_sequence_through_the_c_abi_only(model_dir, oracle_lib, tmp_path, bitdepth, width, height, frames, qp):
-    from oracle import nets_torch as O
+    from oracle import parity as Y
     from pmp_vvc_tip2023_amd import _lib, engine as E, synth, weights as W
     lib = _lib.load()
     y, u, v = synth.recipe_r_frames(frames, height, width, 900 + qp, bitdepth=bitdepth)   # both sizes drop a right/bottom remainder
@@ -84,9 +84,7 @@ def test_hook_sequence_through_the_c_abi_only(model_dir, oracle_lib, tmp_path, b
                                            _vp(qt), _vp(bt), _vp(dire))
             assert rc == 0, lib.pmp_last_error(ctx)
             wq = W.load_pmpw(pq.decode())[1]; wb = W.load_pmpw(pb.decode())[1]      # the CHECKER's copy of the same files
-            x = O.luma_input(oy) if luma else O.chroma_input(oy, ou, ov)
-            oq, obt, odire = O.infer_qbd(wq, wb, x, luma)
-            err = max(np.abs(qt - oq).max(), np.abs(bt - obt).max(), np.abs(dire - odire).max())
+            err = Y.per_block_error((qt, bt, dire), Y.oracle_logits(comp, qp, oy, ou, ov, wbd=wb, wq=wq)).max()
             assert err < TOL, "%s logits off by %g" % (comp, err)
             # the hook's own call passes NULL for the logits: same flags
             hor2 = np.empty_like(hor); ver2 = np.empty_like(ver); q82 = np.empty_like(q8); d82 = np.empty_like(d8)
@@ -96,7 +94,7 @@ def test_hook_sequence_through_the_c_abi_only(model_dir, oracle_lib, tmp_path, b
             # flags == oracle post-processing of the DEVICE logits, which also writes the oracle's text file
             txt = str(tmp_path / ("%s.txt" % comp))
             oh, ovv, oq8, od8 = oracle_lib.seq_post_process(qt, bt, dire, comp, frames, width, height, txt)
-            assert np.array_equal(hor, oh) and np.array_equal(ver, ovv) and np.array_equal(q8, oq8.astype(np.uint8)) and np.array_equal(d8, od8)
+            assert Y.flags_equal((hor, ver, q8, d8), (oh, ovv, oq8, od8))
 
             # ---- pmp_tile_partition_maps (pmp_hook.cpp:184-187) == the matrices parsePartitionMatrix would build from that file
             th = np.zeros((frames, R, Cc), np.uint8); tv = np.zeros_like(th)

@@ -24,7 +24,8 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import layers64 as L, nets_torch as O, range_cases as R, taps as T
+import gpu_rig
+from oracle import layers64 as L, parity as Y, range_cases as R, taps as T
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
@@ -40,9 +41,7 @@ _taps_on = T.taps_on
 
 
 def _oracle(gw, comp, blocks):
-    y, u, v = blocks
-    x = O.luma_input(y) if comp == "Luma" else O.chroma_input(y, u, v)
-    return O.infer_qbd(gw[0], gw[1], x, comp == "Luma")
+    return Y.oracle_logits(comp, 22, *blocks, wbd=gw[1], wq=gw[0])
 
 
 def _bound_ratio(e, comp, gw, blocks, out, name, exps):
@@ -166,16 +165,9 @@ def run_case(case, comp, blocks, e_over, e_under, gw_over, gw_under, e32, exps=(
 
 @pytest.fixture(scope="module")
 def engines():
-    from pmp_vvc_tip2023_amd import engine
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-    e16 = engine.Engine(0, allow_synthetic_mtt=True)
-    e16.set_precision("f16x3")
-    e16.set_activation_scales(False)           # exponents of zero: stored = true value
-    e32 = engine.Engine(0, allow_synthetic_mtt=True)
-    e32.set_precision("fp32")
-    yield e16, e32
-    e16.close()
-    e32.close()
+    scales_off = lambda e: e.set_activation_scales(False)           # exponents of zero: stored = true value
+    with gpu_rig.engine("f16x3", synthetic_mtt=True, threads=16, setup=scales_off) as e16, gpu_rig.engine("fp32", synthetic_mtt=True) as e32:
+        yield e16, e32
 
 
 @pytest.mark.parametrize("comp", ["Luma", "Chroma"])

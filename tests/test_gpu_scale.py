@@ -15,7 +15,8 @@ import pytest
 
 import conftest  # noqa: F401 - puts tools/ on sys.path
 import trained_like  # tools/trained_like.py: test-weight data (round 6: out of the product package)
-import torch
+
+from oracle import parity as Y
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -52,32 +53,21 @@ def test_full_size_logit_tail_default_datapath_and_guard_fallback(comp, qp, n, m
     on every one of 4096 blocks of a net with trunks at 1e3 and gate products at 1e4, no re-run - and the split flags of those device
     logits are the oracle's, bit for bit.  The fp32 fallback keeps a bound on its maximum again (8.5e-4: 7.6e-4 is the largest value any
     campaign saw on it) beside the quantile trip wire."""
-    from oracle import nets_torch as O
-    from pmp_vvc_tip2023_amd import engine, synth, weights as W
-    luma = comp == "Luma"
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-    y, u, v = synth.recipe_r_blocks(n, 5000 + qp + (0 if luma else 500))
-    wq, _ = W.load_net_weights(comp + "_Q", qp)
-    if mtt == "trained_like":
-        wbd = trained_like.msbd_weights(comp, qp)
-    else:
-        wbd, _ = W.load_net_weights(comp + "_MSBD", qp, allow_synthetic=True)
-    oq, obt, od = O.infer_qbd(wq, wbd, O.luma_input(y) if luma else O.chroma_input(y, u, v), luma, batch=64)
+    from pmp_vvc_tip2023_amd import engine, synth
+    y, u, v = synth.recipe_r_blocks(n, 5000 + qp + (0 if comp == "Luma" else 500))
+    wbd = trained_like.msbd_weights(comp, qp) if mtt == "trained_like" else None      # None: the shipped or synthetic net, on both sides
+    want = Y.oracle_logits(comp, qp, y, u, v, wbd)
     e = engine.Engine(0, allow_synthetic_mtt=True)
     try:
         out = {}
-        e.load(comp, qp, msbd_weights=wbd if mtt == "trained_like" else None)
+        e.load(comp, qp, msbd_weights=wbd)
         for prec in ("f16x3", "fp32"):
             e.set_precision(prec)
             hor, ver, q8, d8, qt, bt, dire = e.infer_postprocess(comp, qp, y, u, v, want_logits=True)
             assert not e.saturated() and e.saturation_reruns() == 0
             if prec == "f16x3":
-                from oracle import postproc as P
-                oh, ov, of, odd = P.seq_post_process(qt, bt, dire, comp, 1, 64 * n, 64, None)
-                assert np.array_equal(hor, oh) and np.array_equal(ver, ov) and np.array_equal(d8, odd) and np.array_equal(q8, of.astype(np.uint8))
-            per_block = np.maximum(np.abs(qt - oq).reshape(n, -1).max(1),
-                                   np.maximum(np.abs(bt - obt).reshape(n, -1).max(1), np.abs(dire - od).reshape(n, -1).max(1)))
-            out[prec] = per_block
+                assert Y.flags_equal((hor, ver, q8, d8), Y.oracle_flags(comp, qt, bt, dire))
+            out[prec] = per_block = Y.per_block_error((qt, bt, dire), want)
             print("\n  %s QP%d (%s MTT weights) %-5s %d blocks: max |logit - oracle| %.2e (margin %.2fx inside 1e-3), per block median %.1e p99 %.1e p99.9 %.1e"
                   % (comp, qp, mtt, prec, n, per_block.max(), TOL / per_block.max(), np.median(per_block), np.quantile(per_block, 0.99),
                      np.quantile(per_block, 0.999)), flush=True)

@@ -22,11 +22,11 @@ pytestmark = pytest.mark.gpu
 
 
 def _inputs():
+    from oracle.parity import range_stress_weights
     from pmp_vvc_tip2023_amd import synth
-    from test_gpu_parity import _range_stress_weights
     y, u, v = synth.recipe_r_blocks(1100, 4711)
     qt, bt, dire = synth.random_partition_batch(600, 99, 1, 0.2)
-    return dict(y=y, u=u, v=v, tl=trained_like.msbd_weights("Luma", 22), stress=_range_stress_weights(),
+    return dict(y=y, u=u, v=v, tl=trained_like.msbd_weights("Luma", 22), stress=range_stress_weights(),
                 benign=synth.synth_msbd_weights("Luma", 22), m2p=(qt, bt, dire))
 
 

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import golden
+import gpu_rig
 import train_loss_cases as K
 import val_cases as V
 
@@ -16,15 +17,7 @@ pytestmark = pytest.mark.gpu
 ORDER = ("qt", "bt", "dire", "qt8", "msbt", "msdire")
 GRADS = ("qt", "bt", "dire")
 
-
-@pytest.fixture(scope="module")
-def eng():
-    import torch
-    from pmp_vvc_tip2023_amd import engine
-    assert torch.cuda.is_available()
-    e = engine.Engine(0)
-    yield e
-    e.close()
+eng = gpu_rig.engine_fixture()
 
 
 @pytest.fixture(scope="module")

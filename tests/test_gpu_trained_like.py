@@ -8,22 +8,17 @@ import numpy as np
 import pytest
 
 import conftest  # noqa: F401 - puts tools/ on sys.path
+import gpu_rig
 import trained_like  # tools/trained_like.py: test-weight data (round 6: out of the product package)
 import torch
 
 from conftest import golden
+from oracle import parity as Y
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
 
-
-@pytest.fixture(scope="module", params=["f16x3", "bf16x6", "fp32"])
-def eng(request):
-    from pmp_vvc_tip2023_amd import engine
-    e = engine.Engine(0, allow_synthetic_mtt=True)
-    e.set_precision(request.param)
-    yield e
-    e.close()
+eng = gpu_rig.engine_fixture(gpu_rig.DATAPATHS, synthetic_mtt=True)
 
 
 def _load_tl(e, comp, qp, **gains):
@@ -56,31 +51,7 @@ def test_trained_like_logits_vs_reference_golden(eng, comp, qp):
     assert eng.saturation_reruns() == 0 and not eng.saturated()
 
 
-_ORACLE = {}
-
-
-def _oracle(comp, qp, n):
-    from oracle import nets_torch as O
-    from pmp_vvc_tip2023_amd import synth, weights as W
-    key = (comp, qp, n)
-    if key not in _ORACLE:
-        import os
-        torch.set_num_threads(min(16, os.cpu_count() or 1))
-        y, u, v = synth.recipe_r_blocks(n, 7000 + qp + (3 if comp == "Chroma" else 0))
-        y[0] = 0; u[0] = 0; v[0] = 0
-        y[1] = 255; u[1] = 255; v[1] = 255
-        rng = np.random.default_rng(qp)
-        y[2] = rng.integers(0, 256, y[2].shape); u[2] = rng.integers(0, 256, u[2].shape); v[2] = rng.integers(0, 256, v[2].shape)   # white noise
-        y[3] = np.where((np.arange(68)[:, None] // 2 + np.arange(68)[None, :] // 2) % 2, 255, 0)                                   # 2-px checkerboard
-        luma = comp == "Luma"
-        wq, _ = W.load_net_weights(comp + "_Q", qp)
-        wbd = trained_like.msbd_weights(comp, qp)
-        x = O.luma_input(y) if luma else O.chroma_input(y, u, v)
-        _ORACLE[key] = (y, u, v) + tuple(O.infer_qbd(wq, wbd, x, luma, batch=64))
-    return _ORACLE[key]
-
-
-# Blocks of _oracle()'s set that an OPT-IN datapath puts outside the plain 1e-3 on the QT logits (Luma_Q's conditioning at low QP leaves
+# Blocks of the fresh set below that an OPT-IN datapath puts outside the plain 1e-3 on the QT logits (Luma_Q's conditioning at low QP leaves
 # bf16x6 no margin): excluded BY INDEX from the QT assertion of that datapath - every other block, and every block on
 # the default datapath and on fp32, gets the plain tolerance.
 _QT_KNOWN = {("bf16x6", "Luma", 22): (), ("fp32", "Luma", 22): ()}
@@ -93,33 +64,28 @@ def test_trained_like_fresh_blocks_vs_oracle(eng, oracle_lib, comp, qp):
     (|logit| <= 8) - only the synthetic extremes beyond it get a relative tolerance; the record of what the guard did rides along.  Then the DEVICE logits of all 320
     blocks - the checkerboard's +-300 and the noise block's +-75 among them - through pmp_postprocess against the oracle's
     post-processing of the same numbers (the kernel's +-100 saturation of the rounded depth sees real net output)."""
-    y, u, v, oq, obt, odire = _oracle(comp, qp, 320)
-    _load_tl(eng, comp, qp)
+    wbd = _load_tl(eng, comp, qp)
+    # computed once, shared by the three datapaths; blocks 0..3: flat, saturated, white noise, 2-px checkerboard
+    y, u, v, oq, obt, odire = Y.fresh_oracle(comp, qp, 320, 7000 + qp + (3 if comp == "Chroma" else 0), wbd=wbd, extremes=qp)
     eng.clear_saturation()
     hor, ver, q8, d8, qt, bt, dire = eng.infer_postprocess(comp, qp, y, u, v, want_logits=True)
-
-    def per_block(pairs):
-        e = np.max([np.abs(a - b).reshape(len(a), -1).max(axis=1) for a, b in pairs], axis=0)
-        m = np.max([np.abs(b).reshape(len(b), -1).max(axis=1) for _, b in pairs], axis=0)
-        return e, m
     # the QT nets (real weights; not this test's subject, but they run first): plain 1e-3 on every block
-    e_q, _ = per_block([(qt, oq)])
+    e_q = Y.per_block_error([qt], [oq])
     known = _QT_KNOWN.get((eng.get_precision(), comp, qp), ())
     over = [int(i) for i in np.flatnonzero(e_q >= TOL) if int(i) not in known]
     assert not over, "QT logits: blocks %s off by %s" % (over, e_q[over])
     assert all(e_q[i] < 1.25 * TOL for i in known)
     # (a) the MTT net ALONE on identical inputs: the oracle fed with the QT logits the HIP path produced
     from oracle import nets_torch as O
-    from pmp_vvc_tip2023_amd import synth
     luma = comp == "Luma"
     x = O.luma_input(y) if luma else O.chroma_input(y, u, v)
     with torch.no_grad():
-        o = O.msbd_forward(trained_like.msbd_weights(comp, qp), x, torch.from_numpy(qt), luma)
+        o = O.msbd_forward(wbd, x, torch.from_numpy(qt), luma)
     abt = np.stack([t[:, 0].numpy() for t in o], 1); adire = np.stack([t[:, 1].numpy() for t in o], 1)
-    e_a, m_a = per_block([(bt, abt), (dire, adire)])
+    e_a, m_a = Y.per_block_error((bt, dire), (abt, adire)), Y.per_block_max((abt, adire))
     # (b) end to end, QT net included: the oracle's own q feeds the oracle's MTT net (the trained-like nets pass an error of q on
     # 0.5..1.7x, synth.py: _TL_Q_STEM)
-    e_b, m_b = per_block([(bt, obt), (dire, odire)])
+    e_b, m_b = Y.per_block_error((bt, dire), (obt, odire)), Y.per_block_max((obt, odire))
     inside = np.maximum(m_a, m_b) <= 8.0
     natural = np.arange(len(y)) >= 4
     n_out = int((natural & ~inside).sum())
@@ -137,13 +103,11 @@ def test_trained_like_fresh_blocks_vs_oracle(eng, oracle_lib, comp, qp):
     # only the synthetic extremes beyond the operating range (2-px checkerboard: +-300, white noise: +-75; the torch oracle itself is 6.6e-4
     # from an fp64 evaluation on the checkerboard block) get the same tolerance RELATIVE to |logit| / 8
     assert (~absolute).sum() <= 4
-    assert (e_a[~absolute] < TOL * np.maximum(1.0, m_a[~absolute] / 8.0)).all() and (e_b[~absolute] < TOL * np.maximum(1.0, m_b[~absolute] / 8.0)).all()
+    assert (e_a < Y.block_tolerance(TOL, m_a))[~absolute].all() and (e_b < Y.block_tolerance(TOL, m_b))[~absolute].all()
     assert max(m_b[:4].max(), m_a[:4].max()) > 50 or not luma    # the extremes ARE extreme (luma): the post-processing below sees them
     assert eng.saturation_reruns() == 0
     # the split flags of the fused call = the reference's post-processing of ITS device logits, the +-300 blocks included
-    with np.errstate(invalid="ignore"):
-        oh, ov, of, od = oracle_lib.seq_post_process(qt, bt, dire, comp, 1, 64 * len(y), 64, None)
-    assert np.array_equal(hor, oh) and np.array_equal(ver, ov) and np.array_equal(d8, od) and np.array_equal(q8, of.astype(np.uint8))
+    assert Y.flags_equal((hor, ver, q8, d8), Y.oracle_flags(comp, qt, bt, dire))
     h2, v2, q82, d82 = eng.post_process(qt, bt, dire, comp)       # and through the host-pointer seam (pmp_postprocess)
     assert np.array_equal(hor, h2) and np.array_equal(ver, v2) and np.array_equal(q8, q82) and np.array_equal(d8, d82)
 

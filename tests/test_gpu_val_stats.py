@@ -11,7 +11,9 @@ import numpy as np
 import pytest
 
 from conftest import golden
+import gpu_rig
 import val_cases as K
+from oracle import parity as Y
 
 pytestmark = pytest.mark.gpu
 
@@ -19,15 +21,7 @@ SUM_TOL = 1e-12
 TOL = 1e-3          # the project's logit tolerance against the oracle
 MODES = (("qbd", "vqbd"), ("q", "pre0"), ("bd", "pre1"))
 
-
-@pytest.fixture(scope="module")
-def eng():
-    import torch
-    from pmp_vvc_tip2023_amd import engine
-    assert torch.cuda.is_available()
-    e = engine.Engine(0, allow_synthetic_mtt=True)
-    yield e
-    e.close()
+eng = gpu_rig.engine_fixture(synthetic_mtt=True)
 
 
 @pytest.fixture(scope="module")
@@ -343,8 +337,8 @@ _DATAPATH_HITS = {}
 
 @pytest.mark.parametrize("comp,qp", [("Luma", 22), ("Chroma", 32)])
 def test_real_nets_stats_vs_restatement_and_oracle(eng, comp, qp):
-    import test_gpu_parity as P
-    y, u, v, oq, obt, odire, _ = P._oracle_512(comp, qp)
+    # the 512 blocks of tests/test_gpu_parity.py: their oracle is computed once for both files
+    y, u, v, oq, obt, odire = Y.fresh_oracle(comp, qp, 512, 1000 + qp + (7 if comp == "Chroma" else 0))
     n = len(y)
     qt8, msbt, msdire = K.labels(n, 4000 + qp)
     lab = dict(qt8=qt8, msbt=msbt, msdire=msdire)
@@ -360,7 +354,7 @@ def test_real_nets_stats_vs_restatement_and_oracle(eng, comp, qp):
             got = eng.val_stats(qp, qt=qt, bt=bt, dire=dire, **lab)
         finally:
             eng.set_precision("f16x3")
-        assert max(np.abs(qt - oq).max(), np.abs(bt - obt).max(), np.abs(dire - odire).max()) < TOL
+        assert Y.per_block_error((qt, bt, dire), (oq, obt, odire)).max() < TOL
         same(got, K.stats(qp, qt=qt.reshape(n, 8, 8), bt=bt, dire=dire, **lab), prec)          # on the device's own logits
         hits[prec] = got[K.COUNTS]
         print("%s QP%d %s: hits %s, oracle %s, near-boundary cells %s" % (comp, qp, prec, got[K.COUNTS].astype(int), ref[K.COUNTS].astype(int),

@@ -15,7 +15,7 @@ from conftest import golden
 import grad_cases as G
 import resblock_cases as K
 import trunk_cases as T
-from test_conv_cases_cpu import LIB, kernel_symbols
+from cases_common import LIB, kernel_symbols
 
 
 @functools.lru_cache(maxsize=None)

@@ -23,16 +23,6 @@ def d(a):
     return torch.from_numpy(np.asarray(a, np.float64).copy())
 
 
-def autograd(c):
-    """The stem as float64 torch ops under autograd, the way the nets' forward writes it."""
-    x = d(c["x"]).requires_grad_()
-    ws, bs = [d(w).requires_grad_() for w in c["w"]], [d(b).requires_grad_() for b in c["b"]]
-    y = torch.cat([F.relu(F.conv2d(F.pad(x, pd), w, b)) for w, b, pd in zip(ws, bs, S.pads(c["shape"]))], 1)
-    (y * d(c["g_y"])).sum().backward()
-    num = lambda v: v.detach().numpy()
-    return S.flat({"y": num(y), "g_x": num(x.grad), "g_w": [num(w.grad) for w in ws], "g_b": [num(b.grad) for b in bs]})
-
-
 @pytest.mark.parametrize("name", list(S.EXACT))
 def test_exact_case_fits_float32_in_any_order(name):
     c = S.make_case(name)
@@ -61,7 +51,7 @@ def test_partition_cases_are_what_they_promise():
 @pytest.mark.parametrize("name", list(S.EXACT))
 def test_restatement_equals_autograd(name):
     c = S.make_case(name)
-    got, want = S.flat(S.restate(c)), autograd(c)
+    got, want = S.flat(S.restate(c)), S.autograd(c)
     assert sorted(got) == sorted(want)
     for key, v in want.items():
         assert got[key].shape == v.shape and np.array_equal(got[key], v), (name, key)
@@ -70,7 +60,7 @@ def test_restatement_equals_autograd(name):
 @pytest.mark.parametrize("name", list(S.FLOAT))
 def test_float_restatement_is_close_to_autograd(name):
     c = S.make_case(*S.FLOAT[name])
-    got, want = S.flat(S.restate(c)), autograd(c)
+    got, want = S.flat(S.restate(c)), S.autograd(c)
     for key, v in want.items():
         assert np.abs(got[key] - v).max() <= 1e-12 * max(1.0, np.abs(v).max()), (name, key)
 

@@ -7,7 +7,6 @@ import pytest
 
 import stem_cases as S
 import stem_sweep_cases as W
-from test_stem_cases_cpu import autograd
 
 UNITS = {}                                         # kernel -> (largest emulated error in units of 2^-24 A, case, output)
 
@@ -29,7 +28,7 @@ def test_exact_case_fits_float32_and_equals_autograd(name):
     y = want["y"]
     assert 0.25 < (y == 0).mean() < 0.75, "the zeros of y exercise the mask"
     assert ((c["g_y"] != 0) & (y == 0)).any() and ((c["g_y"] != 0) & (y > 0)).any()
-    ref = autograd(c)
+    ref = S.autograd(c)
     assert sorted(ref) == sorted(want)
     for key, v in ref.items():
         assert want[key].dtype == np.float32 and want[key].shape == v.shape and np.array_equal(want[key].astype(np.float64), v), (name, key)

@@ -5,10 +5,10 @@ keeps its own cases, bounds and tables."""
 import ctypes as C
 
 import numpy as np
-import pytest
 import torch
 import torch.nn.functional as F
 
+import gpu_rig
 import stem_cases as S
 import trunk_cases as T
 from cases_common import same_bits
@@ -16,18 +16,7 @@ from cases_common import same_bits
 
 def engine_fixture(poison=0):
     """-> a module-scoped fixture: an Engine of the module's own, its workspaces poisoned with pattern `poison` from the start."""
-    @pytest.fixture(scope="module")
-    def eng():
-        from pmp_vvc_tip2023_amd import engine
-        assert torch.cuda.is_available()
-        torch.set_num_threads(16)
-        e = engine.Engine(0)
-        if poison:
-            e._ck(e.lib.pmp_debug_poison_workspace(e.h, poison))
-        yield e
-        e._ck(e.lib.pmp_debug_poison_workspace(e.h, 0))
-        e.close()
-    return eng
+    return gpu_rig.engine_fixture(poison=poison, threads=16)
 
 
 def P(t):

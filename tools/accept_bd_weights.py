@@ -85,29 +85,17 @@ def convert(src, out, log):
     return pairs, problems
 
 
-def special_blocks(y, u, v, seed):
-    """The first four blocks become the extremes tests/test_gpu_trained_like.py uses: flat black, flat white, white noise, a 2-px checkerboard."""
-    rng = np.random.default_rng(seed)
-    y[0] = 0; u[0] = 0; v[0] = 0
-    y[1] = 255; u[1] = 255; v[1] = 255
-    y[2] = rng.integers(0, 256, y[2].shape); u[2] = rng.integers(0, 256, u[2].shape); v[2] = rng.integers(0, 256, v[2].shape)
-    y[3] = np.where((np.arange(68)[:, None] // 2 + np.arange(68)[None, :] // 2) % 2, 255, 0)
-
-
 def verify_pair(eng, out, comp, qp, blocks, log):
-    import torch
-    from oracle import nets_torch as O, postproc as P
+    from oracle import parity as Y
     from pmp_vvc_tip2023_amd import synth, weights as W
     luma = comp == "Luma"
     y, u, v = synth.recipe_r_blocks(blocks, 8800 + qp + (5 if luma else 0))
-    special_blocks(y, u, v, qp)
+    Y.extreme_blocks(y, u, v, qp)              # the first four blocks: flat black, flat white, white noise, a 2-px checkerboard
     wq = W.load_pmpw(os.path.join(out, "%s_Q_%d.pmpw" % (comp, qp)))[1]
     man_b, wb = W.load_pmpw(os.path.join(out, "%s_BD_%d.pmpw" % (comp, qp)))
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
     t0 = time.time()
-    oq, obt, od = O.infer_qbd(wq, wb, O.luma_input(y) if luma else O.chroma_input(y, u, v), luma, batch=64)
-    with np.errstate(invalid="ignore"):
-        o_flags = P.seq_post_process(oq, obt, od, comp, 1, 64 * blocks, 64, None)
+    oq, obt, od = Y.oracle_logits(comp, qp, y, u, v, wb, wq=wq)
+    o_flags = Y.oracle_flags(comp, oq, obt, od)
     t_oracle = time.time() - t0
     res = {"blocks": blocks, "oracle_s": round(t_oracle, 1), "manifest_act_exp": man_b.get("act_exp"), "manifest_act_fp": man_b.get("act_fp"),
            "logit_range": {"qt": [float(oq.min()), float(oq.max())], "bt": [float(obt.min()), float(obt.max())], "dire": [float(od.min()), float(od.max())]},
@@ -118,19 +106,14 @@ def verify_pair(eng, out, comp, qp, blocks, log):
         eng.load(comp, qp)                     # from the .pmpw files of --out (the engine's weight_dir): the manifest's exponents are used
         eng.clear_saturation()
         hor, ver, q8, d8, qt, bt, dire = eng.infer_postprocess(comp, qp, y, u, v, want_logits=True)
-        per_block = np.maximum(np.abs(qt - oq).reshape(blocks, -1).max(1),
-                               np.maximum(np.abs(bt - obt).reshape(blocks, -1).max(1), np.abs(dire - od).reshape(blocks, -1).max(1)))
-        with np.errstate(invalid="ignore"):
-            dh, dv, dq, dd = P.seq_post_process(qt, bt, dire, comp, 1, 64 * blocks, 64, None)
-        exact = bool(np.array_equal(hor, dh) and np.array_equal(ver, dv) and np.array_equal(d8, dd) and
-                     np.array_equal(q8, np.nan_to_num(dq, nan=0.0).astype(np.uint8)))
-        e2e = int(((hor != o_flags[0]).any(axis=(1, 2)) | (ver != o_flags[1]).any(axis=(1, 2)) | (d8 != o_flags[3]).any(axis=(1, 2, 3)) |
-                   (q8 != np.nan_to_num(o_flags[2], nan=0.0).astype(np.uint8)).any(axis=(1, 2))).sum())
+        per_block = Y.per_block_error((qt, bt, dire), (oq, obt, od))
+        exact = Y.flags_equal((hor, ver, q8, d8), Y.oracle_flags(comp, qt, bt, dire), nan_to_zero=True)
+        e2e = int(Y.blocks_differing((hor, ver, q8, d8), o_flags, nan_to_zero=True).sum())
         # north_star's ABSOLUTE 1e-3 on every natural (recipe-R) block; the four synthetic extremes get it relative to |logit| / 8 beyond
         # Map2Partition's operating range (|logit| <= 8: a net that emits +-300 on a checkerboard - float32 itself: the torch oracle is
         # 6.6e-4 from an fp64 evaluation there); how many natural blocks leave the operating range is reported
-        mag = np.maximum(np.abs(oq).reshape(blocks, -1).max(1), np.maximum(np.abs(obt).reshape(blocks, -1).max(1), np.abs(od).reshape(blocks, -1).max(1)))
-        tol_b = TOL * np.where(np.arange(blocks) < 4, np.maximum(1.0, mag / 8.0), 1.0)     # relative only for the four synthetic extremes
+        mag = Y.per_block_max((oq, obt, od))
+        tol_b = Y.block_tolerance(TOL, mag)
         over = per_block >= tol_b
         worst = int(np.argmax(per_block / tol_b))
         r = {"max_abs_err": {"qt": float(np.abs(qt - oq).max()), "bt": float(np.abs(bt - obt).max()), "dire": float(np.abs(dire - od).max())},

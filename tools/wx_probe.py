@@ -8,6 +8,7 @@ import numpy as np, torch
 import abl_lib  # tools/abl_lib.py: the measurement library lives in tools/abl/
 from pmp_vvc_tip2023_amd import _lib, engine, synth, weights as W
 from oracle import nets_torch as O, postproc as P
+from oracle.parity import range_stress_weights
 _lib.load(abl_lib.ensure())
 
 eng = engine.Engine(0, allow_synthetic_mtt=True)
@@ -54,14 +55,8 @@ for comp in ("Luma", "Chroma"):
     assert np.array_equal(hor, oh) and np.array_equal(ver, ov) and np.array_equal(q8, oq8.astype(np.uint8)) and np.array_equal(d8, od8)
     assert not eng.saturated()
     print("%s QP27, 40 blocks, Winograd form: max |logit - oracle| %.2e, split flags bit-exact on the device logits" % (comp, err), flush=True)
-# range guard through the Winograd kernels: trunk activations 2^17 x the usual ones, logits unchanged (tests/test_gpu_parity.py: _range_stress_weights)
-K = 2.0 ** 17
-ws = dict(synth.synth_msbd_weights("Luma", 22))
-for k in ("conv_b1_1", "conv_b1_2", "conv_b1_3"):
-    ws[k + ".weight"] = (ws[k + ".weight"] * K).astype(np.float32); ws[k + ".bias"] = (ws[k + ".bias"] * K).astype(np.float32)
-for t in ("trunk_B1.0", "trunk_B2.0", "trunk_B3.0"):
-    for k in (".left.0.weight", ".shortcut.0.weight"):
-        ws[t + k] = (ws[t + k] / K).astype(np.float32)
+# range guard through the Winograd kernels: trunk activations 2^17 x the usual ones, logits unchanged (oracle/parity.py: range_stress_weights)
+ws = range_stress_weights()
 yb = np.ascontiguousarray(y40[:6])
 wq, _ = W.load_net_weights("Luma_Q", 22)
 oq, obt, od = O.infer_qbd(wq, ws, O.luma_input(yb), True)
