@@ -611,6 +611,63 @@ int pmp_gate_forward_device(pmp_ctx *ctx, int64_t count, const float *d_x, const
 int pmp_gate_backward_device(pmp_ctx *ctx, int64_t count, const float *d_x, const float *d_a, const float *d_g_y,
                              const float *d_g_acc /* may be NULL */, float *d_g_x, float *d_g_a);
 
+/* ---- training: a QT net's TAIL - everything of Luma_Q_Net / Chroma_Q_Net behind its second pool except the head conv_q2
+ *      (Model_QBD.py:83-90, :181-188), forward and backward, as one call (qtail_train.hip, api_train.cpp):
+ *        x5 = resblock_q3(x4)                                     64 -> 32, 3x3, 1x1 shortcut
+ *        x6 = cat[x5, up2(mp2(x5)), up4(mp4(x5)), up8(mp8(x5))]   32 -> 128: x6[:, 0:32] = x5 and, for s = 2, 4, 8,
+ *                                                                 x6[:, 32 log2(s) + c][y][x] = max of x5[c] over the s x s window, aligned
+ *                                                                 to multiples of s, that holds (y, x)
+ *        x7 = resblock_q4(x6)                                     128 -> 32, 3x3, 1x1 shortcut
+ *        x8 = max_pool2d(resblock_q5(x7), 2)                      32 -> 32, identity shortcut, then h/2 x w/2
+ *        x9 = resblock_q6(x8)                                     32 -> 8, 3x3, 1x1 shortcut, on the h/2 x w/2 map
+ *      TENSORS (device pointers, dense NCHW fp32): x4, g_x4 [n][64][h][w]; x9, g_x9 [n][8][h/2][w/2]; d_w and d_g_w are HOST arrays of
+ *      12 device pointers - w0, w2, wsc of q3, q4, q5, q6 in pmp_trunk_*'s layouts ([32][64][3][3], [32][32][3][3], [32][64]; [32][128][3][3],
+ *      [32][32][3][3], [32][128]; [32][32][3][3] twice, NULL; [8][32][3][3], [8][8][3][3], [8][32]) - with the trunk's NULL rule: q5's wsc
+ *      and g_wsc NULL, the other three present.  SHAPES: n 1..256; h and w multiples of 16 in 16..256 (the nets: 16 x 16).
+ *      d_saved: pmp_qtail_saved_bytes(shape) bytes the caller owns, 16-byte aligned, OPAQUE: the blocked x4 and t, out of q3, q4, q5 and
+ *      q6.  x6 and x8 are NOT saved: backward rebuilds them from x5 and q5's out, bit for bit (a maximum has no rounding).  At n = 200,
+ *      16 x 16: 58 982 400 bytes (x6 would add 26 214 400).  Forward writes every byte backward or unpack reads; they only read it.
+ *      pmp_qtail_unpack_device: index 0 = x4; 1, 2 = t, out of q3 (out = x5); 3, 4 = of q4; 5, 6 = of q5 (un-pooled); 7, 8 = of q6
+ *      ([n][8][h/2][w/2]; out = x9), in torch's dense layout.
+ *      ARITHMETIC: always the exact fp32 MFMA datapath.  q3, q4 and q5 are pmp_resblock_forward's block - its formulas, and backward its
+ *      six steps in its order; the forward results of q3 and q5 are pmp_resblock_forward_device's bit for bit.  q4 reads its 128 inputs
+ *      as eight channel groups through the same convolution kernel; its weight gradients g_w0 and g_wsc follow conv_wgrad.hip's
+ *      two-stage order with Ca = 128: eight channel groups, NP = min(ceil(items / 2), 32) partitions of the items (n, 16x16 tile).  Its
+ *      data gradient g6 [n][128][h][w] is two convolutions of 64 outputs each (channels 0..63 and 64..127), every element the chain
+ *      pmp_resblock_backward's g_x has.
+ *      q6: the h/2 x w/2 map lies in the top-left corner of a map of h2 x w2 = the sides rounded up to multiples of 16 whose other
+ *      pixels are +0, and the block runs on that map through the SAME kernels as the other three: a pixel outside the h/2 x w/2
+ *      region enters every convolution as the zero that torch's padding is.  Forward, t and out are multiplied by the region's 0/1
+ *      mask behind their ReLU; backward needs no mask (gu and gt are zero outside the region through `out > 0` and `t > 0`).  Per
+ *      element inside the region the chains are therefore pmp_resblock_*'s chains of an h/2 x w/2 map; the weight gradients are
+ *      reduced over the items (n, 16x16 tile of the h2 x w2 map) with the order above (NP from those items), the added products
+ *      being exact zeros.
+ *      q5's POOL and its backward follow pmp_trunk_*'s rule: the gradient of a 2x2 window goes to its first maximum in the order (0,0),
+ *      (0,1), (1,0), (1,1) where q5's out > 0, recomputed from the saved un-pooled out, no index tensor.
+ *      MULTI-SCALE POOL, BACKWARD.  One element of g_x5 [n][32][h][w], from g6:  g = g6[c], then g = g + r2, g = g + r4, g = g + r8 in
+ *      that order.  r_s = +0 unless (y, x) is the FIRST maximum of x5[c] over its whole s x s window in row-major order (torch's
+ *      max_pool2d rule, `val > maxval` replaces - not the argmax of a hierarchy of 2x2 maxima, which differs on ties); for that pixel
+ *      r_s starts from +0 and adds g6[32 log2(s) + c] over the window in row-major order.  q3's upstream gradient is g where
+ *      x5 > 0, else +0.
+ *      BACKWARD walks q6, the pool, q5, q4, the multi-scale pool, q3.  d_g_x4 may be NULL: q3's data gradient is then not computed
+ *      and nothing is written for it.  Every byte of every requested output is written.  No atomics anywhere: the same bits on every
+ *      run, stream and context.  Behaviour on non-finite values is NOT specified.
+ *      PMP_E_INVALID before any launch, nothing written: a NULL or unsupported shape; a missing tensor or array; a NULL pattern of d_w
+ *      or d_g_w against the rule; an output that overlaps an input or another output (d_saved is an output of forward and an input of
+ *      backward and unpack); a pointer that is not 4-byte aligned (d_saved: 16-byte); an unpack index outside 0..8.
+ *      pmp_qtail_saved_bytes returns PMP_E_INVALID (< 0) for such a shape; it needs no context and no GPU.
+ *      Like pmp_trunk_*_device the calls first SETTLE the context's calls in flight and run stream-ordered on its stream; x6, x8, the
+ *      running gradient and one block's working set live in the activation workspace. ---- */
+typedef struct pmp_qtail_shape {
+    int n, h, w;
+} pmp_qtail_shape;
+int64_t pmp_qtail_saved_bytes(const pmp_qtail_shape *shape);
+int pmp_qtail_forward_device(pmp_ctx *ctx, const pmp_qtail_shape *shape, const float *d_x4, const float *const *d_w, void *d_saved,
+                             float *d_x9);
+int pmp_qtail_backward_device(pmp_ctx *ctx, const pmp_qtail_shape *shape, const void *d_saved, const float *const *d_w,
+                              const float *d_g_x9, float *d_g_x4 /* may be NULL */, float *const *d_g_w);
+int pmp_qtail_unpack_device(pmp_ctx *ctx, const pmp_qtail_shape *shape, const void *d_saved, int index, float *d_dense);
+
 /* ---- teacher-forced MTT inference: the MTT net of (comp, qp) on the blocks with a GIVEN QT map instead of the QT net's output, what
  *      pre_validation predID 1 runs (Net(input_batch, qt_label_batch), Metrics.py:226).  qt_in f32[n][8][8] is read, never written
  *      (for the reference's validation: float(qt8 - 1) with the u8 wrap above).  Everything else is pmp_infer's: the context's datapath,

@@ -84,6 +84,16 @@ def head_shape(shape):
     return shape if isinstance(shape, HeadShape) else HeadShape(*(int(v) for v in shape))
 
 
+class QtailShape(C.Structure):
+    """pmp_qtail_shape: a QT net's tail, x4 [n][64][h][w] -> x9 [n][8][h/2][w/2]."""
+    _fields_ = [("n", C.c_int), ("h", C.c_int), ("w", C.c_int)]
+
+
+def qtail_shape(shape):
+    """(n, h, w) -> QtailShape (a QtailShape passes through)."""
+    return shape if isinstance(shape, QtailShape) else QtailShape(*(int(v) for v in shape))
+
+
 def pointer_array(ptrs, count):
     """A host array of `count` device pointers (None = NULL) for the C ABI; None stays None."""
     if ptrs is None:
@@ -150,6 +160,10 @@ SIGNATURES = {
     "pmp_trunk_forward_device": (_I, [_VP, C.POINTER(TrunkShape), _VP, _VP, _VP, _VP]),
     "pmp_trunk_backward_device": (_I, [_VP, C.POINTER(TrunkShape), _VP, _VP, _VP, _VP, _VP]),
     "pmp_trunk_unpack_device": (_I, [_VP, C.POINTER(TrunkShape), _VP, _I, _VP]),
+    "pmp_qtail_saved_bytes": (_I64, [C.POINTER(QtailShape)]),
+    "pmp_qtail_forward_device": (_I, [_VP, C.POINTER(QtailShape), _VP, _VP, _VP, _VP]),
+    "pmp_qtail_backward_device": (_I, [_VP, C.POINTER(QtailShape), _VP, _VP, _VP, _VP, _VP]),
+    "pmp_qtail_unpack_device": (_I, [_VP, C.POINTER(QtailShape), _VP, _I, _VP]),
     "pmp_stem_forward_device": (_I, [_VP, C.POINTER(StemShape), _VP, _VP, _VP, _VP]),
     "pmp_stem_backward_device": (_I, [_VP, C.POINTER(StemShape)] + [_VP] * 7),
     "pmp_head_forward_device": (_I, [_VP, C.POINTER(HeadShape)] + [_VP] * 7),

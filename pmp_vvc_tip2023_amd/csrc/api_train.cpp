@@ -2,7 +2,8 @@
 // activations blocked between the blocks and between the two directions (trunk_glue.hip), ONE block (pmp_resblock_forward /
 // _backward): a shell around the trunk's block that takes the caller's dense tensors through the blocked layout in the context's
 // workspace arena, and a net's stem (pmp_stem_*, stem_train.hip), dense in and out, and an MTT net's heads and gate products
-// (pmp_head_*, pmp_gate_*, head_train.hip), dense too.  There is one statement of the block, TrainGraph::block_forward /
+// (pmp_head_*, pmp_gate_*, head_train.hip), dense too, and a QT net's tail (pmp_qtail_*, qtail_train.hip): four blocks, one with
+// 128 inputs and one on a map of half the size, and the pools between them.  There is one statement of the block, TrainGraph::block_forward /
 // block_backward, and one of what a call must satisfy (train_check.h).  The convolutions are conv_mfma.hip's (the data gradients are
 // ordinary convolutions with mirrored, transposed weights), the weight gradients conv_wgrad.hip's.  Always the exact fp32 MFMA
 // datapath: the Pass says so, whatever pmp_set_precision chose for inference.
@@ -48,7 +49,17 @@ struct TrunkPtrs {
 
 struct Tensor { float *p; size_t off, bytes; };   // bytes != 0: the arena's, and the call's to reuse;  0: a view of the caller's memory
 
-Tensor view(const TrunkLayout &lay, const void *saved, int i) { return Tensor{(float *)((char *)saved + lay.off[i]), 0, 0}; }
+template <class Layout>
+Tensor view(const Layout &lay, const void *saved, int i) { return Tensor{(float *)((char *)saved + lay.off[i]), 0, 0}; }
+
+struct QtailPtrs {
+    const float *x4, *g_x9;
+    const float *const *w;
+    const char *saved_in;
+    char *saved_out;
+    float *x9, *g_x4;
+    float *const *g_w;
+};
 
 // The graph of one call on a Pass: run_train() runs it twice, measuring (no launches, null pointers) and live.  rc is the call's: behind
 // a failed launch nothing more is launched, and the arena's bookkeeping runs on to the end.
@@ -115,13 +126,14 @@ struct TrainGraph {
 
     // ---- the block, on blocked tensors
     // t = relu(conv0(x)), out = relu(conv2(t) + sc(x))  (Model_QBD.py:40-44): the launches of Graph::rb() on the fp32 datapath
-    void block_forward(const Block &b, const Tensor &x, Tensor &t, Tensor &y)
+    // region: a 0/1 tensor both results are multiplied by behind their ReLU (a QT tail's q6, whose map fills a corner of its tiles)
+    void block_forward(const Block &b, const Tensor &x, Tensor &t, Tensor &y, const Tensor *region = nullptr)
     {
         const bool sc = b.cin != b.cout;
         Tensor w0 = packed(b.w0, b.cout, b.cin, b.k, b.cop(), b.cip(), false), w2 = packed(b.w2, b.cout, b.cout, b.k, b.cop(), b.cop(), false);
         Tensor wsc = sc ? packed(b.wsc, b.cout, b.cin, 1, b.cop(), b.cip(), false) : Tensor{};
-        conv(x, b.cip(), w0, b.k, nullptr, 0, nullptr, nullptr, nullptr, true, t, b.cop());
-        conv(t, b.cop(), w2, b.k, sc ? &x : nullptr, b.cip(), sc ? &wsc : nullptr, sc ? nullptr : &x, nullptr, true, y, b.cop());
+        conv(x, b.cip(), w0, b.k, nullptr, 0, nullptr, nullptr, region, true, t, b.cop());
+        conv(t, b.cop(), w2, b.k, sc ? &x : nullptr, b.cip(), sc ? &wsc : nullptr, sc ? nullptr : &x, region, true, y, b.cop());
         for (Tensor *p : {&w0, &w2, &wsc}) release(*p);
     }
 
@@ -130,7 +142,9 @@ struct TrainGraph {
     // memory (a trunk's d_saved), read only, or the call's own copies in the arena (a single block's).  Own copies end here: t's words
     // become the mask [t > 0] in place, as Graph::rb() decides in_place, and both are released behind their last reader.  That keeps the
     // workspace need of a single block's call where a mask of its own would add an activation to it; nothing else here asks who owns what.
-    void block_backward(const Block &b, Tensor &x, Tensor &t, const Tensor &gu, Tensor *dx)
+    // A block of 128 inputs (a QT tail's q4) hands its data gradient back as two tensors, dx = channels 0..63 and dx_hi = 64..127:
+    // conv_mfma writes at most 64.
+    void block_backward(const Block &b, Tensor &x, Tensor &t, const Tensor &gu, Tensor *dx, Tensor *dx_hi = nullptr)
     {
         const bool sc = b.cin != b.cout;
         wgrad(t, b.cop(), gu, b.cop(), b.k, b.g_w2, b.cout, b.cout);
@@ -145,11 +159,13 @@ struct TrainGraph {
         release(w2t);
         wgrad(x, b.cip(), gt, b.cop(), b.k, b.g_w0, b.cout, b.cin);
         release(x);
-        if (dx) {
-            Tensor w0t = packed(b.w0, b.cout, b.cin, b.k, b.cip(), b.cop(), true);
-            Tensor wsct = sc ? packed(b.wsc, b.cout, b.cin, 1, b.cip(), b.cop(), true) : Tensor{};
-            *dx = act(b.cip());
-            conv(gt, b.cop(), w0t, b.k, sc ? &gu : nullptr, b.cop(), sc ? &wsct : nullptr, sc ? nullptr : &gu, nullptr, false, *dx, b.cip());
+        const int part = b.cip() > 64 ? 64 : b.cip();
+        for (int c0 = 0; dx && c0 < b.cip(); c0 += part) {
+            Tensor w0t = packed(b.w0 + c0 * b.k * b.k, b.cout, b.cin, b.k, part, b.cop(), true);
+            Tensor wsct = sc ? packed(b.wsc + c0, b.cout, b.cin, 1, part, b.cop(), true) : Tensor{};
+            Tensor &d = c0 ? *dx_hi : *dx;
+            d = act(part);
+            conv(gt, b.cop(), w0t, b.k, sc ? &gu : nullptr, b.cop(), sc ? &wsct : nullptr, sc ? nullptr : &gu, nullptr, false, d, part);
             release(w0t);
             release(wsct);
         }
@@ -217,6 +233,74 @@ struct TrainGraph {
             gu = dx;
         }
         if (q.g_x) dense(gu, q.g_x, s.cin);
+        release(gu);
+    }
+
+    // ---- pmp_qtail_*: q3, the multi-scale pool, q4, q5 and its pool, q6 on its own map (qtail_train.hip); d_saved as a trunk's
+    void qstep(int step, const float *a, const float *b, const float *c3, float *out, float *out2, int hh, int ww)
+    {
+        if (live()) check(launch_qtail_step(ps.stream, step, a, b, c3, out, out2, n, hh, ww), "qtail_step");
+    }
+    static Block qtail_block_of(const QtailPtrs &q, int i)
+    {
+        Block b{qtail_block(i), q.w[3 * i], q.w[3 * i + 1], q.w[3 * i + 2], nullptr, nullptr, nullptr};
+        if (q.g_w) { b.g_w0 = q.g_w[3 * i]; b.g_w2 = q.g_w[3 * i + 1]; b.g_wsc = q.g_w[3 * i + 2]; }
+        return b;
+    }
+
+    void qtail_forward(const QtailLayout &lay, const QtailPtrs &q)
+    {
+        const int H = h, W = w;
+        Tensor s[QTAIL_SAVED];
+        for (int i = 0; i < QTAIL_SAVED; ++i) s[i] = view(lay, q.saved_out, i);
+        to_blocked(q.x4, nullptr, 0, 64, s[0]);
+        block_forward(qtail_block_of(q, 0), s[0], s[1], s[2]);
+        Tensor x6 = act(128);
+        qstep(QT_MULTIPOOL, s[2].p, nullptr, nullptr, x6.p, nullptr, H, W);
+        block_forward(qtail_block_of(q, 1), x6, s[3], s[4]);
+        release(x6);
+        block_forward(qtail_block_of(q, 2), s[4], s[5], s[6]);
+        h = lay.h2; w = lay.w2;                                                  // q6's map
+        Tensor x8 = act(32), region = act(16);
+        qstep(QT_POOL_EMBED, s[6].p, nullptr, nullptr, x8.p, region.p, H, W);
+        block_forward(qtail_block_of(q, 3), x8, s[7], s[8], &region);
+        qstep(QT_CROP_DENSE, s[8].p, nullptr, nullptr, q.x9, nullptr, H, W);
+        release(region);
+        release(x8);
+        h = H; w = W;
+    }
+
+    void qtail_backward(const QtailLayout &lay, const QtailPtrs &q)
+    {
+        const int H = h, W = w;
+        Tensor s[QTAIL_SAVED];
+        for (int i = 0; i < QTAIL_SAVED; ++i) s[i] = view(lay, q.saved_in, i);
+        h = lay.h2; w = lay.w2;
+        Tensor gu = act(16), x8 = act(32), dx{}, dx_hi{};
+        qstep(QT_EMBED_GRAD, q.g_x9, s[8].p, nullptr, gu.p, nullptr, H, W);
+        qstep(QT_POOL_EMBED, s[6].p, nullptr, nullptr, x8.p, nullptr, H, W);
+        block_backward(qtail_block_of(q, 3), x8, s[7], gu, &dx);                 // x8 is the call's own: released behind dW0
+        release(gu);
+        h = H; w = W;
+        gu = act(32);
+        qstep(QT_POOL_BACK, dx.p, s[6].p, nullptr, gu.p, nullptr, H, W);
+        release(dx);
+        block_backward(qtail_block_of(q, 2), s[4], s[5], gu, &dx);
+        release(gu);
+        gu = dx;
+        if (live()) check(launch_blocked_relu(ps.stream, 1, gu.p, s[4].p, gu.p, n, 32, H, W), "blocked_relu");
+        Tensor x6 = act(128);
+        qstep(QT_MULTIPOOL, s[2].p, nullptr, nullptr, x6.p, nullptr, H, W);
+        block_backward(qtail_block_of(q, 1), x6, s[3], gu, &dx, &dx_hi);
+        release(gu);
+        gu = act(32);
+        qstep(QT_MULTIPOOL_BACK, dx.p, dx_hi.p, s[2].p, gu.p, nullptr, H, W);
+        release(dx);
+        release(dx_hi);
+        dx = Tensor{};
+        block_backward(qtail_block_of(q, 0), s[0], s[1], gu, q.g_x4 ? &dx : nullptr);
+        if (q.g_x4) dense(dx, q.g_x4, 64);
+        release(dx);
         release(gu);
     }
 
@@ -343,6 +427,33 @@ int trunk_entry(pmp_ctx *c, const char *fn, const pmp_trunk_shape *s, const Trun
     return run_train(c, *s, [&](TrainGraph &g) { dir ? g.trunk_backward(*s, q) : g.trunk_forward(*s, q); });
 }
 
+// pmp_qtail_forward_device (dir 0), _backward_device (1) and _unpack_device (2)
+int qtail_entry(pmp_ctx *c, const char *fn, const pmp_qtail_shape *s, const QtailPtrs &q, int dir, int index = 0, float *dense = nullptr)
+{
+    CHECK_CTX(c);
+    if (!qtail_shape_ok(s)) return refuse(c, fn, QTAIL_SHAPE_RULE);
+    const QtailLayout lay(*s);
+    if (dir == 2 && (index < 0 || index >= QTAIL_SAVED)) return refuse(c, fn, "index out of range (0 .. 8)");
+    const size_t saved = lay.off[QTAIL_SAVED];
+    std::vector<Span> ins, outs;
+    if (dir == 0) { ins = {{q.x4, lay.x4}}; outs = {{q.saved_out, saved, false, 16}, {q.x9, lay.x9}}; }
+    if (dir == 1) { ins = {{q.saved_in, saved, false, 16}, {q.g_x9, lay.x9}}; outs = {{q.g_x4, lay.x4, true}}; }
+    if (dir == 2) { ins = {{q.saved_in, saved, false, 16}}; outs = {{dense, lay.dense_bytes(index)}}; }
+    BlockShape blocks[QTAIL_BLOCKS];
+    for (int i = 0; i < QTAIL_BLOCKS; ++i) blocks[i] = qtail_block(i);
+    const char *why = dir == 2 ? nullptr : weights_refused(blocks, QTAIL_BLOCKS, q.w, q.g_w, dir == 1, ins, outs);
+    if (why || (why = spans_refused(ins, outs, true))) return refuse(c, fn, why);
+    int rc;
+    if ((rc = settle_before_host_call(c))) return rc;
+    if (dir == 2) {
+        const float *src = view(lay, q.saved_in, index).p;
+        const hipError_t e = index < 7 ? launch_blocked_to_dense(c->stream, src, dense, s->n, lay.c[index], pad_channels(lay.c[index]), s->h, s->w)
+                                       : launch_qtail_step(c->stream, QT_CROP_DENSE, src, nullptr, nullptr, dense, nullptr, s->n, s->h, s->w);
+        return e == hipSuccess ? PMP_OK : hip_fail(c, e, "qtail_step");
+    }
+    return run_train(c, s->n, s->h, s->w, [&](TrainGraph &g) { dir ? g.qtail_backward(lay, q) : g.qtail_forward(lay, q); });
+}
+
 // pmp_stem_forward_device (backward = false) and pmp_stem_backward_device
 int stem_entry(pmp_ctx *c, const char *fn, const pmp_stem_shape *s, bool backward, const float *x, const float *y, const float *const *w,
                const float *const *b, const float *g_y, float *y_out, float *g_x, float *const *g_w, float *const *g_b)
@@ -461,6 +572,34 @@ int pmp_stem_backward_device(pmp_ctx *c, const pmp_stem_shape *s, const float *x
                              float *g_x, float *const g_w[3], float *const g_b[3])
 {
     return stem_entry(c, "pmp_stem_backward_device", s, true, x, y, w, nullptr, g_y, nullptr, g_x, g_w, g_b);
+}
+
+int64_t pmp_qtail_saved_bytes(const pmp_qtail_shape *s)
+{
+    if (!qtail_shape_ok(s)) return PMP_E_INVALID;
+    return (int64_t)QtailLayout(*s).off[QTAIL_SAVED];
+}
+
+int pmp_qtail_forward_device(pmp_ctx *c, const pmp_qtail_shape *s, const float *x4, const float *const *w, void *saved, float *x9)
+{
+    QtailPtrs q{};
+    q.x4 = x4; q.w = w; q.saved_out = (char *)saved; q.x9 = x9;
+    return qtail_entry(c, "pmp_qtail_forward_device", s, q, 0);
+}
+
+int pmp_qtail_backward_device(pmp_ctx *c, const pmp_qtail_shape *s, const void *saved, const float *const *w, const float *g_x9, float *g_x4,
+                              float *const *g_w)
+{
+    QtailPtrs q{};
+    q.saved_in = (const char *)saved; q.w = w; q.g_x9 = g_x9; q.g_x4 = g_x4; q.g_w = g_w;
+    return qtail_entry(c, "pmp_qtail_backward_device", s, q, 1);
+}
+
+int pmp_qtail_unpack_device(pmp_ctx *c, const pmp_qtail_shape *s, const void *saved, int index, float *dense)
+{
+    QtailPtrs q{};
+    q.saved_in = (const char *)saved;
+    return qtail_entry(c, "pmp_qtail_unpack_device", s, q, 2, index, dense);
 }
 
 int64_t pmp_trunk_saved_bytes(const pmp_trunk_shape *s)

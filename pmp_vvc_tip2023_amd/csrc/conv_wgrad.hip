@@ -135,7 +135,7 @@ static hipError_t launch_wgrad_k(hipStream_t s, const WgradArgs &a, int NP, int 
 hipError_t launch_wgrad(hipStream_t s, const float *a, const float *g, int N, int H, int W, int Ca, int Cg, int K, float *part,
                         float *dw, int cout, int cin)
 {
-    if (N <= 0 || (H & 15) || (W & 15) || H <= 0 || W <= 0 || (Ca != 16 && Ca != 32 && Ca != 64) || (Cg != 16 && Cg != 32 && Cg != 64) ||
+    if (N <= 0 || (H & 15) || (W & 15) || H <= 0 || W <= 0 || (Ca != 16 && Ca != 32 && Ca != 64 && Ca != 128) || (Cg != 16 && Cg != 32 && Cg != 64) ||
         cout < 1 || cout > Cg || cin < 1 || cin > Ca)
         return hipErrorInvalidValue;
     const int NP = wgrad_np(N, H, W, Ca), CB = Ca >> 4, NCO = Cg >> 4;
@@ -227,7 +227,8 @@ __global__ __launch_bounds__(256) void pack_mfma_kernel(const float *__restrict_
 hipError_t launch_pack_mfma(hipStream_t s, const float *w, float *out, int cout, int cin, int K, int NT, int CB, int flip_t)
 {
     const int o = flip_t ? cin : cout, c = flip_t ? cout : cin;
-    if (cout < 1 || cin < 1 || o > NT * 16 || c > CB * 16 || (K != 1 && K != 3 && K != 5)) return hipErrorInvalidValue;
+    // flip_t with more than 16 NT input channels: the first 16 NT of them (a QT tail's 128-channel gradient is packed in two halves)
+    if (cout < 1 || cin < 1 || (o > NT * 16 && !flip_t) || c > CB * 16 || (K != 1 && K != 3 && K != 5)) return hipErrorInvalidValue;
     const int total = CB * K * K * NT * 256;
     hipLaunchKernelGGL(pack_mfma_kernel, dim3((total + 255) / 256), dim3(256), 0, s, w, out, cout, cin, K * K, NT, CB, flip_t);
     return hipGetLastError();

@@ -232,7 +232,7 @@ __host__ __device__ double train_loss_value(const double T[PMP_LOSS_NTERMS], con
 // ------------------------------------------------------------------------------------------------ training (conv_wgrad.hip)
 // Weight gradient of a stride-1 KxK convolution (K = 1, 3, 5): dw[cout][cin][K][K] (torch's dense layout, real channels only) =
 // sum over (n, y, x) of g[n][co][y][x] * a[n][ci][y + dy - K/2][x + dx - K/2].  a [N][Ca/16][H][W][16] and g [N][Cg/16][H][W][16] are
-// blocked, Ca, Cg = 16, 32 or 64; cin <= Ca, cout <= Cg.  part: scratch of wgrad_partial_floats() floats, every one written.  Two
+// blocked, Ca = 16, 32, 64 or 128, Cg = 16, 32 or 64; cin <= Ca, cout <= Cg.  part: scratch of wgrad_partial_floats() floats, every one written.  Two
 // launches, a fixed order of additions that depends on the shape only, no atomics.
 size_t wgrad_partial_floats(int N, int H, int W, int Ca, int Cg, int K);
 hipError_t launch_wgrad(hipStream_t s, const float *a, const float *g, int N, int H, int W, int Ca, int Cg, int K, float *part,
@@ -242,7 +242,8 @@ hipError_t launch_wgrad(hipStream_t s, const float *a, const float *g, int N, in
 hipError_t launch_dense_to_blocked(hipStream_t s, const float *src, const float *m, int mode, float *dst, int N, int C, int Cp, int H, int W);
 hipError_t launch_blocked_to_dense(hipStream_t s, const float *src, float *dst, int N, int C, int Cp, int H, int W);
 // pack_mfma() on the device, from w [cout][cin][K][K] into [CB][K*K][NT][64][4].  flip_t = 0: as is (16 NT >= cout, 16 CB >= cin);
-// flip_t = 1: taps mirrored, cin and cout swapped - the data gradient's weights (16 NT >= cin, 16 CB >= cout).
+// flip_t = 1: taps mirrored, cin and cout swapped - the data gradient's weights (16 CB >= cout; its first 16 NT output channels where
+// cin is larger: w + 16 NT K K then packs the next ones).
 hipError_t launch_pack_mfma(hipStream_t s, const float *w, float *out, int cout, int cin, int K, int NT, int CB, int flip_t);
 
 // ------------------------------------------------------------------------------------------------ training, blocked in and out (trunk_glue.hip)
@@ -291,6 +292,20 @@ hipError_t launch_head_backward(hipStream_t s, const HeadTrainArgs &a, float *pa
 hipError_t launch_gate_forward(hipStream_t s, size_t count, const float *x, const float *a, float *y);
 hipError_t launch_gate_backward(hipStream_t s, size_t count, const float *x, const float *a, const float *g_y, const float *g_acc, float *g_x,
                                 float *g_a);
+
+// ------------------------------------------------------------------------------------------------ training, a QT net's tail (qtail_train.hip)
+// The steps of pmp_qtail_* between its ResidualBlocks, all on blocked tensors of an H x W map (multiples of 16) and of q6's map
+// H2 x W2 = (H/2, W/2) rounded up to 16, which holds the H/2 x W/2 pixels top-left and +0 elsewhere.  One launcher: step, then
+//   QT_MULTIPOOL       a = x5 [N][2][H][W][16]                              -> out = x6 [N][8][H][W][16]
+//   QT_MULTIPOOL_BACK  a, b = g6's channels 0..63, 64..127 [N][4][H][W][16], c = x5 -> out = q3's upstream gradient [N][2][H][W][16]
+//   QT_POOL_EMBED      a = q5's out [N][2][H][W][16]                        -> out = x8 [N][2][H2][W2][16], out2 (may be null) = the
+//                                                                              region's 0/1 mask [N][1][H2][W2][16]
+//   QT_POOL_BACK       a = q6's data gradient [N][2][H2][W2][16], b = q5's out -> out = q5's upstream gradient [N][2][H][W][16]
+//   QT_EMBED_GRAD      a = g_x9 dense [N][8][H/2][W/2], b = q6's out [N][1][H2][W2][16] -> out = q6's upstream gradient, same shape
+//   QT_CROP_DENSE      a = a tensor of q6's map [N][1][H2][W2][16]          -> out = dense [N][8][H/2][W/2]
+// Every element of every output is written; the arithmetic is include/pmp.h's.
+enum { QT_MULTIPOOL, QT_MULTIPOOL_BACK, QT_POOL_EMBED, QT_POOL_BACK, QT_EMBED_GRAD, QT_CROP_DENSE };
+hipError_t launch_qtail_step(hipStream_t s, int step, const float *a, const float *b, const float *c, float *out, float *out2, int N, int H, int W);
 
 // Block cutter (Inference_QBD.py:104-149).
 hipError_t launch_cut_blocks(hipStream_t s, const void *y, const void *u, const void *v, int F, int H, int W,

@@ -13,7 +13,8 @@
 
 namespace pmp {
 
-inline int pad_channels(int c) { return c <= 16 ? 16 : c <= 32 ? 32 : 64; }      // the channel counts the convolution kernels have
+// the channel counts the convolution kernels have; 128 only as an input: a QT net's resblock_q4 (pmp_qtail_*)
+inline int pad_channels(int c) { return c <= 16 ? 16 : c <= 32 ? 32 : c <= 64 ? 64 : 128; }
 
 constexpr const char *TRAIN_SHAPE_RULE =
     "null or unsupported shape (n 1..256, h and w multiples of 16 in 16..256, channels 1..64, k 3 or 5, 1..8 blocks, pool 0 or 1)";
@@ -64,15 +65,15 @@ inline bool overlaps(const Span &a, const Span &b)
     return a.p && b.p && x < y + b.bytes && y < x + a.bytes;
 }
 
-// The weights of every block of s, w0, w2, wsc per block as in pmp_trunk_*'s d_w and d_g_w (a single block's: three pointers), go IN
+// The weights of the blocks, w0, w2, wsc per block as in pmp_trunk_*'s d_w and d_g_w (a single block's: three pointers), go IN
 // FRONT of the call's other tensors in ins / outs (the gradients only backward).  -> why the call is refused, or NULL
-inline const char *weights_refused(const pmp_trunk_shape &s, const float *const *w, float *const *g_w, bool backward, std::vector<Span> &ins,
-                                   std::vector<Span> &outs)
+inline const char *weights_refused(const BlockShape *blocks, int nblocks, const float *const *w, float *const *g_w, bool backward,
+                                   std::vector<Span> &ins, std::vector<Span> &outs)
 {
     if (!w || (backward && !g_w)) return "null tensor";
     std::vector<Span> wi, wo;
-    for (int i = 0; i < s.nblocks; ++i) {
-        const BlockShape b = block_shape(s, i);
+    for (int i = 0; i < nblocks; ++i) {
+        const BlockShape b = blocks[i];
         const size_t kk = (size_t)b.k * b.k * 4, bytes[3] = {kk * b.cout * b.cin, kk * b.cout * b.cout, (size_t)4 * b.cout * b.cin};
         for (int j = 0; j < 3; ++j) {
             const bool need = j < 2 || b.cin != b.cout;                 // w0, w2 required; wsc and g_wsc exactly when cin != cout
@@ -87,6 +88,15 @@ inline const char *weights_refused(const pmp_trunk_shape &s, const float *const 
     ins.insert(ins.begin(), wi.begin(), wi.end());
     outs.insert(outs.begin(), wo.begin(), wo.end());
     return nullptr;
+}
+
+// ... of every block of the trunk s
+inline const char *weights_refused(const pmp_trunk_shape &s, const float *const *w, float *const *g_w, bool backward, std::vector<Span> &ins,
+                                   std::vector<Span> &outs)
+{
+    BlockShape blocks[PMP_TRUNK_MAX_BLOCKS];
+    for (int i = 0; i < s.nblocks; ++i) blocks[i] = block_shape(s, i);
+    return weights_refused(blocks, s.nblocks, w, g_w, backward, ins, outs);
 }
 
 // Every tensor that is not optional present, no output over an input or another output and, for device pointers, every one aligned.
@@ -179,6 +189,39 @@ __attribute__((noinline)) inline const char *head_att_refused(const pmp_head_sha
     if (g_q && !s.up_y) return "g_q may be asked for only with g_att";
     return nullptr;
 }
+
+// ---- a QT net's tail (pmp_qtail_*): resblock_q3, the multi-scale pool, resblock_q4, resblock_q5 + max_pool2d, resblock_q6
+constexpr const char *QTAIL_SHAPE_RULE = "null or unsupported shape (n 1..256, h and w multiples of 16 in 16..256)";
+
+inline bool qtail_shape_ok(const pmp_qtail_shape *s)
+{
+    auto side = [](int v) { return v >= 16 && v <= 256 && !(v & 15); };
+    return s && s->n >= 1 && s->n <= 256 && side(s->h) && side(s->w);
+}
+
+constexpr int QTAIL_BLOCKS = 4, QTAIL_SAVED = 9;
+inline BlockShape qtail_block(int i) { return BlockShape{i == 0 ? 64 : i == 1 ? 128 : 32, i == 3 ? 8 : 32, 3}; }
+
+// d_saved: blocked x4, then t and out of q3, q4, q5 at h x w, then t and out of q6: its h/2 x w/2 map lies top-left in a map of
+// h2 x w2, the sides rounded up to 16, whose other pixels are zero (the convolution kernels work on 16x16 tiles).  x6 is not saved.
+struct QtailLayout {
+    int h2, w2;
+    int c[QTAIL_SAVED];                          // the real channels of saved tensor 0 .. 8 (pmp_qtail_unpack_device's index)
+    size_t off[QTAIL_SAVED + 1];                 // bytes; off[9] = the size
+    size_t x4, x9;                               // bytes of the dense x4 / g_x4 and x9 / g_x9
+    explicit QtailLayout(const pmp_qtail_shape &s) : h2((s.h / 2 + 15) & ~15), w2((s.w / 2 + 15) & ~15)
+    {
+        const size_t px = (size_t)s.n * s.h * s.w * sizeof(float), px2 = (size_t)s.n * h2 * w2 * sizeof(float);
+        off[0] = 0;
+        for (int i = 0; i < QTAIL_SAVED; ++i) {
+            c[i] = i == 0 ? 64 : i < 7 ? 32 : 8;
+            off[i + 1] = off[i] + (i < 7 ? px : px2) * pad_channels(c[i]);
+        }
+        x4 = px * 64;
+        x9 = px / 4 * 8;
+    }
+    size_t dense_bytes(int i) const { return i < 7 ? x4 / 64 * c[i] : x9; }
+};
 
 // ---- the gate (pmp_gate_*)
 constexpr const char *GATE_COUNT_RULE = "count must be in 1 .. 2^31 - 1";

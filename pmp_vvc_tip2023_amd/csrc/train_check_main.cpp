@@ -173,6 +173,44 @@ int main()
         ho[0].p = nullptr; ho[1].p = nullptr;
         expect(says(spans_refused(hi, ho, true), "null"), "no g_w");
     }
+    // ---- a QT net's tail: the shapes of the refusal matrix of tests/test_gpu_qtail_grad.py, d_saved, and the weight rule of its blocks
+    const pmp_qtail_shape qbad[] = {{0, 16, 16}, {257, 16, 16}, {-1, 16, 16}, {2, 8, 16}, {2, 24, 16}, {2, 272, 16}, {2, -16, 16},
+                                    {2, 16, 0}, {2, 16, 8}, {2, 16, 40}, {2, 16, 272}};
+    for (const pmp_qtail_shape &t : qbad) expect(!qtail_shape_ok(&t), "a tail shape of the refusal matrix is refused");
+    const pmp_qtail_shape qgood[] = {{1, 16, 16}, {200, 16, 16}, {3, 32, 16}, {2, 16, 48}, {256, 256, 256}};
+    for (const pmp_qtail_shape &t : qgood) expect(qtail_shape_ok(&t), "an accepted tail shape");
+    expect(!qtail_shape_ok(nullptr), "a null tail shape");
+    {
+        const QtailLayout nets(pmp_qtail_shape{200, 16, 16}), wide(pmp_qtail_shape{2, 16, 48}), big(pmp_qtail_shape{256, 256, 256});
+        expect(nets.h2 == 16 && nets.w2 == 16 && nets.off[QTAIL_SAVED] == (size_t)58982400 && nets.x4 == (size_t)4 * 200 * 64 * 256 &&
+                   nets.x9 == (size_t)4 * 200 * 8 * 64 && nets.dense_bytes(0) == nets.x4 && nets.dense_bytes(6) == nets.x4 / 2 &&
+                   nets.dense_bytes(8) == nets.x9,
+               "the tail's d_saved at the nets' shape");
+        expect(wide.h2 == 16 && wide.w2 == 32 && wide.off[7] == (size_t)4 * 2 * 16 * 48 * 256 &&
+                   wide.off[9] == wide.off[7] + (size_t)4 * 2 * 16 * 32 * 32 && wide.x9 == (size_t)4 * 2 * 8 * 8 * 24,
+               "q6's map is rounded up to whole tiles");
+        expect(big.h2 == 128 && big.w2 == 128, "a map of whole tiles is not padded");
+        for (int i = 0; i <= QTAIL_SAVED; ++i) expect(!(big.off[i] & 15) && !(wide.off[i] & 15), "the tail's d_saved offsets");
+        expect(big.c[0] == 64 && big.c[1] == 32 && big.c[6] == 32 && big.c[7] == 8 && big.c[8] == 8, "the tail's saved channels");
+        BlockShape qb[QTAIL_BLOCKS];
+        for (int i = 0; i < QTAIL_BLOCKS; ++i) qb[i] = qtail_block(i);
+        expect(qb[0].cin == 64 && qb[1].cin == 128 && qb[1].cip() == 128 && qb[2].cin == 32 && qb[2].cout == 32 && qb[3].cout == 8 &&
+                   qb[3].cop() == 16 && qb[1].k == 3,
+               "the tail's blocks");
+        const float *qw[12];
+        float *qg[12];
+        for (int j = 0; j < 12; ++j) { qw[j] = j == 8 ? nullptr : at(0); qg[j] = j == 8 ? nullptr : at(1); }
+        std::vector<Span> qi, qo;
+        expect(!weights_refused(qb, QTAIL_BLOCKS, qw, qg, true, qi, qo) && qi.size() == 12 && qo.size() == 12 &&
+                   qi[3].bytes == (size_t)4 * 9 * 32 * 128 && qi[5].bytes == (size_t)4 * 32 * 128 && qi[11].bytes == (size_t)4 * 8 * 32,
+               "the tail's weights, with their sizes");
+        { const float *v[12]; memcpy(v, qw, sizeof v); v[8] = at(2); expect(says(weights_refused(qb, 4, v, qg, true, qi, qo), "shortcut"), "q5 with a wsc"); }
+        { const float *v[12]; memcpy(v, qw, sizeof v); v[5] = nullptr; expect(says(weights_refused(qb, 4, v, qg, true, qi, qo), "shortcut"), "q4 without its wsc"); }
+        { float *v[12]; memcpy(v, qg, sizeof v); v[8] = at(2); expect(says(weights_refused(qb, 4, qw, v, true, qi, qo), "NULL exactly"), "a g_wsc for q5"); }
+        { float *v[12]; memcpy(v, qg, sizeof v); v[3] = nullptr; expect(says(weights_refused(qb, 4, qw, v, true, qi, qo), "NULL exactly"), "no g_w0 for q4"); }
+        expect(says(weights_refused(qb, 4, nullptr, qg, true, qi, qo), "null") && says(weights_refused(qb, 4, qw, nullptr, true, qi, qo), "null"),
+               "the tail without a weight array");
+    }
     expect(gate_count_ok(1) && gate_count_ok(INT32_MAX) && !gate_count_ok(0) && !gate_count_ok(-5) && !gate_count_ok((int64_t)INT32_MAX + 1),
            "the gate's count");
     if (!failures) printf("train_check: ok\n");

@@ -463,6 +463,30 @@ class Engine:
         s = _lib.trunk_shape(shape)
         self._ck(self.lib.pmp_trunk_unpack_device(self.h, C.byref(s), d_saved, int(index), d_dense))
 
+    # ------------------------------------------------------------------------------------------ a QT net's tail: resblock_q3 .. q6
+    @staticmethod
+    def qtail_saved_bytes(shape):
+        """pmp_qtail_saved_bytes: the size of the saved-activation buffer of shape = (n, h, w), the map of x4."""
+        size = _lib.load().pmp_qtail_saved_bytes(C.byref(_lib.qtail_shape(shape)))
+        if size < 0:                                   # no context, so no pmp_last_error
+            raise _lib.PmpError(int(size), "pmp_qtail_saved_bytes: unsupported shape %s" % (tuple(shape),))
+        return size
+
+    def qtail_forward_device(self, shape, d_x4, d_w, d_saved, d_x9):
+        """pmp_qtail_forward_device: d_w = 12 device pointers, w0, w2, wsc of q3, q4, q5 (wsc None), q6; d_saved
+        qtail_saved_bytes(shape) bytes, 16-byte aligned; stream-ordered on the engine's stream, the host does not wait."""
+        self._ck(self.lib.pmp_qtail_forward_device(self.h, C.byref(_lib.qtail_shape(shape)), d_x4, _lib.pointer_array(d_w, 12), d_saved, d_x9))
+
+    def qtail_backward_device(self, shape, d_saved, d_w, d_g_x9, d_g_x4, d_g_w):
+        """pmp_qtail_backward_device: d_g_x4 None = not computed; d_g_w None exactly where d_w is."""
+        self._ck(self.lib.pmp_qtail_backward_device(self.h, C.byref(_lib.qtail_shape(shape)), d_saved, _lib.pointer_array(d_w, 12), d_g_x9,
+                                                    d_g_x4, _lib.pointer_array(d_g_w, 12)))
+
+    def qtail_unpack_device(self, shape, d_saved, index, d_dense):
+        """pmp_qtail_unpack_device: saved tensor `index` (0: x4; 1, 2: t, out of q3; 3, 4: q4; 5, 6: q5, un-pooled; 7, 8: q6 at half
+        resolution) -> torch's dense layout."""
+        self._ck(self.lib.pmp_qtail_unpack_device(self.h, C.byref(_lib.qtail_shape(shape)), d_saved, int(index), d_dense))
+
     # ------------------------------------------------------------------------------------------ a net's stem, forward and backward
     @staticmethod
     def _stem_arrays(*arrays):
