@@ -4,9 +4,11 @@
 // workspace arena, and a net's stem (pmp_stem_*, stem_train.hip), dense in and out, and an MTT net's heads and gate products
 // (pmp_head_*, pmp_gate_*, head_train.hip), dense too, and a QT net's tail (pmp_qtail_*, qtail_train.hip): four blocks, one with
 // 128 inputs and one on a map of half the size, and the pools between them.  There is one statement of the block, TrainGraph::block_forward /
-// block_backward, and one of what a call must satisfy (train_check.h).  The convolutions are conv_mfma.hip's (the data gradients are
-// ordinary convolutions with mirrored, transposed weights), the weight gradients conv_wgrad.hip's.  Always the exact fp32 MFMA
-// datapath: the Pass says so, whatever pmp_set_precision chose for inference.
+// block_backward, one of a chain of blocks with a d_saved (Chain, ChainPtrs of train_check.h, chain_entry here: trunk and tail differ in
+// layout, blocks and bodies), one of what a call must satisfy (train_check.h's *_refused: no memory is read, so they also run on the CPU),
+// one of what an entry does before it runs (admit).  The convolutions are conv_mfma.hip's (the data gradients are ordinary convolutions
+// with mirrored, transposed weights), the weight gradients conv_wgrad.hip's.  Always the exact fp32 MFMA datapath: the Pass says so,
+// whatever pmp_set_precision chose for inference.
 #include <initializer_list>
 
 #include "pmp_host.h"
@@ -21,45 +23,17 @@ struct Block : BlockShape {            // a block and its weights; the gradients
     float *g_w0, *g_w2, *g_wsc;
 };
 
-// block i of a trunk whose weights are d_w / d_g_w of pmp_trunk_*: w0, w2, wsc per block
-Block block_of(const pmp_trunk_shape &s, const float *const *w, float *const *g_w, int i)
+// block i, of shape s, of a chain whose weights are d_w / d_g_w of pmp_trunk_* and pmp_qtail_*: w0, w2, wsc per block
+Block block_of(const BlockShape &s, const float *const *w, float *const *g_w, int i)
 {
-    Block b{block_shape(s, i), w[3 * i], w[3 * i + 1], w[3 * i + 2], nullptr, nullptr, nullptr};
+    Block b{s, w[3 * i], w[3 * i + 1], w[3 * i + 2], nullptr, nullptr, nullptr};
     if (g_w) { b.g_w0 = g_w[3 * i]; b.g_w2 = g_w[3 * i + 1]; b.g_wsc = g_w[3 * i + 2]; }
     return b;
 }
 
-// The tensors of a pmp_resblock_* call, in the order of c->d_rb.  in: w0, w2, wsc, x and, backward, t, out, g_out;  out: t, out
-// (forward) or g_w0, g_w2, g_wsc, g_x (backward): the weights in front, as a one-block trunk's d_w and d_g_w
-struct RbCall {
-    bool backward;
-    const float *in[7];
-    float *out[4];
-};
-enum { X = 3, T, OUT, G_OUT, T_O = 0, OUT_O, G_X = 3 };
-
-struct TrunkPtrs {
-    const float *x, *g_y;
-    const float *const *w;
-    const char *saved_in;
-    char *saved_out;
-    float *y, *g_x;
-    float *const *g_w;
-};
-
 struct Tensor { float *p; size_t off, bytes; };   // bytes != 0: the arena's, and the call's to reuse;  0: a view of the caller's memory
 
-template <class Layout>
-Tensor view(const Layout &lay, const void *saved, int i) { return Tensor{(float *)((char *)saved + lay.off[i]), 0, 0}; }
-
-struct QtailPtrs {
-    const float *x4, *g_x9;
-    const float *const *w;
-    const char *saved_in;
-    char *saved_out;
-    float *x9, *g_x4;
-    float *const *g_w;
-};
+Tensor view(const SavedLayout &lay, const void *saved, int i) { return Tensor{(float *)((char *)saved + lay.off[i]), 0, 0}; }
 
 // The graph of one call on a Pass: run_train() runs it twice, measuring (no launches, null pointers) and live.  rc is the call's: behind
 // a failed launch nothing more is launched, and the arena's bookkeeping runs on to the end.
@@ -173,13 +147,13 @@ struct TrainGraph {
     }
 
     // ---- pmp_resblock_*: dense -> blocked, the block, blocked -> dense
-    void resblock_forward(const pmp_trunk_shape &s, const RbCall &q)
+    void resblock_forward(const BlockShape &s, const RbCall &q)
     {
         const Block b = block_of(s, q.in, nullptr, 0);
-        Tensor x = blocked(q.in[X], nullptr, 0, b.cin), t = act(b.cop()), y = act(b.cop());
+        Tensor x = blocked(q.in[q.X], nullptr, 0, b.cin), t = act(b.cop()), y = act(b.cop());
         block_forward(b, x, t, y);
-        dense(t, q.out[T_O], b.cout);
-        dense(y, q.out[OUT_O], b.cout);
+        dense(t, q.out[q.T_O], b.cout);
+        dense(y, q.out[q.OUT_O], b.cout);
         for (Tensor *p : {&x, &t, &y}) release(*p);
     }
 
@@ -187,52 +161,52 @@ struct TrainGraph {
     // peak is then gu, x, t and gt with the packed w2 - at a trainer's sizes, to the byte, what the call needed when it converted x
     // only behind dW2 and kept a mask of its own (test_workspace_need_of_block_calls, profiles/train_workspace.txt).  With t in front
     // of x small shapes, where partial sums and packed weights dominate, need up to a fifth more.
-    void resblock_backward(const pmp_trunk_shape &s, const RbCall &q)
+    void resblock_backward(const BlockShape &s, const RbCall &q)
     {
         const Block b = block_of(s, q.in, q.out, 0);
-        Tensor gu = blocked(q.in[G_OUT], q.in[OUT], 1, b.cout);                  // g where out > 0
-        Tensor x = blocked(q.in[X], nullptr, 0, b.cin), t = blocked(q.in[T], nullptr, 0, b.cout), dx{};
-        block_backward(b, x, t, gu, q.out[G_X] ? &dx : nullptr);
-        if (q.out[G_X]) dense(dx, q.out[G_X], b.cin);
+        Tensor gu = blocked(q.in[q.G_OUT], q.in[q.OUT], 1, b.cout);              // g where out > 0
+        Tensor x = blocked(q.in[q.X], nullptr, 0, b.cin), t = blocked(q.in[q.T], nullptr, 0, b.cout), dx{};
+        block_backward(b, x, t, gu, q.out[q.G_X] ? &dx : nullptr);
+        if (q.out[q.G_X]) dense(dx, q.out[q.G_X], b.cin);
         release(dx);
         release(gu);
     }
 
     // ---- pmp_trunk_*: a chain of blocks whose activations stay blocked, in the caller's d_saved between forward and backward
-    void trunk_forward(const pmp_trunk_shape &s, const TrunkPtrs &q)
+    void trunk_forward(const Chain &ch, const ChainPtrs &q)
     {
-        const TrunkLayout lay(s);
-        const int clast = s.cout[s.nblocks - 1];
-        Tensor x = view(lay, q.saved_out, 0);
-        to_blocked(q.x, nullptr, 0, s.cin, x);
-        for (int i = 0; i < s.nblocks; ++i) {
-            Tensor t = view(lay, q.saved_out, 2 * i + 1), y = view(lay, q.saved_out, 2 * i + 2);
-            block_forward(block_of(s, q.w, nullptr, i), x, t, y);
+        const SavedLayout &lay = ch.lay;
+        const int clast = lay.c[lay.nt - 1];
+        Tensor x = view(lay, q.saved, 0);
+        to_blocked(q.x, nullptr, 0, lay.c[0], x);
+        for (int i = 0; i < ch.nblocks; ++i) {
+            Tensor t = view(lay, q.saved, 2 * i + 1), y = view(lay, q.saved, 2 * i + 2);
+            block_forward(block_of(ch.blocks[i], q.w, nullptr, i), x, t, y);
             x = y;
         }
-        if (!s.pool) dense(x, q.y, clast);
+        if (!ch.pool) dense(x, q.y, clast);
         else if (live()) check(launch_pool_to_dense(ps.stream, x.p, q.y, n, clast, pad_channels(clast), h, w), "pool_to_dense");
     }
 
-    void trunk_backward(const pmp_trunk_shape &s, const TrunkPtrs &q)
+    void trunk_backward(const Chain &ch, const ChainPtrs &q)
     {
-        const TrunkLayout lay(s);
-        const int L = s.nblocks, clast = s.cout[L - 1];
+        const SavedLayout &lay = ch.lay;
+        const int L = ch.nblocks, clast = lay.c[2 * L];
         // the running gradient, g_out of block i behind its ReLU: the pool's backward and the last ReLU's in one pass over the dense g_y
         Tensor gu = act(pad_channels(clast));
         if (live())
-            check(launch_grad_to_blocked(ps.stream, s.pool, q.g_y, view(lay, q.saved_in, 2 * L).p, gu.p, n, clast, pad_channels(clast), h, w),
+            check(launch_grad_to_blocked(ps.stream, ch.pool, q.g_y, view(lay, q.saved, 2 * L).p, gu.p, n, clast, pad_channels(clast), h, w),
                   "grad_to_blocked");
         for (int i = L - 1; i >= 0; --i) {
-            const Block b = block_of(s, q.w, q.g_w, i);
-            Tensor x = view(lay, q.saved_in, 2 * i), t = view(lay, q.saved_in, 2 * i + 1), dx{};
+            const Block b = block_of(ch.blocks[i], q.w, q.g_w, i);
+            Tensor x = view(lay, q.saved, 2 * i), t = view(lay, q.saved, 2 * i + 1), dx{};
             if (i < L - 1 && live())             // gu holds block i + 1's g_x: this block's g_out, masked in place
-                check(launch_blocked_relu(ps.stream, 1, gu.p, view(lay, q.saved_in, 2 * i + 2).p, gu.p, n, b.cop(), h, w), "blocked_relu");
+                check(launch_blocked_relu(ps.stream, 1, gu.p, view(lay, q.saved, 2 * i + 2).p, gu.p, n, b.cop(), h, w), "blocked_relu");
             block_backward(b, x, t, gu, i > 0 || q.g_x ? &dx : nullptr);
             release(gu);
             gu = dx;
         }
-        if (q.g_x) dense(gu, q.g_x, s.cin);
+        if (q.g_x) dense(gu, q.g_x, lay.c[0]);
         release(gu);
     }
 
@@ -241,65 +215,60 @@ struct TrainGraph {
     {
         if (live()) check(launch_qtail_step(ps.stream, step, a, b, c3, out, out2, n, hh, ww), "qtail_step");
     }
-    static Block qtail_block_of(const QtailPtrs &q, int i)
+    void qtail_forward(const Chain &ch, const ChainPtrs &q)
     {
-        Block b{qtail_block(i), q.w[3 * i], q.w[3 * i + 1], q.w[3 * i + 2], nullptr, nullptr, nullptr};
-        if (q.g_w) { b.g_w0 = q.g_w[3 * i]; b.g_w2 = q.g_w[3 * i + 1]; b.g_wsc = q.g_w[3 * i + 2]; }
-        return b;
-    }
-
-    void qtail_forward(const QtailLayout &lay, const QtailPtrs &q)
-    {
+        const SavedLayout &lay = ch.lay;
         const int H = h, W = w;
         Tensor s[QTAIL_SAVED];
-        for (int i = 0; i < QTAIL_SAVED; ++i) s[i] = view(lay, q.saved_out, i);
-        to_blocked(q.x4, nullptr, 0, 64, s[0]);
-        block_forward(qtail_block_of(q, 0), s[0], s[1], s[2]);
+        for (int i = 0; i < QTAIL_SAVED; ++i) s[i] = view(lay, q.saved, i);
+        to_blocked(q.x, nullptr, 0, 64, s[0]);
+        block_forward(block_of(ch.blocks[0], q.w, q.g_w, 0), s[0], s[1], s[2]);
         Tensor x6 = act(128);
         qstep(QT_MULTIPOOL, s[2].p, nullptr, nullptr, x6.p, nullptr, H, W);
-        block_forward(qtail_block_of(q, 1), x6, s[3], s[4]);
+        block_forward(block_of(ch.blocks[1], q.w, q.g_w, 1), x6, s[3], s[4]);
         release(x6);
-        block_forward(qtail_block_of(q, 2), s[4], s[5], s[6]);
+        block_forward(block_of(ch.blocks[2], q.w, q.g_w, 2), s[4], s[5], s[6]);
         h = lay.h2; w = lay.w2;                                                  // q6's map
         Tensor x8 = act(32), region = act(16);
         qstep(QT_POOL_EMBED, s[6].p, nullptr, nullptr, x8.p, region.p, H, W);
-        block_forward(qtail_block_of(q, 3), x8, s[7], s[8], &region);
-        qstep(QT_CROP_DENSE, s[8].p, nullptr, nullptr, q.x9, nullptr, H, W);
+        block_forward(block_of(ch.blocks[3], q.w, q.g_w, 3), x8, s[7], s[8], &region);
+        qstep(QT_CROP_DENSE, s[8].p, nullptr, nullptr, q.y, nullptr, H, W);
         release(region);
         release(x8);
         h = H; w = W;
     }
 
-    void qtail_backward(const QtailLayout &lay, const QtailPtrs &q)
+    void qtail_backward(const Chain &ch, const ChainPtrs &q)
     {
+        const SavedLayout &lay = ch.lay;
         const int H = h, W = w;
         Tensor s[QTAIL_SAVED];
-        for (int i = 0; i < QTAIL_SAVED; ++i) s[i] = view(lay, q.saved_in, i);
+        for (int i = 0; i < QTAIL_SAVED; ++i) s[i] = view(lay, q.saved, i);
         h = lay.h2; w = lay.w2;
         Tensor gu = act(16), x8 = act(32), dx{}, dx_hi{};
-        qstep(QT_EMBED_GRAD, q.g_x9, s[8].p, nullptr, gu.p, nullptr, H, W);
+        qstep(QT_EMBED_GRAD, q.g_y, s[8].p, nullptr, gu.p, nullptr, H, W);
         qstep(QT_POOL_EMBED, s[6].p, nullptr, nullptr, x8.p, nullptr, H, W);
-        block_backward(qtail_block_of(q, 3), x8, s[7], gu, &dx);                 // x8 is the call's own: released behind dW0
+        block_backward(block_of(ch.blocks[3], q.w, q.g_w, 3), x8, s[7], gu, &dx);                 // x8 is the call's own: released behind dW0
         release(gu);
         h = H; w = W;
         gu = act(32);
         qstep(QT_POOL_BACK, dx.p, s[6].p, nullptr, gu.p, nullptr, H, W);
         release(dx);
-        block_backward(qtail_block_of(q, 2), s[4], s[5], gu, &dx);
+        block_backward(block_of(ch.blocks[2], q.w, q.g_w, 2), s[4], s[5], gu, &dx);
         release(gu);
         gu = dx;
         if (live()) check(launch_blocked_relu(ps.stream, 1, gu.p, s[4].p, gu.p, n, 32, H, W), "blocked_relu");
         Tensor x6 = act(128);
         qstep(QT_MULTIPOOL, s[2].p, nullptr, nullptr, x6.p, nullptr, H, W);
-        block_backward(qtail_block_of(q, 1), x6, s[3], gu, &dx, &dx_hi);
+        block_backward(block_of(ch.blocks[1], q.w, q.g_w, 1), x6, s[3], gu, &dx, &dx_hi);
         release(gu);
         gu = act(32);
         qstep(QT_MULTIPOOL_BACK, dx.p, dx_hi.p, s[2].p, gu.p, nullptr, H, W);
         release(dx);
         release(dx_hi);
         dx = Tensor{};
-        block_backward(qtail_block_of(q, 0), s[0], s[1], gu, q.g_x4 ? &dx : nullptr);
-        if (q.g_x4) dense(dx, q.g_x4, 64);
+        block_backward(block_of(ch.blocks[0], q.w, q.g_w, 0), s[0], s[1], gu, q.g_x ? &dx : nullptr);
+        if (q.g_x) dense(dx, q.g_x, 64);
         release(dx);
         release(gu);
     }
@@ -336,17 +305,23 @@ int run_train(pmp_ctx *c, int n, int h, int w, const std::function<void(TrainGra
     });
 }
 
-int run_train(pmp_ctx *c, const pmp_trunk_shape &s, const std::function<void(TrainGraph &)> &body) { return run_train(c, s.n, s.h, s.w, body); }
-
-int refuse(pmp_ctx *c, const char *fn, const char *why) { return set_err(c, PMP_E_INVALID, std::string(fn) + ": " + why); }
-
-int rb_run(pmp_ctx *c, const pmp_trunk_shape &s, const RbCall &q)
+// Every entry point, before it runs.  why: the call's *_refused of train_check.h, so nothing is launched or written before the checks
+// pass.  Then, like pmp_train_loss_device, whatever is in flight on the context is made final (nothing, for a trainer's own tensors)
+int admit(pmp_ctx *c, const char *fn, const char *why)
 {
-    return run_train(c, s, [&](TrainGraph &g) { q.backward ? g.resblock_backward(s, q) : g.resblock_forward(s, q); });
+    CHECK_CTX(c);
+    if (why) return set_err(c, PMP_E_INVALID, std::string(fn) + ": " + why);
+    return settle_before_host_call(c);
+}
+
+int rb_run(pmp_ctx *c, const pmp_rb_shape &s, const RbCall &q)
+{
+    const BlockShape b{s.cin, s.cout, s.k};
+    return run_train(c, s.n, s.h, s.w, [&](TrainGraph &g) { q.backward ? g.resblock_backward(b, q) : g.resblock_forward(b, q); });
 }
 
 // The host forms: every tensor through a staging buffer of the context, the device form in between
-int rb_staged(pmp_ctx *c, const pmp_trunk_shape &s, const RbCall &q, const std::vector<Span> &ins, const std::vector<Span> &outs)
+int rb_staged(pmp_ctx *c, const pmp_rb_shape &s, const RbCall &q, const std::vector<Span> &ins, const std::vector<Span> &outs)
 {
     int rc;
     RbCall dq{q.backward, {}, {}};
@@ -371,24 +346,12 @@ int rb_staged(pmp_ctx *c, const pmp_trunk_shape &s, const RbCall &q, const std::
     return sync(c);
 }
 
-// Every entry point: nothing is launched or written before the checks of train_check.h pass
-int rb_entry(pmp_ctx *c, const char *fn, bool device, const pmp_rb_shape *rs, const RbCall &q)
+// pmp_resblock_forward, _backward and their _device forms
+int rb_entry(pmp_ctx *c, const char *fn, bool device, const pmp_rb_shape *s, const RbCall &q)
 {
-    CHECK_CTX(c);
-    const pmp_trunk_shape s = rs ? one_block(*rs) : pmp_trunk_shape{};
-    if (!train_shape_ok(&s)) return refuse(c, fn, TRAIN_SHAPE_RULE);
-    const size_t px = (size_t)s.n * s.h * s.w * 4, bx = px * s.cin, by = px * s.cout[0];
-    std::vector<Span> ins = {{q.in[X], bx}}, outs = {{q.out[T_O], by}, {q.out[OUT_O], by}};
-    if (q.backward) {
-        ins.insert(ins.end(), {{q.in[T], by}, {q.in[OUT], by}, {q.in[G_OUT], by}});
-        outs = {{q.out[G_X], bx, true}};
-    }
-    const char *why = weights_refused(s, q.in, q.out, q.backward, ins, outs);
-    if (why || (why = spans_refused(ins, outs, device))) return refuse(c, fn, why);
-    // like pmp_train_loss_device: whatever is in flight on the context is made final first (nothing, for a trainer's own tensors)
-    int rc;
-    if ((rc = settle_before_host_call(c))) return rc;
-    return device ? rb_run(c, s, q) : rb_staged(c, s, q, ins, outs);
+    std::vector<Span> ins, outs;
+    if (int rc = admit(c, fn, rb_refused(s, q, device, ins, outs))) return rc;
+    return device ? rb_run(c, *s, q) : rb_staged(c, *s, q, ins, outs);
 }
 
 int rb_forward(pmp_ctx *c, const char *fn, bool device, const pmp_rb_shape *s, const float *x, const float *w0, const float *w2,
@@ -403,131 +366,58 @@ int rb_backward(pmp_ctx *c, const char *fn, bool device, const pmp_rb_shape *s, 
     return rb_entry(c, fn, device, s, RbCall{true, {w0, w2, wsc, x, t, out, g_out}, {g_w0, g_w2, g_wsc, g_x}});
 }
 
-// pmp_trunk_forward_device (dir 0), _backward_device (1) and _unpack_device (2)
-int trunk_entry(pmp_ctx *c, const char *fn, const pmp_trunk_shape *s, const TrunkPtrs &q, int dir, int index = 0, float *dense = nullptr)
+// pmp_trunk_* and pmp_qtail_*: _forward_device (dir 0), _backward_device (1), each with its body, and _unpack_device (2), which has none.
+// ch holds what tells the chains apart: layout, blocks, n, h, w, and which saved tensors lie on the half map: QT_CROP_DENSE unpacks those
+using ChainBody = void (TrainGraph::*)(const Chain &, const ChainPtrs &);
+
+int chain_entry(pmp_ctx *c, const char *fn, const Chain &ch, const ChainPtrs &q, int dir, ChainBody body = nullptr, int index = 0)
 {
-    CHECK_CTX(c);
-    if (!train_shape_ok(s)) return refuse(c, fn, TRAIN_SHAPE_RULE);
-    const TrunkLayout lay(*s);
-    if (dir == 2 && (index < 0 || index >= lay.nt)) return refuse(c, fn, "index out of range (0 .. 2 * nblocks)");
-    const size_t px = (size_t)s->n * s->h * s->w * 4, py = (s->pool ? px / 4 : px) * s->cout[s->nblocks - 1], saved = lay.off[lay.nt];
     std::vector<Span> ins, outs;
-    if (dir == 0) { ins = {{q.x, px * s->cin}}; outs = {{q.saved_out, saved, false, 16}, {q.y, py}}; }
-    if (dir == 1) { ins = {{q.saved_in, saved, false, 16}, {q.g_y, py}}; outs = {{q.g_x, px * s->cin, true}}; }
-    if (dir == 2) { ins = {{q.saved_in, saved, false, 16}}; outs = {{dense, px * lay.c[index]}}; }
-    const char *why = dir == 2 ? nullptr : weights_refused(*s, q.w, q.g_w, dir == 1, ins, outs);
-    if (why || (why = spans_refused(ins, outs, true))) return refuse(c, fn, why);
-    int rc;
-    if ((rc = settle_before_host_call(c))) return rc;
+    if (int rc = admit(c, fn, chain_refused(ch, q, dir, index, ins, outs))) return rc;
+    const SavedLayout &lay = ch.lay;
     if (dir == 2) {
-        const hipError_t e = launch_blocked_to_dense(c->stream, view(lay, q.saved_in, index).p, dense, s->n, lay.c[index],
-                                                     pad_channels(lay.c[index]), s->h, s->w);
-        return e == hipSuccess ? PMP_OK : hip_fail(c, e, "blocked_to_dense");
+        const float *src = view(lay, q.saved, index).p;
+        const hipError_t e = lay.half[index]
+                                 ? launch_qtail_step(c->stream, QT_CROP_DENSE, src, nullptr, nullptr, q.dense, nullptr, lay.n, lay.h, lay.w)
+                                 : launch_blocked_to_dense(c->stream, src, q.dense, lay.n, lay.c[index], pad_channels(lay.c[index]), lay.h, lay.w);
+        return e == hipSuccess ? PMP_OK : hip_fail(c, e, ch.unpack_name);
     }
-    return run_train(c, *s, [&](TrainGraph &g) { dir ? g.trunk_backward(*s, q) : g.trunk_forward(*s, q); });
+    return run_train(c, lay.n, lay.h, lay.w, [&](TrainGraph &g) { (g.*body)(ch, q); });
 }
 
-// pmp_qtail_forward_device (dir 0), _backward_device (1) and _unpack_device (2)
-int qtail_entry(pmp_ctx *c, const char *fn, const pmp_qtail_shape *s, const QtailPtrs &q, int dir, int index = 0, float *dense = nullptr)
-{
-    CHECK_CTX(c);
-    if (!qtail_shape_ok(s)) return refuse(c, fn, QTAIL_SHAPE_RULE);
-    const QtailLayout lay(*s);
-    if (dir == 2 && (index < 0 || index >= QTAIL_SAVED)) return refuse(c, fn, "index out of range (0 .. 8)");
-    const size_t saved = lay.off[QTAIL_SAVED];
-    std::vector<Span> ins, outs;
-    if (dir == 0) { ins = {{q.x4, lay.x4}}; outs = {{q.saved_out, saved, false, 16}, {q.x9, lay.x9}}; }
-    if (dir == 1) { ins = {{q.saved_in, saved, false, 16}, {q.g_x9, lay.x9}}; outs = {{q.g_x4, lay.x4, true}}; }
-    if (dir == 2) { ins = {{q.saved_in, saved, false, 16}}; outs = {{dense, lay.dense_bytes(index)}}; }
-    BlockShape blocks[QTAIL_BLOCKS];
-    for (int i = 0; i < QTAIL_BLOCKS; ++i) blocks[i] = qtail_block(i);
-    const char *why = dir == 2 ? nullptr : weights_refused(blocks, QTAIL_BLOCKS, q.w, q.g_w, dir == 1, ins, outs);
-    if (why || (why = spans_refused(ins, outs, true))) return refuse(c, fn, why);
-    int rc;
-    if ((rc = settle_before_host_call(c))) return rc;
-    if (dir == 2) {
-        const float *src = view(lay, q.saved_in, index).p;
-        const hipError_t e = index < 7 ? launch_blocked_to_dense(c->stream, src, dense, s->n, lay.c[index], pad_channels(lay.c[index]), s->h, s->w)
-                                       : launch_qtail_step(c->stream, QT_CROP_DENSE, src, nullptr, nullptr, dense, nullptr, s->n, s->h, s->w);
-        return e == hipSuccess ? PMP_OK : hip_fail(c, e, "qtail_step");
-    }
-    return run_train(c, s->n, s->h, s->w, [&](TrainGraph &g) { dir ? g.qtail_backward(lay, q) : g.qtail_forward(lay, q); });
-}
+int64_t saved_bytes(const Chain &ch) { return ch.refused ? PMP_E_INVALID : (int64_t)ch.lay.off[ch.lay.nt]; }
 
 // pmp_stem_forward_device (backward = false) and pmp_stem_backward_device
-int stem_entry(pmp_ctx *c, const char *fn, const pmp_stem_shape *s, bool backward, const float *x, const float *y, const float *const *w,
-               const float *const *b, const float *g_y, float *y_out, float *g_x, float *const *g_w, float *const *g_b)
+int stem_entry(pmp_ctx *c, const char *fn, const pmp_stem_shape *s, bool backward, const StemPtrs &t)
 {
-    CHECK_CTX(c);
-    if (!stem_shape_ok(s)) return refuse(c, fn, STEM_SHAPE_RULE);
-    const StemSizes z(*s);
-    std::vector<Span> ins, outs;
-    ins.push_back({x, z.x});
-    if (backward) {
-        ins.push_back({y, z.y});
-        ins.push_back({g_y, z.y});
-    }
-    outs.push_back(backward ? Span{g_x, z.x, true} : Span{y_out, z.y});
-    const char *why = stem_array_refused(*s, w, z.w, ins);
-    if (!why && !backward) why = stem_array_refused(*s, b, z.b, ins);
-    if (!why && backward) why = stem_array_refused(*s, g_w, z.w, outs);
-    if (!why && backward) why = stem_array_refused(*s, g_b, z.b, outs);
-    if (why || (why = spans_refused(ins, outs, true))) return refuse(c, fn, why);
-    int rc;
-    if ((rc = settle_before_host_call(c))) return rc;
+    if (int rc = admit(c, fn, stem_refused(s, t, backward))) return rc;
     StemTrainArgs q{};
     q.N = s->n; q.H = s->h; q.W = s->w; q.cin = s->cin; q.K = s->k; q.split = s->split;
-    q.x = x; q.y = y; q.g_y = g_y; q.y_out = y_out; q.g_x = g_x;
+    q.x = t.x; q.y = t.y; q.g_y = t.g_y; q.y_out = t.y_out; q.g_x = t.g_x;
     for (int j = 0; j < (s->split ? 3 : 1); ++j) {
-        q.w[j] = w[j];
-        if (!backward) q.b[j] = b[j];
-        else { q.g_w[j] = g_w[j]; q.g_b[j] = g_b[j]; }
+        q.w[j] = t.w[j];
+        if (!backward) q.b[j] = t.b[j];
+        else { q.g_w[j] = t.g_w[j]; q.g_b[j] = t.g_b[j]; }
     }
     return run_train(c, s->n, s->h, s->w, [&](TrainGraph &g) { g.stem(q, backward); });
 }
 
 // pmp_head_forward_device (backward = false) and pmp_head_backward_device
-int head_entry(pmp_ctx *c, const char *fn, const pmp_head_shape *s, bool backward, const HeadTrainArgs &t)
+int head_entry(pmp_ctx *c, const char *fn, const pmp_head_shape *s, bool backward, const HeadPtrs &t)
 {
-    CHECK_CTX(c);
-    if (!head_shape_ok(s)) return refuse(c, fn, HEAD_SHAPE_RULE);
-    const HeadSizes z(*s);
-    std::vector<Span> ins = {{t.x, z.x}, {t.w, z.w}}, outs;
-    const char *why;
-    if (!backward) {
-        why = head_att_refused(*s, {t.q, t.att}, nullptr);
-        ins.insert(ins.end(), {{t.b, z.b}, {t.prev, z.y, true}, {t.q, z.q, true}});
-        outs = {{t.y, z.y}, {t.att, z.att, true}};
-    } else {
-        why = head_att_refused(*s, {t.g_att}, t.g_q);
-        ins.insert(ins.end(), {{t.g_y, z.y}, {t.g_att, z.att, true}});
-        outs = {{t.g_x, z.x, true}, {t.g_w, z.w}, {t.g_b, z.b}, {t.g_q, z.q, true}, {t.g_prev, z.y, true}};
-    }
-    if (why || (why = spans_refused(ins, outs, true))) return refuse(c, fn, why);
-    int rc;
-    if ((rc = settle_before_host_call(c))) return rc;
-    HeadTrainArgs q = t;
-    q.N = s->n; q.H = s->h; q.W = s->w; q.cin = s->cin; q.cout = s->cout; q.up_q = s->up_q; q.up_y = s->up_y;
+    if (int rc = admit(c, fn, head_refused(s, t, backward))) return rc;
+    const HeadTrainArgs q{s->n, s->h, s->w, s->cin, s->cout, s->up_q, s->up_y, t.x, t.w, t.b, t.prev, t.q, t.y, t.att, t.g_y, t.g_att,
+                          t.g_x, t.g_w, t.g_b, t.g_q, t.g_prev};
     return run_train(c, s->n, s->h, s->w, [&](TrainGraph &g) { g.head(q, backward); });
 }
 
-// pmp_gate_forward_device (g_y = null) and pmp_gate_backward_device
-int gate_entry(pmp_ctx *c, const char *fn, int64_t count, const float *x, const float *a, const float *g_y, const float *g_acc, float *o0,
-               float *o1)
+// pmp_gate_forward_device and pmp_gate_backward_device
+int gate_entry(pmp_ctx *c, const char *fn, int64_t count, bool backward, const float *x, const float *a, const float *g_y, const float *g_acc,
+               float *o0, float *o1)
 {
-    CHECK_CTX(c);
-    if (!gate_count_ok(count)) return refuse(c, fn, GATE_COUNT_RULE);
-    const size_t bytes = (size_t)count * 4;
-    std::vector<Span> ins = {{x, bytes}, {a, bytes}}, outs = {{o0, bytes}};
-    if (g_y) {
-        ins.insert(ins.end(), {{g_y, bytes}, {g_acc, bytes, true}});
-        outs.push_back({o1, bytes});
-    }
-    if (const char *why = spans_refused(ins, outs, true)) return refuse(c, fn, why);
-    int rc;
-    if ((rc = settle_before_host_call(c))) return rc;
-    const hipError_t e = g_y ? launch_gate_backward(c->stream, (size_t)count, x, a, g_y, g_acc, o0, o1)
-                             : launch_gate_forward(c->stream, (size_t)count, x, a, o0);
+    if (int rc = admit(c, fn, gate_refused(count, backward, x, a, g_y, g_acc, o0, o1))) return rc;
+    const hipError_t e = backward ? launch_gate_backward(c->stream, (size_t)count, x, a, g_y, g_acc, o0, o1)
+                                  : launch_gate_forward(c->stream, (size_t)count, x, a, o0);
     return e == hipSuccess ? PMP_OK : hip_fail(c, e, "gate");
 }
 
@@ -538,97 +428,89 @@ extern "C" {
 int pmp_head_forward_device(pmp_ctx *c, const pmp_head_shape *s, const float *x, const float *w, const float *b, const float *prev,
                             const float *q, float *y, float *att)
 {
-    HeadTrainArgs t{};
-    t.x = x; t.w = w; t.b = b; t.prev = prev; t.q = q; t.y = y; t.att = att;
-    return head_entry(c, "pmp_head_forward_device", s, false, t);
+    return head_entry(c, "pmp_head_forward_device", s, false, HeadPtrs{x, w, b, prev, q, y, att});
 }
 
 int pmp_head_backward_device(pmp_ctx *c, const pmp_head_shape *s, const float *x, const float *w, const float *g_y, const float *g_att,
                              float *g_x, float *g_w, float *g_b, float *g_q, float *g_prev)
 {
-    HeadTrainArgs t{};
+    HeadPtrs t{};
     t.x = x; t.w = w; t.g_y = g_y; t.g_att = g_att; t.g_x = g_x; t.g_w = g_w; t.g_b = g_b; t.g_q = g_q; t.g_prev = g_prev;
     return head_entry(c, "pmp_head_backward_device", s, true, t);
 }
 
 int pmp_gate_forward_device(pmp_ctx *c, int64_t count, const float *x, const float *a, float *y)
 {
-    return gate_entry(c, "pmp_gate_forward_device", count, x, a, nullptr, nullptr, y, nullptr);
+    return gate_entry(c, "pmp_gate_forward_device", count, false, x, a, nullptr, nullptr, y, nullptr);
 }
 
 int pmp_gate_backward_device(pmp_ctx *c, int64_t count, const float *x, const float *a, const float *g_y, const float *g_acc, float *g_x,
                              float *g_a)
 {
-    if (c && !g_y) return refuse(c, "pmp_gate_backward_device", "null tensor");
-    return gate_entry(c, "pmp_gate_backward_device", count, x, a, g_y, g_acc, g_x, g_a);
+    return gate_entry(c, "pmp_gate_backward_device", count, true, x, a, g_y, g_acc, g_x, g_a);
 }
 
 int pmp_stem_forward_device(pmp_ctx *c, const pmp_stem_shape *s, const float *x, const float *const w[3], const float *const b[3], float *y)
 {
-    return stem_entry(c, "pmp_stem_forward_device", s, false, x, nullptr, w, b, nullptr, y, nullptr, nullptr, nullptr);
+    StemPtrs t{};
+    t.x = x; t.w = w; t.b = b; t.y_out = y;
+    return stem_entry(c, "pmp_stem_forward_device", s, false, t);
 }
 
 int pmp_stem_backward_device(pmp_ctx *c, const pmp_stem_shape *s, const float *x, const float *y, const float *const w[3], const float *g_y,
                              float *g_x, float *const g_w[3], float *const g_b[3])
 {
-    return stem_entry(c, "pmp_stem_backward_device", s, true, x, y, w, nullptr, g_y, nullptr, g_x, g_w, g_b);
+    StemPtrs t{};
+    t.x = x; t.y = y; t.w = w; t.g_y = g_y; t.g_x = g_x; t.g_w = g_w; t.g_b = g_b;
+    return stem_entry(c, "pmp_stem_backward_device", s, true, t);
 }
 
-int64_t pmp_qtail_saved_bytes(const pmp_qtail_shape *s)
-{
-    if (!qtail_shape_ok(s)) return PMP_E_INVALID;
-    return (int64_t)QtailLayout(*s).off[QTAIL_SAVED];
-}
+int64_t pmp_qtail_saved_bytes(const pmp_qtail_shape *s) { return saved_bytes(chain_of(s)); }
 
 int pmp_qtail_forward_device(pmp_ctx *c, const pmp_qtail_shape *s, const float *x4, const float *const *w, void *saved, float *x9)
 {
-    QtailPtrs q{};
-    q.x4 = x4; q.w = w; q.saved_out = (char *)saved; q.x9 = x9;
-    return qtail_entry(c, "pmp_qtail_forward_device", s, q, 0);
+    ChainPtrs q{};
+    q.x = x4; q.w = w; q.saved = saved; q.y = x9;
+    return chain_entry(c, "pmp_qtail_forward_device", chain_of(s), q, 0, &TrainGraph::qtail_forward);
 }
 
 int pmp_qtail_backward_device(pmp_ctx *c, const pmp_qtail_shape *s, const void *saved, const float *const *w, const float *g_x9, float *g_x4,
                               float *const *g_w)
 {
-    QtailPtrs q{};
-    q.saved_in = (const char *)saved; q.w = w; q.g_x9 = g_x9; q.g_x4 = g_x4; q.g_w = g_w;
-    return qtail_entry(c, "pmp_qtail_backward_device", s, q, 1);
+    ChainPtrs q{};
+    q.saved = saved; q.w = w; q.g_y = g_x9; q.g_x = g_x4; q.g_w = g_w;
+    return chain_entry(c, "pmp_qtail_backward_device", chain_of(s), q, 1, &TrainGraph::qtail_backward);
 }
 
 int pmp_qtail_unpack_device(pmp_ctx *c, const pmp_qtail_shape *s, const void *saved, int index, float *dense)
 {
-    QtailPtrs q{};
-    q.saved_in = (const char *)saved;
-    return qtail_entry(c, "pmp_qtail_unpack_device", s, q, 2, index, dense);
+    ChainPtrs q{};
+    q.saved = saved; q.dense = dense;
+    return chain_entry(c, "pmp_qtail_unpack_device", chain_of(s), q, 2, nullptr, index);
 }
 
-int64_t pmp_trunk_saved_bytes(const pmp_trunk_shape *s)
-{
-    if (!train_shape_ok(s)) return PMP_E_INVALID;
-    const TrunkLayout lay(*s);
-    return (int64_t)lay.off[lay.nt];
-}
+int64_t pmp_trunk_saved_bytes(const pmp_trunk_shape *s) { return saved_bytes(chain_of(s)); }
 
 int pmp_trunk_forward_device(pmp_ctx *c, const pmp_trunk_shape *s, const float *x, const float *const *w, void *saved, float *y)
 {
-    TrunkPtrs q{};
-    q.x = x; q.w = w; q.saved_out = (char *)saved; q.y = y;
-    return trunk_entry(c, "pmp_trunk_forward_device", s, q, 0);
+    ChainPtrs q{};
+    q.x = x; q.w = w; q.saved = saved; q.y = y;
+    return chain_entry(c, "pmp_trunk_forward_device", chain_of(s), q, 0, &TrainGraph::trunk_forward);
 }
 
 int pmp_trunk_backward_device(pmp_ctx *c, const pmp_trunk_shape *s, const void *saved, const float *const *w, const float *g_y, float *g_x,
                               float *const *g_w)
 {
-    TrunkPtrs q{};
-    q.saved_in = (const char *)saved; q.w = w; q.g_y = g_y; q.g_x = g_x; q.g_w = g_w;
-    return trunk_entry(c, "pmp_trunk_backward_device", s, q, 1);
+    ChainPtrs q{};
+    q.saved = saved; q.w = w; q.g_y = g_y; q.g_x = g_x; q.g_w = g_w;
+    return chain_entry(c, "pmp_trunk_backward_device", chain_of(s), q, 1, &TrainGraph::trunk_backward);
 }
 
 int pmp_trunk_unpack_device(pmp_ctx *c, const pmp_trunk_shape *s, const void *saved, int index, float *dense)
 {
-    TrunkPtrs q{};
-    q.saved_in = (const char *)saved;
-    return trunk_entry(c, "pmp_trunk_unpack_device", s, q, 2, index, dense);
+    ChainPtrs q{};
+    q.saved = saved; q.dense = dense;
+    return chain_entry(c, "pmp_trunk_unpack_device", chain_of(s), q, 2, nullptr, index);
 }
 
 int pmp_resblock_forward_device(pmp_ctx *c, const pmp_rb_shape *s, const float *x, const float *w0, const float *w2, const float *wsc,

@@ -1,7 +1,9 @@
-// train_check.h — what pmp_resblock_*, pmp_trunk_*, pmp_stem_*, pmp_head_* and pmp_gate_* (api_train.cpp) accept: the shape rules, a
-// trunk's blocks and its d_saved layout, a stem's and a head's sizes, and the rules on a call's tensors.  A single block is checked as
-// the one-block trunk it is.  Pure host code without the HIP runtime, so that it also builds, with a main of its own, for the CPU
-// under a sanitizer (train_check_main.cpp, `make traincheck`).
+// train_check.h — what pmp_resblock_*, pmp_trunk_*, pmp_qtail_*, pmp_stem_*, pmp_head_* and pmp_gate_* (api_train.cpp) accept, whole:
+// the shape rules, a chain's blocks and its d_saved layout (SavedLayout: a trunk's and a QT tail's), a stem's and a head's sizes, the
+// rules on a call's tensors, and per call family ONE function that states everything the call is refused for (rb_refused,
+// chain_refused, stem_refused, head_refused, gate_refused): which tensors the call has, which are optional, which need 16 bytes.
+// A single block is checked as the one-block trunk it is.  Pure host code without the HIP runtime, no pointer is dereferenced, so
+// that it also builds, with a main of its own, for the CPU under a sanitizer (train_check_main.cpp, `make traincheck`).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -40,21 +42,33 @@ struct BlockShape {
 
 inline BlockShape block_shape(const pmp_trunk_shape &s, int i) { return BlockShape{i ? s.cout[i - 1] : s.cin, s.cout[i], s.k[i]}; }
 
-// d_saved: blocked x, then t_i and out_i of every block, each [n][pad_channels(c)/16][h][w][16]
-struct TrunkLayout {
-    int nt;
-    int c[2 * PMP_TRUNK_MAX_BLOCKS + 1];         // the real channels of saved tensor 0 .. nt-1 (pmp_trunk_unpack_device's index)
-    size_t off[2 * PMP_TRUNK_MAX_BLOCKS + 2];    // bytes; off[nt] = the size
-    explicit TrunkLayout(const pmp_trunk_shape &s) : nt(2 * s.nblocks + 1)
+// d_saved of a chain of blocks (a trunk, a QT net's tail): nt blocked tensors, each [n][pad_channels(c)/16][rows][cols][16] on the map
+// h x w or, the tail's last two, on h2 x w2: h/2 x w/2 top-left in a map of whole 16x16 tiles (the kernels' unit) whose other pixels are 0
+constexpr int SAVED_MAX = 2 * PMP_TRUNK_MAX_BLOCKS + 1;
+struct SavedLayout {
+    int nt = 0, n, h, w, h2, w2;
+    int c[SAVED_MAX];                            // the real channels of saved tensor 0 .. nt-1 (pmp_*_unpack_device's index)
+    bool half[SAVED_MAX];                        // on h2 x w2; dense [n][c][h/2][w/2]
+    size_t off[SAVED_MAX + 1];                   // bytes; off[nt] = the size
+    SavedLayout(int n = 0, int h = 0, int w = 0) : n(n), h(h), w(w), h2((h / 2 + 15) & ~15), w2((w / 2 + 15) & ~15) { off[0] = 0; }
+    void add(int ch, bool on_half = false)
     {
-        const size_t px = (size_t)s.n * s.h * s.w * sizeof(float);
-        off[0] = 0;
-        for (int i = 0; i < nt; ++i) {
-            c[i] = i == 0 ? s.cin : s.cout[(i - 1) / 2];
-            off[i + 1] = off[i] + px * pad_channels(c[i]);
-        }
+        c[nt] = ch;
+        half[nt] = on_half;
+        off[nt + 1] = off[nt] + (size_t)n * (on_half ? h2 * w2 : h * w) * sizeof(float) * pad_channels(ch);
+        ++nt;
     }
+    size_t dense_bytes(int i) const { return (size_t)n * (half[i] ? (h / 2) * (w / 2) : h * w) * sizeof(float) * c[i]; }
 };
+
+// a trunk's: blocked x, then t_i and out_i of every block
+inline SavedLayout saved_layout(const pmp_trunk_shape &s)
+{
+    SavedLayout lay(s.n, s.h, s.w);
+    lay.add(s.cin);
+    for (int i = 0; i < s.nblocks; ++i) { lay.add(s.cout[i]); lay.add(s.cout[i]); }
+    return lay;
+}
 
 // A tensor of a call.  optional: may be NULL (a g_x that is not asked for, the shortcut's weights of a block that has none)
 struct Span { const void *p; size_t bytes; bool optional = false; unsigned align = 4; };
@@ -67,8 +81,9 @@ inline bool overlaps(const Span &a, const Span &b)
 
 // The weights of the blocks, w0, w2, wsc per block as in pmp_trunk_*'s d_w and d_g_w (a single block's: three pointers), go IN
 // FRONT of the call's other tensors in ins / outs (the gradients only backward).  -> why the call is refused, or NULL
-inline const char *weights_refused(const BlockShape *blocks, int nblocks, const float *const *w, float *const *g_w, bool backward,
-                                   std::vector<Span> &ins, std::vector<Span> &outs)
+// (out of line: one copy for a block's call and a chain's)
+__attribute__((noinline)) inline const char *weights_refused(const BlockShape *blocks, int nblocks, const float *const *w, float *const *g_w,
+                                                             bool backward, std::vector<Span> &ins, std::vector<Span> &outs)
 {
     if (!w || (backward && !g_w)) return "null tensor";
     std::vector<Span> wi, wo;
@@ -90,18 +105,9 @@ inline const char *weights_refused(const BlockShape *blocks, int nblocks, const 
     return nullptr;
 }
 
-// ... of every block of the trunk s
-inline const char *weights_refused(const pmp_trunk_shape &s, const float *const *w, float *const *g_w, bool backward, std::vector<Span> &ins,
-                                   std::vector<Span> &outs)
-{
-    BlockShape blocks[PMP_TRUNK_MAX_BLOCKS];
-    for (int i = 0; i < s.nblocks; ++i) blocks[i] = block_shape(s, i);
-    return weights_refused(blocks, s.nblocks, w, g_w, backward, ins, outs);
-}
-
 // Every tensor that is not optional present, no output over an input or another output and, for device pointers, every one aligned.
-// -> why the call is refused, or NULL
-inline const char *spans_refused(const std::vector<Span> &ins, const std::vector<Span> &outs, bool device)
+// -> why the call is refused, or NULL  (out of line: every *_refused below ends in it)
+__attribute__((noinline)) inline const char *spans_refused(const std::vector<Span> &ins, const std::vector<Span> &outs, bool device)
 {
     for (const std::vector<Span> *v : {&ins, &outs})
         for (const Span &t : *v)
@@ -116,6 +122,32 @@ inline const char *spans_refused(const std::vector<Span> &ins, const std::vector
         for (const Span &t : *v)
             if (device && ((uintptr_t)t.p & (t.align - 1))) return "every tensor must be 4-byte aligned, d_saved 16-byte";
     return nullptr;
+}
+
+// ---- one block (pmp_resblock_*).  The tensors of a call, in the order of the context's staging buffers.  in: w0, w2, wsc, x and, backward,
+// t, out, g_out;  out: t, out (forward) or g_w0, g_w2, g_wsc, g_x (backward): the weights in front, as a one-block trunk's d_w and d_g_w
+struct RbCall {
+    enum { X = 3, T, OUT, G_OUT, T_O = 0, OUT_O, G_X = 3 };
+    bool backward;
+    const float *in[7];
+    float *out[4];
+};
+
+// -> why the call is refused, or NULL; ins and outs: its tensors, which the host forms stage one by one
+inline const char *rb_refused(const pmp_rb_shape *rs, const RbCall &q, bool device, std::vector<Span> &ins, std::vector<Span> &outs)
+{
+    const pmp_trunk_shape s = rs ? one_block(*rs) : pmp_trunk_shape{};
+    if (!train_shape_ok(&s)) return TRAIN_SHAPE_RULE;
+    const size_t px = (size_t)s.n * s.h * s.w * 4, bx = px * s.cin, by = px * s.cout[0];
+    ins = {{q.in[q.X], bx}};
+    outs = {{q.out[q.T_O], by}, {q.out[q.OUT_O], by}};
+    if (q.backward) {
+        ins.insert(ins.end(), {{q.in[q.T], by}, {q.in[q.OUT], by}, {q.in[q.G_OUT], by}});
+        outs = {{q.out[q.G_X], bx, true}};
+    }
+    const BlockShape b = block_shape(s, 0);
+    const char *why = weights_refused(&b, 1, q.in, q.out, q.backward, ins, outs);
+    return why ? why : spans_refused(ins, outs, device);
 }
 
 // ---- a stem (pmp_stem_*): the shape rule, the sizes of its three convolutions and the rule on its pointer arrays
@@ -151,6 +183,29 @@ __attribute__((noinline)) inline const char *stem_array_refused(const pmp_stem_s
         if ((arr[j] != nullptr) != (s.split == 1)) return "entries 1 and 2 of a stem's pointer arrays are passed exactly when split = 1";
     for (int j = 0; j < (s.split ? 3 : 1); ++j) v.push_back({arr[j], bytes[j]});
     return nullptr;
+}
+
+// The tensors of a stem call.  forward: x, w, b -> y_out;  backward: x, y, w, g_y -> g_x (optional), g_w, g_b
+struct StemPtrs {
+    const float *x, *y, *g_y;
+    const float *const *w, *const *b;
+    float *y_out, *g_x;
+    float *const *g_w, *const *g_b;
+};
+
+// -> why the call is refused, or NULL
+inline const char *stem_refused(const pmp_stem_shape *s, const StemPtrs &q, bool backward)
+{
+    if (!stem_shape_ok(s)) return STEM_SHAPE_RULE;
+    const StemSizes z(*s);
+    std::vector<Span> ins = {{q.x, z.x}}, outs;
+    if (backward) ins.insert(ins.end(), {{q.y, z.y}, {q.g_y, z.y}});
+    outs.push_back(backward ? Span{q.g_x, z.x, true} : Span{q.y_out, z.y});
+    const char *why = stem_array_refused(*s, q.w, z.w, ins);
+    if (!why && !backward) why = stem_array_refused(*s, q.b, z.b, ins);
+    if (!why && backward) why = stem_array_refused(*s, q.g_w, z.w, outs);
+    if (!why && backward) why = stem_array_refused(*s, q.g_b, z.b, outs);
+    return why ? why : spans_refused(ins, outs, true);
 }
 
 // ---- a head (pmp_head_*): the shape rule, its sizes, and which of its tensors go with an attention input
@@ -190,6 +245,33 @@ __attribute__((noinline)) inline const char *head_att_refused(const pmp_head_sha
     return nullptr;
 }
 
+// The tensors of a head call.  forward: x, w, b, prev?, q? -> y, att?;  backward: x, w, g_y, g_att? -> g_w, g_b, g_x?, g_q?, g_prev?  (?: optional)
+struct HeadPtrs {
+    const float *x, *w, *b, *prev, *q;
+    float *y, *att;
+    const float *g_y, *g_att;
+    float *g_x, *g_w, *g_b, *g_q, *g_prev;
+};
+
+// -> why the call is refused, or NULL
+inline const char *head_refused(const pmp_head_shape *s, const HeadPtrs &t, bool backward)
+{
+    if (!head_shape_ok(s)) return HEAD_SHAPE_RULE;
+    const HeadSizes z(*s);
+    std::vector<Span> ins = {{t.x, z.x}, {t.w, z.w}}, outs;
+    const char *why;
+    if (!backward) {
+        why = head_att_refused(*s, {t.q, t.att}, nullptr);
+        ins.insert(ins.end(), {{t.b, z.b}, {t.prev, z.y, true}, {t.q, z.q, true}});
+        outs = {{t.y, z.y}, {t.att, z.att, true}};
+    } else {
+        why = head_att_refused(*s, {t.g_att}, t.g_q);
+        ins.insert(ins.end(), {{t.g_y, z.y}, {t.g_att, z.att, true}});
+        outs = {{t.g_x, z.x, true}, {t.g_w, z.w}, {t.g_b, z.b}, {t.g_q, z.q, true}, {t.g_prev, z.y, true}};
+    }
+    return why ? why : spans_refused(ins, outs, true);
+}
+
 // ---- a QT net's tail (pmp_qtail_*): resblock_q3, the multi-scale pool, resblock_q4, resblock_q5 + max_pool2d, resblock_q6
 constexpr const char *QTAIL_SHAPE_RULE = "null or unsupported shape (n 1..256, h and w multiples of 16 in 16..256)";
 
@@ -202,30 +284,93 @@ inline bool qtail_shape_ok(const pmp_qtail_shape *s)
 constexpr int QTAIL_BLOCKS = 4, QTAIL_SAVED = 9;
 inline BlockShape qtail_block(int i) { return BlockShape{i == 0 ? 64 : i == 1 ? 128 : 32, i == 3 ? 8 : 32, 3}; }
 
-// d_saved: blocked x4, then t and out of q3, q4, q5 at h x w, then t and out of q6: its h/2 x w/2 map lies top-left in a map of
-// h2 x w2, the sides rounded up to 16, whose other pixels are zero (the convolution kernels work on 16x16 tiles).  x6 is not saved.
-struct QtailLayout {
-    int h2, w2;
-    int c[QTAIL_SAVED];                          // the real channels of saved tensor 0 .. 8 (pmp_qtail_unpack_device's index)
-    size_t off[QTAIL_SAVED + 1];                 // bytes; off[9] = the size
-    size_t x4, x9;                               // bytes of the dense x4 / g_x4 and x9 / g_x9
-    explicit QtailLayout(const pmp_qtail_shape &s) : h2((s.h / 2 + 15) & ~15), w2((s.w / 2 + 15) & ~15)
-    {
-        const size_t px = (size_t)s.n * s.h * s.w * sizeof(float), px2 = (size_t)s.n * h2 * w2 * sizeof(float);
-        off[0] = 0;
-        for (int i = 0; i < QTAIL_SAVED; ++i) {
-            c[i] = i == 0 ? 64 : i < 7 ? 32 : 8;
-            off[i + 1] = off[i] + (i < 7 ? px : px2) * pad_channels(c[i]);
-        }
-        x4 = px * 64;
-        x9 = px / 4 * 8;
-    }
-    size_t dense_bytes(int i) const { return i < 7 ? x4 / 64 * c[i] : x9; }
+// d_saved: blocked x4, then t and out of q3, q4, q5 at h x w, then t and out of q6 on its own map.  x6 is not saved.
+inline SavedLayout saved_layout(const pmp_qtail_shape &s)
+{
+    SavedLayout lay(s.n, s.h, s.w);
+    for (int i = 0; i < QTAIL_SAVED; ++i) lay.add(i == 0 ? 64 : i < 7 ? 32 : 8, i >= 7);
+    return lay;
+}
+
+// ---- a chain of blocks whose activations stay blocked in the caller's d_saved (pmp_trunk_*, pmp_qtail_*): what tells one chain from
+// another, and the tensors of a call.  forward: x, w -> saved, y;  backward: saved, w, g_y -> g_x (optional), g_w;  unpack: saved -> dense
+struct Chain {
+    const char *refused;                         // the shape rule where the shape breaks it (nothing else is set then), else NULL
+    const char *index_rule, *unpack_name;        // unpack's message for an index outside 0 .. nt-1; how it names a failed launch
+    SavedLayout lay;
+    int nblocks, pool;
+    BlockShape blocks[PMP_TRUNK_MAX_BLOCKS];
+    size_t y_bytes;                              // of the dense y and g_y; x and g_x: lay.dense_bytes(0)
 };
+
+struct ChainPtrs {
+    const float *x, *g_y;
+    const float *const *w;
+    const void *saved;
+    float *y, *g_x, *dense;
+    float *const *g_w;
+};
+
+inline Chain chain_of(const pmp_trunk_shape *s)
+{
+    Chain ch{};
+    ch.index_rule = "index out of range (0 .. 2 * nblocks)";
+    ch.unpack_name = "blocked_to_dense";
+    if (!train_shape_ok(s)) { ch.refused = TRAIN_SHAPE_RULE; return ch; }
+    ch.lay = saved_layout(*s);
+    ch.nblocks = s->nblocks;
+    ch.pool = s->pool;
+    for (int i = 0; i < s->nblocks; ++i) ch.blocks[i] = block_shape(*s, i);
+    ch.y_bytes = ch.lay.dense_bytes(ch.lay.nt - 1) / (s->pool ? 4 : 1);
+    return ch;
+}
+
+inline Chain chain_of(const pmp_qtail_shape *s)
+{
+    Chain ch{};
+    ch.index_rule = "index out of range (0 .. 8)";
+    ch.unpack_name = "qtail_step";
+    if (!qtail_shape_ok(s)) { ch.refused = QTAIL_SHAPE_RULE; return ch; }
+    ch.lay = saved_layout(*s);
+    ch.nblocks = QTAIL_BLOCKS;
+    for (int i = 0; i < QTAIL_BLOCKS; ++i) ch.blocks[i] = qtail_block(i);
+    ch.y_bytes = ch.lay.dense_bytes(QTAIL_SAVED - 1);
+    return ch;
+}
+
+// forward (dir 0), backward (1) and unpack of saved tensor `index` (2)  -> why the call is refused, or NULL; ins and outs: its tensors
+inline const char *chain_refused(const Chain &ch, const ChainPtrs &q, int dir, int index, std::vector<Span> &ins, std::vector<Span> &outs)
+{
+    if (ch.refused) return ch.refused;
+    const SavedLayout &lay = ch.lay;
+    if (dir == 2 && (index < 0 || index >= lay.nt)) return ch.index_rule;
+    const Span saved{q.saved, lay.off[lay.nt], false, 16};
+    const size_t x_bytes = lay.dense_bytes(0);
+    if (dir == 0) { ins = {{q.x, x_bytes}}; outs = {saved, {q.y, ch.y_bytes}}; }
+    if (dir == 1) { ins = {saved, {q.g_y, ch.y_bytes}}; outs = {{q.g_x, x_bytes, true}}; }
+    if (dir == 2) { ins = {saved}; outs = {{q.dense, lay.dense_bytes(index)}}; }
+    const char *why = dir == 2 ? nullptr : weights_refused(ch.blocks, ch.nblocks, q.w, q.g_w, dir == 1, ins, outs);
+    return why ? why : spans_refused(ins, outs, true);
+}
 
 // ---- the gate (pmp_gate_*)
 constexpr const char *GATE_COUNT_RULE = "count must be in 1 .. 2^31 - 1";
 
 inline bool gate_count_ok(int64_t count) { return count >= 1 && count <= INT32_MAX; }
+
+// forward: x, a -> o0 = y;  backward: x, a, g_y, g_acc (optional) -> o0 = g_x, o1 = g_a  -> why the call is refused, or NULL
+inline const char *gate_refused(int64_t count, bool backward, const float *x, const float *a, const float *g_y, const float *g_acc,
+                                const float *o0, const float *o1)
+{
+    if (backward && !g_y) return "null tensor";
+    if (!gate_count_ok(count)) return GATE_COUNT_RULE;
+    const size_t bytes = (size_t)count * 4;
+    std::vector<Span> ins = {{x, bytes}, {a, bytes}}, outs = {{o0, bytes}};
+    if (backward) {
+        ins.insert(ins.end(), {{g_y, bytes}, {g_acc, bytes, true}});
+        outs.push_back({o1, bytes});
+    }
+    return spans_refused(ins, outs, true);
+}
 
 }  // namespace pmp

@@ -1,8 +1,10 @@
 // train_check_main.cpp — train_check.h on the CPU, with a main of its own, for `make traincheck` (-fsanitize=address,undefined): the
 // shapes of the refusal matrices of tests/test_gpu_resblock_grad.py and tests/test_gpu_trunk_grad.py, the weight rule per block, and
-// spans that overlap, are missing or are misaligned, a stem's shapes, sizes and pointer arrays (tests/test_gpu_stem_grad.py), and a
-// head's shapes, sizes and the tensors tied to its attention input (tests/test_gpu_head_grad.py).  No pointer is dereferenced; exit
-// status 0 and "train_check: ok" when all hold.
+// spans that overlap, are missing or are misaligned, a stem's shapes, sizes and pointer arrays (tests/test_gpu_stem_grad.py), a
+// head's shapes, sizes and the tensors tied to its attention input (tests/test_gpu_head_grad.py), a QT tail's (tests/
+// test_gpu_qtail_grad.py), and the pointer-level rows of those matrices through the functions the entry points call: chain_refused,
+// rb_refused, stem_refused, head_refused and gate_refused on fake addresses.  No pointer is dereferenced; exit status 0 and
+// "train_check: ok" when all hold.
 #include <stdio.h>
 #include <string.h>
 
@@ -18,6 +20,13 @@ static void expect(bool ok, const char *what)
 }
 
 static bool says(const char *why, const char *word) { return why && strstr(why, word); }
+
+// the weight rule over every block of the trunk s
+static const char *weights_refused(const pmp_trunk_shape &s, const float *const *w, float *const *g_w, bool backward, std::vector<Span> &ins,
+                                   std::vector<Span> &outs)
+{
+    return weights_refused(chain_of(&s).blocks, s.nblocks, w, g_w, backward, ins, outs);
+}
 
 int main()
 {
@@ -50,7 +59,7 @@ int main()
     // ---- d_saved of the largest trunk: 17 tensors, offsets that add up, every one a multiple of 16 bytes
     pmp_trunk_shape big{256, 256, 256, 64, 8, {64, 33, 17, 1, 64, 16, 32, 48}, {3, 5, 3, 5, 3, 5, 3, 5}, 0};
     expect(train_shape_ok(&big), "the largest trunk");
-    const TrunkLayout lay(big);
+    const SavedLayout lay = saved_layout(big);
     size_t sum = 0;
     for (int i = 0; i < lay.nt; ++i) {
         expect(lay.off[i] == sum && !(lay.off[i] & 15), "d_saved offsets");
@@ -59,7 +68,8 @@ int main()
     expect(lay.nt == 17 && lay.off[17] == sum && lay.c[0] == 64 && lay.c[1] == 64 && lay.c[2] == 64 && lay.c[3] == 33 && lay.c[16] == 48, "d_saved layout");
     expect(block_shape(big, 0).cin == 64 && block_shape(big, 1).cin == 64 && block_shape(big, 7).cin == 32 && block_shape(big, 7).cout == 48, "block_shape");
     // ---- the weights of every block
-    alignas(16) static float mem[16 * 2560];                                   // 2560 floats apart: the largest tensor here has 9 * 16 * 16
+    alignas(16) static float mem[16 * 2560 + 1024 * 1024];                      // 2560 floats apart: the largest tensor here has 9 * 16 * 16;
+                                                                               // behind them, room for the whole calls further down (place())
     auto at = [&](int i) { return mem + i * 2560; };
     const pmp_trunk_shape two{n, h, w, 16, 2, {16, 8}, {3, 3}, 0};             // block 0 identity, block 1 with a 1x1 shortcut
     const float *wt[6] = {at(0), at(1), nullptr, at(2), at(3), at(4)};
@@ -181,13 +191,14 @@ int main()
     for (const pmp_qtail_shape &t : qgood) expect(qtail_shape_ok(&t), "an accepted tail shape");
     expect(!qtail_shape_ok(nullptr), "a null tail shape");
     {
-        const QtailLayout nets(pmp_qtail_shape{200, 16, 16}), wide(pmp_qtail_shape{2, 16, 48}), big(pmp_qtail_shape{256, 256, 256});
-        expect(nets.h2 == 16 && nets.w2 == 16 && nets.off[QTAIL_SAVED] == (size_t)58982400 && nets.x4 == (size_t)4 * 200 * 64 * 256 &&
-                   nets.x9 == (size_t)4 * 200 * 8 * 64 && nets.dense_bytes(0) == nets.x4 && nets.dense_bytes(6) == nets.x4 / 2 &&
-                   nets.dense_bytes(8) == nets.x9,
+        const pmp_qtail_shape s200{200, 16, 16}, swide{2, 16, 48}, sbig{256, 256, 256};
+        const SavedLayout nets = saved_layout(s200), wide = saved_layout(swide), big = saved_layout(sbig);
+        const size_t x4 = (size_t)4 * 200 * 64 * 256, x9 = (size_t)4 * 200 * 8 * 64;
+        expect(nets.nt == QTAIL_SAVED && nets.h2 == 16 && nets.w2 == 16 && nets.off[QTAIL_SAVED] == (size_t)58982400 && nets.dense_bytes(0) == x4 &&
+                   nets.dense_bytes(6) == x4 / 2 && nets.dense_bytes(7) == x9 && nets.dense_bytes(8) == x9 && chain_of(&s200).y_bytes == x9,
                "the tail's d_saved at the nets' shape");
         expect(wide.h2 == 16 && wide.w2 == 32 && wide.off[7] == (size_t)4 * 2 * 16 * 48 * 256 &&
-                   wide.off[9] == wide.off[7] + (size_t)4 * 2 * 16 * 32 * 32 && wide.x9 == (size_t)4 * 2 * 8 * 8 * 24,
+                   wide.off[9] == wide.off[7] + (size_t)4 * 2 * 16 * 32 * 32 && wide.dense_bytes(8) == (size_t)4 * 2 * 8 * 8 * 24,
                "q6's map is rounded up to whole tiles");
         expect(big.h2 == 128 && big.w2 == 128, "a map of whole tiles is not padded");
         for (int i = 0; i <= QTAIL_SAVED; ++i) expect(!(big.off[i] & 15) && !(wide.off[i] & 15), "the tail's d_saved offsets");
@@ -213,6 +224,268 @@ int main()
     }
     expect(gate_count_ok(1) && gate_count_ok(INT32_MAX) && !gate_count_ok(0) && !gate_count_ok(-5) && !gate_count_ok((int64_t)INT32_MAX + 1),
            "the gate's count");
+    // ---- whole calls through the functions the entry points call, on fake addresses: the tensors of a call laid out one behind the
+    // other in mem, behind the slots of at(), 64 bytes between them (a tensor moved by a few bytes is misaligned, not over its neighbour:
+    // overlaps are looked at first)
+    const size_t slots = 16 * 2560 * sizeof(float);
+    size_t used = slots;
+    auto place = [&](size_t bytes) {
+        float *p = (float *)((char *)mem + used);
+        used += ((bytes + 15) & ~(size_t)15) + 64;
+        expect(used <= sizeof mem, "mem holds the call's tensors");
+        return p;
+    };
+    auto off = [](const void *p, long bytes) { return (float *)((char *)const_cast<void *>(p) + bytes); };
+    auto is = [](const char *why, const char *all) {
+        const bool same = why && !strcmp(why, all);
+        if (!same) fprintf(stderr, "train_check: \"%s\" where \"%s\" was expected\n", why ? why : "(accepted)", all);
+        return same;
+    };
+    // a chain: forward (0), backward (1), unpack (2) of a trunk and of the tail
+    std::vector<Span> c_in, c_out;
+    auto chain_why = [&](const Chain &ch, const ChainPtrs &q, int dir, int index = 0) { return chain_refused(ch, q, dir, index, c_in, c_out); };
+    auto chain_rows = [&](const Chain &ch, const Chain &null_shape, const char *index_rule) {
+        used = slots;
+        const SavedLayout &lay = ch.lay;
+        const float *wt[3 * PMP_TRUNK_MAX_BLOCKS] = {};
+        float *gw[3 * PMP_TRUNK_MAX_BLOCKS] = {};
+        int conv_sc = -1, id_sc = -1;                                          // some wsc that exists / that does not
+        for (int i = 0; i < ch.nblocks; ++i) {
+            const BlockShape b = ch.blocks[i];
+            const size_t kk = (size_t)4 * b.k * b.k, bytes[3] = {kk * b.cout * b.cin, kk * b.cout * b.cout, (size_t)4 * b.cout * b.cin};
+            for (int j = 0; j < (b.cin != b.cout ? 3 : 2); ++j) { wt[3 * i + j] = place(bytes[j]); gw[3 * i + j] = place(bytes[j]); }
+            (b.cin != b.cout ? conv_sc : id_sc) = 3 * i + 2;
+        }
+        size_t dense = 0;
+        for (int i = 0; i < lay.nt; ++i) dense = lay.dense_bytes(i) > dense ? lay.dense_bytes(i) : dense;
+        ChainPtrs ok{};
+        ok.w = wt; ok.g_w = gw;
+        ok.saved = place(lay.off[lay.nt]);
+        ok.x = place(lay.dense_bytes(0)); ok.g_x = place(lay.dense_bytes(0));
+        ok.y = place(ch.y_bytes); ok.g_y = place(ch.y_bytes);
+        ok.dense = place(dense);
+        float *spare = place(dense), *room = place(lay.off[lay.nt] + dense);
+        for (int dir = 0; dir < 3; ++dir) {
+            auto why = [&](const ChainPtrs &q, int index = 1) { return chain_why(ch, q, dir, index); };
+            expect(!why(ok), "an accepted call of a chain");
+            expect(says(chain_why(null_shape, ok, dir, 1), "null or unsupported shape"), "a chain's null shape");
+            ChainPtrs q = ok;
+            q.saved = nullptr; expect(is(why(q), "null tensor"), "null d_saved");
+            expect(says(chain_why(null_shape, q, dir, 1), "null or unsupported shape"), "the shape is looked at first");
+            for (int d : {4, 8}) { q.saved = off(ok.saved, d); expect(says(why(q), "d_saved 16-byte"), "d_saved at +4 and +8 bytes"); }
+            q.saved = off(ok.saved, 16); expect(!why(q), "d_saved at +16 bytes");
+            q = ok;
+            (dir == 0 ? q.y : dir == 1 ? q.g_x : q.dense) = off(ok.saved, 256 << dir);
+            expect(is(why(q), dir ? "an output tensor overlaps an input" : "two output tensors overlap"), "an output inside d_saved");
+            q = ok; q.saved = room;
+            (dir == 0 ? q.y : dir == 1 ? q.g_x : q.dense) = off(room, (long)lay.off[lay.nt]);
+            expect(!why(q), "an output right behind d_saved");
+            (dir == 0 ? q.y : dir == 1 ? q.g_x : q.dense) = off(room, (long)lay.off[lay.nt] - 4);
+            expect(is(why(q), dir ? "an output tensor overlaps an input" : "two output tensors overlap"), "an output over d_saved's last word");
+            q = ok;
+            (dir == 0 ? q.y : dir == 1 ? q.g_x : q.dense) = nullptr;
+            expect(dir == 1 ? !why(q) : is(why(q), "null tensor"), "only g_x is optional");
+            if (dir == 2) continue;
+            q = ok; q.w = nullptr; expect(is(why(q), "null tensor"), "null d_w");
+            q = ok; (dir ? q.g_y : q.x) = nullptr; expect(is(why(q), "null tensor"), "null x, null g_y");
+            q = ok; (dir ? q.g_y : q.x) = off(dir ? ok.g_y : ok.x, 2); expect(says(why(q), "aligned"), "misaligned x, g_y");
+            const float *v[3 * PMP_TRUNK_MAX_BLOCKS];
+            float *g[3 * PMP_TRUNK_MAX_BLOCKS];
+            q = ok; q.w = v; q.g_w = g;
+            auto fresh = [&] { memcpy(v, wt, sizeof v); memcpy(g, gw, sizeof g); };
+            fresh(); v[1] = nullptr; g[1] = nullptr; expect(is(why(q), "null tensor"), "null w2 of block 0");
+            fresh(); v[0] = off(wt[0], 2); expect(says(why(q), "aligned"), "misaligned w0");
+            if (conv_sc >= 0) { fresh(); v[conv_sc] = nullptr; g[conv_sc] = nullptr; expect(says(why(q), "shortcut"), "no wsc with a conv shortcut"); }
+            if (id_sc >= 0) {
+                fresh(); v[id_sc] = spare; g[id_sc] = spare + 64; expect(says(why(q), "shortcut"), "wsc with an identity shortcut");
+                q.y = off(ok.x, 64); q.g_x = const_cast<float *>(ok.g_y);
+                expect(says(why(q), "shortcut"), "the weights' pattern is looked at before overlaps");
+                q.y = ok.y; q.g_x = ok.g_x;
+            }
+        }
+        ChainPtrs q = ok;
+        q.y = off(ok.x, 64); expect(is(chain_why(ch, q, 0), "an output tensor overlaps an input"), "y overlaps x");
+        q = ok; q.saved = ok.x; expect(is(chain_why(ch, q, 0), "an output tensor overlaps an input"), "d_saved is x");
+        q = ok; q.saved = wt[1]; expect(is(chain_why(ch, q, 0), "an output tensor overlaps an input"), "d_saved overlaps w2");
+        q = ok; q.g_w = nullptr; expect(!chain_why(ch, q, 0) && is(chain_why(ch, q, 1), "null tensor"), "d_g_w: backward only");
+        q = ok; q.g_x = const_cast<float *>(ok.g_y); expect(is(chain_why(ch, q, 1), "an output tensor overlaps an input"), "g_x over g_y");
+        float *g[3 * PMP_TRUNK_MAX_BLOCKS];
+        q = ok; q.g_w = g;
+        memcpy(g, gw, sizeof g); g[1] = gw[0]; expect(is(chain_why(ch, q, 1), "two output tensors overlap"), "g_w2 is g_w0");
+        memcpy(g, gw, sizeof g); g[1] = off(wt[0], 4); expect(is(chain_why(ch, q, 1), "an output tensor overlaps an input"), "g_w2 overlaps w0");
+        memcpy(g, gw, sizeof g); g[1] = off(ok.g_x, 16); expect(is(chain_why(ch, q, 1), "two output tensors overlap"), "g_w2 overlaps g_x");
+        memcpy(g, gw, sizeof g); g[0] = nullptr; expect(says(chain_why(ch, q, 1), "NULL exactly"), "null g_w0");
+        memcpy(g, gw, sizeof g); g[0] = off(gw[0], 2); expect(says(chain_why(ch, q, 1), "aligned"), "misaligned g_w0");
+        // unpack: every index of the layout and no other, the tensors' sizes, and which one is written
+        for (int i = 0; i < lay.nt; ++i) {
+            std::vector<Span> in, out;
+            expect(!chain_refused(ch, ok, 2, i, in, out) && in.size() == 1 && out.size() == 1 && in[0].p == ok.saved && in[0].bytes == lay.off[lay.nt] &&
+                       in[0].align == 16 && out[0].p == ok.dense && out[0].bytes == lay.dense_bytes(i) && !out[0].optional,
+                   "unpack reads d_saved and writes the dense tensor of that index");
+        }
+        for (int i : {-1, lay.nt, lay.nt + 1, 1 << 30}) expect(is(chain_why(ch, ok, 2, i), index_rule), "an index outside 0 .. nt-1");
+        q = ok; q.saved = nullptr; expect(is(chain_why(ch, q, 2, lay.nt), index_rule), "the index is looked at before the tensors");
+        q = ok; q.dense = off(ok.dense, 2); expect(says(chain_why(ch, q, 2, 1), "aligned"), "misaligned dense");
+        std::vector<Span> in, out;
+        expect(!chain_refused(ch, ok, 0, 0, in, out) && in.size() == (size_t)3 * ch.nblocks + 1 && out.size() == 2 && in.back().p == ok.x &&
+                   in.back().bytes == lay.dense_bytes(0) && out[0].p == ok.saved && out[0].align == 16 && out[1].p == ok.y && out[1].bytes == ch.y_bytes,
+               "forward's tensors");
+        in.clear(); out.clear();
+        expect(!chain_refused(ch, ok, 1, 0, in, out) && in.size() == (size_t)3 * ch.nblocks + 2 && out.size() == (size_t)3 * ch.nblocks + 1 &&
+                   in[in.size() - 2].p == ok.saved && in.back().p == ok.g_y && in.back().bytes == ch.y_bytes && out.back().p == ok.g_x &&
+                   out.back().optional && out.back().bytes == lay.dense_bytes(0),
+               "backward's tensors");
+    };
+    {
+        const pmp_trunk_shape one_pool{1, 16, 16, 16, 1, {16}, {3}, 1}, mixed{2, 16, 32, 16, 3, {16, 8, 8}, {3, 5, 3}, 0};
+        const pmp_qtail_shape tail{1, 16, 16}, wide{1, 16, 48};
+        const char *trunk_rule = "index out of range (0 .. 2 * nblocks)", *tail_rule = "index out of range (0 .. 8)";
+        chain_rows(chain_of(&one_pool), chain_of((const pmp_trunk_shape *)nullptr), trunk_rule);
+        chain_rows(chain_of(&mixed), chain_of((const pmp_trunk_shape *)nullptr), trunk_rule);
+        chain_rows(chain_of(&tail), chain_of((const pmp_qtail_shape *)nullptr), tail_rule);
+        chain_rows(chain_of(&wide), chain_of((const pmp_qtail_shape *)nullptr), tail_rule);
+        const Chain p = chain_of(&one_pool), m = chain_of(&mixed), t = chain_of(&wide);
+        expect(p.lay.nt == 3 && p.y_bytes == (size_t)4 * 16 * 8 * 8 && p.pool == 1 && m.lay.nt == 7 && m.y_bytes == (size_t)4 * 2 * 8 * 16 * 32 && !m.pool &&
+                   m.blocks[1].cin == 16 && m.blocks[1].cout == 8 && m.blocks[1].k == 5 && !m.lay.half[6],
+               "a trunk as a chain");
+        expect(t.lay.nt == 9 && t.nblocks == 4 && t.y_bytes == (size_t)4 * 8 * 8 * 24 && !t.lay.half[6] && t.lay.half[7] && t.lay.half[8] &&
+                   t.blocks[1].cin == 128 && !strcmp(t.unpack_name, "qtail_step") && !strcmp(m.unpack_name, "blocked_to_dense"),
+               "the tail as a chain");
+        const pmp_trunk_shape bad = {1, 24, 16, 16, 1, {16}, {3}, 1};
+        expect(chain_of(&bad).refused == TRAIN_SHAPE_RULE && chain_of(&one_pool).refused == nullptr, "a chain of a refused shape");
+    }
+    // a single block: the device forms and the host forms, whose staging goes by the order of ins and outs
+    {
+        used = slots;
+        const pmp_rb_shape rs{2, 16, 16, 16, 8, 3};
+        const size_t bx = (size_t)4 * 2 * 16 * 256, by = bx / 2, w0 = (size_t)4 * 9 * 8 * 16, w2 = w0 / 2, wsc = (size_t)4 * 8 * 16;
+        float *x = place(bx), *t = place(by), *out = place(by), *g_out = place(by), *g_x = place(bx);
+        float *pw0 = place(w0), *pw2 = place(w2), *pwsc = place(wsc), *g0 = place(w0), *g2 = place(w2), *gsc = place(wsc);
+        const RbCall fwd{false, {pw0, pw2, pwsc, x}, {t, out}}, bwd{true, {pw0, pw2, pwsc, x, t, out, g_out}, {g0, g2, gsc, g_x}};
+        std::vector<Span> in, o;
+        for (bool device : {true, false}) {
+            expect(!rb_refused(&rs, fwd, device, in, o) && in.size() == 4 && o.size() == 2 && in[3].p == x && in[3].bytes == bx && in[2].bytes == wsc &&
+                       o[0].p == t && o[1].p == out && o[1].bytes == by,
+                   "a block's forward call and its tensors");
+            expect(!rb_refused(&rs, bwd, device, in, o) && in.size() == 7 && o.size() == 4 && in[4].p == t && in[6].p == g_out && o[0].p == g0 &&
+                       o[3].p == g_x && o[3].optional && o[3].bytes == bx,
+                   "a block's backward call and its tensors");
+            expect(says(rb_refused(nullptr, fwd, device, in, o), "null or unsupported shape"), "a block's null shape");
+            RbCall q = bwd;
+            q.out[q.G_X] = nullptr; expect(!rb_refused(&rs, q, device, in, o), "g_x is optional");
+            q.out[q.G_X] = off(g_out, 64); expect(is(rb_refused(&rs, q, device, in, o), "an output tensor overlaps an input"), "g_x inside g_out");
+            q = bwd; q.out[0] = g2; expect(is(rb_refused(&rs, q, device, in, o), "two output tensors overlap"), "g_w0 is g_w2");
+            q = bwd; q.in[q.T] = nullptr; expect(is(rb_refused(&rs, q, device, in, o), "null tensor"), "null t");
+            q = fwd; q.out[q.T_O] = off(x, 16); expect(is(rb_refused(&rs, q, device, in, o), "an output tensor overlaps an input"), "t overlaps x");
+            q = fwd; q.in[2] = nullptr; expect(says(rb_refused(&rs, q, device, in, o), "shortcut"), "no wsc with cin != cout");
+            q = fwd; q.in[q.X] = off(x, 2); expect(device ? says(rb_refused(&rs, q, device, in, o), "aligned") : !rb_refused(&rs, q, device, in, o), "misaligned x: device forms only");
+        }
+    }
+    // a stem: the pointer-level rows of tests/test_gpu_stem_grad.py
+    {
+        used = slots;
+        const pmp_stem_shape qs{1, 16, 16, 1, 9, 0}, ms{1, 16, 16, 4, 9, 1};
+        const StemSizes z(ms);                                                 // the larger of the two
+        float *w[3], *b[3], *g_w[3], *g_b[3];
+        for (int j = 0; j < 3; ++j) { w[j] = place(z.w[j]); b[j] = place(z.b[j]); g_w[j] = place(z.w[j]); g_b[j] = place(z.b[j]); }
+        float *x = place(z.x), *y = place(z.y), *g_y = place(z.y), *g_x = place(z.x);
+        const float *w1[3] = {w[0], nullptr, nullptr}, *b1[3] = {b[0], nullptr, nullptr};
+        float *gw1[3] = {g_w[0], nullptr, nullptr}, *gb1[3] = {g_b[0], nullptr, nullptr};
+        StemPtrs f{}, r{};                                                     // of the QT stem; f3, r3 below of the MTT stem
+        f.x = x; f.w = w1; f.b = b1; f.y_out = y;
+        r.x = x; r.y = y; r.w = w1; r.g_y = g_y; r.g_x = g_x; r.g_w = gw1; r.g_b = gb1;
+        StemPtrs f3 = f, r3 = r;
+        f3.w = w; f3.b = b; r3.w = w; r3.g_w = g_w; r3.g_b = g_b;
+        expect(!stem_refused(&qs, f, false) && !stem_refused(&qs, r, true) && !stem_refused(&ms, f3, false) && !stem_refused(&ms, r3, true), "accepted stem calls");
+        expect(says(stem_refused(nullptr, f, false), "null or unsupported shape") && says(stem_refused(nullptr, r, true), "null or unsupported shape"), "a stem's null shape");
+        expect(says(stem_refused(&ms, f, false), "exactly when split") && says(stem_refused(&qs, r3, true), "exactly when split"), "split against the arrays");
+        StemPtrs q = f;
+        q.x = nullptr; expect(is(stem_refused(&qs, q, false), "null tensor"), "null x");
+        expect(says(stem_refused(nullptr, q, false), "null or unsupported shape"), "a stem's shape is looked at first");
+        q = f; q.w = nullptr; expect(is(stem_refused(&qs, q, false), "null tensor"), "null d_w");
+        q = f; q.b = nullptr; expect(is(stem_refused(&qs, q, false), "null tensor"), "null d_b");
+        q = f; q.y_out = nullptr; expect(is(stem_refused(&qs, q, false), "null tensor"), "null y");
+        q = f; q.x = off(x, 2); expect(says(stem_refused(&qs, q, false), "aligned"), "misaligned x");
+        q = f; q.y_out = off(x, 64); expect(is(stem_refused(&qs, q, false), "an output tensor overlaps an input"), "y overlaps x");
+        q = f; q.y_out = off(x, 4 * (20 * 20 - 1)); expect(is(stem_refused(&qs, q, false), "an output tensor overlaps an input"), "y overlaps the end of x");
+        q = f; q.y_out = off(x, 4 * 20 * 20); expect(!stem_refused(&qs, q, false), "y right behind x");
+        q = f; q.y_out = w[0]; expect(is(stem_refused(&qs, q, false), "an output tensor overlaps an input"), "y is w[0]");
+        q = f3; q.y_out = off(b[1], -4 * 100); expect(is(stem_refused(&ms, q, false), "an output tensor overlaps an input"), "y overlaps b[1]");
+        q = r; q.b = nullptr; q.y_out = nullptr; expect(!stem_refused(&qs, q, true), "backward has neither b nor y_out");
+        q = r; q.g_x = nullptr; expect(!stem_refused(&qs, q, true), "a stem's g_x is optional");
+        q = r; q.y = nullptr; expect(is(stem_refused(&qs, q, true), "null tensor"), "backward without y");
+        q = r; q.g_y = nullptr; expect(is(stem_refused(&qs, q, true), "null tensor"), "null g_y");
+        q = r; q.g_w = nullptr; expect(is(stem_refused(&qs, q, true), "null tensor"), "null d_g_w");
+        q = r; q.g_b = nullptr; expect(is(stem_refused(&qs, q, true), "null tensor"), "null d_g_b");
+        q = r; q.g_x = off(x, 16); expect(is(stem_refused(&qs, q, true), "an output tensor overlaps an input"), "g_x overlaps x");
+        q = r; q.g_x = g_y; expect(is(stem_refused(&qs, q, true), "an output tensor overlaps an input"), "g_x is g_y");
+        q = r; q.g_x = off(y, 1024); expect(is(stem_refused(&qs, q, true), "an output tensor overlaps an input"), "g_x inside y");
+        { float *u[3] = {w[0], nullptr, nullptr}; q = r; q.g_w = u; expect(is(stem_refused(&qs, q, true), "an output tensor overlaps an input"), "g_w[0] is w[0]"); }
+        { float *u[3] = {off(g_x, 16), nullptr, nullptr}; q = r; q.g_w = u; expect(is(stem_refused(&qs, q, true), "two output tensors overlap"), "g_w[0] overlaps g_x"); }
+        { float *u[3] = {off(g_w[0], 64), nullptr, nullptr}; q = r; q.g_b = u; expect(is(stem_refused(&qs, q, true), "two output tensors overlap"), "g_b[0] inside g_w[0]"); }
+        { float *u[3] = {g_w[0], g_w[2], g_w[2]}; q = r3; q.g_w = u; expect(is(stem_refused(&ms, q, true), "two output tensors overlap"), "g_w[1] is g_w[2]"); }
+        { float *u[3] = {g_b[0], g_b[1], off(g_b[2], 2)}; q = r3; q.g_b = u; expect(says(stem_refused(&ms, q, true), "aligned"), "misaligned g_b[2]"); }
+    }
+    // a head and the gate: the pointer-level rows of tests/test_gpu_head_grad.py
+    {
+        used = slots;
+        const pmp_head_shape plain{3, 16, 16, 8, 2, 0, 0}, att{3, 24, 16, 8, 2, 4, 2};
+        const HeadSizes z(att);                                                // the larger of the two
+        HeadPtrs f{}, r{};                                                     // of the head with an attention input
+        f.x = place(z.x); f.w = place(z.w); f.b = place(z.b); f.prev = place(z.y); f.q = place(z.q); f.y = place(z.y); f.att = place(z.att);
+        r.x = f.x; r.w = f.w; r.g_y = place(z.y); r.g_att = place(z.att); r.g_x = place(z.x); r.g_w = place(z.w); r.g_b = place(z.b);
+        r.g_q = place(z.q); r.g_prev = place(z.y);
+        HeadPtrs fp = f, rp = r;                                               // of the plain head
+        fp.q = nullptr; fp.att = nullptr; rp.g_att = nullptr; rp.g_q = nullptr;
+        float *spare = place(z.att);
+        expect(!head_refused(&att, f, false) && !head_refused(&att, r, true) && !head_refused(&plain, fp, false) && !head_refused(&plain, rp, true), "accepted head calls");
+        expect(says(head_refused(nullptr, f, false), "null or unsupported shape") && says(head_refused(nullptr, r, true), "null or unsupported shape"), "a head's null shape");
+        HeadPtrs q = fp;
+        q.prev = nullptr; expect(!head_refused(&plain, q, false), "prev is optional");
+        q = rp; q.g_x = nullptr; q.g_prev = nullptr; expect(!head_refused(&plain, q, true), "g_x and g_prev are optional");
+        q = r; q.g_q = nullptr; expect(!head_refused(&att, q, true), "g_q is optional");
+        q = fp; q.x = nullptr; expect(is(head_refused(&plain, q, false), "null tensor"), "a head's null x");
+        expect(says(head_refused(nullptr, q, false), "null or unsupported shape"), "a head's shape is looked at first");
+        q = f; q.w = off(f.w, 1); expect(says(head_refused(&att, q, false), "aligned"), "misaligned w");
+        q = fp; q.b = nullptr; expect(is(head_refused(&plain, q, false), "null tensor"), "null b");
+        q = fp; q.y = nullptr; expect(is(head_refused(&plain, q, false), "null tensor"), "a head's null y");
+        q = fp; q.q = spare; expect(says(head_refused(&plain, q, false), "exactly when up_y"), "q without up_y");
+        q = fp; q.att = spare; q.y = const_cast<float *>(fp.x); expect(says(head_refused(&plain, q, false), "exactly when up_y"), "att without up_y, before overlaps");
+        q = f; q.att = nullptr; expect(says(head_refused(&att, q, false), "exactly when up_y"), "up_y without att");
+        q = fp; q.y = off(fp.x, 64); expect(is(head_refused(&plain, q, false), "an output tensor overlaps an input"), "a head's y overlaps x");
+        q = fp; q.y = const_cast<float *>(fp.prev); expect(is(head_refused(&plain, q, false), "an output tensor overlaps an input"), "y is prev");
+        q = fp; q.y = off(fp.w, 4 * 143); expect(is(head_refused(&plain, q, false), "an output tensor overlaps an input"), "y overlaps the end of w");
+        q = f; q.att = off(f.q, -16); expect(is(head_refused(&att, q, false), "an output tensor overlaps an input"), "att overlaps q");
+        q = f; q.att = f.y; expect(is(head_refused(&att, q, false), "two output tensors overlap"), "att is y");
+        q = rp; q.g_y = nullptr; expect(is(head_refused(&plain, q, true), "null tensor"), "a head's null g_y");
+        q = rp; q.g_w = nullptr; expect(is(head_refused(&plain, q, true), "null tensor"), "null g_w");
+        q = r; q.g_b = nullptr; expect(is(head_refused(&att, q, true), "null tensor"), "null g_b");
+        q = rp; q.g_att = spare; expect(says(head_refused(&plain, q, true), "exactly when up_y"), "g_att without up_y");
+        q = r; q.g_att = nullptr; expect(says(head_refused(&att, q, true), "exactly when up_y"), "up_y without g_att");
+        q = rp; q.g_q = spare; expect(says(head_refused(&plain, q, true), "only with g_att"), "g_q without g_att");
+        q = rp; q.g_x = const_cast<float *>(rp.g_y); expect(is(head_refused(&plain, q, true), "an output tensor overlaps an input"), "a head's g_x is g_y");
+        q = rp; q.g_w = const_cast<float *>(rp.w); expect(is(head_refused(&plain, q, true), "an output tensor overlaps an input"), "g_w is w");
+        q = rp; q.g_b = off(rp.g_w, 64); expect(is(head_refused(&plain, q, true), "two output tensors overlap"), "g_b inside g_w");
+        q = r; q.g_q = off(r.g_att, 1024); expect(is(head_refused(&att, q, true), "an output tensor overlaps an input"), "g_q inside g_att");
+        q = r; q.g_prev = r.g_x; expect(is(head_refused(&att, q, true), "two output tensors overlap"), "g_prev is g_x");
+        q = r; q.g_q = off(r.g_q, 1); expect(says(head_refused(&att, q, true), "aligned"), "misaligned g_q");
+        // the gate: 1024 floats each
+        float *a = spare, *b = spare + 1024, *o = spare + 4096, *o2 = spare + 8192, *acc = spare + 12288, *g_y = spare + 2048;
+        auto fw = [&](int64_t count, const float *x, const float *g, const float *y) { return gate_refused(count, false, x, g, nullptr, nullptr, y, nullptr); };
+        expect(!fw(1024, a, b, o) && !fw(1024, a, a, o) && !fw(1024, a, b, b + 1024), "accepted gate calls");
+        for (int64_t count : {(int64_t)0, (int64_t)-1, (int64_t)1 << 31}) expect(is(fw(count, a, b, o), GATE_COUNT_RULE), "the gate's count");
+        expect(is(fw(1024, nullptr, b, o), "null tensor") && is(fw(1024, a, nullptr, o), "null tensor") && is(fw(1024, a, b, nullptr), "null tensor"), "the gate's null tensors");
+        expect(is(fw(1024, a, b, a), "an output tensor overlaps an input") && is(fw(1024, a, b, b + 1023), "an output tensor overlaps an input"), "y over x, over the end of a");
+        expect(says(fw(1024, off(a, 2), b, o), "aligned") && says(fw(1024, a, b, off(o, 1)), "aligned"), "the gate's alignment");
+        auto bw = [&](int64_t count, const float *gy, const float *gacc, const float *gx, const float *ga) { return gate_refused(count, true, a, b, gy, gacc, gx, ga); };
+        expect(!bw(1024, g_y, acc, o, o2) && !bw(1024, g_y, nullptr, o, o2), "accepted gate backward calls; g_acc is optional");
+        expect(is(bw(1024, nullptr, acc, o, o2), "null tensor") && is(bw(0, nullptr, acc, o, o2), "null tensor"), "a null g_y is looked at before the count");
+        expect(is(bw(0, g_y, acc, o, o2), GATE_COUNT_RULE), "the gate's backward count");
+        expect(is(bw(1024, g_y, acc, nullptr, o2), "null tensor") && is(bw(1024, g_y, acc, o, nullptr), "null tensor"), "null g_x, null g_a");
+        expect(is(bw(1024, g_y, acc, acc, o2), "an output tensor overlaps an input") && is(bw(1024, g_y, acc, o, a), "an output tensor overlaps an input"), "g_x is g_acc, g_a is x");
+        expect(is(bw(1024, g_y, acc, o, o), "two output tensors overlap") && is(bw(1024, g_y, acc, o + 512, o), "two output tensors overlap"), "g_a over g_x");
+        expect(says(bw(1024, g_y, off(acc, 2), o, o2), "aligned"), "misaligned g_acc");
+    }
     if (!failures) printf("train_check: ok\n");
     return failures ? 1 : 0;
 }

@@ -439,12 +439,16 @@ class Engine:
 
     # ------------------------------------------------------------------------------------------ a trunk of ResidualBlocks, kept blocked
     @staticmethod
+    def _saved_bytes(name, struct, shape):
+        size = getattr(_lib.load(), name)(C.byref(struct(shape)))
+        if size < 0:                                   # no context, so no pmp_last_error
+            raise _lib.PmpError(int(size), "%s: unsupported shape %s" % (name, tuple(shape)))
+        return size
+
+    @staticmethod
     def trunk_saved_bytes(shape):
         """pmp_trunk_saved_bytes: the size of the saved-activation buffer of shape = (n, h, w, cin, [(cout, k), ...], pool)."""
-        size = _lib.load().pmp_trunk_saved_bytes(C.byref(_lib.trunk_shape(shape)))
-        if size < 0:                                   # no context, so no pmp_last_error
-            raise _lib.PmpError(int(size), "pmp_trunk_saved_bytes: unsupported shape %s" % (tuple(shape),))
-        return size
+        return Engine._saved_bytes("pmp_trunk_saved_bytes", _lib.trunk_shape, shape)
 
     def trunk_forward_device(self, shape, d_x, d_w, d_saved, d_y):
         """pmp_trunk_forward_device: d_w = 3 device pointers per block (w0, w2, wsc or None); d_saved trunk_saved_bytes(shape) bytes,
@@ -467,10 +471,7 @@ class Engine:
     @staticmethod
     def qtail_saved_bytes(shape):
         """pmp_qtail_saved_bytes: the size of the saved-activation buffer of shape = (n, h, w), the map of x4."""
-        size = _lib.load().pmp_qtail_saved_bytes(C.byref(_lib.qtail_shape(shape)))
-        if size < 0:                                   # no context, so no pmp_last_error
-            raise _lib.PmpError(int(size), "pmp_qtail_saved_bytes: unsupported shape %s" % (tuple(shape),))
-        return size
+        return Engine._saved_bytes("pmp_qtail_saved_bytes", _lib.qtail_shape, shape)
 
     def qtail_forward_device(self, shape, d_x4, d_w, d_saved, d_x9):
         """pmp_qtail_forward_device: d_w = 12 device pointers, w0, w2, wsc of q3, q4, q5 (wsc None), q6; d_saved

@@ -17,8 +17,7 @@ x4 is f32[n, 64, h, w] with h and w multiples of 16 (the nets: 16 x 16), the res
 the kernels' blocked layout in one opaque uint8 tensor that lives on the autograd context from forward to backward; x6 is rebuilt
 from x5 on the way back.  Streams are handled by torch_call.run(); one Engine serves one stream at a time.  torch is imported on use.
 """
-from . import torch_call
-from .torch_call import P, f32, lazy
+from .torch_call import block_weights, lazy, saved_chain_function
 
 # (cout, cin) of q3, q4, q5, q6; every convolution 3x3, the shortcut 1x1 where cin != cout
 CHANNELS = ((32, 64), (32, 128), (32, 32), (8, 32))
@@ -44,34 +43,8 @@ def shape_of(x4, blocks):
 @lazy
 def _function():
     """The autograd.Function, built on first use (torch is not imported before)."""
-    import torch
-
-    class QtailFn(torch.autograd.Function):
-        """(engine, x4, w0, w2, wsc-or-None of q3, q4, q5, q6) -> x9 f32[n, 8, h/2, w/2]"""
-
-        @staticmethod
-        def forward(ctx, engine, x4, *ws):
-            x_, ws_ = f32(x4, x4.device), [f32(t, x4.device) for t in ws]
-            shape = shape_of(x_, zip(ws_[0::3], ws_[1::3], ws_[2::3]))
-            n, h, w = shape
-            saved = torch.empty(engine.qtail_saved_bytes(shape), dtype=torch.uint8, device=x4.device)
-            x9 = torch.empty((n, 8, h // 2, w // 2), dtype=torch.float32, device=x4.device)
-            torch_call.run(engine, x4.device, lambda: engine.qtail_forward_device(shape, P(x_), [P(t) for t in ws_], P(saved), P(x9)))
-            ctx.engine, ctx.shape, ctx.saved, ctx.ws = engine, shape, saved, ws_
-            return x9
-
-        @staticmethod
-        @torch.autograd.function.once_differentiable
-        def backward(ctx, g_x9):
-            g = f32(g_x9, g_x9.device)
-            n, h, w = ctx.shape
-            g_x4 = torch.empty((n, 64, h, w), dtype=torch.float32, device=g.device) if ctx.needs_input_grad[1] else None
-            g_ws = [None if t is None else torch.empty_like(t) for t in ctx.ws]
-            torch_call.run(ctx.engine, g.device, lambda: ctx.engine.qtail_backward_device(
-                ctx.shape, P(ctx.saved), [P(t) for t in ctx.ws], P(g), P(g_x4), [P(t) for t in g_ws]))
-            return (None, g_x4) + tuple(g_ws)
-
-    return QtailFn
+    return saved_chain_function("QtailFn", "(engine, x4, w0, w2, wsc-or-None of q3, q4, q5, q6) -> x9 f32[n, 8, h/2, w/2]", "qtail", 0,
+                                lambda x4, ws: shape_of(x4, zip(ws[0::3], ws[1::3], ws[2::3])), lambda s: (s[0], 8, s[1] // 2, s[2] // 2))
 
 
 def qtail(engine, x4, blocks):
@@ -83,5 +56,4 @@ def qtail(engine, x4, blocks):
 
 def qtail_of(engine, net, x4):
     """The same with the weights of net.resblock_q3 .. resblock_q6 (Model_QBD.ResidualBlock modules, or q_net.QNet's)."""
-    sc = lambda m: m.shortcut[0].weight if len(m.shortcut) else None
-    return qtail(engine, x4, [(m.left[0].weight, m.left[2].weight, sc(m)) for m in (net.resblock_q3, net.resblock_q4, net.resblock_q5, net.resblock_q6)])
+    return qtail(engine, x4, [block_weights(m) for m in (net.resblock_q3, net.resblock_q4, net.resblock_q5, net.resblock_q6)])

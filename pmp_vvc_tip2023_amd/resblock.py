@@ -18,7 +18,7 @@ on use, so the package stays importable without it.
 """
 
 from . import torch_call
-from .torch_call import P, f32, lazy
+from .torch_call import P, block_weights, f32, lazy
 
 
 @lazy
@@ -66,5 +66,4 @@ def residual_block(engine, x, w0, w2, wsc=None):
 
 def residual_block_of(engine, module, x):
     """The same with the weights of a Model_QBD.ResidualBlock: module.left[0], module.left[2] and, if it has one, module.shortcut[0]."""
-    sc = module.shortcut[0].weight if len(module.shortcut) else None
-    return residual_block(engine, x, module.left[0].weight, module.left[2].weight, sc)
+    return residual_block(engine, x, *block_weights(module))

@@ -14,6 +14,7 @@ into the library's layouts and gradients back is done with torch ops.  The loss 
 nothing synchronises with the host.  torch is imported on use, so the package stays importable without it.
 """
 from . import _lib
+from .torch_call import P, run
 
 _FUNCTION = None
 
@@ -43,10 +44,10 @@ def _function():
             g_qt = torch.empty_like(qt_) if want and qt_ is not None else None
             g_bt = torch.empty_like(bt_) if want and bt_ is not None else None
             g_dire = torch.empty_like(dire_) if want and dire_ is not None else None
-            P = lambda t: None if t is None else t.data_ptr()
-            engine.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-            engine.train_loss_device(comp, qp, P(qt_), P(bt_), P(dire_), P(qt8_), P(msbt_), P(msdire_), n, out.data_ptr(),
-                                     out.data_ptr() + 8 * _lib.PMP_LOSS_NTERMS, P(g_qt), P(g_bt), P(g_dire), params=loss_params(params))
+            # ordered with torch's work on the legacy default stream too: a bare set_stream(0) would select the context's own stream
+            run(engine, dev, lambda: engine.train_loss_device(
+                comp, qp, P(qt_), P(bt_), P(dire_), P(qt8_), P(msbt_), P(msdire_), n, out.data_ptr(),
+                out.data_ptr() + 8 * _lib.PMP_LOSS_NTERMS, P(g_qt), P(g_bt), P(g_dire), params=loss_params(params)))
             ctx.grads = (g_qt, g_bt, g_dire)
             terms = out[:_lib.PMP_LOSS_NTERMS]
             ctx.mark_non_differentiable(terms)

@@ -16,40 +16,22 @@ block's intermediate t and output - stays blocked in one opaque uint8 tensor tha
 backward; the pool's backward is recomputed from it (first maximum of a window, torch's rule).  The results are those of the chain,
 bit for bit.  Streams are handled by torch_call.run(); one Engine serves one stream at a time.  torch is imported on use.
 """
-from . import torch_call
-from .torch_call import P, f32, lazy
+from .torch_call import block_weights, lazy, saved_chain_function
 
 
 @lazy
 def _function():
     """The autograd.Function, built on first use (torch is not imported before)."""
-    import torch
+    def _shape_of(x, ws, pool):
+        n, cin, h, w = x.shape
+        return (n, h, w, cin, [(w0.shape[0], w0.shape[2]) for w0 in ws[0::3]], 1 if pool else 0)
 
-    class TrunkFn(torch.autograd.Function):
-        """(engine, pool, x, w0, w2, wsc-or-None of block 0, of block 1, ...) -> y f32[n, cout_last, h(/2), w(/2)]"""
+    def _y_shape(shape):
+        n, h, w, _, blocks, pool = shape
+        return (n, blocks[-1][0], h // 2 if pool else h, w // 2 if pool else w)
 
-        @staticmethod
-        def forward(ctx, engine, pool, x, *ws):
-            x_, ws_ = f32(x, x.device), [f32(t, x.device) for t in ws]
-            n, cin, h, w = x_.shape
-            shape = (n, h, w, cin, [(w0.shape[0], w0.shape[2]) for w0 in ws_[0::3]], 1 if pool else 0)
-            saved = torch.empty(engine.trunk_saved_bytes(shape), dtype=torch.uint8, device=x.device)
-            y = torch.empty((n, shape[4][-1][0], h // 2 if pool else h, w // 2 if pool else w), dtype=torch.float32, device=x.device)
-            torch_call.run(engine, x.device, lambda: engine.trunk_forward_device(shape, P(x_), [P(t) for t in ws_], P(saved), P(y)))
-            ctx.engine, ctx.shape, ctx.saved, ctx.ws = engine, shape, saved, ws_
-            return y
-
-        @staticmethod
-        def backward(ctx, g_y):
-            g = f32(g_y, g_y.device)
-            n, h, w, cin = ctx.shape[:4]
-            g_x = torch.empty((n, cin, h, w), dtype=torch.float32, device=g.device) if ctx.needs_input_grad[2] else None
-            g_ws = [None if t is None else torch.empty_like(t) for t in ctx.ws]
-            torch_call.run(ctx.engine, g.device, lambda: ctx.engine.trunk_backward_device(
-                ctx.shape, P(ctx.saved), [P(t) for t in ctx.ws], P(g), P(g_x), [P(t) for t in g_ws]))
-            return (None, None, g_x) + tuple(g_ws)
-
-    return TrunkFn
+    return saved_chain_function("TrunkFn", "(engine, pool, x, w0, w2, wsc-or-None of block 0, of block 1, ...) -> y f32[n, cout_last, h(/2), w(/2)]",
+                                "trunk", 1, _shape_of, _y_shape)
 
 
 def trunk(engine, x, blocks, pool=False):
@@ -62,5 +44,4 @@ def trunk(engine, x, blocks, pool=False):
 
 def trunk_of(engine, sequential, x, pool=False):
     """The same with the weights of an nn.Sequential of Model_QBD.ResidualBlock modules (trunk_M1, trunk_B3, ...)."""
-    sc = lambda m: m.shortcut[0].weight if len(m.shortcut) else None
-    return trunk(engine, x, [(m.left[0].weight, m.left[2].weight, sc(m)) for m in sequential], pool)
+    return trunk(engine, x, [block_weights(m) for m in sequential], pool)

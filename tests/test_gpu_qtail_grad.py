@@ -12,7 +12,6 @@ The gradients far from g_x9 (q3's, q4's, g_x4) sit at a few thousandths of their
 may carry, is pushed through four blocks' absolute-value companions and dominates there.  What holds those tensors tightly is the
 exact cases.
 """
-import ctypes as C
 import functools
 
 import numpy as np
@@ -31,58 +30,7 @@ pytestmark = pytest.mark.gpu
 
 P, up, nan, num, check_bits = R.P, R.up, R.nan, R.num, R.check_bits
 eng = R.engine_fixture(poison=1)
-WKEYS = [("%s_%d" % (nm, i), 3 * i + j) for i in range(4) for j, nm in enumerate(("g_w0", "g_w2", "g_wsc")) if (i, j) != (2, 2)]
-
-
-class Dev:
-    """A tail case on the device: inputs, NaN-filled outputs and a 0xFF-filled saved buffer."""
-
-    def __init__(self, e, c):
-        self.shape = n, h, w = c["shape"]
-        self.x4, self.g_x9 = up(c["x4"]), up(c["g_x9"])
-        self.w = [up(a) for blk in c["blocks"] for a in blk]
-        self.saved = torch.full((e.qtail_saved_bytes(self.shape),), 0xFF, dtype=torch.uint8, device="cuda")
-        self.x9, self.g_x4 = nan(n, 8, h // 2, w // 2), nan(n, 64, h, w)
-        self.g_w = [None if a is None else nan(*a.shape) for a in self.w]
-        R.torch_done()
-
-    def forward(self, e):
-        e.qtail_forward_device(self.shape, P(self.x4), [P(a) for a in self.w], P(self.saved), P(self.x9))
-
-    def backward(self, e, want_g_x=True):
-        e.qtail_backward_device(self.shape, P(self.saved), [P(a) for a in self.w], P(self.g_x9), P(self.g_x4) if want_g_x else None,
-                                [P(a) for a in self.g_w])
-
-    def unpack(self, e):
-        n, h, w = self.shape
-        s = [nan(n, ch, h, w) for ch in (64, 32, 32, 32, 32, 32, 32)] + [nan(n, 8, h // 2, w // 2) for _ in range(2)]
-        R.torch_done()
-        for i, a in enumerate(s):
-            e.qtail_unpack_device(self.shape, P(self.saved), i, P(a))
-        return s
-
-    def results(self, e):
-        """Everything the calls produced, flat like qtail_cases.flat (g_x4 the untouched NaN buffer if it was not asked for)."""
-        s = self.unpack(e)
-        e.synchronize()
-        d = {"x9": num(self.x9), "g_x4": num(self.g_x4)}
-        d.update({"s%d" % i: num(a) for i, a in enumerate(s)})
-        d.update({k: num(self.g_w[j]) for k, j in WKEYS})
-        return d
-
-    def outputs(self):
-        return [("x9", self.x9), ("g_x4", self.g_x4), ("d_saved", self.saved)] + [("g_w%d" % i, a) for i, a in enumerate(self.g_w) if a is not None]
-
-    def inputs(self, c):
-        return [("x4", self.x4, c["x4"]), ("g_x9", self.g_x9, c["g_x9"])] + \
-               [("w%d" % i, a, src) for i, (a, src) in enumerate(zip(self.w, [a for blk in c["blocks"] for a in blk])) if a is not None]
-
-
-def run(e, c, want_g_x=True):
-    d = Dev(e, c)
-    d.forward(e)
-    d.backward(e, want_g_x)
-    return d.results(e)
+Dev, run = R.TailDev, R.TailDev.run
 
 
 @functools.lru_cache(maxsize=None)
@@ -258,34 +206,15 @@ def test_same_bits_on_every_run_stream_and_context(eng):
 
 # ---- 6. refusals: PMP_E_INVALID before any launch, nothing written
 def test_refusals_write_nothing(eng):
-    from pmp_vvc_tip2023_amd import _lib
     c = exact("nets")[0]
     d = Dev(eng, c)                                                    # never run: everything it owns must stay as filled
     ok = Dev(eng, c)                                                   # a finished forward, for the calls that read d_saved
     ok.forward(eng)
     eng.synchronize()
     saved_ok = ok.saved.clone()
-    dense = nan(*ok.x4.shape)
+    dense = nan(*ok.x.shape)
     other, other_g = up(c["blocks"][0][2]), nan(*c["blocks"][0][2].shape)
-    arr = lambda ps: (C.c_void_p * len(ps))(*ps)
-
-    def call(nm, what, shape=None, null_shape=False, w=None, g_w=None, null_w=False, null_g_w=False, index=1, **swap):
-        t = d if what == "forward" else ok
-        p = {"x4": P(t.x4), "saved": P(t.saved), "x9": P(t.x9), "g_x9": P(t.g_x9), "g_x4": P(t.g_x4), "dense": P(dense)}
-        p.update(swap)
-        ws, gws = [P(a) for a in t.w], [P(a) for a in t.g_w]
-        for i, v in (w or {}).items():
-            ws[i] = v
-        for i, v in (g_w or {}).items():
-            gws[i] = v
-        s = _lib.qtail_shape(shape or t.shape)
-        sp = None if null_shape else C.byref(s)
-        wa, ga = None if null_w else arr(ws), None if null_g_w else arr(gws)
-        if what == "forward":
-            return eng.lib.pmp_qtail_forward_device(eng.h, sp, p["x4"], wa, p["saved"], p["x9"])
-        if what == "backward":
-            return eng.lib.pmp_qtail_backward_device(eng.h, sp, p["saved"], wa, p["g_x9"], p["g_x4"], ga)
-        return eng.lib.pmp_qtail_unpack_device(eng.h, sp, p["saved"], index, p["dense"])
+    call = R.chain_refusal_call(eng, Dev, lambda nm, what: d if what == "forward" else ok, dense)
 
     bad_shapes = [(0, 16, 16), (257, 16, 16), (1, 8, 16), (1, 24, 16), (1, 272, 16), (1, 16, 0), (1, 16, 40)]
     tries = []
@@ -300,13 +229,13 @@ def test_refusals_write_nothing(eng):
                   ("q4 without its wsc", "nets", what, dict(w={5: None}, g_w={5: None})),
                   ("misaligned w0", "nets", what, dict(w={0: P(d.w[0]) + 2}))]
     tries += [("null x4", "nets", "forward", dict(x4=None)), ("null x9", "nets", "forward", dict(x9=None)),
-              ("x9 overlaps x4", "nets", "forward", dict(x9=P(d.x4) + 64)), ("x9 inside d_saved", "nets", "forward", dict(x9=P(d.saved) + 256)),
-              ("d_saved is x4", "nets", "forward", dict(saved=P(d.x4))), ("misaligned x4", "nets", "forward", dict(x4=P(d.x4) + 2)),
+              ("x9 overlaps x4", "nets", "forward", dict(x9=P(d.x) + 64)), ("x9 inside d_saved", "nets", "forward", dict(x9=P(d.saved) + 256)),
+              ("d_saved is x4", "nets", "forward", dict(saved=P(d.x))), ("misaligned x4", "nets", "forward", dict(x4=P(d.x) + 2)),
               ("null g_x9", "nets", "backward", dict(g_x9=None)), ("null d_g_w", "nets", "backward", dict(null_g_w=True)),
               ("null g_w0 of q4", "nets", "backward", dict(g_w={3: None})), ("a g_wsc for q5", "nets", "backward", dict(g_w={8: P(other_g)})),
               ("no g_wsc for q4", "nets", "backward", dict(g_w={5: None})),
-              ("g_x4 over g_x9", "nets", "backward", dict(g_x4=P(ok.g_x9))), ("g_x4 inside d_saved", "nets", "backward", dict(g_x4=P(ok.saved) + 1024)),
-              ("g_w0 is g_w2", "nets", "backward", dict(g_w={6: P(ok.g_w[7])})), ("misaligned g_x9", "nets", "backward", dict(g_x9=P(ok.g_x9) + 2)),
+              ("g_x4 over g_x9", "nets", "backward", dict(g_x4=P(ok.g_y))), ("g_x4 inside d_saved", "nets", "backward", dict(g_x4=P(ok.saved) + 1024)),
+              ("g_w0 is g_w2", "nets", "backward", dict(g_w={6: P(ok.g_w[7])})), ("misaligned g_x9", "nets", "backward", dict(g_x9=P(ok.g_y) + 2)),
               ("null dense", "nets", "unpack", dict(dense=None)), ("index -1", "nets", "unpack", dict(index=-1)),
               ("index 9", "nets", "unpack", dict(index=9)), ("dense inside d_saved", "nets", "unpack", dict(dense=P(ok.saved) + 512)),
               ("misaligned dense", "nets", "unpack", dict(dense=P(dense) + 2))]

@@ -6,7 +6,6 @@ every result - y, every saved t_i and out_i, g_x, every weight gradient - must e
 left out, in poisoned workspaces, into NaN-filled outputs and a NaN-filled d_saved.  On float values the trunk must equal the chain of
 pmp_resblock_*_device calls through dense tensors with torch's max_pool2d, again bit for bit: both sides run the same convolution
 and weight-gradient kernels on the same values in the same order, and everything in between is a copy, a select or a maximum."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -92,7 +91,6 @@ def test_same_bits_on_every_run_stream_and_context(eng):
 
 # ---- 5. refusals: PMP_E_INVALID before any launch, nothing written
 def test_refusals_write_nothing(eng):
-    from pmp_vvc_tip2023_amd import _lib
     cs = {nm: exact(nm)[0] for nm in ("one_pool", "b_like")}           # identity shortcuts only / conv shortcuts only
     dev = {nm: Dev(eng, c) for nm, c in cs.items()}
     ok = Dev(eng, cs["one_pool"])                                      # a finished forward, for the calls that read d_saved
@@ -102,25 +100,7 @@ def test_refusals_write_nothing(eng):
     dense = nan(*ok.x.shape)
     other = up(cs["b_like"]["blocks"][0][2])                           # some shortcut tensor
     other_g = nan(*other.shape)
-    arr = lambda ps: (C.c_void_p * len(ps))(*ps)
-
-    def call(nm, what, shape=None, null_shape=False, w=None, g_w=None, null_w=False, null_g_w=False, index=1, **swap):
-        d = ok if what != "forward" and nm == "one_pool" else dev[nm]
-        p = {"x": P(d.x), "saved": P(d.saved), "y": P(d.y), "g_y": P(d.g_y), "g_x": P(d.g_x), "dense": P(dense)}
-        p.update(swap)
-        ws, gws = [P(a) for a in d.w], [P(a) for a in d.g_w]
-        for i, v in (w or {}).items():
-            ws[i] = v
-        for i, v in (g_w or {}).items():
-            gws[i] = v
-        s = _lib.trunk_shape(shape or d.shape)
-        sp = None if null_shape else C.byref(s)
-        wa, ga = None if null_w else arr(ws), None if null_g_w else arr(gws)
-        if what == "forward":
-            return eng.lib.pmp_trunk_forward_device(eng.h, sp, p["x"], wa, p["saved"], p["y"])
-        if what == "backward":
-            return eng.lib.pmp_trunk_backward_device(eng.h, sp, p["saved"], wa, p["g_y"], p["g_x"], ga)
-        return eng.lib.pmp_trunk_unpack_device(eng.h, sp, p["saved"], index, p["dense"])
+    call = R.chain_refusal_call(eng, Dev, lambda nm, what: ok if what != "forward" and nm == "one_pool" else dev[nm], dense)
 
     n, h, w, cin, blocks, pool = cs["one_pool"]["shape"]
     bad_shapes = [(0, h, w, cin, blocks, pool), (257, h, w, cin, blocks, pool), (n, 8, w, cin, blocks, pool), (n, 24, w, cin, blocks, pool),

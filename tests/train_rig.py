@@ -1,6 +1,7 @@
-"""The rig of the training calls' GPU tests (test_gpu_resblock_grad, test_gpu_trunk_grad, test_gpu_stem_grad and the two sweeps): the
-engine fixture, tensors to and from the device, the bit check, a case of each call on the device (BlockDev, TrunkDev, StemDev: the
-only parts that name a call's tensors), the determinism check and the harness of the refusal tests.  A plain module: every test file
+"""The rig of the training calls' GPU tests (test_gpu_resblock_grad, test_gpu_trunk_grad, test_gpu_qtail_grad, test_gpu_stem_grad and the
+two sweeps): the engine fixture, tensors to and from the device, the bit check, a case of each call on the device (BlockDev, ChainDev
+as TrunkDev and TailDev, StemDev: the only parts that name a call's tensors), the determinism check and the harness of the refusal
+tests.  A plain module: every test file
 keeps its own cases, bounds and tables."""
 import ctypes as C
 
@@ -162,68 +163,109 @@ def host_calls(e, c):
     return rf, rb, o
 
 
-# ---- a trunk: pmp_trunk_forward_device / pmp_trunk_backward_device / pmp_trunk_unpack_device
-class TrunkDev:
-    """A trunk case on the device: inputs, NaN-filled outputs and a NaN-filled saved buffer (0xFF bytes)."""
+# ---- a chain with a saved buffer: pmp_trunk_* and pmp_qtail_* (forward_device / backward_device / unpack_device)
+class ChainDev:
+    """A case of a chain on the device: inputs, NaN-filled outputs and a saved buffer of 0xFF bytes (NaNs, read as floats).  The two
+    variants say which calls (CALLS), how the case names x, y, g_y and g_x (NAMES), the shapes and unpack's indices."""
 
-    def __init__(self, e, c, pool=None):
-        n, h, w, cin, blocks, p = c["shape"]
-        self.shape = (n, h, w, cin, blocks, p if pool is None else pool)
-        self.x, self.g_y = up(c["x"]), up(c["g_y"])
+    def __init__(self, e, c, shape, y_shape):
+        self.shape = shape
+        self.x, self.g_y = up(c[self.NAMES[0]]), up(c[self.NAMES[2]])
         self.w = [up(a) for blk in c["blocks"] for a in blk]
-        self.saved = torch.full((e.trunk_saved_bytes(self.shape),), 0xFF, dtype=torch.uint8, device="cuda")
-        self.y = nan(*T.y_shape(self.shape))
-        self.g_x = nan(n, cin, h, w)
+        self.saved = torch.full((self.engine_call(e, "saved_bytes")(shape),), 0xFF, dtype=torch.uint8, device="cuda")
+        self.y = nan(*y_shape)
+        self.g_x = nan(*self.x.shape)
         self.g_w = [None if a is None else nan(*a.shape) for a in self.w]
         torch_done()
 
+    def engine_call(self, e, what):
+        return getattr(e, "%s_%s" % (self.CALLS, what))
+
     def forward(self, e):
-        e.trunk_forward_device(self.shape, P(self.x), [P(a) for a in self.w], P(self.saved), P(self.y))
+        self.engine_call(e, "forward_device")(self.shape, P(self.x), [P(a) for a in self.w], P(self.saved), P(self.y))
 
     def backward(self, e, want_g_x=True):
-        e.trunk_backward_device(self.shape, P(self.saved), [P(a) for a in self.w], P(self.g_y), P(self.g_x) if want_g_x else None,
-                                [P(a) for a in self.g_w])
+        self.engine_call(e, "backward_device")(self.shape, P(self.saved), [P(a) for a in self.w], P(self.g_y), P(self.g_x) if want_g_x else None,
+                                               [P(a) for a in self.g_w])
+
+    def dense(self, e, shapes):
+        """shapes = {index: shape} -> [saved tensor `index` as a dense device tensor], through unpack_device into NaN-filled buffers."""
+        out = [nan(*shape) for shape in shapes.values()]
+        torch_done()
+        for i, a in zip(shapes, out):
+            self.engine_call(e, "unpack_device")(self.shape, P(self.saved), i, P(a))
+        return out
+
+    @classmethod
+    def run(cls, e, c, want_g_x=True, **kw):
+        """forward and backward of a fresh case -> its flat results"""
+        d = cls(e, c, **kw)
+        d.forward(e)
+        d.backward(e, want_g_x)
+        return d.results(e)
+
+    def outputs(self):
+        """-> [(name, tensor)]: what the calls write."""
+        return [(self.NAMES[1], self.y), (self.NAMES[3], self.g_x), ("d_saved", self.saved)] + \
+               [("g_w%d" % i, a) for i, a in enumerate(self.g_w) if a is not None]
+
+    def inputs(self, c):
+        """-> [(name, tensor, its values in the case)]"""
+        return [(self.NAMES[0], self.x, c[self.NAMES[0]]), (self.NAMES[2], self.g_y, c[self.NAMES[2]])] + \
+               [("w%d" % i, a, src) for i, (a, src) in enumerate(zip(self.w, [a for blk in c["blocks"] for a in blk])) if a is not None]
+
+
+class TrunkDev(ChainDev):
+    """A trunk case (trunk_cases) on the device."""
+    CALLS, NAMES = "trunk", ("x", "y", "g_y", "g_x")
+
+    def __init__(self, e, c, pool=None):
+        n, h, w, cin, blocks, p = c["shape"]
+        shape = (n, h, w, cin, blocks, p if pool is None else pool)
+        super().__init__(e, c, shape, T.y_shape(shape))
 
     def unpack(self, e):
-        """-> (t, out): lists of dense device tensors, through pmp_trunk_unpack_device into NaN-filled buffers."""
+        """-> (t, out): lists of dense device tensors."""
         n, h, w = self.shape[:3]
-        ts, outs = [], []
-        for i, (cout, _) in enumerate(self.shape[4]):
-            ts.append(nan(n, cout, h, w))
-            outs.append(nan(n, cout, h, w))
-            torch_done()
-            e.trunk_unpack_device(self.shape, P(self.saved), 2 * i + 1, P(ts[-1]))
-            e.trunk_unpack_device(self.shape, P(self.saved), 2 * i + 2, P(outs[-1]))
-        return ts, outs
+        d = self.dense(e, {1 + j: (n, cout, h, w) for i, (cout, _) in enumerate(self.shape[4]) for j in (2 * i, 2 * i + 1)})
+        return d[0::2], d[1::2]
 
     def results(self, e, ts=None, outs=None):
         """Everything the calls produced, flat like trunk_cases.flat (g_x the untouched NaN buffer if it was not asked for)."""
         if ts is None:
             ts, outs = self.unpack(e)
-        x0 = nan(*self.x.shape)
-        torch_done()
-        e.trunk_unpack_device(self.shape, P(self.saved), 0, P(x0))
+        x0, = self.dense(e, {0: self.x.shape})
         e.synchronize()
         r = T.flat({"y": num(self.y), "g_x": num(self.g_x), "t": [num(a) for a in ts], "out": [num(a) for a in outs],
                     "g_w": [tuple(num(a) for a in self.g_w[3 * i:3 * i + 3]) for i in range(len(ts))]})
         r["x"] = num(x0)
         return r
 
-    def outputs(self):
-        """-> [(name, tensor)]: what the calls write."""
-        return [("y", self.y), ("g_x", self.g_x), ("d_saved", self.saved)] + [("g_w%d" % i, a) for i, a in enumerate(self.g_w) if a is not None]
 
-    def inputs(self, c):
-        """-> [(name, tensor, its values in the case)]"""
-        return [("x", self.x, c["x"]), ("g_y", self.g_y, c["g_y"])] + \
-               [("w%d" % i, a, src) for i, (a, src) in enumerate(zip(self.w, [a for blk in c["blocks"] for a in blk])) if a is not None]
+class TailDev(ChainDev):
+    """A QT tail's case (qtail_cases) on the device."""
+    CALLS, NAMES = "qtail", ("x4", "x9", "g_x9", "g_x4")
+    WKEYS = [("%s_%d" % (nm, i), 3 * i + j) for i in range(4) for j, nm in enumerate(("g_w0", "g_w2", "g_wsc")) if (i, j) != (2, 2)]
+
+    def __init__(self, e, c):
+        n, h, w = c["shape"]
+        super().__init__(e, c, c["shape"], (n, 8, h // 2, w // 2))
+
+    def unpack(self, e):
+        n, h, w = self.shape
+        return self.dense(e, {i: (n, ch, h, w) if i < 7 else (n, 8, h // 2, w // 2) for i, ch in enumerate((64, 32, 32, 32, 32, 32, 32, 8, 8))})
+
+    def results(self, e):
+        """Everything the calls produced, flat like qtail_cases.flat (g_x4 the untouched NaN buffer if it was not asked for)."""
+        s = self.unpack(e)
+        e.synchronize()
+        d = {"x9": num(self.y), "g_x4": num(self.g_x)}
+        d.update({"s%d" % i: num(a) for i, a in enumerate(s)})
+        d.update({k: num(self.g_w[j]) for k, j in self.WKEYS})
+        return d
 
 
-def run_trunk(e, c, want_g_x=True, pool=None):
-    d = TrunkDev(e, c, pool)
-    d.forward(e)
-    d.backward(e, want_g_x)
-    return d.results(e)
+run_trunk = TrunkDev.run
 
 
 def chain(e, c, ts_in, outs_in):
@@ -347,6 +389,35 @@ def refuse_all(eng, tries, call):
         assert eng.lib.pmp_last_error(eng.h), what
     eng.synchronize()
     torch.cuda.synchronize()
+
+
+def chain_refusal_call(eng, variant, pick, dense):
+    """-> call(nm, what, ...) of a chain's refusal test, through the C ABI: "forward", "backward" or "unpack" of pick(nm, what), a
+    TrunkDev or TailDev (variant: its class), the keyword arguments replacing what the call passes: shape (null_shape: none), w and g_w
+    {position in the array: pointer} (null_w, null_g_w: no array), index, and by name x, y, g_y, g_x (as in NAMES), saved and dense."""
+    from pmp_vvc_tip2023_amd import _lib
+    x, y, g_y, g_x = variant.NAMES
+    arr = lambda ps: (C.c_void_p * len(ps))(*ps)
+    fn = lambda what: getattr(eng.lib, "pmp_%s_%s_device" % (variant.CALLS, what))
+
+    def call(nm, what, shape=None, null_shape=False, w=None, g_w=None, null_w=False, null_g_w=False, index=1, **swap):
+        d = pick(nm, what)
+        p = {x: P(d.x), "saved": P(d.saved), y: P(d.y), g_y: P(d.g_y), g_x: P(d.g_x), "dense": P(dense)}
+        p.update(swap)
+        ws, gws = [P(a) for a in d.w], [P(a) for a in d.g_w]
+        for i, v in (w or {}).items():
+            ws[i] = v
+        for i, v in (g_w or {}).items():
+            gws[i] = v
+        s = getattr(_lib, variant.CALLS + "_shape")(shape or d.shape)
+        sp = None if null_shape else C.byref(s)
+        wa, ga = None if null_w else arr(ws), None if null_g_w else arr(gws)
+        if what == "forward":
+            return fn(what)(eng.h, sp, p[x], wa, p["saved"], p[y])
+        if what == "backward":
+            return fn(what)(eng.h, sp, p["saved"], wa, p[g_y], p[g_x], ga)
+        return fn(what)(eng.h, sp, p["saved"], index, p["dense"])
+    return call
 
 
 def check_untouched(nm, outputs, inputs, skip=()):
