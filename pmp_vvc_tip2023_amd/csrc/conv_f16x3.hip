@@ -56,18 +56,20 @@ __device__ __forceinline__ void h2_plan(StagePlanH<KH, KW, NTHR> &p, size_t plan
     }
 }
 
-template <int KH, int KW, int NTHR = 256>
+template <int KH, int KW, int NTHR = 256, bool OPQ = false>
 __device__ __forceinline__ void h2_stage_load(const StagePlanH<KH, KW, NTHR> &p, const unsigned short *__restrict__ grp,
                                               u32x4 (&r)[GeoH<KH, KW, 16, NTHR>::NLD], int k0 = 0, int k1 = 1 << 20)
 {
 #pragma unroll
     for (int k = 0; k < GeoH<KH, KW, 16, NTHR>::NLD; ++k) {
         if (k < k0 || k >= k1) continue;   // folds away: callers pass constants into unrolled code
-        r[k] = *reinterpret_cast<const u32x4 *>(grp + p.off[k]);   // default cache policy: the non-temporal hint measured 1 % slower
+        unsigned off = p.off[k];
+        if (OPQ) asm volatile("" : "+v"(off));   // opaque: the offset stays ONE register across the group loop (hipcc otherwise keeps its 64-bit extension, NLD more registers)
+        r[k] = *reinterpret_cast<const u32x4 *>(grp + off);   // default cache policy: the non-temporal hint measured 1 % slower
     }
 }
 
-template <int KH, int KW, int NTHR = 256>
+template <int KH, int KW, int NTHR = 256, bool OPQ = false>
 __device__ __forceinline__ void h2_stage_store(const StagePlanH<KH, KW, NTHR> &p, u32x4 *lds, const u32x4 (&r)[GeoH<KH, KW, 16, NTHR>::NLD],
                                                int k0 = 0, int k1 = 1 << 20)
 {
@@ -75,13 +77,15 @@ __device__ __forceinline__ void h2_stage_store(const StagePlanH<KH, KW, NTHR> &p
 #pragma unroll
     for (int k = 0; k < G::NLD; ++k) {
         if (k < k0 || k >= k1) continue;
-        const int i = min((int)threadIdx.x + k * NTHR, G::PIECES);   // pieces past the tile all land in one spare slot
+        int tid = threadIdx.x;
+        if (OPQ) asm volatile("" : "+v"(tid));   // opaque: the LDS addresses are formed at the store, not kept across the group loop
+        const int i = min(tid + k * NTHR, G::PIECES);   // pieces past the tile all land in one spare slot
         const u32x4 z = {0u, 0u, 0u, 0u};
         lds[i] = ((p.valid >> k) & 1u) ? r[k] : z;   // LDS image: [split][pixel][2 halves], linear
     }
 }
 
-template <int KH, int KW, int NT, bool LEAN = false>
+template <int KH, int KW, int NT, bool LEAN = false, bool SLIM = false>
 __device__ __forceinline__ void h2_accumulate(const unsigned short *__restrict__ x, size_t plane_stride,
                                               const unsigned short *__restrict__ wpk, int C, int H, int W, int n, int ty,
                                               int tx, u32x4 *lds, f32x4 (&acc)[WaveTile<NT>::RW][WaveTile<NT>::CW])
@@ -130,7 +134,7 @@ __device__ __forceinline__ void h2_accumulate(const unsigned short *__restrict__
     __syncthreads();
     const int pb = ((rh * RW * G::TW + xl) * 2 + (g & 1)) * 16;   // bytes inside a split plane, tap (0,0)
     int stream = 0;
-    int tapsel = g >> 1;
+    int tapsel = SLIM ? -(g >> 1) : g >> 1;
     constexpr int O_LAST = (((G::TAPS - 1) / KW) * G::TW + (G::TAPS - 1) % KW) * 32;   // byte offset of the last tap
     f16x8 x0[RW], x1[RW];   // pixel fragments of the current K-step (split 0 / split 1)
 
@@ -153,6 +157,8 @@ __device__ __forceinline__ void h2_accumulate(const unsigned short *__restrict__
             int tA = 2 * j, tB = 2 * j + 1;
             if (MODE == 0 && tB >= G::TAPS) tB = tA;
             const int oA = ((tA / KW) * G::TW + tA % KW) * 32, oB = ((tB / KW) * G::TW + tB % KW) * 32;
+            // SLIM: tapsel is an all-ones mask there - an AND and an add with literals instead of a select between two constants held in registers
+            if (SLIM) return buf + (oA + pb) + (tapsel & (oB - oA));
             return buf + (tapsel ? oB : oA) + pb;
         };
         if constexpr (LEAN) {
@@ -160,6 +166,11 @@ __device__ __forceinline__ void h2_accumulate(const unsigned short *__restrict__
             // waves of the SIMD cover the LDS round trip), both weight splits double-buffered one K-step ahead, and the
             // cross-group tap read from the partner buffer instead of carried in 64 registers - with a barrier before that
             // buffer's first rolling store.
+            // SLIM (the 5x5 kernels of this form): at 5x5 hipcc kept, across the group loop, every plan offset as a 64-bit pair (its zero
+            // extension is loop-invariant), the staging threads' LDS addresses and the K-steps' tap offsets as constants in registers
+            // (v_cndmask takes no literal) - 33 spilled registers, reloaded behind s_waitcnt vmcnt(0) in front of the weight and halo
+            // requests.  With the offsets and the lane id opaque at their use and the tap offset as mask arithmetic the kernels have no
+            // spilled register and no scratch (tests/test_conv5_resources_cpu.py); the results are the same bits.
             constexpr int RS = 2, SUB = RW / RS;   // 2-row sub-steps: 4-row ones spill (-15 %), 1-row ones expose more LDS round trips (-1 %)
             const char *part = reinterpret_cast<const char *>(lds + bprev * G::BUF);
             if (NK == 0 && FETCH) h2_stage_load<KH, KW, NTHR>(plan, nxt_grp, rl);   // 1x1 source, even group: only fetch the partner group
@@ -193,9 +204,9 @@ __device__ __forceinline__ void h2_accumulate(const unsigned short *__restrict__
                         for (int nt = 0; nt < CW; ++nt) w0[nt] = w0n[nt];
 #pragma unroll
                         for (int nt = 0; nt < CW; ++nt) { w1n[nt] = wf[(1 * NT + nt) * 64]; w0n[nt] = wf[(0 * NT + nt) * 64]; }
-                        if (FETCH) h2_stage_load<KH, KW, NTHR>(plan, nxt_grp, rl, ks * PER, (ks + 1) * PER);   // slices: one burst per group measured 1 % slower here
+                        if (FETCH) h2_stage_load<KH, KW, NTHR, SLIM>(plan, nxt_grp, rl, ks * PER, (ks + 1) * PER);   // slices: one burst per group measured 1 % slower here
                         if (more && ks >= LAG)
-                            h2_stage_store<KH, KW, NTHR>(plan, lds + ((cb + 1) & 1) * G::BUF, rs, (ks - LAG) * PER, (ks - LAG + 1) * PER);
+                            h2_stage_store<KH, KW, NTHR, SLIM>(plan, lds + ((cb + 1) & 1) * G::BUF, rs, (ks - LAG) * PER, (ks - LAG + 1) * PER);
                     } else if (h == SUB - 1) {
 #pragma unroll
                         for (int nt = 0; nt < CW; ++nt) w1[nt] = w1n[nt];
@@ -347,13 +358,19 @@ __device__ __forceinline__ void h2_epilogue(const ConvX6Args &a, f32x4 (&acc)[Wa
 // Instead of the general staging pipeline (five barriers, its own plan, weights and staging registers) the whole 16x16 x 32 ch
 // tile goes to LDS at once - no halo - and each wave runs that K-step in 2-row sub-steps.  Same MFMA order per accumulator as
 // the general pass (x0*w1, x0*w0, x1*w0 after the main pass), so the results are bit-identical.
-template <int NT>
+// GEN (the 5x5 kernel with a shortcut source of any width, <5,5,4,1,0>): the same pass once per K-step of the general 1x1 pass - a pair of
+// channel groups where their count is even, else one group, which then fills both halves of the tile as the zero-padded tap pair of the
+// general pass reads one pixel twice - in that pass's order and from its weight stream: the same bits, without its plan, staging
+// pipeline and second weight set, which spilled 57-82 registers behind a 168-VGPR main pass.
+template <int NT, bool OPQ = false>
 __device__ __forceinline__ void h2_shortcut32(const ConvX6Args &a, int n, int ty, int tx, u32x4 *lds,
                                               f32x4 (&acc)[WaveTile<NT>::RW][WaveTile<NT>::CW])
 {
     typedef WaveTile<NT> WT;
     constexpr int RW = WT::RW, CW = WT::CW;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, xl = lane & 15, g = lane >> 4;
+    int tid = threadIdx.x;
+    if (OPQ) asm volatile("" : "+v"(tid));   // opaque, as in h2_epilogue: none of this pass's lane arithmetic is live in the main pass's K-loop
+    const int lane = tid & 63, wave = tid >> 6, xl = lane & 15, g = lane >> 4;
     const int rh = wave % WT::RSPLIT, ch = wave / WT::RSPLIT;
     const int W = a.W;
     const size_t grp_sz = (size_t)a.H * W * 16;
@@ -396,8 +413,73 @@ __device__ __forceinline__ void h2_shortcut32(const ConvX6Args &a, int n, int ty
     }
 }
 
+// The same pass for a shortcut source of ANY width (the 5x5 kernel <5,5,4,1,0>), once per K-step of the general 1x1 pass: a pair of channel
+// groups where their count is even, else one group, which then fills both halves of the tile as the zero-padded tap pair of the general
+// pass reads one pixel twice - in that pass's order and from its weight stream, so the same bits, without its plan, staging pipeline and
+// second weight set, which spilled 57-82 registers behind a 168-VGPR main pass.
+template <int NT>
+__device__ __forceinline__ void h2_shortcut_any(const ConvX6Args &a, int n, int ty, int tx, u32x4 *lds,
+                                                f32x4 (&acc)[WaveTile<NT>::RW][WaveTile<NT>::CW])
+{
+    typedef WaveTile<NT> WT;
+    constexpr int RW = WT::RW, CW = WT::CW;
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));   // opaque, as in h2_epilogue
+    const int lane = tid & 63, wave = tid >> 6, xl = lane & 15, g = lane >> 4;
+    const int rh = wave % WT::RSPLIT, ch = wave / WT::RSPLIT;
+    const int W = a.W;
+    const size_t grp_sz = (size_t)a.H * W * 16;
+    const int CB = a.Csc >> 4, per = (CB & 1) ? 1 : 2, steps = CB / per;   // channel groups, groups per K-step, K-steps
+    const unsigned short *base = a.x_sc + (size_t)n * CB * grp_sz + ((size_t)(ty * 16) * W + tx * 16) * 16;
+    for (int s = 0; s < steps; ++s) {
+        __syncthreads();   // every wave is done with the main pass's halo tiles, or with the previous K-step's tile
+        u32x4 r[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int i = tid + k * 256, grp = s * per + (per == 2 ? i >> 10 : 0), plane = (i >> 9) & 1, j = i & 511, pix = j >> 1, half = j & 1;
+            r[k] = *reinterpret_cast<const u32x4 *>(base + plane * a.sc_stride + grp * grp_sz + ((size_t)(pix >> 4) * W + (pix & 15)) * 16 + half * 8);
+        }
+        const f16x8 *wf = reinterpret_cast<const f16x8 *>(a.w_sc) + lane + ch * CW * 64 + (size_t)s * (2 * NT * 64);
+        f16x8 w0[CW], w1[CW];
+#pragma unroll
+        for (int nt = 0; nt < CW; ++nt) { w0[nt] = wf[(0 * NT + nt) * 64]; w1[nt] = wf[(1 * NT + nt) * 64]; }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) lds[tid + k * 256] = r[k];
+        __syncthreads();
+        const char *px = reinterpret_cast<const char *>(lds) + (g >> 1) * 16384 + ((rh * RW * 16 + xl) * 2 + (g & 1)) * 16;
+#pragma unroll
+        for (int h = 0; h < RW / 2; ++h) {
+            f16x8 xa[2], xb[2];
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+                xa[m] = *reinterpret_cast<const f16x8 *>(px + (h * 2 + m) * 16 * 32);
+                xb[m] = *reinterpret_cast<const f16x8 *>(px + 8192 + (h * 2 + m) * 16 * 32);
+            }
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int nt = 0; nt < CW; ++nt) acc[h * 2 + m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w1[nt], xa[m], acc[h * 2 + m][nt], 0, 0, 0);
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int nt = 0; nt < CW; ++nt) acc[h * 2 + m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w0[nt], xa[m], acc[h * 2 + m][nt], 0, 0, 0);
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int nt = 0; nt < CW; ++nt) acc[h * 2 + m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w0[nt], xb[m], acc[h * 2 + m][nt], 0, 0, 0);
+        }
+    }
+}
+
+// Which Cout = 64 kernels take the 168-VGPR, three-workgroup form: the ones the launcher asks it of (LEAN: no shortcut source) and the 5x5
+// kernels with a shortcut source, whose LDS-tile passes (h2_shortcut32, h2_shortcut_any) run when the K-loop's registers are dead.  Those
+// keep their instantiation names <5,5,4,2,0> and <5,5,4,1,0>: the kernel table that the tests hold the library's symbols and the launch
+// reports to names them so.
+template <int KH, int NT, int SC, bool LEAN>
+constexpr bool h2_lean_form = LEAN || (KH == 5 && NT == 4 && SC != 0);
+
 template <int KH, int KW, int NT, int SC, bool LEAN = false>   // SC: 0 none, 1 general 1x1 shortcut pass, 2 the 32-channel one
-__global__ __launch_bounds__(256, NT == 4 && !LEAN ? 2 : 3) void conv_h2_kernel(ConvX6Args a)
+__global__ __launch_bounds__(256, (NT == 4 && !h2_lean_form<KH, NT, SC, LEAN> ? 2 : 3)) void conv_h2_kernel(ConvX6Args a)
 {
     typedef GeoH<KH, KW> G;
     __shared__ u32x4 lds[2 * G::BUF];
@@ -416,9 +498,12 @@ __global__ __launch_bounds__(256, NT == 4 && !LEAN ? 2 : 3) void conv_h2_kernel(
 #pragma unroll
         for (int nt = 0; nt < CW; ++nt) acc[m][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    h2_accumulate<KH, KW, NT, LEAN>(a.x, a.x_stride, a.w, a.Cin, a.H, a.W, n, ty, tx, lds, acc);
-    if (SC == 2) h2_shortcut32<NT>(a, n, ty, tx, lds, acc);
-    else if (SC) h2_accumulate<1, 1, NT, LEAN>(a.x_sc, a.sc_stride, a.w_sc, a.Csc, a.H, a.W, n, ty, tx, lds, acc);
+    constexpr bool LF = h2_lean_form<KH, NT, SC, LEAN>;
+    constexpr bool SLIM = LF && KH == 5;   // the 5x5 lean kernels: lane arithmetic, plan offsets and tap offsets kept out of the K-loop's registers
+    h2_accumulate<KH, KW, NT, LF, SLIM>(a.x, a.x_stride, a.w, a.Cin, a.H, a.W, n, ty, tx, lds, acc);
+    if (SC == 2) h2_shortcut32<NT, SLIM>(a, n, ty, tx, lds, acc);
+    else if (SC && SLIM) h2_shortcut_any<NT>(a, n, ty, tx, lds, acc);
+    else if (SC) h2_accumulate<1, 1, NT, LF, SLIM>(a.x_sc, a.sc_stride, a.w_sc, a.Csc, a.H, a.W, n, ty, tx, lds, acc);
     h2_epilogue<NT>(a, acc, n, ty, tx);
 }
 
@@ -549,12 +634,16 @@ static hipError_t launch_h2(hipStream_t s, const ConvX6Args &a)
     case 4:
         if constexpr (KH > 1) {
             if (a.x_sc && a.Csc == 32) {
-                // RB(32,64,k): the whole 32-channel shortcut tile goes to LDS at once (h2_shortcut32); two workgroups per CU - in the
-                // 168-VGPR form these kernels measure the same (5x5 class 5.94 vs 5.95 ms per 1024 blocks)
+                // RB(32,64,k): the whole 32-channel shortcut tile goes to LDS at once (h2_shortcut32).  3x3: two workgroups per CU.  5x5:
+                // the 168-VGPR form under this name (h2_lean_form) - with the spilling K-loop it measured the same as two workgroups
+                // (5x5 class 5.94 vs 5.95 ms per 1024 blocks), spill-free 7042 -> 6909 us per 4096-block launch
                 PMP_H2_LAUNCH_SC(4, 2, false);
             } else if (!a.x_sc) {
                 // the Cout = 64 layers without a shortcut source: the 168-VGPR form, three workgroups per CU (3x3: -5.6 %, 5x5: -1.9 %
-                // against the two-workgroup form; the shortcut instantiations would spill 70 registers in this form)
+                // against the two-workgroup form while its K-loop spilled 33 registers, another -1.4 % without: 2487 -> 2452 us per
+                // launch; at 3x3 the general 1x1 shortcut pass would spill 89 registers in this form and stays at two workgroups, at 5x5
+                // <5,5,4,1,0> runs its shortcut tile by tile through LDS instead, h2_shortcut_any, in this form).
+                // Both 5x5 changes together, same-box A/B: luma step -0.58 / -0.95 ms on two boxes (profiles/r07_conv5_3wg_ab.txt)
                 PMP_H2_LAUNCH_SC(4, 0, true);
             } else {
                 PMP_H2_LAUNCH_SC(4, 1, false);   // (no <KH, KW, 4, 0, false> for KH > 1: nothing could reach it)
