@@ -31,6 +31,7 @@ import os
 import sys
 import time
 from concurrent.futures import ThreadPoolExecutor
+from dataclasses import dataclass, field
 
 import numpy as np
 
@@ -205,6 +206,7 @@ class DeviceBlocks:
     """Device-resident blocks of one sequence shard: the sub-sampled frames are uploaded once, cut by
     pmp_cut_blocks_device (Inference_QBD.py:104-149 on the GPU) and reused by all eight (component, QP) passes; only the split
     flags (1344 B per block) come back.  torch is the device allocator here, nothing else."""
+    lookahead = True     # enqueue() returns while the GPU works: run_sequence loads the nets of the pass after next beside it
 
     def __init__(self, eng, dev, y, u, v, bitdepth, lo, hi):
         import torch
@@ -235,11 +237,44 @@ class DeviceBlocks:
                                                   self.bv.data_ptr() if chroma else None, self.n, rec.data_ptr())
         return rec
 
-    def infer_postprocess_records(self, comp, qp):
-        """One pass, finished: the records as a device tensor."""
-        rec = self.enqueue(comp, qp)
+    def collect(self, rec):
+        """The pass behind `rec` is done and final (range guard settled): the engine has been synchronised, here is the tensor."""
         self.eng.synchronize()
         return rec
+
+    def infer_postprocess_records(self, comp, qp):
+        """One pass, finished: the records as a device tensor."""
+        return self.collect(self.enqueue(comp, qp))
+
+
+class HostBlocks:
+    """The same interface over blocks in HOST arrays (--hostBlocks, or torch without a GPU): every pass uploads them again, as the
+    reference does, and runs inside collect() - which also loads that pass's nets.  Without blocks - a rank without rows, a
+    sequence without a full 64x64 block - collect() gives u8[0, 1344] and makes no GPU call."""
+    lookahead = False
+
+    def __init__(self, job, blocks=None):
+        self.job, self.blocks, self.n = job, blocks, (blocks[0].shape[0] if blocks else 0)
+
+    def enqueue(self, comp, qp):
+        return comp, qp
+
+    def collect(self, handle):
+        self.job.load_weights(*handle)
+        if not self.n:
+            return np.zeros((0, parallel.RECORD), np.uint8)
+        return parallel.pack_records(*self.job.eng.infer_postprocess(*handle, *self.blocks))
+
+
+def open_blocks(job, seq):
+    """The block source of this rank's shard of `seq`: by default the frames go up once, are cut on the GPU and the blocks never
+    leave it."""
+    if seq.planes is None:
+        return HostBlocks(job)
+    bitdepth, o = 10 if seq.is10bit else 8, seq.f0 * seq.per_frame
+    if job.torch_dev is not None:
+        return DeviceBlocks(job.eng, job.torch_dev, *seq.planes, bitdepth, seq.lo - o, seq.hi - o)
+    return HostBlocks(job, [a[seq.lo - o:seq.hi - o] for a in job.eng.output_block_yuv(*seq.planes, bitdepth)])
 
 
 def _emit(rec, save_path, frames, height, width, binary):
@@ -290,10 +325,48 @@ def partition_params(args):
     return {"Luma": luma, "Chroma": chroma}
 
 
-def inference_VVC_seqs(args):
-    """Inference_QBD.py:151-255."""
-    global LAST_STAGES
-    t_entry = time.perf_counter()
+class Job:
+    """What one rank's process holds for the whole job: its place among the ranks, the engine, the devices, the pinned pool - and,
+    once inference_VVC_seqs has made them, the reader and the sink, so that release() can reach them."""
+    reader = sink = None
+
+    def __init__(self, rank, world, eng, device=None, torch_dev=None, pinned=None):
+        self.rank, self.world, self.eng, self.device, self.torch_dev, self.pinned = rank, world, eng, device, torch_dev, pinned
+        self.announced = set()
+
+    def load_weights(self, comp, qp):
+        """Weights once per (comp, qp), not once per sequence; rank 0 says where each net came from the first time it sees it."""
+        self.eng.load(comp, qp)
+        if self.rank == 0:
+            for (net, q), src in sorted(self.eng.provenance.items()):
+                if (net, q) not in self.announced:
+                    self.announced.add((net, q))
+                    print("weights %s QP%d: %s" % (net, q, src), flush=True)
+                    if str(src).startswith("synthetic") and "warned" not in self.announced:
+                        self.announced.add("warned")
+                        print("WARNING: MTT nets run on SYNTHETIC weights (--allowSyntheticMTT): the PartitionMat files are not usable "
+                              "for encoding", file=sys.stderr, flush=True)
+
+    def close(self):
+        """The normal end, at the same point on every rank."""
+        self.eng.close()
+        if self.world > 1:
+            import torch.distributed as dist
+            dist.barrier()
+            dist.destroy_process_group()
+
+    def release(self):
+        """After a failure: give up what THIS process owns and nothing else.  No drain, finish, barrier or any other collective -
+        the other ranks may be gone, and parallel.spawn_ranks ends the job on the first failing rank anyway."""
+        if self.reader is not None:
+            self.reader.close(wait=False)
+        if self.sink is not None:
+            self.sink.abandon()
+        self.eng.close()
+
+
+def open_job(args):
+    """Rank and device, the engine with its settings, the rendezvous with its preflight collective, torch's device, the pinned pool."""
     rank, world, local = parallel.env_world()
     if world > 1 and args.device is not None:
         raise SystemExit("--device selects the GPU of a single-process run; with %d ranks every rank takes the GPU of its LOCAL_RANK" % world)
@@ -323,6 +396,15 @@ def inference_VVC_seqs(args):
     eng.set_chunk(min(max(1, args.batchSize), 4096) if args.strictBatch else 4096)
     eng.set_precision(args.precision)
     eng.set_overlap(args.overlap)            # opt-in: measured to buy nothing at job level (see --overlap)
+    try:
+        return Job(rank, world, eng, *_open_devices(args, rank, world, dev_id))
+    except BaseException:
+        eng.close()
+        raise
+
+
+def _open_devices(args, rank, world, dev_id):
+    """(the collectives' device after rendezvous and preflight, torch's device for the blocks, the pinned pool); None where unused."""
     device = None
     if world > 1:
         import torch
@@ -334,223 +416,292 @@ def inference_VVC_seqs(args):
         parallel.relax_timeout()                     # PMP_DIST_TIMEOUT_S bounded the rendezvous; the passes' collectives get PMP_DIST_COLLECTIVE_TIMEOUT_S
         if rank == 0:
             print("ranks: %d (%s), first collective %.1f ms" % (info["ranks"], info["backend"], info["ms"]), flush=True)
-
-    torch_dev = None
-    if not args.hostBlocks:
-        try:
-            import torch
-            if torch.cuda.is_available():
-                torch_dev = torch.device("cuda", dev_id)
-            else:
-                print("WARNING: torch sees no GPU although the library runs on one: blocks stay on the HOST (as with --hostBlocks)",
-                      file=sys.stderr, flush=True)
-        except ImportError:
-            torch_dev = None
-    pinned = None
-    if torch_dev is not None:
+    if args.hostBlocks:
+        return device, None, None
+    try:
         import torch
-        pinned = PinnedPool(torch)
+    except ImportError:
+        return device, None, None
+    if not torch.cuda.is_available():
+        print("WARNING: torch sees no GPU although the library runs on one: blocks stay on the HOST (as with --hostBlocks)",
+              file=sys.stderr, flush=True)
+        return device, None, None
+    return device, torch.device("cuda", dev_id), PinnedPool(torch)
 
-    save_dir = os.path.join(args.outDir, args.jobID, "PartitionMat")
-    os.makedirs(save_dir, exist_ok=True)             # every rank writes its own rows into the files
-    qps = [int(q) for q in args.qps.split(",") if q]
-    comps = [c for c in args.comps.split(",") if c]
-    sharded = args.emit == "sharded"
 
-    names, files, widths, heights, frames, sub_frames, _ = load_sequences_info(_resolve(args.seqTable, args.inputDir), args.ssRatio)
-    end = min(args.startSeqID + args.seqNum, len(names))
-    nseq = max(0, end - args.startSeqID)
-    seqs_block_time = np.zeros(max(nseq, 1))
-    seqs_net_time = np.zeros((max(nseq, 1), 4, 2))
-    seqs_post_time = np.zeros((max(nseq, 1), 4, 2))
-    st = Stages()
-    LAST_STAGES = st
+@dataclass
+class Sequence:
+    """One sequence as the reader hands it to the passes: its geometry, this rank's shard of its blocks and - where the shard has
+    any - the frames that hold them."""
+    name: str
+    stem: str                   # of the output files' names
+    width: int
+    height: int
+    sub_numfrm: int
+    is10bit: bool
+    per_frame: int              # blocks per frame, n_total in the whole sequence
+    n_total: int
+    lo: int                     # this rank's blocks [lo, hi) ...
+    hi: int
+    g_lo: int                   # ... which sharded emission takes as whole block rows [g_lo, g_hi) (emit.py)
+    g_hi: int
+    f0: int = 0                 # the first sub-sampled frame in `planes`
+    planes: tuple = None        # (y, u, v) of the frames that hold blocks lo..hi; None: the shard has no block, nothing was read
+    bufs: list = field(default_factory=list)     # the pinned buffers behind the planes
+    read_s: float = 0.0         # what the reader thread spent on it
 
-    emitter = emit.ShardEmitter(rank, world, threads=args.emitThreads, device=device) if sharded else None
-    writers = ThreadPoolExecutor(max_workers=4) if (rank == 0 and not sharded) else None
-    pending = []
-    # Weights once per (comp, qp), not once per sequence.  A missing file raises HERE, before any output - but only the first
-    # pass's nets are loaded now: the others go up while the GPU runs the pass before theirs (30 ms of packing each, hidden).
-    for comp in comps:
-        for qp in qps:
-            eng.check_available(comp, qp)
-    announced = set()
+    def give_back(self, pinned):
+        """The blocks are cut: the frames go, their pinned buffers return to the pool."""
+        for t in self.bufs:
+            pinned.give(t)
+        self.planes, self.bufs = None, []
 
-    def load_weights(comp, qp):
-        eng.load(comp, qp)
-        if rank == 0:
-            for (net, q), src in sorted(eng.provenance.items()):
-                if (net, q) not in announced:
-                    announced.add((net, q))
-                    print("weights %s QP%d: %s" % (net, q, src), flush=True)
-                    if str(src).startswith("synthetic") and "warned" not in announced:
-                        announced.add("warned")
-                        print("WARNING: MTT nets run on SYNTHETIC weights (--allowSyntheticMTT): the PartitionMat files are not usable "
-                              "for encoding", file=sys.stderr, flush=True)
 
-    # ---- the reader: one thread, one sequence ahead.  A rank reads only the frames that hold its own block rows.
-    def load_sequence(seq_id):
+class SequenceReader:
+    """The reader: one thread, one sequence ahead of the passes.  A rank reads only the frames that hold its own block rows.
+    Iterating yields the Sequences; the thread's I/O time goes to Stages.prefetch_read, the main thread's wait to read_wait."""
+
+    def __init__(self, job, args, table, seq_ids, st):
+        self.job, self.args, self.table, self.seq_ids, self.st = job, args, table, list(seq_ids), st
+        self.pool = ThreadPoolExecutor(max_workers=1)
+        self.nxt = self.pool.submit(self.load, self.seq_ids[0]) if self.seq_ids else None
+
+    def load(self, seq_id):
         t0 = time.perf_counter()
-        seq_name = names[seq_id]
-        width, height, numfrm, sub_numfrm = widths[seq_id], heights[seq_id], frames[seq_id], sub_frames[seq_id]
-        seq_path, is10bit = parse_seq_cfg(os.path.join(args.cfgDir, seq_name + ".cfg"))
-        seq_path = _resolve(seq_path, args.inputDir)
+        args, rank, world, pinned = self.args, self.job.rank, self.job.world, self.job.pinned
+        names, files, widths, heights, frames, sub_frames, _ = self.table
+        width, height, sub_numfrm = widths[seq_id], heights[seq_id], sub_frames[seq_id]
+        seq_path, is10bit = parse_seq_cfg(os.path.join(args.cfgDir, names[seq_id] + ".cfg"))
         bh, bw = height // 64, width // 64
         per_frame = bh * bw
-        if sharded:      # whole block rows per rank (emit.py)
+        if args.emit == "sharded":      # whole block rows per rank (emit.py)
             g_lo, g_hi = emit.shard_rows(sub_numfrm, bh, rank, world)
             lo, hi = g_lo * bw, g_hi * bw
-        else:            # contiguous block ranges, gathered to rank 0
+        else:                           # contiguous block ranges, gathered to rank 0
             lo, hi = parallel.shard_bounds(per_frame * sub_numfrm, rank, world)
             g_lo = g_hi = 0
-        d = dict(name=seq_name, stem=strip_yuv_suffix(files[seq_id]), width=width, height=height, sub_numfrm=sub_numfrm, is10bit=is10bit,
-                 bh=bh, bw=bw, per_frame=per_frame, n_total=per_frame * sub_numfrm, lo=lo, hi=hi, g_lo=g_lo, g_hi=g_hi, y=None, bufs=[])
+        seq = Sequence(names[seq_id], strip_yuv_suffix(files[seq_id]), width, height, sub_numfrm, is10bit, per_frame,
+                       per_frame * sub_numfrm, lo, hi, g_lo, g_hi)
         if hi > lo and per_frame:
-            f0, f1 = shard_frames(lo, hi, per_frame)
+            seq.f0, f1 = shard_frames(lo, hi, per_frame)
             alloc = None
             if pinned is not None:
                 def alloc(shape, dtype):
                     a, t = pinned.array(shape, dtype)
-                    d["bufs"].append(t)
+                    seq.bufs.append(t)
                     return a
-            d["y"], d["u"], d["v"] = import_yuv420(seq_path, width, height, numfrm, args.ssRatio, is10bit, frames=(f0, f1), alloc=alloc)
-            d["f0"] = f0
-        d["read_s"] = time.perf_counter() - t0
-        return d
+            seq.planes = import_yuv420(_resolve(seq_path, args.inputDir), width, height, frames[seq_id], args.ssRatio, is10bit,
+                                       frames=(seq.f0, f1), alloc=alloc)
+        seq.read_s = time.perf_counter() - t0
+        return seq
 
-    reader = ThreadPoolExecutor(max_workers=1)
-    seq_ids = list(range(args.startSeqID, end))
-    nxt = reader.submit(load_sequence, seq_ids[0]) if seq_ids else None
-    st.add("setup", t_entry)                          # context, rendezvous, weights of every (component, QP): once per job
-    passes = [(comp, qp) for comp in comps for qp in qps]
-    rec_host = [None, None]      # pinned double buffer for the records of the pass being formatted / the pass being copied
+    def __iter__(self):
+        for i in range(len(self.seq_ids)):
+            tw = time.perf_counter()
+            seq = self.nxt.result()
+            self.nxt = self.pool.submit(self.load, self.seq_ids[i + 1]) if i + 1 < len(self.seq_ids) else None
+            self.st.prefetch_read += seq.read_s
+            self.st.add("read_wait", tw)
+            yield seq
 
-    for si, seq_id in enumerate(seq_ids):
-        t0 = tw = time.perf_counter()
-        sq = nxt.result()
-        nxt = reader.submit(load_sequence, seq_ids[si + 1]) if si + 1 < len(seq_ids) else None
-        st.prefetch_read += sq["read_s"]
-        tw = st.add("read_wait", tw)
-        width, height, sub_numfrm, per_frame, n_total = sq["width"], sq["height"], sq["sub_numfrm"], sq["per_frame"], sq["n_total"]
-        lo, hi, bw = sq["lo"], sq["hi"], sq["bw"]
-        if rank == 0:
-            print(sq["name"], flush=True)
-        # ---- load input blocks: frames go up once, are cut on the GPU and the blocks never leave it
-        dblk = None
-        by = np.zeros((0, 68, 68), np.uint8); bu = np.zeros((0, 34, 34), np.uint8); bv = np.zeros((0, 34, 34), np.uint8)
-        if sq["y"] is not None:
-            o = sq["f0"] * per_frame
-            if torch_dev is not None:
-                dblk = DeviceBlocks(eng, torch_dev, sq["y"], sq["u"], sq["v"], 10 if sq["is10bit"] else 8, lo - o, hi - o)
-            else:
-                by, bu, bv = eng.output_block_yuv(sq["y"], sq["u"], sq["v"], 10 if sq["is10bit"] else 8)
-                by, bu, bv = (a[lo - o:hi - o] for a in (by, bu, bv))
-        for t in sq["bufs"]:
-            pinned.give(t)
-        sq["y"] = sq["u"] = sq["v"] = None
-        st.add("h2d_cut", tw)
-        st.blocks += (hi - lo) * len(passes)
-        st.passes += len(passes)
-        seqs_block_time[si] = time.perf_counter() - t0
+    def close(self, wait=True):
+        self.pool.shutdown(wait=wait, cancel_futures=True)
 
-        n_local = hi - lo
+
+class ShardedSink:
+    """--emit sharded: every rank formats and pwrites its own block rows (emit.ShardEmitter, owned here).  Device records come down
+    into a pinned double buffer, slot k & 1 for pass k, and the emitter reads a slot until finish() of its pass has returned.  The
+    rule that keeps that safe is this class's alone: put(k) copies into its slot FIRST - the slot's last user, pass k-2, was
+    finished by put(k-1) - then finishes pass k-1, whose formatting ran beside pass k on the GPU, then starts pass k.
+    The collectives, at the same points on every rank: finish() (the size all-reduce) once per pass, in put() of the next pass or
+    in end_sequence(); drain() (a barrier) once per sequence in end_sequence() and once in close()."""
+
+    def __init__(self, emitter, pinned, st, binary=False):
+        self.emitter, self.pinned, self.st, self.binary = emitter, pinned, st, binary
+        self.slots, self.busy, self.prev = [None, None], [False, False], None      # prev: (the emitter's pending pass, its slot)
+
+    def put(self, k, save_path, seq, records):
+        tw, s, n = time.perf_counter(), k & 1, records.shape[0]
+        assert not self.busy[s], "pinned record slot %d is still being formatted: finish() of its pass has not run" % s
+        if isinstance(records, np.ndarray):
+            host = np.ascontiguousarray(records).reshape(n, parallel.RECORD)
+        else:                                       # D2H into a pinned buffer on torch's stream, next to pass k+1 on the library's
+            need = n * parallel.RECORD
+            if self.slots[s] is None or self.slots[s].numel() < need:
+                self.slots[s] = self.pinned.take(need)
+            ht = self.slots[s][:need].view(n, parallel.RECORD)
+            ht.copy_(records)
+            host = ht.numpy()
+        tw = self.st.add("d2h", tw)
+        tw = self._finish_prev(tw)                  # exchange the byte counts of pass k-1, queue its writes
+        self.prev = self.emitter.start(save_path, seq.sub_numfrm, seq.height, seq.width, seq.g_lo, seq.g_hi, host, binary=self.binary), s
+        self.busy[s] = True
+        self.st.add("emit_start", tw)
+
+    def _finish_prev(self, tw):
+        if self.prev is None:
+            return tw
+        p, s = self.prev
+        self.emitter.finish(p)
+        self.busy[s], self.prev = False, None
+        return self.st.add("emit_finish", tw)
+
+    def end_sequence(self):
+        tw = self._finish_prev(time.perf_counter())
+        self.emitter.drain()                        # bound memory: a sequence's files are on disk before the next one starts
+        self.st.add("drain", tw)
+
+    def close(self):
+        self.emitter.close()
+
+    def abandon(self):
+        self.emitter.pool.shutdown(wait=False, cancel_futures=True)
+
+
+class GatherSink:
+    """--emit gather: one gather of the records to rank 0 per pass (a collective: every rank's put() takes part), and rank 0 writes
+    the file alone.  Text emission (645 k lines per 1080p frame and file) runs on writer threads - the C writer releases the GIL -
+    so it overlaps the next (component, QP) pass instead of serialising rank 0."""
+
+    def __init__(self, rank, device, st, binary=False):
+        self.device, self.st, self.binary = device, st, binary
+        self.writers, self.pending = (ThreadPoolExecutor(max_workers=4) if rank == 0 else None), []
+
+    def put(self, k, save_path, seq, records):
         tw = time.perf_counter()
-        if passes:
-            load_weights(*passes[0])
-        tw = st.add("weights", tw)
-        cur = dblk.enqueue(*passes[0]) if (dblk is not None and passes) else None
-        tw = st.add("first_enqueue", tw)               # the job's first pass also sizes and allocates the activation workspace
-        if len(passes) > 1:
-            load_weights(*passes[1])                   # next to pass 0 on the GPU
-            st.add("weights", tw)
-        prev = None
-        for k, (comp, qp) in enumerate(passes):
-            comp_id = COMP_COLUMN[comp]                # Time_Sta columns: Luma first, whatever --comps lists
-            qi = (qp - 22) // 5 if qp in QPS else 0
-            save_path = os.path.join(save_dir, "%s_%s_QP%d_PartitionMat.txt" % (sq["stem"], comp, qp))
-            t0 = tw = time.perf_counter()
-            reruns = eng.saturation_reruns()
-            if dblk is not None:
-                eng.synchronize()                      # pass k is done and final (range guard settled)
-                tw = st.add("gpu_wait", tw)
-                local = cur
-                if k + 1 < len(passes):                # the GPU starts on pass k+1 before the host touches pass k's records
-                    cur = dblk.enqueue(*passes[k + 1])
-                    tw = st.add("enqueue", tw)
-                    if k + 2 < len(passes):
-                        load_weights(*passes[k + 2])   # no-op after the first sequence
-                        tw = st.add("weights", tw)
-            else:
-                load_weights(comp, qp)
-                local = parallel.pack_records(*eng.infer_postprocess(comp, qp, by, bu, bv)) if n_local else np.zeros((0, parallel.RECORD), np.uint8)
-                tw = st.add("gpu_wait", tw)
-            seqs_net_time[si, qi, comp_id] = time.perf_counter() - t0
-            if eng.saturation_reruns() != reruns:   # f16x3 range guard (include/pmp.h): results are right, the pass cost 3x
-                print("WARNING: rank %d: %s %s QP%d drove an activation beyond the fp16 range of the f16x3 datapath; the pass was "
-                      "re-run on the fp32 datapath (consider --precision bf16x6 for this model)" % (rank, sq["name"], comp, qp), file=sys.stderr, flush=True)
-            t0 = tw = time.perf_counter()
-            if rank == 0:
-                print("Save:", save_path, flush=True)
-            if sharded:
-                if dblk is not None:                   # D2H into a pinned buffer on torch's stream, next to pass k+1 on the library's
-                    import torch
-                    need = n_local * parallel.RECORD
-                    if rec_host[k & 1] is None or rec_host[k & 1].numel() < need:
-                        rec_host[k & 1] = pinned.take(need)
-                    ht = rec_host[k & 1][:need].view(n_local, parallel.RECORD)
-                    ht.copy_(local)
-                    host = ht.numpy()
-                else:
-                    host = np.ascontiguousarray(local).reshape(n_local, parallel.RECORD)
-                tw = st.add("d2h", tw)
-                if prev is not None:                   # pass k-1: exchange the byte counts, queue the writes (its formatting ran beside pass k)
-                    emitter.finish(prev)
-                    tw = st.add("emit_finish", tw)
-                prev = emitter.start(save_path, sub_numfrm, height, width, sq["g_lo"], sq["g_hi"], host, binary=args.binary)
-                tw = st.add("emit_start", tw)
-            else:
-                rec = parallel.gather_records(local, n_total, device)
-                tw = st.add("gather", tw)
-                if rank == 0:
-                    # text emission (645 k lines per 1080p frame and file) runs on writer threads - the C writer releases
-                    # the GIL - so it overlaps the next (component, QP) pass instead of serialising rank 0
-                    pending.append(writers.submit(_emit, rec, save_path, sub_numfrm, height, width, args.binary))
-            seqs_post_time[si, qi, comp_id] = time.perf_counter() - t0
+        rec = parallel.gather_records(records, seq.n_total, self.device)
+        self.st.add("gather", tw)
+        if self.writers:
+            self.pending.append(self.writers.submit(_emit, rec, save_path, seq.sub_numfrm, seq.height, seq.width, self.binary))
 
+    def end_sequence(self):
         tw = time.perf_counter()
-        if prev is not None:
-            emitter.finish(prev)
-            tw = st.add("emit_finish", tw)
-        if emitter is not None:
-            emitter.drain()                            # bound memory: a sequence's files are on disk before the next one starts
-        for fut in pending:
+        for fut in self.pending:
             fut.result()
-        pending = []
-        st.add("drain", tw)
-        del dblk
-    tw = time.perf_counter()
-    reader.shutdown(wait=True)
-    if emitter is not None:
-        emitter.close()
-    if writers:
-        writers.shutdown(wait=True)
-    if rank == 0:  # Time_Sta log, Inference_QBD.py:243-253 (net column = inference + GPU post-processing here)
-        sta = os.path.join(args.outDir, args.jobID, "Time_Sta_%d_%d.txt" % (args.startSeqID, args.startSeqID + args.seqNum))
-        with open(sta, "w") as fp:
-            for si in range(nseq):
-                for qp_id in range(4):
-                    for s in (seqs_block_time[si], seqs_net_time[si, qp_id, 0], seqs_net_time[si, qp_id, 1],
-                              seqs_post_time[si, qp_id, 0], seqs_post_time[si, qp_id, 1]):
+        self.pending = []
+        self.st.add("drain", tw)
+
+    def close(self):
+        if self.writers:
+            self.writers.shutdown(wait=True)
+
+    def abandon(self):
+        if self.writers:
+            self.writers.shutdown(wait=False, cancel_futures=True)
+
+
+class TimeSta:
+    """The Time_Sta log, Inference_QBD.py:243-253: per sequence four QP rows of block-loading, net Luma, net Chroma, post Luma and
+    post Chroma seconds (the net column is inference + GPU post-processing here)."""
+
+    def __init__(self, nseq):
+        self.nseq = nseq
+        self.block, self.net, self.post = np.zeros(max(nseq, 1)), np.zeros((max(nseq, 1), 4, 2)), np.zeros((max(nseq, 1), 4, 2))
+
+    @staticmethod
+    def cell(comp, qp):
+        """(QP row, component column): Luma is column 0 whatever --comps lists; a QP outside the reference's four shares row 0."""
+        return ((qp - 22) // 5 if qp in QPS else 0), COMP_COLUMN[comp]
+
+    def total(self):
+        return np.sum(self.block) + np.sum(self.net) + np.sum(self.post)
+
+    def write(self, path):
+        with open(path, "w") as fp:
+            for si in range(self.nseq):
+                for qi in range(4):
+                    for s in (self.block[si], self.net[si, qi, 0], self.net[si, qi, 1], self.post[si, qi, 0], self.post[si, qi, 1]):
                         fp.write(str(s))
                         fp.write(",")
                     fp.write("\n")
-        print("Sum time:", np.sum(seqs_block_time) + np.sum(seqs_net_time) + np.sum(seqs_post_time))
-    eng.close()
-    if world > 1:
-        import torch.distributed as dist
-        dist.barrier()
-        dist.destroy_process_group()
-    st.add("teardown", tw)
+
+
+def run_sequence(job, si, seq, src, sink, passes, save_dir, sta, st):
+    """The pipeline schedule of one sequence and nothing else: pass k+1 is enqueued before the host touches pass k's records, the
+    nets of pass k+2 are loaded beside it, the range guard of pass k is settled by collect(k).  Only the first pass's nets are
+    loaded ahead of the GPU: the others go up while it runs the pass before theirs (30 ms of packing each, hidden)."""
+    tw = time.perf_counter()
+    if passes:
+        job.load_weights(*passes[0])
+    tw = st.add("weights", tw)
+    cur = src.enqueue(*passes[0]) if passes else None
+    tw = st.add("first_enqueue", tw)     # the job's first pass also sizes and allocates the activation workspace
+    if len(passes) > 1:
+        job.load_weights(*passes[1])     # next to pass 0 on the GPU
+        st.add("weights", tw)
+    for k, (comp, qp) in enumerate(passes):
+        cell = (si,) + TimeSta.cell(comp, qp)
+        save_path = os.path.join(save_dir, "%s_%s_QP%d_PartitionMat.txt" % (seq.stem, comp, qp))
+        t0 = tw = time.perf_counter()
+        reruns = job.eng.saturation_reruns()
+        records = src.collect(cur)
+        tw = st.add("gpu_wait", tw)
+        if k + 1 < len(passes):          # the GPU starts on pass k+1 before the host touches pass k's records
+            cur = src.enqueue(*passes[k + 1])
+            tw = st.add("enqueue", tw)
+            if k + 2 < len(passes) and src.lookahead:
+                job.load_weights(*passes[k + 2])      # no-op after the first sequence
+                st.add("weights", tw)
+        sta.net[cell] = time.perf_counter() - t0
+        if job.eng.saturation_reruns() != reruns:     # f16x3 range guard (include/pmp.h): results are right, the pass cost 3x
+            print("WARNING: rank %d: %s %s QP%d drove an activation beyond the fp16 range of the f16x3 datapath; the pass was "
+                  "re-run on the fp32 datapath (consider --precision bf16x6 for this model)" % (job.rank, seq.name, comp, qp), file=sys.stderr, flush=True)
+        t0 = time.perf_counter()
+        if job.rank == 0:
+            print("Save:", save_path, flush=True)
+        sink.put(k, save_path, seq, records)
+        sta.post[cell] = time.perf_counter() - t0
+    sink.end_sequence()
+
+
+def inference_VVC_seqs(args):
+    """Inference_QBD.py:151-255: the outline of a job.  A failure anywhere in it releases what this process owns (Job.release) and
+    goes on up; the success path ends with the reader, the sink, the Time_Sta log and Job.close(), in that order."""
+    global LAST_STAGES
+    t_entry = time.perf_counter()
+    job = open_job(args)
+    try:
+        save_dir = os.path.join(args.outDir, args.jobID, "PartitionMat")
+        os.makedirs(save_dir, exist_ok=True)             # every rank writes its own rows into the files
+        qps = [int(q) for q in args.qps.split(",") if q]
+        passes = [(comp, qp) for comp in args.comps.split(",") if comp for qp in qps]
+        table = load_sequences_info(_resolve(args.seqTable, args.inputDir), args.ssRatio)
+        seq_ids = range(args.startSeqID, min(args.startSeqID + args.seqNum, len(table[0])))
+        sta = TimeSta(len(seq_ids))
+        st = LAST_STAGES = Stages()
+        if args.emit == "sharded":
+            job.sink = ShardedSink(emit.ShardEmitter(job.rank, job.world, threads=args.emitThreads, device=job.device), job.pinned, st, args.binary)
+        else:
+            job.sink = GatherSink(job.rank, job.device, st, args.binary)
+        for comp, qp in passes:                          # a missing model file raises HERE, before any output
+            job.eng.check_available(comp, qp)
+        job.reader = SequenceReader(job, args, table, seq_ids, st)
+        st.add("setup", t_entry)                         # context, rendezvous, the first read under way: once per job
+        t0 = time.perf_counter()
+        for si, seq in enumerate(job.reader):
+            tw = time.perf_counter()
+            if job.rank == 0:
+                print(seq.name, flush=True)
+            src = open_blocks(job, seq)
+            seq.give_back(job.pinned)
+            st.add("h2d_cut", tw)
+            st.blocks += (seq.hi - seq.lo) * len(passes)
+            st.passes += len(passes)
+            sta.block[si] = time.perf_counter() - t0
+            run_sequence(job, si, seq, src, job.sink, passes, save_dir, sta, st)
+            del src                                      # the device blocks go before the next sequence's come
+            t0 = time.perf_counter()
+        tw = time.perf_counter()
+        job.reader.close()
+        job.sink.close()
+        if job.rank == 0:
+            sta.write(os.path.join(args.outDir, args.jobID, "Time_Sta_%d_%d.txt" % (args.startSeqID, args.startSeqID + args.seqNum)))
+            print("Sum time:", sta.total())
+        job.close()
+        st.add("teardown", tw)
+    except BaseException:
+        job.release()
+        raise
     return st
 
 
