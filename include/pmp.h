@@ -79,7 +79,24 @@ int pmp_destroy(pmp_ctx *ctx);
  * environment: nothing is parked then).  pmp_trim leaves the calling thread's current device as it is. */
 int pmp_trim(void);
 
-/* Use the caller's hipStream_t (e.g. torch's current stream); NULL restores the context's own stream. */
+/* Use the caller's hipStream_t (e.g. torch's current stream); NULL restores the context's own stream.
+ *
+ * Who orders what across a change of stream.  Every call of a context, whatever stream it runs on, works in memory the caller never
+ * sees: the activation workspace, the scratch of the loss, statistics and gradient kernels, the staging and logit buffers of the
+ * host-pointer forms.  THE LIBRARY orders that memory: when the stream changes and a call has run on the old stream since it became
+ * the context's or was last drained (by pmp_synchronize, or by a host-pointer call that ends with its wait), pmp_set_stream records an event on
+ * the old stream, and the context's next call makes the stream it runs on wait for that event, on the device, before it enqueues
+ * anything (no wait where that is the stream of the record itself).  Everything the context enqueues after the change therefore
+ * starts behind everything it enqueued before; the host does not wait, and no call synchronises because of it.  The old stream must
+ * still be the caller's to use when pmp_set_stream is called (an idle context records nothing: the old stream may be destroyed after
+ * pmp_synchronize), and pmp_destroy waits for an old stream's work that nothing has waited for since.
+ * THE CALLER orders its own tensors, as with any stream: an input written on stream A and read by a call on stream B, an output read
+ * on another stream than the one its call ran on, need the caller's own event or synchronisation - except that calls of ONE context
+ * are ordered among themselves by the rule above, so one call's output may feed the context's next call on any stream.
+ *
+ * pmp_synchronize waits for the context's CURRENT stream and resolves the range guard; it first makes that stream wait for the event
+ * of the stream before it, as every call does, so it makes the outputs of every *_device call made so far final, on whichever stream
+ * each was enqueued. */
 int pmp_set_stream(pmp_ctx *ctx, void *hip_stream);
 int pmp_synchronize(pmp_ctx *ctx);
 

@@ -183,7 +183,7 @@ static int staged_logit_sums(pmp_ctx *c, const LogitLabels &h, int64_t n, std::i
                        });
     if (rc != PMP_OK) return rc;
     std::vector<double> r((size_t)passes * ncols);
-    if ((rc = d2h(c, r.data(), rows.p, r.size() * sizeof(double))) || (rc = sync(c))) return rc;
+    if ((rc = d2h(c, r.data(), rows.p, r.size() * sizeof(double))) || (rc = sync_idle(c))) return rc;
     for (int64_t p = 0; p < passes; ++p)
         for (int i = 0; i < ncols; ++i) sums[i] += r[(size_t)p * ncols + i];
     return PMP_OK;
@@ -377,7 +377,7 @@ int pmp_infer_msbd(pmp_ctx *c, int comp, int qp, const uint8_t *by, const uint8_
         return rc;
     if ((rc = resolve_pending(c, true))) return rc;      // range guard: a re-run is enqueued before the copies below
     if ((rc = d2h(c, bt, db, (size_t)n * 768 * 4)) || (rc = d2h(c, dire, dd, (size_t)n * 768 * 4))) return rc;
-    return sync(c);
+    return sync_idle(c);
 }
 
 }  // extern "C"

@@ -343,7 +343,7 @@ int rb_staged(pmp_ctx *c, const pmp_rb_shape &s, const RbCall &q, const std::vec
     if ((rc = rb_run(c, s, dq))) return rc;
     for (size_t i = 0; i < outs.size(); ++i)
         if (outs[i].p && (rc = d2h(c, const_cast<void *>(outs[i].p), dq.out[i], outs[i].bytes))) return rc;
-    return sync(c);
+    return sync_idle(c);
 }
 
 // pmp_resblock_forward, _backward and their _device forms

@@ -107,6 +107,14 @@ int stage_blocks(pmp_ctx *c, int comp, const uint8_t *by, const uint8_t *bu, con
     return PMP_OK;
 }
 
+// c->stream waits, on the device, for the fence of the stream the context left with work on it (pmp_set_stream below)
+int fence_wait(pmp_ctx *c)
+{
+    c->fence_due = false;
+    const hipError_t e = hipStreamWaitEvent(c->stream, c->fence[c->fence_at], 0);
+    return e == hipSuccess ? PMP_OK : hip_fail(c, e, "ordering the stream behind the one the context was on before");
+}
+
 }  // namespace pmp
 
 using namespace pmp;
@@ -155,6 +163,7 @@ int pmp_destroy(pmp_ctx *c)
     if (!c) return PMP_OK;
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
+    if (c->fence_due) hipEventSynchronize(c->fence[c->fence_at]);   // work on the stream the context was on before, never waited for since
     if (c->stream2) hipStreamSynchronize(c->stream2);
     drop_pending(c);                                  // their events go back to the pool ...
     ktime_drain(c);                                   // ... and those of the timing scopes
@@ -170,15 +179,41 @@ int pmp_trim(void)
     return PMP_OK;
 }
 
+// The context's hidden state - activation workspace, scratch and staging buffers, the logit buffers - is shared by every call, whatever
+// stream it ran on, and the caller cannot order what it cannot see.  So a change of stream orders the NEW stream behind everything the
+// context has enqueued on the OLD one.  The record happens here, while the old stream is still the caller's to use, and only if an
+// entry point has run on it since it became current or was last drained (an idle context records nothing: its old stream may be gone).
+// The wait is enqueued on the new stream when the next entry point runs on it (CHECK_CTX), not here: torch_call.run() goes to torch's
+// stream and back around every call, and the stream it comes back to is mostly never used - so a training step pays one record per call
+// and no wait at all (coming back to the stream of the last record needs none: stream order).  The host never waits.  A fence covers
+// the streams before it, because a stream has waited for the previous fence before the context enqueued anything on it.
 int pmp_set_stream(pmp_ctx *c, void *hip_stream)
 {
-    CHECK_CTX(c);
+    if (!c) return set_err(nullptr, PMP_E_INVALID, "null context");      // not CHECK_CTX: this call runs nothing on either stream
+    hipSetDevice(c->device);
     if (!c->pending.empty()) { const int rc = settle(c); if (rc != PMP_OK) return rc; }   // calls in flight belong to the old stream
-    c->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->own_stream.h;
+    const hipStream_t next = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->own_stream.h;
+    if (next == c->stream) return PMP_OK;
+    if (c->unsettled) {
+        const int k = c->fence_at ^ 1;
+        hipError_t e = c->fence[k].h ? hipSuccess : hipEventCreateWithFlags(&c->fence[k].h, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventRecord(c->fence[k], c->stream);
+        if (e != hipSuccess) return hip_fail(c, e, "pmp_set_stream: fence on the old stream");
+        c->fence_at = k;
+        c->fence_stream = c->stream;
+    }
+    c->stream = next;
+    c->unsettled = false;
+    c->fence_due = c->fence_stream && c->fence_stream != next;
     return PMP_OK;
 }
 
-int pmp_synchronize(pmp_ctx *c) { CHECK_CTX(c); return settle(c); }
+int pmp_synchronize(pmp_ctx *c)
+{
+    CHECK_CTX(c);
+    const int rc = resolve_pending(c, true);
+    return rc != PMP_OK ? rc : sync_idle(c);
+}
 
 int pmp_set_overlap(pmp_ctx *c, int on)
 {
@@ -410,7 +445,7 @@ int pmp_infer(pmp_ctx *c, int comp, int qp, const uint8_t *by, const uint8_t *bu
     if ((rc = d2h(c, qt, dq, (size_t)n * 64 * 4)) || (rc = d2h(c, bt, db, (size_t)n * 768 * 4)) ||
         (rc = d2h(c, dire, dd, (size_t)n * 768 * 4)))
         return rc;
-    return sync(c);
+    return sync_idle(c);
 }
 
 static int alloc_out(pmp_ctx *c, int64_t n)
@@ -429,7 +464,7 @@ static int fetch_out(pmp_ctx *c, int64_t n, uint8_t *hor, uint8_t *ver, uint8_t 
     if ((rc = d2h(c, hor, c->d_out[0].p, (size_t)n * 256)) || (rc = d2h(c, ver, c->d_out[1].p, (size_t)n * 256)) ||
         (rc = d2h(c, qt_u8, c->d_out[2].p, (size_t)n * 64)) || (rc = d2h(c, dire_i8, c->d_out[3].p, (size_t)n * 768)))
         return rc;
-    return sync(c);
+    return sync_idle(c);
 }
 
 int pmp_postprocess(pmp_ctx *c, int comp, const float *qt, const float *bt, const float *dire, int64_t n, uint8_t *hor,
@@ -515,7 +550,7 @@ int pmp_cut_blocks(pmp_ctx *c, const void *y, const void *u, const void *v, int 
     if ((rc = d2h(c, by, c->d_in[0].p, (size_t)n * 68 * 68)) || (rc = d2h(c, bu, c->d_in[1].p, (size_t)n * 34 * 34)) ||
         (rc = d2h(c, bv, c->d_in[2].p, (size_t)n * 34 * 34)))
         return rc;
-    return sync(c);
+    return sync_idle(c);
 }
 
 }  // extern "C"

@@ -53,6 +53,7 @@ struct Owned {
     operator T() const { return h; }
 };
 using OwnedStream = Owned<hipStream_t, hipStreamDestroy>;
+using OwnedEvent = Owned<hipEvent_t, hipEventDestroy>;
 using DevWords = Owned<unsigned *, hipFree>;
 using PinnedWords = Owned<unsigned *, hipHostFree>;
 
@@ -218,6 +219,13 @@ struct pmp_ctx {
     pmp::OwnedStream cal_stream;           // calibration runs on its own stream and workspace: it neither waits for the passes in flight on the
                                            // context's stream nor touches their workspace (created on first use)
     hipStream_t stream = nullptr;          // the caller's (pmp_set_stream) or own_stream; a pass runs on its Pass::stream
+    // pmp_set_stream with work in flight (include/pmp.h): leaving a stream the context has used since it became current or was last
+    // drained records a fence on it; the stream the context arrives on waits for the last fence before the next entry point's work
+    bool unsettled = false;                // an entry point has run on `stream` since then (CHECK_CTX sets it, sync_idle() clears it)
+    pmp::OwnedEvent fence[2];              // used in turn, created on first use without timing; [fence_at] holds the last record
+    int fence_at = 0;
+    hipStream_t fence_stream = nullptr;    // the stream of the last record; null: nothing outstanding
+    bool fence_due = false;                // `stream` has yet to be made to wait for it (CHECK_CTX does, before anything is enqueued)
     int chunk = 4096;   // blocks per pass: the 16x16-resolution layers need >= 4096 tiles to fill 256 CUs x 3 workgroups evenly (+2.5 % over 1024)
     int precision = 2;                     // 0: fp32 MFMA, 1: bf16x6 split, 2: f16x3 split (default; both splits fp32-equivalent) - the caller's setting; a pass runs on its Pass::precision
     int fuse16 = 1;                        // f16x3: run the 16x16-resolution tails LDS-resident (chain16.hip: two / three launches per net); 0 = launch per layer (pmp_debug_set_fusion: A/B and the bit-identity tests)
@@ -283,6 +291,7 @@ constexpr int PMP_CAL_SLOTS = 128;
 // internals shared by the translation units of the C ABI (pmp_api.cpp, range_guard.cpp, api_labels.cpp, api_train.cpp, api_debug.cpp) and calibrate.cpp
 // pmp_api.cpp
 int ensure(pmp_ctx *c, DevBuf &b, size_t bytes);                    // grow-only device buffer
+int fence_wait(pmp_ctx *c);                                         // c->stream waits, on the device, for the fence of the stream the context left
 NetWeights *find_net(pmp_ctx *c, int net_id, int qp);               // loaded weights of (net, qp) or nullptr
 int ensure_logits(pmp_ctx *c, int64_t n);                           // the context's own logit buffers, settled before one is regrown
 int stage_blocks(pmp_ctx *c, int comp, const uint8_t *by, const uint8_t *bu, const uint8_t *bv, int64_t n);   // host blocks -> c->d_in
@@ -297,6 +306,7 @@ int resolve_pending(pmp_ctx *c, bool wait);                         // looks at 
 void drop_pending(pmp_ctx *c);
 int sat_fetch(pmp_ctx *c, unsigned *out);                           // reads and clears the device flag word (synchronises)
 int sync(pmp_ctx *c);                                               // hipStreamSynchronize(c->stream)
+int sync_idle(pmp_ctx *c);                                          // ... as the last thing an entry point does: the context is idle afterwards
 int settle(pmp_ctx *c);                                             // everything asked of the context so far is done and final
 // Host-pointer entry points stage through the context's own buffers (d_in, d_logit, d_out) and return final results.  A *_device call
 // that is still in flight may re-run into those very buffers once its range flag is looked at (and a replayed post-processing call may
@@ -334,6 +344,6 @@ struct KScope {
 
 }  // namespace pmp
 
-#define CHECK_CTX(c) do { if (!(c)) return pmp::set_err(nullptr, PMP_E_INVALID, "null context"); hipSetDevice((c)->device); } while (0)
+#define CHECK_CTX(c) do { if (!(c)) return pmp::set_err(nullptr, PMP_E_INVALID, "null context"); hipSetDevice((c)->device); if ((c)->fence_due) { const int rc_ = pmp::fence_wait(c); if (rc_ != PMP_OK) return rc_; } (c)->unsettled = true; } while (0)
 
 #include "abl_hooks.h"   // hooks/ in the product build (no-op inlines), abl/ in the measurement library

@@ -253,6 +253,21 @@ int sync(pmp_ctx *c)
     return e == hipSuccess ? PMP_OK : hip_fail(c, e, "hipStreamSynchronize");
 }
 
+// sync() as the LAST thing an entry point does (pmp_synchronize, the host-pointer calls): the context is idle when it returns, so the
+// next change of stream has nothing to order (pmp_set_stream).  With the stream everything it was ordered behind has finished: the
+// second stream's join, and the streams the context was on before (the entry point made this one wait for their fence: CHECK_CTX).
+// A sync() in the MIDDLE of a call - a training call that first settles a pending re-run - is followed by that call's own work, and
+// leaves the flag alone.
+int sync_idle(pmp_ctx *c)
+{
+    const int rc = sync(c);
+    if (rc != PMP_OK) return rc;
+    c->unsettled = false;
+    c->fence_stream = nullptr;
+    c->fence_due = false;
+    return PMP_OK;
+}
+
 // Everything this context has been asked to do is done and final: range flags looked at, re-runs finished.
 int settle(pmp_ctx *c)
 {

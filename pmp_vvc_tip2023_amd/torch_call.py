@@ -10,7 +10,12 @@ def run(engine, dev, call):
     """call() with the engine on torch's current stream, and back on the stream it was on afterwards.  The legacy default stream
     has no handle the library could adopt (a null stream selects the context's OWN non-blocking stream, which torch's work is not
     ordered with): the call then runs on a side stream fenced against the current one on both ends, still without a host
-    synchronisation.  Shared by every training wrapper."""
+    synchronisation.  Shared by every training wrapper.
+
+    Two calls from two torch streams on one engine are safe: every set_stream here that changes the stream of a context with work in
+    flight makes the new stream wait, on the device, for what the context enqueued on the old one (include/pmp.h, pmp_set_stream), so
+    the context's workspace and scratch buffers are never used by two calls at once.  The tensors handed to call() are the caller's:
+    torch's stream rules order them, as for any op on the current stream."""
     import torch
     cur = torch.cuda.current_stream(dev)
     before = engine.stream_ptr

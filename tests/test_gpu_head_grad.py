@@ -21,48 +21,7 @@ pytestmark = pytest.mark.gpu
 RATIOS = {}
 P, nan, up = R.P, R.nan, R.up
 eng = R.engine_fixture(poison=1)
-IN_F, IN_B = ("x", "w", "b", "prev", "q"), ("x", "w", "g_y", "g_att")
-OUT_F, OUT_B = ("y", "att"), ("g_x", "g_w", "g_b", "g_q", "g_prev")
-
-
-class HeadDev:
-    """A head case on the device: its inputs as .d, NaN-filled outputs as .o (att and g_q only with an attention input).  off4: every
-    tensor 4 bytes behind a 16-byte boundary inside one NaN-patterned allocation each (train_rig.Off4)."""
-
-    def __init__(self, c, off4=False):
-        self.c, self.shape = c, c["shape"]
-        sz = H.sizes(self.shape)
-        self.d = {k: up(c[k]) for k in set(IN_F + IN_B)}
-        self.o = {k: nan(*sz[k]) for k in OUT_F + OUT_B if sz[k]}
-        self.guards = []
-        if off4:
-            for group in (self.d, self.o):
-                for k, t in group.items():
-                    if t is not None:
-                        self.guards.append(R.Off4(t))
-                        group[k] = self.guards[-1].view
-        R.torch_done()
-
-    def forward(self, e):
-        d, o = self.d, self.o
-        e.head_forward_device(self.shape, P(d["x"]), P(d["w"]), P(d["b"]), P(d["prev"]), P(d["q"]), P(o["y"]), P(o.get("att")))
-
-    def backward(self, e, want_g_x=None, want_g_q=None, want_g_prev=None):
-        c, d, o = self.c, self.d, self.o
-        pick = lambda flag, default, k: P(o.get(k)) if (default if flag is None else flag) else None
-        e.head_backward_device(self.shape, P(d["x"]), P(d["w"]), P(d["g_y"]), P(d["g_att"]), pick(want_g_x, c["want_g_x"], "g_x"), P(o["g_w"]),
-                               P(o["g_b"]), pick(want_g_q, c["want_g_q"], "g_q"), pick(want_g_prev, c["prev"] is not None, "g_prev"))
-
-    def results(self, e):
-        e.synchronize()
-        assert all(g.guards_intact() for g in self.guards)
-        return {k: R.num(v) for k, v in self.o.items()}
-
-    def outputs(self):
-        return list(self.o.items())
-
-    def inputs(self):
-        return [(k, t, self.c[k]) for k, t in self.d.items() if t is not None]
+HeadDev, IN_F = R.HeadDev, R.HeadDev.IN_F
 
 
 def run(e, c, off4=False):

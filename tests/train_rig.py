@@ -1,7 +1,7 @@
-"""The rig of the training calls' GPU tests (test_gpu_resblock_grad, test_gpu_trunk_grad, test_gpu_qtail_grad, test_gpu_stem_grad and the
-two sweeps): the engine fixture, tensors to and from the device, the bit check, a case of each call on the device (BlockDev, ChainDev
-as TrunkDev and TailDev, StemDev: the only parts that name a call's tensors), the determinism check and the harness of the refusal
-tests.  A plain module: every test file
+"""The rig of the training calls' GPU tests (test_gpu_resblock_grad, test_gpu_trunk_grad, test_gpu_qtail_grad, test_gpu_stem_grad,
+test_gpu_head_grad, the two sweeps and test_gpu_api_sequences_train): the engine fixture, tensors to and from the device, the bit check,
+a case of each call on the device (BlockDev, ChainDev as TrunkDev and TailDev, StemDev, HeadDev: the only parts that name a call's
+tensors), the determinism check and the harness of the refusal tests.  A plain module: every test file
 keeps its own cases, bounds and tables."""
 import ctypes as C
 
@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 import gpu_rig
+import head_cases as H
 import stem_cases as S
 import trunk_cases as T
 from cases_common import same_bits
@@ -351,6 +352,49 @@ def run_stem(e, c, want_g_x=True, y=None):
         d.forward(e)
     d.backward(e, want_g_x)
     return d.results(e)
+
+
+# ---- a head: pmp_head_forward_device / pmp_head_backward_device
+class HeadDev:
+    """A head case on the device: its inputs as .d, NaN-filled outputs as .o (att and g_q only with an attention input).  off4: every
+    tensor 4 bytes behind a 16-byte boundary inside one NaN-patterned allocation each (Off4)."""
+    IN_F, IN_B = ("x", "w", "b", "prev", "q"), ("x", "w", "g_y", "g_att")
+    OUT_F, OUT_B = ("y", "att"), ("g_x", "g_w", "g_b", "g_q", "g_prev")
+
+    def __init__(self, c, off4=False):
+        self.c, self.shape = c, c["shape"]
+        sz = H.sizes(self.shape)
+        self.d = {k: up(c[k]) for k in set(self.IN_F + self.IN_B)}
+        self.o = {k: nan(*sz[k]) for k in self.OUT_F + self.OUT_B if sz[k]}
+        self.guards = []
+        if off4:
+            for group in (self.d, self.o):
+                for k, t in group.items():
+                    if t is not None:
+                        self.guards.append(Off4(t))
+                        group[k] = self.guards[-1].view
+        torch_done()
+
+    def forward(self, e):
+        d, o = self.d, self.o
+        e.head_forward_device(self.shape, P(d["x"]), P(d["w"]), P(d["b"]), P(d["prev"]), P(d["q"]), P(o["y"]), P(o.get("att")))
+
+    def backward(self, e, want_g_x=None, want_g_q=None, want_g_prev=None):
+        c, d, o = self.c, self.d, self.o
+        pick = lambda flag, default, k: P(o.get(k)) if (default if flag is None else flag) else None
+        e.head_backward_device(self.shape, P(d["x"]), P(d["w"]), P(d["g_y"]), P(d["g_att"]), pick(want_g_x, c["want_g_x"], "g_x"), P(o["g_w"]),
+                               P(o["g_b"]), pick(want_g_q, c["want_g_q"], "g_q"), pick(want_g_prev, c["prev"] is not None, "g_prev"))
+
+    def results(self, e):
+        e.synchronize()
+        assert all(g.guards_intact() for g in self.guards)
+        return {k: num(v) for k, v in self.o.items()}
+
+    def outputs(self):
+        return list(self.o.items())
+
+    def inputs(self):
+        return [(k, t, self.c[k]) for k, t in self.d.items() if t is not None]
 
 
 # ---- determinism: twice, on a second stream, on a second context
