@@ -477,13 +477,13 @@ int pmp_train_loss_device(pmp_ctx *ctx, int comp, int qp, const pmp_loss_params 
  *        g_w0  = wgrad(x, gt)
  *        g_x   = conv(gt, flipT(w0)) + gu             (cin == cout)
  *              = conv(gt, flipT(w0)) + conv1x1(gu, wsc transposed)   (cin != cout)
- *      The masks are exactly `> 0` of the t and out the CALLER passes (torch's ReLU backward for finite values), so a trainer may hand
- *      in the tensors the forward call returned or its own.
+ *      The masks are exactly `> 0` of the t and out the CALLER passes - and open where t or out is NaN, torch's ReLU backward - so a
+ *      trainer may hand in the tensors the forward call returned or its own.
  *      ARITHMETIC: always the fp32 MFMA datapath (v_mfma_f32_16x16x4_f32, a chain of fused multiply-adds in float32), whatever
  *      pmp_set_precision says.  The forward is the launches of the inference graph on PMP_PRECISION_F32, bit for bit.  The weight
  *      gradients are reduced over (n, 16x16 tile) in two stages in an order that depends on the shape only, without atomics: the same
  *      bits on every run, stream, context and device.  On values whose every product and sum is exactly representable in float32 every
- *      result is exact.  Behaviour on non-finite values (NaN, +-inf in any tensor) is NOT specified.
+ *      result is exact.  NaN and +-inf in any tensor: NON-FINITE VALUES IN THE TRAINING CALLS, below.
  *      TENSORS: dense fp32 in torch's layouts at true scale - x, g_x [n][cin][h][w]; t, out, g_out [n][cout][h][w]; w0, g_w0
  *      [cout][cin][k][k]; w2, g_w2 [cout][cout][k][k]; wsc, g_wsc [cout][cin].  wsc (and, backward, g_wsc) are passed exactly when
  *      cin != cout and NULL otherwise.  g_x may be NULL: it is then not computed and nothing is written for it (a first block whose
@@ -509,6 +509,36 @@ int pmp_resblock_backward_device(pmp_ctx *ctx, const pmp_rb_shape *shape, const 
                                  const float *d_w0, const float *d_w2, const float *d_wsc, const float *d_g_out, float *d_g_x,
                                  float *d_g_w0, float *d_g_w2, float *d_g_wsc);
 
+/* ---- NON-FINITE VALUES IN THE TRAINING CALLS (pmp_resblock_*, pmp_trunk_*, pmp_qtail_*, pmp_stem_*, pmp_head_* / pmp_gate_*).  A trainer
+ *      notices a diverged run by a NaN or inf loss, so NaN and +-inf are ordinary data here and travel as they do in torch.  For every
+ *      tensor a call writes let R be the elements that are not finite when torch computes the same call on the CPU under autograd
+ *      (F.conv2d, F.relu, F.max_pool2d, F.interpolate as Model_QBD.py uses them), L those that are not finite in this library's result,
+ *      and S the REACH of the non-finite inputs: what the same net reaches with every weight non-zero (a split stem: with its three
+ *      kernels zero-padded to the one k x k kernel the library runs), every ReLU open and the pools kept - forward from the non-finite
+ *      input elements; backward from the non-finite gradient elements and from whatever the forward pass reached in a tensor that a
+ *      gradient is masked or routed by.  Weight and bias gradients are reachable as a whole, and a non-finite weight reaches everything.
+ *        1. DETECT   R is inside L.  Whether an element is NaN or inf, and its sign, is not specified.
+ *        2. CONTAIN  L is inside S.
+ *        3. Outside S every element is what the call gives without the non-finite inputs: the same bits.
+ *      How: relu(NaN) = NaN, relu(-inf) = +0; the maximum of a window that holds a NaN is NaN (2x2 pools, the QT tail's 2/4/8 windows);
+ *      a ReLU's backward passes g where the output is > 0 OR NaN (`out <= 0 ? 0 : g`, torch's threshold_backward); a pool's backward
+ *      gives the window's gradient to its LAST NaN if it holds one, else to its first maximum.  On finite values every result has the
+ *      bits it had before this was specified.
+ *      Where L is larger than R (all inside S):
+ *        - zero times non-finite is NaN.  Padded channel lanes and a split stem's zero taps have zero weights; the QT tail's q6 runs on
+ *          a map padded to 16 with a 0/1 region product; gt is the transposed convolution TIMES the 0/1 mask of t.  So an inf in a real
+ *          channel makes its pixel's padded lanes NaN, the next convolution spreads that over its window in every channel, and an inf
+ *          may come out as NaN.  The invariant "padded channels are zero" holds for FINITE inputs only.
+ *        - a pool window with several NaNs: which of them gets the gradient is torch's rule here, but a caller should not rely on it.
+ *      Where a result need not be non-finite on either side: a sum that overflows float32 in one order of summation and not in another
+ *      (a * 3e38 - b * 3e38: an MFMA's four-term inner product does not round in between, a chain of float32 additions does).
+ *      INFERENCE is not part of this: conv_mfma is also the fp32 inference datapath (PMP_PRECISION_F32, the range guard's fallback),
+ *      and there its ReLU and pool stay max(v, 0) and max(a, b), which map a NaN to 0 or to the other operand - one kernel, the
+ *      NaN's way through the ReLU behind a flag that only the training calls set.  Inference results do not move, on finite data or
+ *      any other.  The
+ *      f16x3 and bf16x6 datapaths and the fused 16x16 / 32x32 kernels are unchanged as well: a NaN raises their range flag.
+ *      tests/nonfinite_cases.py, tests/test_gpu_nonfinite.py. ---- */
+
 /* ---- training: a TRUNK - an nn.Sequential of 1..8 ResidualBlocks, optionally followed by F.max_pool2d(., 2) (Model_QBD.py:112-125,
  *      :136-137, :151: trunk_M1 = 6 blocks + pool, trunk_M2 = 4 + pool, trunk_B1..B3 = 3, trunk_Att1/2 = 2, resblock_q1/q2 = 1 + pool):
  *        y = [max_pool2d(., 2)] (block_{L-1} o ... o block_0)(x)
@@ -528,7 +558,8 @@ int pmp_resblock_backward_device(pmp_ctx *ctx, const pmp_rb_shape *shape, const 
  *      is then not computed and nothing is written for it.  Every byte of every requested output is written.
  *      POOL BACKWARD: the gradient of a 2x2 window goes to its FIRST maximum in the order (0,0), (0,1), (1,0), (1,1) - torch's
  *      max_pool2d rule (`val > maxval` replaces, so ties keep the earlier element) - recomputed from the saved un-pooled out; no index
- *      tensor is stored.  As in pmp_resblock_*, behaviour on non-finite values is NOT specified.
+ *      tensor is stored.  With a NaN in the window the gradient goes to the window's LAST NaN, as torch's (`|| isnan(val)`); non-finite
+ *      values otherwise as in pmp_resblock_* (NON-FINITE VALUES IN THE TRAINING CALLS, above).
  *      PMP_E_INVALID before any launch, nothing written: a NULL or unsupported shape; a missing tensor; a shortcut pointer present
  *      where cin_i == cout[i] or absent where they differ; a d_g_w whose NULL pattern differs from d_w's; an output that overlaps an
  *      input or another output (d_saved is an output of forward and an input of backward and unpack); a pointer that is not 4-byte
@@ -564,7 +595,7 @@ int pmp_trunk_unpack_device(pmp_ctx *ctx, const pmp_trunk_shape *shape, const vo
  *      BACKWARD: gm = g_y where y > 0, else 0 (torch's mask rule); g_w[j], g_b[j] have the shapes of w[j], b[j]; g_x [n][cin][h+p][w+p]
  *      is optional: NULL = not computed, nothing written.  Every element of every requested output is written.  The weight and bias
  *      gradients are a two-stage reduction whose order depends on the shape only, the input gradient a fixed chain per element: no
- *      atomics, the same bits on every run, stream and context.  Behaviour on non-finite values is NOT specified.
+ *      atomics, the same bits on every run, stream and context.  Non-finite values: NON-FINITE VALUES IN THE TRAINING CALLS, above.
  *      SHAPES: n 1..256; h and w multiples of 16 in 16..256; cin 1..4; k 5 or 9; split 0 or 1.  d_w, d_b, d_g_w, d_g_b are HOST arrays
  *      of three device pointers; entries 1 and 2 are non-NULL exactly when split = 1.
  *      PMP_E_INVALID before any launch, nothing written: a NULL or unsupported shape, a missing tensor or array, entries 1 and 2
@@ -608,7 +639,8 @@ int pmp_stem_backward_device(pmp_ctx *ctx, const pmp_stem_shape *shape, const fl
  *      PMP_E_INVALID before any launch, nothing written: a NULL or unsupported shape, a missing tensor, q / att / g_att against the
  *      rule, g_q without g_att, an output that overlaps an input or another output, a pointer that is not 4-byte aligned.  Every
  *      element of every requested output is written.  Settles the context's calls in flight, then runs stream-ordered on its stream;
- *      the partial sums live in the activation workspace.  Behaviour on non-finite values is NOT specified. ---- */
+ *      the partial sums live in the activation workspace.  Non-finite values: NON-FINITE VALUES IN THE TRAINING CALLS, above - a
+ *      head is a convolution, a carry, copies and window sums, a gate a product: no ReLU, no maximum, nothing masked or routed. ---- */
 typedef struct pmp_head_shape {
     int n, h, w, cin, cout, up_q, up_y;
 } pmp_head_shape;
@@ -668,7 +700,7 @@ int pmp_gate_backward_device(pmp_ctx *ctx, int64_t count, const float *d_x, cons
  *      x5 > 0, else +0.
  *      BACKWARD walks q6, the pool, q5, q4, the multi-scale pool, q3.  d_g_x4 may be NULL: q3's data gradient is then not computed
  *      and nothing is written for it.  Every byte of every requested output is written.  No atomics anywhere: the same bits on every
- *      run, stream and context.  Behaviour on non-finite values is NOT specified.
+ *      run, stream and context.  Non-finite values: NON-FINITE VALUES IN THE TRAINING CALLS, above.
  *      PMP_E_INVALID before any launch, nothing written: a NULL or unsupported shape; a missing tensor or array; a NULL pattern of d_w
  *      or d_g_w against the rule; an output that overlaps an input or another output (d_saved is an output of forward and an input of
  *      backward and unpack); a pointer that is not 4-byte aligned (d_saved: 16-byte); an unpack index outside 0..8.
@@ -815,7 +847,9 @@ int64_t pmp_debug_get_tap(pmp_ctx *ctx, const char *name, double *out, int64_t c
 
 /* ---- test hook: poisoned workspaces.  pattern 1: before every pass, fill every activation workspace the context uses (its own, the
  *      second one of overlap mode, one taken over from a destroyed context - the whole buffer) with 0xFF bytes, a NaN in fp32, bf16 and
- *      fp16; pattern 2: with 0x3C bytes, a finite value (0.0115 in fp32, 1.06 in fp16) that a ReLU would not swallow as it swallows a NaN.
+ *      fp16; pattern 2: with 0x3C bytes, a finite value (0.0115 in fp32, 1.06 in fp16): in the inference graph a ReLU is a hardware
+ *      maximum, which returns 0 for a NaN, so in an inference pass a NaN that was read can vanish before it shows.  (The training calls
+ *      carry a NaN through ReLU and pool - NON-FINITE VALUES IN THE TRAINING CALLS - so there pattern 1 shows it too.)
  *      The context's own logit buffers (fused entry points called without logit pointers, host-pointer entry points) are filled too
  *      before each call that uses them.  hipMemsetAsync on the context's streams, nothing else; 0 (default) turns it off.  A kernel that
  *      reads a byte it did not write shows up as a difference from an unpoisoned run (tests/test_gpu_layers.py).  Settles first. ---- */

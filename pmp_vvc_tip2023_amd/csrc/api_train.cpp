@@ -88,7 +88,7 @@ struct TrainGraph {
         if (x_sc) { a.x_sc = x_sc->p; a.w_sc = w_sc->p; a.Csc = csc_p; }
         if (res) a.res = res->p;
         if (gate) a.gate = gate->p;
-        a.N = n; a.H = h; a.W = w; a.Cin = cin_p; a.Cout = cout_p; a.KH = a.KW = k; a.relu = relu ? 1 : 0;
+        a.N = n; a.H = h; a.W = w; a.Cin = cin_p; a.Cout = cout_p; a.KH = a.KW = k; a.relu = relu ? 1 : 0; a.nan = 1;
         check(launch_conv_mfma(ps.stream, a), "conv_mfma");
     }
     void wgrad(const Tensor &a, int ca_p, const Tensor &g, int cg_p, int k, float *dw, int cout, int cin)

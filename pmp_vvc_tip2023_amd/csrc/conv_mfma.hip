@@ -209,6 +209,7 @@ __global__ __launch_bounds__(256, OCC) void conv_mfma_kernel(ConvMfmaArgs a)
     // ---- epilogue: lane owns pixel (row 4*wave+m, x = xl), channels 16*nt + 4g .. +3
     const int H = a.H, W = a.W;
     const size_t plane = (size_t)H * W * 16;
+    const bool carry = __builtin_amdgcn_readfirstlane(a.nan) != 0;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
 #pragma unroll
@@ -218,7 +219,12 @@ __global__ __launch_bounds__(256, OCC) void conv_mfma_kernel(ConvMfmaArgs a)
             f32x4 v = acc[m][nt];
             if (a.res) v += *reinterpret_cast<const f32x4 *>(a.res + off);
             if (a.relu) {
+                const f32x4 pre = v;
                 v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+                if (carry) {            // the training calls: a NaN goes through (relu_nan).  Uniform: the inference graph jumps over it
+                    v.x = pre.x != pre.x ? pre.x : v.x; v.y = pre.y != pre.y ? pre.y : v.y;
+                    v.z = pre.z != pre.z ? pre.z : v.z; v.w = pre.w != pre.w ? pre.w : v.w;
+                }
             }
             if (a.gate) v *= *reinterpret_cast<const f32x4 *>(a.gate + off);
             acc[m][nt] = v;
@@ -231,7 +237,8 @@ __global__ __launch_bounds__(256, OCC) void conv_mfma_kernel(ConvMfmaArgs a)
                 *reinterpret_cast<f32x4 *>(a.out + off) = acc[m][nt];
             }
         } else {
-            // 2x2 max-pool: rows (m, m+1) live in this lane, columns (x, x^1) in the neighbouring lane.
+            // 2x2 max-pool: rows (m, m+1) live in this lane, columns (x, x^1) in the neighbouring lane.  (The inference graph's only: a
+            // trunk's training pool is trunk_glue.hip's pool_to_dense, which carries a NaN.)
             const int Ho = H >> 1, Wo = W >> 1;
 #pragma unroll
             for (int m = 0; m < 4; m += 2) {

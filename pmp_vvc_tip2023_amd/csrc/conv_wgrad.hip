@@ -168,7 +168,7 @@ __global__ __launch_bounds__(256) void dense_to_blocked_kernel(const float *__re
     if (c < C) {
         const size_t i = (((size_t)n * C + c) * H + y) * W + x;
         v = src[i];
-        if (mode == 1) v = m[i] > 0.f ? v : 0.f;
+        if (mode == 1) v = relu_on(m[i]) ? v : 0.f;
     }
     tile[tid >> 4][tid & 15] = v;
     __syncthreads();

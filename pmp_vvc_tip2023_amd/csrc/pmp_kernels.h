@@ -16,6 +16,17 @@ namespace pmp {
 // -1 = absent) - host side, and a no-op unless that hook is collecting on this thread (api_debug.cpp).
 void note_launch(const char *kernel, int t0, int t1, int t2, int t3 = -1, int t4 = -1);
 
+// ReLU and maximum that CARRY a NaN, as torch's relu and max_pool2d do (include/pmp.h: NON-FINITE VALUES): the hardware maximum
+// behind fmaxf returns the operand that is a number.  On numbers (infinities and signed zeros included) the result is fmaxf's, bit for
+// bit; the compare and the select are what a NaN costs.  relu_nan(-inf) = +0, as torch's.
+__device__ __forceinline__ float relu_nan(float v) { const float m = fmaxf(v, 0.f); return v != v ? v : m; }
+// A ReLU's output lets its gradient through: out > 0, or out is NaN - torch's threshold_backward is `out <= 0 ? 0 : g`.  And the element
+// of a pooled window that gets the gradient: torch's max_pool2d replaces its maximum on `val > max || isnan(val)`, so the LAST NaN of a
+// window wins, and without a NaN the first maximum.
+__device__ __forceinline__ bool relu_on(float out) { return !(out <= 0.f); }
+__device__ __forceinline__ bool pool_takes(float v, float best) { return v > best || v != v; }
+__device__ __forceinline__ float max_nan(float a, float b) { const float m = fmaxf(a, b); return __builtin_isunordered(a, b) ? __builtin_nanf("") : m; }
+
 // ------------------------------------------------------------------------------------------------ conv (MFMA)
 // out = epilogue( conv_KHxKW(x, w) [+ conv_1x1(x_sc, w_sc)] [+ res] ), stride 1, zero padding K/2.
 // epilogue: optional ReLU, optional multiply by `gate`, optional 2x2 max-pool.  H, W multiples of 16;
@@ -30,6 +41,7 @@ struct ConvMfmaArgs {
     float *out;         // [N][Cout/16][H(/2)][W(/2)][16]
     int N, H, W, Cin, Csc, Cout, KH, KW;
     int relu, pool;
+    int nan;            // the ReLU carries a NaN (relu_nan): the training calls.  0, the inference graph: max(v, 0), which maps a NaN to 0
 };
 hipError_t launch_conv_mfma(hipStream_t s, const ConvMfmaArgs &a);
 

@@ -15,7 +15,7 @@ namespace {       // the kernels too: the launcher below is this file's one name
 
 __device__ __forceinline__ f32x4 vmax(f32x4 a, f32x4 b)
 {
-    return (f32x4){fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w)};
+    return (f32x4){max_nan(a.x, b.x), max_nan(a.y, b.y), max_nan(a.z, b.z), max_nan(a.w, b.w)};
 }
 
 // The grid of every kernel here: x = the pieces of a row, 256 per workgroup, y = the row, z = (image, channel group) of a tensor
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void qt_multipool_kernel(const f32x4 *__restri
 }
 
 // g6 as two tensors [N][4][H][W][16] (channels 0..63 and 64..127) and x5 -> q3's upstream gradient [N][2][H][W][16]:
-// g = g6[c]; g = g + r2; g = g + r4; g = g + r8; out = x5 > 0 ? g : +0  (include/pmp.h: MULTI-SCALE POOL, BACKWARD)
+// g = g6[c]; g = g + r2; g = g + r4; g = g + r8; out = relu_on(x5) ? g : +0 (x5 > 0 or NaN)  (include/pmp.h: MULTI-SCALE POOL, BACKWARD)
 __global__ __launch_bounds__(256) void qt_multipool_back_kernel(const f32x4 *__restrict__ ga, const f32x4 *__restrict__ gb,
                                                                 const f32x4 *__restrict__ x5, f32x4 *__restrict__ out, int H, int W)
 {
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void qt_multipool_back_kernel(const f32x4 *__r
                 if ((yy >> sh) != (p.y >> sh) || (xx >> sh) != (p.x >> sh)) continue;
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    if (v[j] > best[l][j]) { best[l][j] = v[j]; first[l][j] = (dy << 3) | dx; }
+                    if (pool_takes(v[j], best[l][j])) { best[l][j] = v[j]; first[l][j] = (dy << 3) | dx; }
             }
         }
     const f32x4 g0 = ga[piece_at(p.n, 4, p.grp, H, W, p.y, p.x, p.q)];
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256) void qt_multipool_back_kernel(const f32x4 *__r
         for (int j = 0; j < 4; ++j) g[j] = g[j] + (first[l][j] == mine ? r[j] : 0.f);
     }
     const f32x4 me = x5[i];
-    out[i] = (f32x4){me.x > 0.f ? g[0] : 0.f, me.y > 0.f ? g[1] : 0.f, me.z > 0.f ? g[2] : 0.f, me.w > 0.f ? g[3] : 0.f};
+    out[i] = (f32x4){relu_on(me.x) ? g[0] : 0.f, relu_on(me.y) ? g[1] : 0.f, relu_on(me.z) ? g[2] : 0.f, relu_on(me.w) ? g[3] : 0.f};
 }
 
 // q5's out [N][2][H][W][16] -> x8 [N][2][H2][W2][16]: the 2x2 maximum inside the H/2 x W/2 region, +0 outside it; and, if asked for,
@@ -133,7 +133,8 @@ __global__ __launch_bounds__(256) void qt_pool_embed_kernel(const f32x4 *__restr
 }
 
 // q6's data gradient g8 [N][2][H2][W2][16] and q5's out [N][2][H][W][16] -> q5's upstream gradient [N][2][H][W][16]:
-// g8[y/2][x/2] where out > 0 and (y, x) is the first maximum of its 2x2 window in the order (0,0), (0,1), (1,0), (1,1), else +0
+// g8[y/2][x/2] where out > 0 or NaN (relu_on) and (y, x) is the first maximum of its 2x2 window in the order (0,0), (0,1), (1,0), (1,1) - or
+// the window's last NaN (pool_takes) -, else +0
 __global__ __launch_bounds__(256) void qt_pool_back_kernel(const f32x4 *__restrict__ g8, const f32x4 *__restrict__ o5, f32x4 *__restrict__ out,
                                                            int H, int W, int H2, int W2)
 {
@@ -151,13 +152,13 @@ __global__ __launch_bounds__(256) void qt_pool_back_kernel(const f32x4 *__restri
         int first = 0;
 #pragma unroll
         for (int k = 1; k < 4; ++k)
-            if (e[k][j] > best) { best = e[k][j]; first = k; }
-        res[j] = (first == mine && e[mine][j] > 0.f) ? g[j] : 0.f;
+            if (pool_takes(e[k][j], best)) { best = e[k][j]; first = k; }
+        res[j] = (first == mine && relu_on(e[mine][j])) ? g[j] : 0.f;
     }
     out[i] = (f32x4){res[0], res[1], res[2], res[3]};
 }
 
-// the dense g_x9 [N][8][H/2][W/2] and q6's out [N][1][H2][W2][16] -> q6's upstream gradient [N][1][H2][W2][16]: g where out > 0 (which
+// the dense g_x9 [N][8][H/2][W/2] and q6's out [N][1][H2][W2][16] -> q6's upstream gradient [N][1][H2][W2][16]: g where out > 0 or NaN (which
 // is inside the region and in channels 0..7 only), else +0
 __global__ __launch_bounds__(256) void qt_embed_grad_kernel(const float *__restrict__ g, const f32x4 *__restrict__ o6, f32x4 *__restrict__ out,
                                                             int H, int W, int H2, int W2)
@@ -171,7 +172,7 @@ __global__ __launch_bounds__(256) void qt_embed_grad_kernel(const float *__restr
     if (p.y < hh && p.x < wh && p.q < 2) {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            if (o[j] > 0.f) res[j] = g[(((size_t)p.n * 8 + p.q * 4 + j) * hh + p.y) * wh + p.x];
+            if (relu_on(o[j])) res[j] = g[(((size_t)p.n * 8 + p.q * 4 + j) * hh + p.y) * wh + p.x];
     }
     out[i] = (f32x4){res[0], res[1], res[2], res[3]};
 }

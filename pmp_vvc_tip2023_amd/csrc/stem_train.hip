@@ -21,7 +21,7 @@
 //                     reduction index comes from a table in LDS, built once per workgroup.  ORDER of one output element:
 //                     acc = b[co]; then acc = fma(wu[co][r], x[..r..], acc) for r = 0 .. R-1 in that order (indices R .. 4 ceil(R/4) - 1
 //                     add +0 * 0); relu; store.
-// stem_wgrad_kernel   the GEMM that reduces over pixels (conv_wgrad.hip's): A = gm (16 outputs x 4 pixels), gm = g_y where y > 0 else
+// stem_wgrad_kernel   the GEMM that reduces over pixels (conv_wgrad.hip's): A = gm (16 outputs x 4 pixels), gm = g_y where y > 0 or NaN, else
 //                     0, staged in LDS per tile; B = the shifted input pixels from the staged tile (4 pixels x 16 columns), column
 //                     c < R the reduction index r = c, column R the constant 1.0 - the BIAS gradient, its lanes reading a run of 1.0s
 //                     kept behind the tile in LDS - and columns above R up to the next multiple of 16 padding that is never stored.  NT = ceil((R + 1) / 16) column tiles x 2 co-groups of
@@ -165,7 +165,7 @@ __global__ __launch_bounds__(256) void stem_forward_kernel(StemTrainArgs a, cons
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int co = cg * 16 + 4 * g + r;
-                a.y_out[(((size_t)n * 32 + co) * a.H + ty * 16 + wave * 4 + j) * a.W + tx * 16 + c] = fmaxf(acc[cg][j][r], 0.f);
+                a.y_out[(((size_t)n * 32 + co) * a.H + ty * 16 + wave * 4 + j) * a.W + tx * 16 + c] = relu_nan(acc[cg][j][r]);
             }
 }
 
@@ -200,7 +200,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(StemTrainArgs a, float 
         for (int i = tid; i < 32 * 256; i += 256) {
             const int co = i >> 8, pix = i & 255;
             const size_t at = (((size_t)n * 32 + co) * H + ty * 16 + (pix >> 4)) * W + tx * 16 + (pix & 15);
-            gs[co * GS + pix] = a.y[at] > 0.f ? a.g_y[at] : 0.f;
+            gs[co * GS + pix] = relu_on(a.y[at]) ? a.g_y[at] : 0.f;
         }
         __syncthreads();
         const float *ga = gs + (cg * 16 + c) * GS + g;          // lane (c, g) of k-step s in row yy: gm[co c][pixel (yy, 4 s + g)]
@@ -262,7 +262,7 @@ __global__ __launch_bounds__(256) void stem_dgrad_kernel(StemTrainArgs a)
             float v = 0.f;
             if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
                 const size_t at = (((size_t)n * 32 + c0 + co) * H + gy) * W + gx;
-                v = a.y[at] > 0.f ? a.g_y[at] : 0.f;
+                v = relu_on(a.y[at]) ? a.g_y[at] : 0.f;
             }
             gs[i] = v;
         }

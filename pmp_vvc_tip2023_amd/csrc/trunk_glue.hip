@@ -3,14 +3,15 @@
 // the last block blocked -> dense, and its backward (fused with the last block's ReLU backward) dense -> blocked.  All of them move
 // every element once and are bound by HBM: 16-byte loads and stores on the blocked side, a lane's four words being four channels of
 // one pixel, so that a wave covers 1 KiB of consecutive bytes.  Padded channels (>= the real count) are zero in every blocked input
-// and come out as zero: `> 0` is false for them, and the dense side supplies zeros.
+// and come out as zero: `> 0` is false for them, and the dense side supplies zeros.  (For FINITE inputs: 0 * inf = NaN in a padded lane,
+// and a NaN opens a mask as it opens torch's - include/pmp.h, NON-FINITE VALUES IN THE TRAINING CALLS.)
 #include "pmp_kernels.h"
 
 namespace pmp {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// mode 1: dst = a where m > 0, else +0;  2: dst = [a > 0], the ReLU mask itself.  In both dst may be a: every thread reads its own
+// mode 1: dst = a where m > 0 or m is NaN (relu_on), else +0;  2: dst = [relu_on(a)], the ReLU mask itself.  In both dst may be a: every thread reads its own
 // words before it writes them, and no other thread touches them (mode 2 in place: a single block's backward, api_train.cpp).
 // A workgroup moves 1024 consecutive 16-byte pieces, four per thread; n4 (a whole number of 16x16 tiles of 16 channels) is a multiple
 // of 1024, and the guard is there for a caller that breaks that.
@@ -33,11 +34,11 @@ __global__ __launch_bounds__(256) void blocked_relu_kernel(const f32x4 *a, const
         if (j >= n4) continue;
         f32x4 r;
         if (MODE == 1) {
-            r.x = w[i].x > 0.f ? v[i].x : 0.f; r.y = w[i].y > 0.f ? v[i].y : 0.f;
-            r.z = w[i].z > 0.f ? v[i].z : 0.f; r.w = w[i].w > 0.f ? v[i].w : 0.f;
+            r.x = relu_on(w[i].x) ? v[i].x : 0.f; r.y = relu_on(w[i].y) ? v[i].y : 0.f;
+            r.z = relu_on(w[i].z) ? v[i].z : 0.f; r.w = relu_on(w[i].w) ? v[i].w : 0.f;
         } else {
-            r.x = v[i].x > 0.f ? 1.f : 0.f; r.y = v[i].y > 0.f ? 1.f : 0.f;
-            r.z = v[i].z > 0.f ? 1.f : 0.f; r.w = v[i].w > 0.f ? 1.f : 0.f;
+            r.x = relu_on(v[i].x) ? 1.f : 0.f; r.y = relu_on(v[i].y) ? 1.f : 0.f;
+            r.z = relu_on(v[i].z) ? 1.f : 0.f; r.w = relu_on(v[i].w) ? 1.f : 0.f;
         }
         dst[j] = r;
     }
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(256) void pool_to_dense_kernel(const float *__restr
     const int ch = tid >> 4, ro = (tid >> 3) & 1, xo = tid & 7, c = u.grp * 16 + ch;
     const float *t = reinterpret_cast<const float *>(tile);
     auto at = [&](int row, int col) { return t[((row * 16 + col) * 5) * 4 + ch]; };
-    const float v = fmaxf(fmaxf(at(2 * ro, 2 * xo), at(2 * ro + 1, 2 * xo)), fmaxf(at(2 * ro, 2 * xo + 1), at(2 * ro + 1, 2 * xo + 1)));
+    const float v = max_nan(max_nan(at(2 * ro, 2 * xo), at(2 * ro + 1, 2 * xo)), max_nan(at(2 * ro, 2 * xo + 1), at(2 * ro + 1, 2 * xo + 1)));
     if (c < C) dst[(((size_t)u.n * C + c) * (H >> 1) + (u.y0 >> 1) + ro) * (W >> 1) + (u.x0 >> 1) + xo] = v;
 }
 
@@ -99,7 +100,8 @@ hipError_t launch_pool_to_dense(hipStream_t s, const float *src, float *dst, int
 // The upstream gradient of a trunk, dense, -> the blocked gu of its last block (every element written, padded channels +0).
 // POOL = 0: g [N][C][H][W],      gu = g where out > 0, else +0.
 // POOL = 1: g [N][C][H/2][W/2],  gu[y][x] = g[y/2][x/2] where out[y][x] > 0 and (y, x) is the FIRST maximum of its 2x2 window in the
-//           order (0,0), (0,1), (1,0), (1,1) - torch's max_pool2d keeps the earlier element on a tie (`val > maxval` replaces) - else +0.
+//           order (0,0), (0,1), (1,0), (1,1) - torch's max_pool2d keeps the earlier element on a tie (`val > maxval` replaces) - or the
+//           window's LAST NaN (`|| isnan(val)`), else +0.
 template <int POOL>
 __global__ __launch_bounds__(256) void grad_to_blocked_kernel(const float *__restrict__ g, const float *__restrict__ out, float *__restrict__ dst,
                                                               int C, int G, int H, int W)
@@ -123,7 +125,7 @@ __global__ __launch_bounds__(256) void grad_to_blocked_kernel(const float *__res
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int ch = q * 4 + j;
-        bool take = ov[j] > 0.f;
+        bool take = relu_on(ov[j]);
         if (POOL) {
             const float *t = reinterpret_cast<const float *>(tile);
             const int wy = r & ~1, wx = px & ~1;
@@ -132,7 +134,7 @@ __global__ __launch_bounds__(256) void grad_to_blocked_kernel(const float *__res
 #pragma unroll
             for (int e = 1; e < 4; ++e) {
                 const float v = t[(((wy + (e >> 1)) * 16 + wx + (e & 1)) * 5) * 4 + ch];
-                if (v > best) { best = v; first = e; }
+                if (pool_takes(v, best)) { best = v; first = e; }
             }
             take = take && first == ((r & 1) * 2 + (px & 1));
         }
