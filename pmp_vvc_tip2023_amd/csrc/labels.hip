@@ -3,10 +3,8 @@
 // Replaces, bit-exactly wherever the reference finishes:
 //   Map_to_SubMap(qt, bt, dire, cf).get_sub_map()   GenMSBtMap.py:89-368  (called per block by gen_seq_sub_map, :434-449)
 //
-// Same design as postproc.hip (Map2Partition): the block's 16x16 cells spread over the 64 lanes, 4 per lane (lane l: row l>>2,
-// columns 4*(l&3)..+3); the candidate-tree search (get_candidate_map_tree, :188-241) as wave-uniform DFS with region counts by
-// ballot + popcount, CU lists lane-distributed, the three MTT levels unrolled at compile time; four waves per block, wave w
-// searching the QT leaves of quadrant w.  What differs from Map2Partition (all reproduced):
+// The search's frame - cells on lanes, the quadtree walk, split modes, combinations, child CU lists; wave w searching the QT leaves of
+// quadrant w - is m2p_tree.h's, shared with Map2Partition (postproc.hip).  GenMSBtMap's own rules, all reproduced here:
 //   * lamb1..lamb5 = 0.8, 1.0, 1.2, 0.2, 0.2 (:91), counts compared with double products in Python's order;
 //   * the depth map is the integer LABEL bt (u8), one map for every level, and the direction map the i8 label dire (:125-130);
 //   * a direction map that does not dominate returns [0] (:138-139);
@@ -21,20 +19,14 @@
 // of the labels' own partition (label_partition_kernel below; include/pmp.h: pmp_label_partition).  The templates' PART argument
 // selects what a best leaf remembers: its CU list (PART) or the maps of its ancestors (!PART).
 #include "../../include/pmp.h"
+#include "m2p_tree.h"
 #include "pmp_kernels.h"
 
 namespace pmp {
 
+using namespace tree;
+
 namespace {
-
-__device__ __forceinline__ int rlane(int v, int lane)
-{
-    return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(lane));
-}
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ int cnt(bool p) { return __popcll(__ballot(p)); }
-
-__device__ __forceinline__ int pack_cu(int x, int y, int h, int w) { return x | (y << 4) | ((h - 1) << 8) | ((w - 1) << 12); }
 
 // GenMSBtMap.py:91 - Python's float64 values; (1 - lamb5) is formed in float64 as Python does (:180), and it is not 0.8
 constexpr double L1 = 0.8, L2 = 1.0, L3 = 1.2, L4 = 0.2, L5 = 0.2, L5C = 1.0 - L5;
@@ -60,15 +52,15 @@ struct Sub {
 template <int L>
 __device__ __forceinline__ int can_split(const Sub &s, int cu, int &n)
 {
-    const int x = cu & 15, y = (cu >> 4) & 15, h = ((cu >> 8) & 15) + 1, w = ((cu >> 12) & 15) + 1;
+    const CU u = unpack_cu(cu);
     bool in[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) in[k] = s.row >= x && s.row < x + h && s.col0 + k >= y && s.col0 + k < y + w;
+    for (int k = 0; k < 4; ++k) in[k] = s.row >= u.x && s.row < u.x + u.h && s.col0 + k >= u.y && s.col0 + k < u.y + u.w;
     int zero = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) zero += cnt(in[k] && s.lb[k] == s.bt[L][k]);
     n = 1;
-    if ((double)zero >= L1 * h * w) return 0;            // no partition: [0]
+    if ((double)zero >= L1 * u.h * u.w) return 0;            // no partition: [0]
     int hor = 0, ver = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -76,45 +68,25 @@ __device__ __forceinline__ int can_split(const Sub &s, int cu, int &n)
         ver += cnt(in[k] && s.ld[L][k] == -1);
     }
     int direction = 0;
-    if ((double)(ver + hor) >= L2 * h * w) {
+    if ((double)(ver + hor) >= L2 * u.h * u.w) {
         if ((double)hor >= L3 * ver) direction = 1;
         else if ((double)ver >= L3 * hor) direction = 2;
     } else {
         return 0;                                        // [0]
     }
-    const int cf = s.cf;
-    int list = 0;
-    n = 0;
-    for (int mode = 1; mode <= 4; ++mode) {
-        const bool horiz = (mode & 1) != 0;      // 1 BT-H, 3 TT-H
-        const int ext = horiz ? h : w;
-        const int div = (mode <= 2 ? 2 : 4) * cf;
-        if (ext / div == 0 || ext % div != 0) continue;
-        if (horiz && direction == 2) continue;
-        if (!horiz && direction == 1) continue;
-        const int parts = mode <= 2 ? 2 : 3;
-        int ok = 0;
-        for (int p = 0; p < parts; ++p) {
-            int o0, o1, inc;
-            if (mode <= 2) { o0 = p * (ext / 2); o1 = o0 + ext / 2; inc = 1; }
-            else if (p == 0) { o0 = 0; o1 = ext / 4; inc = 2; }
-            else if (p == 1) { o0 = ext / 4; o1 = o0 + ext / 2; inc = 1; }
-            else { o0 = (ext * 3) / 4; o1 = ext; inc = 2; }
-            int minus = 0, zer = 0;
+    n = 0;                                               // the list starts empty (:157)
+    return split_modes(u.h, u.w, s.cf, direction, 0, n, [&](bool horiz, int o0, int o1, int inc, int np_) {
+        int minus = 0, zer = 0;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int t = horiz ? (s.row - x) : (s.col0 + k - y);
-                const bool ins = in[k] && t >= o0 && t < o1;
-                const int tgt = s.bt[L][k] + inc;        // bt_map_temp (i8) after the += 1 (+1): u8 - i8 -> i16, no wrap
-                minus += cnt(ins && s.lb[k] < tgt);
-                zer += cnt(ins && s.lb[k] == tgt);
-            }
-            const int np_ = (o1 - o0) * (horiz ? w : h);
-            if ((double)minus < np_ * L4 && ((double)zer < np_ * L5 || (double)zer > np_ * L5C)) ++ok;
+        for (int k = 0; k < 4; ++k) {
+            const int t = horiz ? (s.row - u.x) : (s.col0 + k - u.y);
+            const bool ins = in[k] && t >= o0 && t < o1;
+            const int tgt = s.bt[L][k] + inc;            // bt_map_temp (i8) after the += 1 (+1): u8 - i8 -> i16, no wrap
+            minus += cnt(ins && s.lb[k] < tgt);
+            zer += cnt(ins && s.lb[k] == tgt);
         }
-        if (ok == parts) { list |= mode << (3 * n); ++n; }
-    }
-    return list;
+        return (double)minus < np_ * L4 && ((double)zer < np_ * L5 || (double)zer > np_ * L5C);
+    });
 }
 
 // A leaf at depth D (get_leaf_nodes order = the order the DFS reaches it).  Budget: the (PMP_MSBT_LEAF_BUDGET + 1)-th leaf stops the
@@ -127,8 +99,7 @@ __device__ __forceinline__ void score_leaf(Sub &s)
     int e = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const int r = s.row - s.rx, c = s.col0 + k - s.ry;
-        if (r >= 0 && r < s.rh && c >= 0 && c < s.rw)
+        if (in_region(s, k))
             e += D == 0 ? s.lb[k] : ((s.bt[D][k] - s.lb[k]) & 255);   // i8 root map: |0 - bt|; u8 child maps: (leaf - bt) mod 256
     }
     e += __shfl_xor(e, 32);
@@ -173,60 +144,14 @@ __device__ __forceinline__ void expand(Sub &s)
             if (n == 0) { score_leaf<L, PART>(s); return; }    // a CU without a proper partition: the node has no children (:201-202)
             if (lane == c) { my_list = list; my_n = n; }
         }
-        // mixed-radix combination index, first CU slowest (Search, :45-79)
-        int my_p = 1, total = 1;
-        for (int c = ncu - 1; c >= 0; --c) {
-            if (lane == c) my_p = total;
-            total *= rlane(my_n, c);
-        }
-        total = uni(total);
+        const auto [my_p, total] = combos(my_n, ncu);   // Search, :45-79
         for (int t = 0; t < total && !s.stop; ++t) {
-            const int my_mode = (my_list >> (3 * ((t / my_p) % my_n))) & 7;
             int nb[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) nb[k] = s.bt[L][k];
-            int child_cu = 0, nchild = 0;
-            for (int c = 0; c < ncu; ++c) {
-                const int mode = rlane(my_mode, c), cu = rlane(s.cu[L], c);
-                const int x = cu & 15, y = (cu >> 4) & 15, h = ((cu >> 8) & 15) + 1, w = ((cu >> 12) & 15) + 1;
-                if (mode == 0) {
-                    if (lane == nchild) child_cu = cu;
-                    nchild += 1;
-                    continue;
-                }
-                const bool horiz = (mode & 1) != 0;
-                const int ext = horiz ? h : w;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int r = s.row - x, cc = s.col0 + k - y;
-                    if (r >= 0 && r < h && cc >= 0 && cc < w) {
-                        const int tt = horiz ? r : cc;
-                        nb[k] += (mode >= 3 && (tt < ext / 4 || tt >= (ext * 3) / 4)) ? 2 : 1;
-                    }
-                }
-                // split_cur_map (:107-121): sub-CUs appended in order
-                if (mode <= 2) {
-                    const int e = ext / 2;
-                    const int c0 = horiz ? pack_cu(x, y, e, w) : pack_cu(x, y, h, e);
-                    const int c1 = horiz ? pack_cu(x + e, y, e, w) : pack_cu(x, y + e, h, e);
-                    if (lane == nchild) child_cu = c0;
-                    if (lane == nchild + 1) child_cu = c1;
-                    nchild += 2;
-                } else {
-                    const int q = ext / 4, e = ext / 2, o2 = (ext * 3) / 4;
-                    const int c0 = horiz ? pack_cu(x, y, q, w) : pack_cu(x, y, h, q);
-                    const int c1 = horiz ? pack_cu(x + q, y, e, w) : pack_cu(x, y + q, h, e);
-                    const int c2 = horiz ? pack_cu(x + o2, y, q, w) : pack_cu(x, y + o2, h, q);
-                    if (lane == nchild) child_cu = c0;
-                    if (lane == nchild + 1) child_cu = c1;
-                    if (lane == nchild + 2) child_cu = c2;
-                    nchild += 3;
-                }
-            }
+            s.ncu[L + 1] = apply_combination(s.row, s.col0, s.cu[L], ncu, mode_in(my_list, my_n, my_p, t), nb, s.cu[L + 1], [](int, bool) {});
 #pragma unroll
             for (int k = 0; k < 4; ++k) s.bt[L + 1][k] = nb[k];
-            s.cu[L + 1] = child_cu;
-            s.ncu[L + 1] = uni(nchild);
             expand<L + 1, PART>(s);
         }
     }
@@ -269,17 +194,14 @@ __global__ __launch_bounds__(256) void msbt_labels_kernel(const uint8_t *__restr
 
     // ---- set_sub_map (:314-324), flattened: a node at depth d is reached iff every ancestor's qt (read at its top-left cell) exceeds
     // the ancestor's depth.  Beyond depth 3 the reference recurses on empty regions only: such a region stays zero (status bit 2).
+    // walk_quadrant's loop and set_region's lines stand here in the open: behind the shared forms this kernel alone is allotted 133
+    // VGPRs with 24 B of scratch per lane, or 205-207 VGPRs at two waves per SIMD, against 150 and 12 B like this (and 152 / 12 B
+    // before the search was shared; profiles/m2p_tree_shared.txt)
     for (int d = 0; d < 4; ++d) {
         const int sms = 8 >> d, nside = 1 << d;
         for (int node = 0; node < nside * nside; ++node) {
             const int qx = (node / nside) * sms, qy = (node % nside) * sms;
-            bool reached = true;
-            for (int a = 0; a < d; ++a) {
-                const int am = ~((8 >> a) - 1);
-                if (!(rlane(q8, (qx & am) * 8 + (qy & am)) > a)) reached = false;
-            }
-            if (!reached) continue;
-            if (wv != (d == 0 ? 0 : ((qx >= 4 ? 2 : 0) + (qy >= 4 ? 1 : 0)))) continue;   // another wave's quadrant
+            if (!node_is_mine(q8, wv, d, qx, qy)) continue;
             const int c = rlane(q8, qx * 8 + qy);
             if (c > d) {
                 if (d == 3) st |= PMP_MSBT_QT_DEEP;
@@ -300,27 +222,11 @@ __global__ __launch_bounds__(256) void msbt_labels_kernel(const uint8_t *__restr
             expand<0, false>(s);
             if (s.best_depth < 3) st |= PMP_MSBT_INCONSISTENT;
             if (s.stop) st |= PMP_MSBT_BUDGET;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int r = s.row - s.rx, cc = s.col0 + k - s.ry;
-                if (r >= 0 && r < s.rh && cc >= 0 && cc < s.rw) {
-                    outd[0][k] = s.best[0][k]; outd[1][k] = s.best[1][k]; outd[2][k] = s.best[2][k];
-                }
-            }
+            copy_region(s, outd, s.best);
         }
     }
     if (lane == 0) st_w[wv] = st;
-    // a lane's four cells lie in one quadrant: its owner holds their labels
-    const bool whole = rlane(q8, 0) == 0;
-    const int quad = ((lane >> 2) >= 8 ? 2 : 0) + ((lane & 3) >= 2 ? 1 : 0);
-    if (whole ? wv == 0 : wv == quad) {
-#pragma unroll
-        for (int k3 = 0; k3 < 3; ++k3) {
-            const uint32_t pk = (uint32_t)(uint8_t)outd[k3][0] | ((uint32_t)(uint8_t)outd[k3][1] << 8) |
-                                ((uint32_t)(uint8_t)outd[k3][2] << 16) | ((uint32_t)(uint8_t)outd[k3][3] << 24);
-            reinterpret_cast<uint32_t *>(msbt + (b * 3 + k3) * 256)[lane] = pk;
-        }
-    }
+    store_planes(msbt + b * 768, outd, q8, wv);
     __syncthreads();
     if (threadIdx.x == 0) status[b] = (uint8_t)(st_w[0] | st_w[1] | st_w[2] | st_w[3]);
 }
@@ -367,52 +273,35 @@ __global__ __launch_bounds__(256) void label_partition_kernel(const uint8_t *__r
     uint32_t em = 0;                             // a wave that paints nothing hands over zeros
     int st = 0;
 
-    for (int d = 0; d < 4; ++d) {
-        const int sms = 8 >> d, nside = 1 << d;
-        for (int node = 0; node < nside * nside; ++node) {
-            const int qx = (node / nside) * sms, qy = (node % nside) * sms;
-            bool reached = true;
-            for (int a = 0; a < d; ++a) {
-                const int am = ~((8 >> a) - 1);
-                if (!(rlane(q8, (qx & am) * 8 + (qy & am)) > a)) reached = false;
-            }
-            if (!reached) continue;
-            if (wv != (d == 0 ? 0 : ((qx >= 4 ? 2 : 0) + (qy >= 4 ? 1 : 0)))) continue;   // another wave's quadrant
-            const int c = rlane(q8, qx * 8 + qy);
-            if (c > d) {
-                // the QT cross of [2qx, 2qy, 2sms, 2sms]: row 2qx + sms and column 2qy + sms (both <= 15)
-                if (part == 0 && j == 2 * qx + sms) em |= ((1u << (2 * sms)) - 1u) << (2 * qy);
-                if (part == 1 && j >= 2 * qx && j < 2 * qx + 2 * sms) em |= 1u << (2 * qy + sms);
-                if (d == 3) st |= PMP_MSBT_QT_DEEP;       // the reference recurses on empty regions from here: nothing more is painted
-                continue;
-            }
-            if (c < d) continue;                          // neither == nor >: nothing is painted
-            // ---- set_bt_partition_vector (:262-292) on [2qx, 2qy, 2sms, 2sms]
-            s.rx = 2 * qx; s.ry = 2 * qy; s.rh = 2 * sms; s.rw = 2 * sms;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) s.bt[0][k] = 0;
-            s.cu[0] = pack_cu(s.rx, s.ry, s.rh, s.rw);
-            s.ncu[0] = 1;
-            s.have_best = 0;
-            s.best_err = 0;
-            s.best_depth = 0;
-            s.best_cu = 0;
-            s.best_ncu = 0;
-            s.nleaf = 0;
-            s.stop = 0;
-            expand<0, true>(s);
-            if (s.stop) st |= PMP_MSBT_BUDGET;
-            const int ncu = uni(s.best_ncu);
-            for (int ci = 0; ci < ncu; ++ci) {
-                const int cu = rlane(s.best_cu, ci);
-                const int x = cu & 15, y = (cu >> 4) & 15, h = ((cu >> 8) & 15) + 1, w = ((cu >> 12) & 15) + 1;
-                // rows x and x + h over columns y..y+w-1; columns y and y + w over rows x..x+h-1.  x + h = 16 matches no lane and
-                // bit y + w = 16 is masked off: the crop of :382
-                if (part == 0 && (j == x || j == x + h)) em |= ((1u << w) - 1u) << y;
-                if (part == 1 && j >= x && j < x + h) em |= (1u << y) | ((1u << (y + w)) & 0xFFFFu);
-            }
+    walk_quadrant(q8, wv, [j, part](int d, int qx, int qy, int sms, int c, Sub &s, int &st, uint32_t &em) {
+        if (c > d) {
+            // the QT cross of [2qx, 2qy, 2sms, 2sms]: row 2qx + sms and column 2qy + sms (both <= 15)
+            if (part == 0 && j == 2 * qx + sms) em |= ((1u << (2 * sms)) - 1u) << (2 * qy);
+            if (part == 1 && j >= 2 * qx && j < 2 * qx + 2 * sms) em |= 1u << (2 * qy + sms);
+            if (d == 3) st |= PMP_MSBT_QT_DEEP;           // the reference recurses on empty regions from here: nothing more is painted
+            return;
         }
-    }
+        if (c < d) return;                                // neither == nor >: nothing is painted
+        // ---- set_bt_partition_vector (:262-292) on [2qx, 2qy, 2sms, 2sms]
+        set_region(s, qx, qy, sms);
+        s.have_best = 0;
+        s.best_err = 0;
+        s.best_depth = 0;
+        s.best_cu = 0;
+        s.best_ncu = 0;
+        s.nleaf = 0;
+        s.stop = 0;
+        expand<0, true>(s);
+        if (s.stop) st |= PMP_MSBT_BUDGET;
+        const int ncu = uni(s.best_ncu);
+        for (int ci = 0; ci < ncu; ++ci) {
+            const CU u = unpack_cu(rlane(s.best_cu, ci));
+            // rows x and x + h over columns y..y+w-1; columns y and y + w over rows x..x+h-1.  x + h = 16 matches no lane and
+            // bit y + w = 16 is masked off: the crop of :382
+            if (part == 0 && (j == u.x || j == u.x + u.h)) em |= ((1u << u.w) - 1u) << u.y;
+            if (part == 1 && j >= u.x && j < u.x + u.h) em |= (1u << u.y) | ((1u << (u.y + u.w)) & 0xFFFFu);
+        }
+    }, s, st, em);
     if (lane < 32) msk[wv][lane] = em;
     if (lane == 0) st_w[wv] = st;
     __syncthreads();
@@ -430,31 +319,34 @@ __global__ __launch_bounds__(256) void label_partition_kernel(const uint8_t *__r
     if (threadIdx.x == 0) status[b] = (uint8_t)(st_w[0] | st_w[1] | st_w[2] | st_w[3]);
 }
 
+// Grids of at most 2^20 blocks (gridDim.x is 32-bit; blocks are independent): launch(o, m) takes blocks o..o+m-1.
+template <class Launch>
+static hipError_t for_grids(int64_t N, Launch &&launch)
+{
+    for (int64_t o = 0; o < N; o += (int64_t)1 << 20) launch(o, (N - o) < ((int64_t)1 << 20) ? (N - o) : ((int64_t)1 << 20));
+    return hipGetLastError();
+}
+
 hipError_t launch_label_partition(hipStream_t st, const uint8_t *qt, const uint8_t *bt, const int8_t *dire, int64_t N, int chroma_factor,
                                   uint8_t *hor, uint8_t *ver, uint8_t *rec, uint8_t *status)
 {
     // rec: one packed PMP_RECORD_BYTES record per block (hor | ver | qt | dire) instead of the two dense arrays
     const int stride = rec ? PMP_RECORD_BYTES : 256;
-    for (int64_t o = 0; o < N; o += (int64_t)1 << 20) {
-        const int64_t m = (N - o) < ((int64_t)1 << 20) ? (N - o) : ((int64_t)1 << 20);
+    return for_grids(N, [&](int64_t o, int64_t m) {
         uint8_t *h = rec ? rec + o * stride : hor + o * stride, *v = rec ? h + 256 : ver + o * stride;
         hipLaunchKernelGGL(label_partition_kernel, dim3((unsigned)m), dim3(256), 0, st, qt + o * 64, bt + o * 256, dire + o * 768, m,
                            chroma_factor, h, v, rec ? h + 512 : (uint8_t *)nullptr, rec ? (int8_t *)(h + 576) : (int8_t *)nullptr, stride,
                            status + o);
-    }
-    return hipGetLastError();
+    });
 }
 
 hipError_t launch_msbt_labels(hipStream_t st, const uint8_t *qt, const uint8_t *bt, const int8_t *dire, int64_t N, int chroma_factor,
                               uint8_t *msbt, uint8_t *status)
 {
-    // grids of at most 2^20 blocks (gridDim.x is 32-bit); blocks are independent
-    for (int64_t o = 0; o < N; o += (int64_t)1 << 20) {
-        const int64_t m = (N - o) < ((int64_t)1 << 20) ? (N - o) : ((int64_t)1 << 20);
+    return for_grids(N, [&](int64_t o, int64_t m) {
         hipLaunchKernelGGL(msbt_labels_kernel, dim3((unsigned)m), dim3(256), 0, st, qt + o * 64, bt + o * 256, dire + o * 768, m,
                            chroma_factor, msbt + o * 768, status + o);
-    }
-    return hipGetLastError();
+    });
 }
 
 }  // namespace pmp

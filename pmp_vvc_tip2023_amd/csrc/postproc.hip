@@ -1,38 +1,28 @@
-// postproc.hip — Map2Partition on the GPU: one wavefront (64 lanes) per 64x64 block.
+// postproc.hip — Map2Partition on the GPU: four wavefronts per 64x64 block, one per QT quadrant.
 //
 // Replaces, bit-exactly:
 //   eli_structual_error / check_square_unity   Metrics.py:612-637
 //   Map_to_Partition                           Map2Partition.py:98-373
 //   output_block_yuv (block cutter)            Inference_QBD.py:104-149
 //
-// Work decomposition (wave64): the block's 16x16 grid of 4x4-pixel cells is spread over the lanes, 4 cells per
-// lane in row-major order (lane l: row l>>2, columns 4*(l&3)..+3).  The reference's candidate-tree search
-// (Map2Partition.py:203-266) is a depth-3 DFS whose control flow is identical for all lanes, so it runs as
-// wave-uniform scalar control with
-//   * region counts  (can_split_mode_list, :140-201)  = ballot + popcount over the lanes' cell predicates,
-//   * small "arrays indexed by a uniform index" (CU lists, candidate lists) kept lane-distributed in VGPRs and
-//     read with v_readlane,
-//   * the three tree levels unrolled at compile time (template recursion), so every level's maps are registers.
+// The reference's candidate-tree search (Map2Partition.py:203-266) is a depth-3 DFS whose control flow is identical for all
+// lanes.  Its frame - cells on lanes, the quadtree walk, split modes, combinations, child CU lists - is m2p_tree.h's, shared with
+// the label kernels (labels.hip); here are Map2Partition's rules (can_split: the call's thresholds on the rounded logits of each
+// level), its direction map, its leaf cost, the edge planes in LDS, and the three tree levels unrolled at compile time (template
+// recursion), so every level's maps are registers.
 // The float32 L1 error (:307-312) must reproduce numpy's pairwise summation order bit for bit: cell values are
 // scattered to LDS in region-flattened order and 8 (or 2x8) lanes run the interleaved accumulators exactly as
 // numpy's FLOAT_pairwise_sum does; the combine tree is done with xor-shuffles (fp add is commutative, so the
 // tree ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) is reproduced exactly).  This file is compiled with
 // -ffp-contract=off so `s + 0.8f*d` is not fused.
+#include "m2p_tree.h"
 #include "pmp_kernels.h"
 
 namespace pmp {
 
+using namespace tree;
+
 namespace {
-
-__device__ __forceinline__ int rlane(int v, int lane)
-{
-    return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(lane));
-}
-__device__ __forceinline__ float rlanef(float v, int lane) { return __int_as_float(rlane(__float_as_int(v), lane)); }
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ int cnt(bool p) { return __popcll(__ballot(p)); }
-
-__device__ __forceinline__ int pack_cu(int x, int y, int h, int w) { return x | (y << 4) | ((h - 1) << 8) | ((w - 1) << 12); }
 
 struct Search {
     // per-lane constants of this block
@@ -104,17 +94,17 @@ __device__ __forceinline__ void region_sums(Search &s, const int (&btm)[4], cons
 template <int L>
 __device__ __forceinline__ int can_split(const Search &s, int cu, int &n)
 {
-    const int x = cu & 15, y = (cu >> 4) & 15, h = ((cu >> 8) & 15) + 1, w = ((cu >> 12) & 15) + 1;
+    const CU u = unpack_cu(cu);
     bool in[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) in[k] = s.row >= x && s.row < x + h && s.col0 + k >= y && s.col0 + k < y + w;
+    for (int k = 0; k < 4; ++k) in[k] = s.row >= u.x && s.row < u.x + u.h && s.col0 + k >= u.y && s.col0 + k < u.y + u.w;
     // lamb1..lamb5 as Python compares them (Map2Partition.py:144,150-153,194): an int count against a double product, left to right
     const double l1 = s.lamb[0], l2 = s.lamb[1], l3 = s.lamb[2], l4 = s.lamb[3], l5 = s.lamb[4];
     int zero = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) zero += cnt(in[k] && s.mb[2][k] == s.bt[L][k]);
     n = 1;
-    if ((double)zero >= l1 * h * w) return 0;  // lamb1
+    if ((double)zero >= l1 * u.h * u.w) return 0;  // lamb1
     int hor = 0, ver = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -122,43 +112,22 @@ __device__ __forceinline__ int can_split(const Search &s, int cu, int &n)
         ver += cnt(in[k] && s.md[L][k] == -1);
     }
     int direction = 0;
-    if ((double)(ver + hor) >= l2 * h * w) {  // lamb2, lamb3
+    if ((double)(ver + hor) >= l2 * u.h * u.w) {  // lamb2, lamb3
         if ((double)hor >= l3 * ver) direction = 1;
         else if ((double)ver >= l3 * hor) direction = 2;
     }
-    const int cf = s.cf;
-    int list = 0;
-    for (int mode = 1; mode <= 4; ++mode) {
-        const bool horiz = (mode & 1) != 0;      // 1 BT-H, 3 TT-H
-        const int ext = horiz ? h : w;
-        const int div = (mode <= 2 ? 2 : 4) * cf;
-        if (ext / div == 0 || ext % div != 0) continue;
-        if (horiz && direction == 2) continue;
-        if (!horiz && direction == 1) continue;
-        const int parts = mode <= 2 ? 2 : 3;
-        int ok = 0;
-        for (int p = 0; p < parts; ++p) {
-            // sub-part extent along the split axis
-            int o0, o1, inc;
-            if (mode <= 2) { o0 = p * (ext / 2); o1 = o0 + ext / 2; inc = 1; }
-            else if (p == 0) { o0 = 0; o1 = ext / 4; inc = 2; }
-            else if (p == 1) { o0 = ext / 4; o1 = o0 + ext / 2; inc = 1; }
-            else { o0 = (ext * 3) / 4; o1 = ext; inc = 2; }
-            int minus = 0, zer = 0;
+    return split_modes(u.h, u.w, s.cf, direction, 0, n, [&](bool horiz, int o0, int o1, int inc, int np_) {
+        int minus = 0, zer = 0;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int t = horiz ? (s.row - x) : (s.col0 + k - y);
-                const bool ins = in[k] && t >= o0 && t < o1;
-                const int tgt = s.bt[L][k] + inc;
-                minus += cnt(ins && s.mb[L][k] < tgt);
-                zer += cnt(ins && s.mb[L][k] == tgt);
-            }
-            const int np_ = (o1 - o0) * (horiz ? w : h);
-            if ((double)minus < np_ * l4 && (double)zer > np_ * l5) ++ok;  // lamb4, lamb5
+        for (int k = 0; k < 4; ++k) {
+            const int t = horiz ? (s.row - u.x) : (s.col0 + k - u.y);
+            const bool ins = in[k] && t >= o0 && t < o1;
+            const int tgt = s.bt[L][k] + inc;
+            minus += cnt(ins && s.mb[L][k] < tgt);
+            zer += cnt(ins && s.mb[L][k] == tgt);
         }
-        if (ok == parts) { list |= mode << (3 * n); ++n; }
-    }
-    return list;
+        return (double)minus < np_ * l4 && (double)zer > np_ * l5;  // lamb4, lamb5
+    });
 }
 
 // get_candidate_map_tree (Map2Partition.py:203-266) for a node at level L; leaves (level 3) are scored in DFS
@@ -174,61 +143,15 @@ __device__ __forceinline__ void expand(Search &s)
         const int list = can_split<L>(s, rlane(s.cu[L], c), n);
         if (lane == c) { my_list = list; my_n = n; }
     }
-    // mixed-radix combination index, first CU slowest (Search, Map2Partition.py:53-87)
-    int my_p = 1, total = 1;
-    for (int c = ncu - 1; c >= 0; --c) {
-        if (lane == c) my_p = total;
-        total *= rlane(my_n, c);
-    }
-    total = uni(total);
+    const auto [my_p, total] = combos(my_n, ncu);   // Search, Map2Partition.py:53-87
     for (int t = 0; t < total; ++t) {
-        const int my_mode = (my_list >> (3 * ((t / my_p) % my_n))) & 7;
         int nb[4], nd[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) { nb[k] = s.bt[L][k]; nd[k] = 0; }  // child dire map starts from zeros (:240)
-        int child_cu = 0, nchild = 0;
-        for (int c = 0; c < ncu; ++c) {
-            const int mode = rlane(my_mode, c), cu = rlane(s.cu[L], c);
-            const int x = cu & 15, y = (cu >> 4) & 15, h = ((cu >> 8) & 15) + 1, w = ((cu >> 12) & 15) + 1;
-            if (mode == 0) {
-                if (lane == nchild) child_cu = cu;
-                nchild += 1;
-                continue;
-            }
-            const bool horiz = (mode & 1) != 0;
-            const int ext = horiz ? h : w;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int r = s.row - x, cc = s.col0 + k - y;
-                if (r >= 0 && r < h && cc >= 0 && cc < w) {
-                    nd[k] = horiz ? 1 : -1;
-                    const int tt = horiz ? r : cc;
-                    nb[k] += (mode >= 3 && (tt < ext / 4 || tt >= (ext * 3) / 4)) ? 2 : 1;
-                }
-            }
-            // split_cur_map (:124-138): sub-CUs appended in order
-            if (mode <= 2) {
-                const int e = ext / 2;
-                const int c0 = horiz ? pack_cu(x, y, e, w) : pack_cu(x, y, h, e);
-                const int c1 = horiz ? pack_cu(x + e, y, e, w) : pack_cu(x, y + e, h, e);
-                if (lane == nchild) child_cu = c0;
-                if (lane == nchild + 1) child_cu = c1;
-                nchild += 2;
-            } else {
-                const int q = ext / 4, e = ext / 2, o2 = (ext * 3) / 4;
-                const int c0 = horiz ? pack_cu(x, y, q, w) : pack_cu(x, y, h, q);
-                const int c1 = horiz ? pack_cu(x + q, y, e, w) : pack_cu(x, y + q, h, e);
-                const int c2 = horiz ? pack_cu(x + o2, y, q, w) : pack_cu(x, y + o2, h, q);
-                if (lane == nchild) child_cu = c0;
-                if (lane == nchild + 1) child_cu = c1;
-                if (lane == nchild + 2) child_cu = c2;
-                nchild += 3;
-            }
-        }
+        s.ncu[L + 1] = apply_combination(s.row, s.col0, s.cu[L], ncu, mode_in(my_list, my_n, my_p, t), nb, s.cu[L + 1],
+                                         [&](int k, bool horiz) { nd[k] = horiz ? 1 : -1; });
 #pragma unroll
         for (int k = 0; k < 4; ++k) { s.bt[L + 1][k] = nb[k]; s.dr[L + 1][k] = nd[k]; }
-        s.cu[L + 1] = child_cu;
-        s.ncu[L + 1] = uni(nchild);
         region_sums(s, nb, nd, s.ob[L], s.od[L], s.sb[L + 1], s.sd[L + 1]);
         if constexpr (L == 2) {
             // error of the leaf and its two ancestors, float32 left to right (Map2Partition.py:307-312)
@@ -349,72 +272,41 @@ __global__ __launch_bounds__(256, 4) void postprocess_kernel(const float *__rest
     __syncthreads();
 
     // ---- set_partition_vector (Map2Partition.py:348-362), flattened: a node is reached iff every ancestor split
-    for (int d = 0; d < 4; ++d) {
-        const int sms = 8 >> d, nside = 1 << d;
-        for (int node = 0; node < nside * nside; ++node) {
-            const int qx = (node / nside) * sms, qy = (node % nside) * sms;
-            bool reached = true;
-            for (int a = 0; a < d; ++a) {
-                const int am = ~((8 >> a) - 1);
-                if (!(rlane(qt8, (qx & am) * 8 + (qy & am)) > a)) reached = false;
+    walk_quadrant(qt8, wv, [&](int d, int qx, int qy, int sms, int c) {
+        if (c > d) {
+            if (d < 3 && lane < 2 * sms) {                // paint the QT cross
+                hor[(2 * qx + sms) * 16 + 2 * qy + lane] = 1;
+                ver[(2 * qx + lane) * 16 + 2 * qy + sms] = 1;
             }
-            if (!reached) continue;
-            if (wv != (d == 0 ? 0 : ((qx >= 4 ? 2 : 0) + (qy >= 4 ? 1 : 0)))) continue;   // another wave's quadrant
-            const int c = rlane(qt8, qx * 8 + qy);
-            if (c > d) {
-                if (d < 3 && lane < 2 * sms) {            // paint the QT cross
-                    hor[(2 * qx + sms) * 16 + 2 * qy + lane] = 1;
-                    ver[(2 * qx + lane) * 16 + 2 * qy + sms] = 1;
-                }
-                continue;
-            }
-            if (c < d) continue;                          // hole: no MTT edges, dire stays 0
-            // ---- set_bt_partition_vector (Map2Partition.py:287-346) on [2qx, 2qy, 2sms, 2sms]
-            s.rx = 2 * qx; s.ry = 2 * qy; s.rh = 2 * sms; s.rw = 2 * sms;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { s.bt[0][k] = 0; s.dr[0][k] = 0; }
-            s.cu[0] = pack_cu(s.rx, s.ry, s.rh, s.rw);
-            s.ncu[0] = 1;
-            s.have_best = 0;
-            s.best_err = 0.f;
-            s.best_ncu = 0;
-            s.best_cu = 0;
-            expand<0>(s);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int r = s.row - s.rx, cc = s.col0 + k - s.ry;
-                if (r >= 0 && r < s.rh && cc >= 0 && cc < s.rw) {
-                    outd[0][k] = s.best_dr[0][k]; outd[1][k] = s.best_dr[1][k]; outd[2][k] = s.best_dr[2][k];
-                }
-            }
-            const int j = lane & 15, part = lane >> 4;
-            for (int ci = 0; ci < s.best_ncu; ++ci) {
-                const int cu = rlane(s.best_cu, ci);
-                const int x = cu & 15, y = (cu >> 4) & 15, h = ((cu >> 8) & 15) + 1, w = ((cu >> 12) & 15) + 1;
-                // par_vec is 17x17 in the reference; row/column 16 is cropped away (Map2Partition.py:373)
-                if (part == 0 && j < w) hor[x * 16 + y + j] = 1;
-                if (part == 1 && j < w && x + h < 16) hor[(x + h) * 16 + y + j] = 1;
-                if (part == 2 && j < h) ver[(x + j) * 16 + y] = 1;
-                if (part == 3 && j < h && y + w < 16) ver[(x + j) * 16 + y + w] = 1;
-            }
+            return;
         }
-    }
+        if (c < d) return;                                // hole: no MTT edges, dire stays 0
+        // ---- set_bt_partition_vector (Map2Partition.py:287-346) on [2qx, 2qy, 2sms, 2sms]
+        set_region(s, qx, qy, sms);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s.dr[0][k] = 0;
+        s.have_best = 0;
+        s.best_err = 0.f;
+        s.best_ncu = 0;
+        s.best_cu = 0;
+        expand<0>(s);
+        copy_region(s, outd, s.best_dr);
+        const int j = lane & 15, part = lane >> 4;
+        for (int ci = 0; ci < s.best_ncu; ++ci) {
+            const CU u = unpack_cu(rlane(s.best_cu, ci));
+            // par_vec is 17x17 in the reference; row/column 16 is cropped away (Map2Partition.py:373)
+            if (part == 0 && j < u.w) hor[u.x * 16 + u.y + j] = 1;
+            if (part == 1 && j < u.w && u.x + u.h < 16) hor[(u.x + u.h) * 16 + u.y + j] = 1;
+            if (part == 2 && j < u.h) ver[(u.x + j) * 16 + u.y] = 1;
+            if (part == 3 && j < u.h && u.y + u.w < 16) ver[(u.x + j) * 16 + u.y + u.w] = 1;
+        }
+    });
     __syncthreads();
     if (wv == 0) {
         reinterpret_cast<uint32_t *>(hor_o + b * s_edge)[lane] = horw[lane];
         reinterpret_cast<uint32_t *>(ver_o + b * s_edge)[lane] = verw[lane];
     }
-    // a lane's four cells (row lane>>2, columns 4*(lane&3)..+3) lie in one quadrant: its owner holds their directions
-    const bool whole = rlane(qt8, 0) == 0;   // the block is one 64x64 leaf: wave 0 searched it
-    const int quad = ((lane >> 2) >= 8 ? 2 : 0) + ((lane & 3) >= 2 ? 1 : 0);
-    if (whole ? wv == 0 : wv == quad) {
-#pragma unroll
-        for (int k3 = 0; k3 < 3; ++k3) {
-            const uint32_t pk = (uint32_t)(uint8_t)outd[k3][0] | ((uint32_t)(uint8_t)outd[k3][1] << 8) |
-                                ((uint32_t)(uint8_t)outd[k3][2] << 16) | ((uint32_t)(uint8_t)outd[k3][3] << 24);
-            reinterpret_cast<uint32_t *>(dire_o + b * s_dire + k3 * 256)[lane] = pk;
-        }
-    }
+    store_planes(dire_o + b * s_dire, outd, qt8, wv);
 }
 
 hipError_t launch_postprocess(hipStream_t st, const float *qt, const float *bt, const float *dire, int64_t N,
