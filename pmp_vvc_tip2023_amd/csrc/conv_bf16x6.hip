@@ -15,55 +15,12 @@
 // GEMM mapping: D[cout][pixel], A = weights, B = pixels (as conv_mfma.hip).  One MFMA K-step (K = 32) covers
 // 16 channels x a PAIR of taps: lane group g = l>>4 reads channels 8(g&1)..+7 of tap 2p+(g>>1).  An odd tap count pads
 // the last pair with zero weights (3x3: 10 % padding, 5x5: 4 %).
-#include <type_traits>
-
-#include "pmp_kernels.h"
-#include "split3.h"
+#include "conv_tile.h"
 
 namespace pmp {
 
-// Per-lane staging plan, computed ONCE per workgroup: element offset (inside one 16-channel group, split plane
-// included) of each 16-B piece this thread copies, and a validity mask for the zero padding.  The per-group work is then
-// one add per piece; recomputing the div/mod chain per group cost ~80 VALU issue slots per K-step, which matters when a
-// 16-cycle bf16 MFMA leaves only 8 free issue cycles.
 template <int KH, int KW>
-struct StagePlan {
-    unsigned off[GeoX<KH, KW>::NLD];
-    unsigned valid;
-};
-
-template <int KH, int KW>
-__device__ __forceinline__ void x6_plan(StagePlan<KH, KW> &p, size_t plane_stride, int H, int W, int ty, int tx)
-{
-    typedef GeoX<KH, KW> G;
-    constexpr int PY = KH / 2, PX = KW / 2;
-    p.valid = 0;
-#pragma unroll
-    for (int k = 0; k < G::NLD; ++k) {
-        const int i = min((int)threadIdx.x + k * 256, G::PIECES - 1);
-        const int sp = i / G::PLANE, j = i - sp * G::PLANE, pix = j >> 1, half = j & 1;
-        const int row = pix / G::TW, col = pix - row * G::TW;
-        const int gy = ty * 16 + row - PY, gx = tx * 16 + col - PX;
-        const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W && (int)threadIdx.x + k * 256 < G::PIECES;
-        if (in) p.valid |= 1u << k;
-        const int cy = min(max(gy, 0), H - 1), cx = min(max(gx, 0), W - 1);   // clamped: loads stay unconditional
-        p.off[k] = (unsigned)(sp * plane_stride + ((size_t)cy * W + cx) * 16 + half * 8);
-    }
-}
-
-template <int KH, int KW>
-__device__ __forceinline__ void x6_stage_load(const StagePlan<KH, KW> &p, const unsigned short *__restrict__ grp,
-                                              u32x4 (&r)[GeoX<KH, KW>::NLD], int k0 = 0, int k1 = 1 << 20)
-{
-#pragma unroll
-    for (int k = 0; k < GeoX<KH, KW>::NLD; ++k) {
-        if (k < k0 || k >= k1) continue;   // folds away: callers pass constants into unrolled code
-        r[k] = *reinterpret_cast<const u32x4 *>(grp + p.off[k]);
-    }
-}
-
-template <int KH, int KW>
-__device__ __forceinline__ void x6_stage_store(const StagePlan<KH, KW> &p, u32x4 *lds, const u32x4 (&r)[GeoX<KH, KW>::NLD])
+__device__ __forceinline__ void x6_stage_store(const TilePlan<GeoX<KH, KW>> &p, u32x4 *lds, const u32x4 (&r)[GeoX<KH, KW>::NLD])
 {
     typedef GeoX<KH, KW> G;
 #pragma unroll
@@ -85,10 +42,10 @@ __device__ __forceinline__ void x6_accumulate(const unsigned short *__restrict__
     const size_t grp_sz = (size_t)H * W * 16;
     const unsigned short *grp0 = x + (size_t)n * CB * grp_sz;
     u32x4 r[G::NLD];
-    StagePlan<KH, KW> plan;
-    x6_plan<KH, KW>(plan, plane_stride, H, W, ty, tx);
+    TilePlan<G> plan;
+    tile_plan<KH, KW>(plan, plane_stride, H, W, ty, tx);
     __syncthreads();
-    x6_stage_load<KH, KW>(plan, grp0, r);
+    tile_load(plan, grp0, r);
     x6_stage_store<KH, KW>(plan, lds, r);
     __syncthreads();
     // ---- K-step schedule -------------------------------------------------------------------------------------
@@ -106,9 +63,10 @@ __device__ __forceinline__ void x6_accumulate(const unsigned short *__restrict__
     // no MFMA work is spent on zero padding (3x3: 9 K-steps per two groups instead of 10).
     //   mode 0 (plain): NKS = ceil(T/2) per group, last pair padded with zero weights
     //   mode 1 (even group of a pair): (T-1)/2 K-steps;  mode 2 (odd group): (T-1)/2 + 1 K-steps
-    const bool paired = (CB & 1) == 0 && (G::TAPS & 1);
+    typedef TapPairs<G> TP;
+    const bool paired = TP::paired(CB);
     const bf16x8 *wl = reinterpret_cast<const bf16x8 *>(wpk) + lane;
-    const int last = paired ? (CB / 2) * G::TAPS - 1 : CB * G::NKS - 1;   // last K-step of the weight stream
+    const int last = TP::last(CB);   // last K-step of the weight stream
     bf16x8 w0[NT], w1[NT], w2[NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) { w2[nt] = wl[(2 * NT + nt) * 64]; w1[nt] = wl[(1 * NT + nt) * 64]; w0[nt] = wl[(0 * NT + nt) * 64]; }
@@ -118,7 +76,7 @@ __device__ __forceinline__ void x6_accumulate(const unsigned short *__restrict__
 
     auto group = [&](auto mode_tag, int cb) {
         constexpr int MODE = decltype(mode_tag)::value;
-        constexpr int NK = MODE == 0 ? G::NKS : (MODE == 1 ? (G::TAPS - 1) / 2 : (G::TAPS - 1) / 2 + 1);
+        constexpr int NK = TP::nk(MODE);
         constexpr int PER = (G::NLD + (NK > 0 ? NK : 1) - 1) / (NK > 0 ? NK : 1);   // staging loads issued per K-step
         const bool more = cb + 1 < CB;
         const unsigned short *nxt_grp = grp0 + (size_t)min(cb + 1, CB - 1) * grp_sz;   // clamped: loads stay unconditional
@@ -133,12 +91,12 @@ __device__ __forceinline__ void x6_accumulate(const unsigned short *__restrict__
                 if (ks == 0) { tA = tB = G::TAPS - 1; prevA = true; }
                 else { tA = 2 * (ks - 1); tB = tA + 1; }
             }
-            const int oA = ((tA / KW) * G::TW + tA % KW) * 32, oB = ((tB / KW) * G::TW + tB % KW) * 32;
+            const int oA = tap_off(tA, KW, G::TW), oB = tap_off(tB, KW, G::TW);
             return (tapsel ? buf + oB : (prevA ? prv : buf) + oA) + pb;
         };
         bf16x8 xa[4], xb[4], x1[4], x2[4];   // x0 fragments alternate between xa (even K-steps) and xb (odd)
         if (NK == 0) {   // 1x1 source, even group: nothing to compute yet, only fetch the partner group
-            x6_stage_load<KH, KW>(plan, nxt_grp, r);
+            tile_load(plan, nxt_grp, r);
         } else {
             const char *p0 = xaddr(0);
 #pragma unroll
@@ -158,7 +116,7 @@ __device__ __forceinline__ void x6_accumulate(const unsigned short *__restrict__
 #pragma unroll
                 for (int m = 0; m < 4; ++m) x2[m] = *reinterpret_cast<const bf16x8 *>(px + 2 * G::PLANE * 16 + m * G::TW * 32);
             }
-            x6_stage_load<KH, KW>(plan, nxt_grp, r, ks * PER, (ks + 1) * PER);
+            tile_load(plan, nxt_grp, r, ks * PER, (ks + 1) * PER);
             __builtin_amdgcn_sched_barrier(0);
             // phase A
 #pragma unroll
@@ -243,7 +201,7 @@ __global__ __launch_bounds__(256, 2) void conv_x6_kernel(ConvX6Args a)
             const size_t off = ((size_t)n * NT + nt) * grp + ((size_t)y * W + x) * 16 + g * 4;
             f32x4 v = acc[m][nt];
             if (a.res) v += load_split4(a.res + off, a.res_stride);
-            if (a.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+            if (a.relu) v = relu4(v);
             if (a.gate) v *= load_split4(a.gate + off, a.gate_stride);
             acc[m][nt] = v;
         }
@@ -259,11 +217,7 @@ __global__ __launch_bounds__(256, 2) void conv_x6_kernel(ConvX6Args a)
             const int Ho = H >> 1, Wo = W >> 1;
 #pragma unroll
             for (int m = 0; m < 4; m += 2) {
-                f32x4 v = acc[m][nt], u = acc[m + 1][nt];
-                v.x = fmaxf(v.x, u.x); v.y = fmaxf(v.y, u.y); v.z = fmaxf(v.z, u.z); v.w = fmaxf(v.w, u.w);
-                f32x4 o;
-                o.x = __shfl_xor(v.x, 1); o.y = __shfl_xor(v.y, 1); o.z = __shfl_xor(v.z, 1); o.w = __shfl_xor(v.w, 1);
-                v.x = fmaxf(v.x, o.x); v.y = fmaxf(v.y, o.y); v.z = fmaxf(v.z, o.z); v.w = fmaxf(v.w, o.w);
+                const f32x4 v = pool2x2_max(acc[m][nt], acc[m + 1][nt]);
                 if ((xl & 1) == 0) {
                     const int yo = ty * 8 + wave * 2 + (m >> 1), xo = tx * 8 + (xl >> 1);
                     const size_t off = (((size_t)n * NT + nt) * Ho + yo) * Wo * 16 + (size_t)xo * 16 + g * 4;
@@ -279,56 +233,31 @@ template <int KH, int KW>
 static hipError_t launch_x6(hipStream_t s, const ConvX6Args &a)
 {
     const int grid = a.N * (a.H >> 4) * (a.W >> 4);
-    if (a.Cout == 16 || a.Cout == 32 || a.Cout == 64) note_launch("conv_x6_kernel", KH, KW, a.Cout >> 4);
-    switch (a.Cout >> 4) {
-    case 1: hipLaunchKernelGGL((conv_x6_kernel<KH, KW, 1>), dim3(grid), dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL((conv_x6_kernel<KH, KW, 2>), dim3(grid), dim3(256), 0, s, a); break;
-    case 4: hipLaunchKernelGGL((conv_x6_kernel<KH, KW, 4>), dim3(grid), dim3(256), 0, s, a); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_cout(a.Cout, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        note_launch("conv_x6_kernel", KH, KW, NT);
+        hipLaunchKernelGGL((conv_x6_kernel<KH, KW, NT>), dim3(grid), dim3(256), 0, s, a);
+    });
 }
 
 hipError_t launch_conv_x6(hipStream_t s, const ConvX6Args &a)
 {
-    if ((a.H & 15) || (a.W & 15) || (a.Cin & 15) || (a.Cout & 15) || (a.x_sc && (a.Csc & 15)) || a.N <= 0)
-        return hipErrorInvalidValue;
-    if (a.pool && a.gate) return hipErrorInvalidValue;
+    if (!conv_shape_ok(a)) return hipErrorInvalidValue;
     if (a.KH == 3 && a.KW == 3) return launch_x6<3, 3>(s, a);
     if (a.KH == 5 && a.KW == 5) return launch_x6<5, 5>(s, a);
     if (a.KH == 1 && a.KW == 1) return launch_x6<1, 1>(s, a);
     return hipErrorInvalidValue;
 }
 
-// ---- format converters ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void f32_to_split3_kernel(const float *__restrict__ x, unsigned short *__restrict__ out,
-                                                            size_t n4, size_t plane_stride)
-{
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256)
-        store_split4(out + i * 4, plane_stride, *reinterpret_cast<const f32x4 *>(x + i * 4));
-}
-
-__global__ __launch_bounds__(256) void split3_to_f32_kernel(const unsigned short *__restrict__ x, float *__restrict__ out,
-                                                            size_t n4, size_t plane_stride)
-{
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256)
-        *reinterpret_cast<f32x4 *>(out + i * 4) = load_split4(x + i * 4, plane_stride);
-}
-
+// ---- format converters (conv_tile.h) ------------------------------------------------------------------------------
 hipError_t launch_f32_to_split3(hipStream_t s, const float *x, unsigned short *out, size_t n, size_t plane_stride)
 {
-    const size_t n4 = n / 4;
-    const unsigned grid = (unsigned)((n4 + 255) / 256 > 16384 ? 16384 : (n4 + 255) / 256);
-    if (n4) hipLaunchKernelGGL(f32_to_split3_kernel, dim3(grid), dim3(256), 0, s, x, out, n4, plane_stride);
-    return hipGetLastError();
+    return launch_f32_to_split<FMT_B3>(s, x, out, n, plane_stride, nullptr);
 }
 
 hipError_t launch_split3_to_f32(hipStream_t s, const unsigned short *x, float *out, size_t n, size_t plane_stride)
 {
-    const size_t n4 = n / 4;
-    const unsigned grid = (unsigned)((n4 + 255) / 256 > 16384 ? 16384 : (n4 + 255) / 256);
-    if (n4) hipLaunchKernelGGL(split3_to_f32_kernel, dim3(grid), dim3(256), 0, s, x, out, n4, plane_stride);
-    return hipGetLastError();
+    return launch_split_to_f32<FMT_B3>(s, x, out, n, plane_stride);
 }
 
 }  // namespace pmp

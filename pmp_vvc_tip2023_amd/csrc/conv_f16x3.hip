@@ -23,63 +23,23 @@
 //   phase B2: x1*w0 -> move the prefetched w0 over
 // Measurements: DESIGN.md 4.1, EXPERIMENTS.md.  The forms of this kernel that were built, parity-tested and measured no better (persistent, loader-wave,
 // 512-thread, 32x16-tile, Winograd-x, two-workgroup forms) and its timing-only builds live in abl/ (measurement library, `make abl`).
-#include <cstdio>
-#include <type_traits>
-
-#include "pmp_kernels.h"
-#include "split3.h"
+#include "conv_tile.h"
 
 namespace pmp {
 
-template <int KH, int KW, int NTHR = 256>
-struct StagePlanH {
-    unsigned off[GeoH<KH, KW, 16, NTHR>::NLD];
-    unsigned valid;
-};
-
-template <int KH, int KW, int NTHR = 256>
-__device__ __forceinline__ void h2_plan(StagePlanH<KH, KW, NTHR> &p, size_t plane_stride, int H, int W, int ty, int tx)
+// Unlike conv_bf16x6.hip's, this store is unconditional: every staging thread writes all NLD of its pieces, the ones past the tile into the
+// buffer's spare slot (GeoH::BUF, split3.h: a conditional store lets hipcc sink the global load into the branch and wait for it there).
+template <int KH, int KW, bool OPQ = false>
+__device__ __forceinline__ void h2_stage_store(const TilePlan<GeoH<KH, KW>> &p, u32x4 *lds, const u32x4 (&r)[GeoH<KH, KW>::NLD], int k0 = 0,
+                                               int k1 = 1 << 20)
 {
-    typedef GeoH<KH, KW, 16, NTHR> G;
-    constexpr int PY = KH / 2, PX = KW / 2;
-    p.valid = 0;
-#pragma unroll
-    for (int k = 0; k < G::NLD; ++k) {
-        const int i = min((int)threadIdx.x + k * NTHR, G::PIECES - 1);
-        const int sp = i / G::PLANE, j = i - sp * G::PLANE, pix = j >> 1, half = j & 1;
-        const int row = pix / G::TW, col = pix - row * G::TW;
-        const int gy = ty * 16 + row - PY, gx = tx * 16 + col - PX;
-        const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W && (int)threadIdx.x + k * NTHR < G::PIECES;
-        if (in) p.valid |= 1u << k;
-        const int cy = min(max(gy, 0), H - 1), cx = min(max(gx, 0), W - 1);   // clamped: loads stay unconditional
-        p.off[k] = (unsigned)(sp * plane_stride + ((size_t)cy * W + cx) * 16 + half * 8);
-    }
-}
-
-template <int KH, int KW, int NTHR = 256, bool OPQ = false>
-__device__ __forceinline__ void h2_stage_load(const StagePlanH<KH, KW, NTHR> &p, const unsigned short *__restrict__ grp,
-                                              u32x4 (&r)[GeoH<KH, KW, 16, NTHR>::NLD], int k0 = 0, int k1 = 1 << 20)
-{
-#pragma unroll
-    for (int k = 0; k < GeoH<KH, KW, 16, NTHR>::NLD; ++k) {
-        if (k < k0 || k >= k1) continue;   // folds away: callers pass constants into unrolled code
-        unsigned off = p.off[k];
-        if (OPQ) asm volatile("" : "+v"(off));   // opaque: the offset stays ONE register across the group loop (hipcc otherwise keeps its 64-bit extension, NLD more registers)
-        r[k] = *reinterpret_cast<const u32x4 *>(grp + off);   // default cache policy: the non-temporal hint measured 1 % slower
-    }
-}
-
-template <int KH, int KW, int NTHR = 256, bool OPQ = false>
-__device__ __forceinline__ void h2_stage_store(const StagePlanH<KH, KW, NTHR> &p, u32x4 *lds, const u32x4 (&r)[GeoH<KH, KW, 16, NTHR>::NLD],
-                                               int k0 = 0, int k1 = 1 << 20)
-{
-    typedef GeoH<KH, KW, 16, NTHR> G;
+    typedef GeoH<KH, KW> G;
 #pragma unroll
     for (int k = 0; k < G::NLD; ++k) {
         if (k < k0 || k >= k1) continue;
         int tid = threadIdx.x;
         if (OPQ) asm volatile("" : "+v"(tid));   // opaque: the LDS addresses are formed at the store, not kept across the group loop
-        const int i = min(tid + k * NTHR, G::PIECES);   // pieces past the tile all land in one spare slot
+        const int i = min(tid + k * 256, G::PIECES);   // pieces past the tile all land in one spare slot
         const u32x4 z = {0u, 0u, 0u, 0u};
         lds[i] = ((p.valid >> k) & 1u) ? r[k] : z;   // LDS image: [split][pixel][2 halves], linear
     }
@@ -90,8 +50,8 @@ __device__ __forceinline__ void h2_accumulate(const unsigned short *__restrict__
                                               const unsigned short *__restrict__ wpk, int C, int H, int W, int n, int ty,
                                               int tx, u32x4 *lds, f32x4 (&acc)[WaveTile<NT>::RW][WaveTile<NT>::CW])
 {
-    constexpr int NTHR = 256;
-    typedef GeoH<KH, KW, 16, NTHR> G;
+    typedef GeoH<KH, KW> G;
+    typedef TapPairs<G> TP;
     typedef WaveTile<NT> WT;
     constexpr int RW = WT::RW, CW = WT::CW;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, xl = lane & 15, g = lane >> 4;
@@ -106,19 +66,19 @@ __device__ __forceinline__ void h2_accumulate(const unsigned short *__restrict__
     constexpr bool W0DB = NT == 4;
     constexpr bool W2 = W0DB && G::TAPS == 9 && !LEAN;
     u32x4 r[G::NLD];
-    StagePlanH<KH, KW, NTHR> plan;
+    TilePlan<G> plan;
     // Tap pairing as in conv_bf16x6.hip: mode 0 plain (last pair zero-padded), mode 1 even group of a pair (its last tap
     // is deferred and carried in registers), mode 2 odd group (first K-step = the deferred tap + its own last tap).
-    const bool paired = (CB & 1) == 0 && (G::TAPS & 1);
+    const bool paired = TP::paired(CB);
     const f16x8 *wl = reinterpret_cast<const f16x8 *>(wpk) + lane + ch * CW * 64;
-    const int last = paired ? (CB / 2) * G::TAPS - 1 : CB * G::NKS - 1;   // last K-step of the weight stream
+    const int last = TP::last(CB);   // last K-step of the weight stream
     f16x8 w0[CW], w1[CW];   // ONE weight set, refilled in place as soon as the last MFMA that reads a split has issued
     f16x8 w0n[CW];          // W0DB: the K-step's w0 fragments land here and move to w0 between its phases A and B1
     // W2: weight fragments are requested TWO K-steps ahead (16 more registers).  The L1 returns data in order for the whole
     // CU, so a weight hit queued behind a halo request that went to HBM - this workgroup's or its neighbour's - waits for
     // it; one K-step of lead (0.8-1.5 k cycles) is less than that round trip, two are more.
     f16x8 w1n[CW], w0nn[CW];
-    h2_plan<KH, KW, NTHR>(plan, plane_stride, H, W, ty, tx);
+    tile_plan<KH, KW>(plan, plane_stride, H, W, ty, tx);
 #pragma unroll
     for (int nt = 0; nt < CW; ++nt) {
         if (W0DB) w0n[nt] = wl[(0 * NT + nt) * 64]; else w0[nt] = wl[(0 * NT + nt) * 64];
@@ -129,26 +89,23 @@ __device__ __forceinline__ void h2_accumulate(const unsigned short *__restrict__
         }
     }
     __syncthreads();
-    h2_stage_load<KH, KW, NTHR>(plan, grp0, r);
-    h2_stage_store<KH, KW, NTHR>(plan, lds, r);
+    tile_load(plan, grp0, r);
+    h2_stage_store<KH, KW>(plan, lds, r);
     __syncthreads();
     const int pb = ((rh * RW * G::TW + xl) * 2 + (g & 1)) * 16;   // bytes inside a split plane, tap (0,0)
     int stream = 0;
     int tapsel = SLIM ? -(g >> 1) : g >> 1;
-    constexpr int O_LAST = (((G::TAPS - 1) / KW) * G::TW + (G::TAPS - 1) % KW) * 32;   // byte offset of the last tap
+    constexpr int O_LAST = tap_off(G::TAPS - 1, KW, G::TW);   // byte offset of the last tap
     f16x8 x0[RW], x1[RW];   // pixel fragments of the current K-step (split 0 / split 1)
 
     auto group = [&](auto mode_tag, auto tail_tag, int cb) {
         constexpr int MODE = decltype(mode_tag)::value;
         constexpr int TAIL = decltype(tail_tag)::value;     // 2: last channel group of the pass, 1: the one before, 0: any other
         constexpr bool LAST = TAIL == 2;
-        constexpr int NK = MODE == 0 ? G::NKS : (MODE == 1 ? (G::TAPS - 1) / 2 : (G::TAPS - 1) / 2 + 1);
+        constexpr int NK = TP::nk(MODE);
         constexpr int PER = (G::NLD + (NK > 0 ? NK : 1) - 1) / (NK > 0 ? NK : 1);   // staging loads issued per K-step
         constexpr int LAG = G::TAPS > 9 ? 3 : 2;             // K-steps between a halo slice's request and its LDS store
         constexpr bool FETCH = TAIL < 2;                      // is there a group cb+1 to request
-        u32x4 (&rl)[G::NLD] = r;                              // requested during this group ...
-        u32x4 (&rs)[G::NLD] = r;                              // ... and written to LDS before its end (for group cb+1)
-        constexpr bool more = !LAST;
         const unsigned short *nxt_grp = grp0 + (size_t)min(cb + 1, CB - 1) * grp_sz;   // clamped: loads stay unconditional
         const int bcur = cb & 1, bprev = (cb + 1) & 1;
         const char *buf = reinterpret_cast<const char *>(lds + bcur * G::BUF);
@@ -156,7 +113,7 @@ __device__ __forceinline__ void h2_accumulate(const unsigned short *__restrict__
             const int j = MODE == 2 ? ks - 1 : ks;
             int tA = 2 * j, tB = 2 * j + 1;
             if (MODE == 0 && tB >= G::TAPS) tB = tA;
-            const int oA = ((tA / KW) * G::TW + tA % KW) * 32, oB = ((tB / KW) * G::TW + tB % KW) * 32;
+            const int oA = tap_off(tA, KW, G::TW), oB = tap_off(tB, KW, G::TW);
             // SLIM: tapsel is an all-ones mask there - an AND and an add with literals instead of a select between two constants held in registers
             if (SLIM) return buf + (oA + pb) + (tapsel & (oB - oA));
             return buf + (tapsel ? oB : oA) + pb;
@@ -173,7 +130,7 @@ __device__ __forceinline__ void h2_accumulate(const unsigned short *__restrict__
             // spilled register and no scratch (tests/test_conv5_resources_cpu.py); the results are the same bits.
             constexpr int RS = 2, SUB = RW / RS;   // 2-row sub-steps: 4-row ones spill (-15 %), 1-row ones expose more LDS round trips (-1 %)
             const char *part = reinterpret_cast<const char *>(lds + bprev * G::BUF);
-            if (NK == 0 && FETCH) h2_stage_load<KH, KW, NTHR>(plan, nxt_grp, rl);   // 1x1 source, even group: only fetch the partner group
+            if (NK == 0 && FETCH) tile_load(plan, nxt_grp, r);   // 1x1 source, even group: only fetch the partner group
 #pragma unroll
             for (int ks = 0; ks < NK; ++ks) {
                 asm volatile("" : "+v"(tapsel));
@@ -204,9 +161,9 @@ __device__ __forceinline__ void h2_accumulate(const unsigned short *__restrict__
                         for (int nt = 0; nt < CW; ++nt) w0[nt] = w0n[nt];
 #pragma unroll
                         for (int nt = 0; nt < CW; ++nt) { w1n[nt] = wf[(1 * NT + nt) * 64]; w0n[nt] = wf[(0 * NT + nt) * 64]; }
-                        if (FETCH) h2_stage_load<KH, KW, NTHR, SLIM>(plan, nxt_grp, rl, ks * PER, (ks + 1) * PER);   // slices: one burst per group measured 1 % slower here
-                        if (more && ks >= LAG)
-                            h2_stage_store<KH, KW, NTHR, SLIM>(plan, lds + ((cb + 1) & 1) * G::BUF, rs, (ks - LAG) * PER, (ks - LAG + 1) * PER);
+                        if (FETCH) tile_load<G, SLIM>(plan, nxt_grp, r, ks * PER, (ks + 1) * PER);   // slices: one burst per group measured 1 % slower here
+                        if (!LAST && ks >= LAG)
+                            h2_stage_store<KH, KW, SLIM>(plan, lds + ((cb + 1) & 1) * G::BUF, r, (ks - LAG) * PER, (ks - LAG + 1) * PER);
                     } else if (h == SUB - 1) {
 #pragma unroll
                         for (int nt = 0; nt < CW; ++nt) w1[nt] = w1n[nt];
@@ -229,7 +186,7 @@ __device__ __forceinline__ void h2_accumulate(const unsigned short *__restrict__
             }
         } else {
             if (NK == 0) {   // 1x1 source, even group: nothing to compute yet, only fetch the partner group
-                if (FETCH) h2_stage_load<KH, KW, NTHR>(plan, nxt_grp, rl);
+                if (FETCH) tile_load(plan, nxt_grp, r);
             } else if (MODE == 2) {
                 // cross-group pair: lanes g < 2 still hold the even group's last tap (picked up before the barrier that ended
                 // it - that buffer is being overwritten by now), lanes g >= 2 read this group's last tap
@@ -287,10 +244,10 @@ __device__ __forceinline__ void h2_accumulate(const unsigned short *__restrict__
                 // The halo requests follow the weight requests: the counter that orders vector-memory operations is in-order, so
                 // a weight fragment requested after an HBM load cannot be used before that load has landed.  Here the next such
                 // fragment is the w1 request of the NEXT K-step, used two K-steps from now.
-                if (FETCH) h2_stage_load<KH, KW, NTHR>(plan, nxt_grp, rl, ks * PER, (ks + 1) * PER);
+                if (FETCH) tile_load(plan, nxt_grp, r, ks * PER, (ks + 1) * PER);
                 // ... and the slice requested LAG K-steps ago goes to the partner LDS buffer, which nobody reads during this group
-                if (more && ks >= LAG)
-                    h2_stage_store<KH, KW, NTHR>(plan, lds + ((cb + 1) & 1) * G::BUF, rs, (ks - LAG) * PER, (ks - LAG + 1) * PER);
+                if (!LAST && ks >= LAG)
+                    h2_stage_store<KH, KW>(plan, lds + ((cb + 1) & 1) * G::BUF, r, (ks - LAG) * PER, (ks - LAG + 1) * PER);
                 __builtin_amdgcn_sched_barrier(0);
                 // phase B1: x0*w0, then x0 is free for the next K-step's pixels
 #pragma unroll
@@ -327,7 +284,7 @@ __device__ __forceinline__ void h2_accumulate(const unsigned short *__restrict__
             }
         }
         // the store goes to the buffer nobody reads during this group (the deferred tap travels in registers)
-        if (more) h2_stage_store<KH, KW, NTHR>(plan, lds + ((cb + 1) & 1) * G::BUF, rs, NK > LAG ? (NK - LAG) * PER : 0);
+        if (!LAST) h2_stage_store<KH, KW>(plan, lds + ((cb + 1) & 1) * G::BUF, r, NK > LAG ? (NK - LAG) * PER : 0);
         __syncthreads();
     };
 
@@ -358,13 +315,13 @@ __device__ __forceinline__ void h2_epilogue(const ConvX6Args &a, f32x4 (&acc)[Wa
 // Instead of the general staging pipeline (five barriers, its own plan, weights and staging registers) the whole 16x16 x 32 ch
 // tile goes to LDS at once - no halo - and each wave runs that K-step in 2-row sub-steps.  Same MFMA order per accumulator as
 // the general pass (x0*w1, x0*w0, x1*w0 after the main pass), so the results are bit-identical.
-// GEN (the 5x5 kernel with a shortcut source of any width, <5,5,4,1,0>): the same pass once per K-step of the general 1x1 pass - a pair of
-// channel groups where their count is even, else one group, which then fills both halves of the tile as the zero-padded tap pair of the
-// general pass reads one pixel twice - in that pass's order and from its weight stream: the same bits, without its plan, staging
+// FIX32 = false (the 5x5 kernel with a shortcut source of any width, <5,5,4,1,0>): the same pass once per K-step of the general 1x1 pass - a
+// pair of channel groups where their count is even, else one group, which then fills both halves of the tile as the zero-padded tap pair
+// of the general pass reads one pixel twice - in that pass's order and from its weight stream: the same bits, without its plan, staging
 // pipeline and second weight set, which spilled 57-82 registers behind a 168-VGPR main pass.
-template <int NT, bool OPQ = false>
-__device__ __forceinline__ void h2_shortcut32(const ConvX6Args &a, int n, int ty, int tx, u32x4 *lds,
-                                              f32x4 (&acc)[WaveTile<NT>::RW][WaveTile<NT>::CW])
+template <int NT, bool FIX32, bool OPQ>
+__device__ __forceinline__ void h2_shortcut_tile(const ConvX6Args &a, int n, int ty, int tx, u32x4 *lds,
+                                                 f32x4 (&acc)[WaveTile<NT>::RW][WaveTile<NT>::CW])
 {
     typedef WaveTile<NT> WT;
     constexpr int RW = WT::RW, CW = WT::CW;
@@ -374,66 +331,11 @@ __device__ __forceinline__ void h2_shortcut32(const ConvX6Args &a, int n, int ty
     const int rh = wave % WT::RSPLIT, ch = wave / WT::RSPLIT;
     const int W = a.W;
     const size_t grp_sz = (size_t)a.H * W * 16;
-    const unsigned short *base = a.x_sc + (size_t)n * 2 * grp_sz + ((size_t)(ty * 16) * W + tx * 16) * 16;
-    __syncthreads();   // every wave is done with the main pass's halo tiles
-    u32x4 r[8];        // piece i = [group][plane][pixel][half]: 2 x 2 x 256 x 2 pieces of 16 B
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int i = tid + k * 256, grp = i >> 10, plane = (i >> 9) & 1, j = i & 511, px = j >> 1, half = j & 1;
-        r[k] = *reinterpret_cast<const u32x4 *>(base + plane * a.sc_stride + grp * grp_sz + ((size_t)(px >> 4) * W + (px & 15)) * 16 + half * 8);
-    }
-    const f16x8 *wl = reinterpret_cast<const f16x8 *>(a.w_sc) + lane + ch * CW * 64;
-    f16x8 w0[CW], w1[CW];
-#pragma unroll
-    for (int nt = 0; nt < CW; ++nt) { w0[nt] = wl[(0 * NT + nt) * 64]; w1[nt] = wl[(1 * NT + nt) * 64]; }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) lds[tid + k * 256] = r[k];
-    __syncthreads();
-    const char *px = reinterpret_cast<const char *>(lds) + (g >> 1) * 16384 + ((rh * RW * 16 + xl) * 2 + (g & 1)) * 16;
-#pragma unroll
-    for (int h = 0; h < RW / 2; ++h) {
-        f16x8 xa[2], xb[2];
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            xa[m] = *reinterpret_cast<const f16x8 *>(px + (h * 2 + m) * 16 * 32);
-            xb[m] = *reinterpret_cast<const f16x8 *>(px + 8192 + (h * 2 + m) * 16 * 32);
-        }
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int nt = 0; nt < CW; ++nt) acc[h * 2 + m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w1[nt], xa[m], acc[h * 2 + m][nt], 0, 0, 0);
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int nt = 0; nt < CW; ++nt) acc[h * 2 + m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w0[nt], xa[m], acc[h * 2 + m][nt], 0, 0, 0);
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int nt = 0; nt < CW; ++nt) acc[h * 2 + m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w0[nt], xb[m], acc[h * 2 + m][nt], 0, 0, 0);
-    }
-}
-
-// The same pass for a shortcut source of ANY width (the 5x5 kernel <5,5,4,1,0>), once per K-step of the general 1x1 pass: a pair of channel
-// groups where their count is even, else one group, which then fills both halves of the tile as the zero-padded tap pair of the general
-// pass reads one pixel twice - in that pass's order and from its weight stream, so the same bits, without its plan, staging pipeline and
-// second weight set, which spilled 57-82 registers behind a 168-VGPR main pass.
-template <int NT>
-__device__ __forceinline__ void h2_shortcut_any(const ConvX6Args &a, int n, int ty, int tx, u32x4 *lds,
-                                                f32x4 (&acc)[WaveTile<NT>::RW][WaveTile<NT>::CW])
-{
-    typedef WaveTile<NT> WT;
-    constexpr int RW = WT::RW, CW = WT::CW;
-    int tid = threadIdx.x;
-    asm volatile("" : "+v"(tid));   // opaque, as in h2_epilogue
-    const int lane = tid & 63, wave = tid >> 6, xl = lane & 15, g = lane >> 4;
-    const int rh = wave % WT::RSPLIT, ch = wave / WT::RSPLIT;
-    const int W = a.W;
-    const size_t grp_sz = (size_t)a.H * W * 16;
-    const int CB = a.Csc >> 4, per = (CB & 1) ? 1 : 2, steps = CB / per;   // channel groups, groups per K-step, K-steps
+    const int CB = FIX32 ? 2 : a.Csc >> 4, per = (CB & 1) ? 1 : 2, steps = CB / per;   // channel groups, groups per K-step, K-steps
     const unsigned short *base = a.x_sc + (size_t)n * CB * grp_sz + ((size_t)(ty * 16) * W + tx * 16) * 16;
     for (int s = 0; s < steps; ++s) {
         __syncthreads();   // every wave is done with the main pass's halo tiles, or with the previous K-step's tile
-        u32x4 r[8];
+        u32x4 r[8];        // piece i = [group][plane][pixel][half]: 2 x 2 x 256 x 2 pieces of 16 B
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int i = tid + k * 256, grp = s * per + (per == 2 ? i >> 10 : 0), plane = (i >> 9) & 1, j = i & 511, pix = j >> 1, half = j & 1;
@@ -472,7 +374,7 @@ __device__ __forceinline__ void h2_shortcut_any(const ConvX6Args &a, int n, int 
 }
 
 // Which Cout = 64 kernels take the 168-VGPR, three-workgroup form: the ones the launcher asks it of (LEAN: no shortcut source) and the 5x5
-// kernels with a shortcut source, whose LDS-tile passes (h2_shortcut32, h2_shortcut_any) run when the K-loop's registers are dead.  Those
+// kernels with a shortcut source, whose LDS-tile pass (h2_shortcut_tile) runs when the K-loop's registers are dead.  Those
 // keep their instantiation names <5,5,4,2,0> and <5,5,4,1,0>: the kernel table that the tests hold the library's symbols and the launch
 // reports to names them so.
 template <int KH, int NT, int SC, bool LEAN>
@@ -501,8 +403,8 @@ __global__ __launch_bounds__(256, (NT == 4 && !h2_lean_form<KH, NT, SC, LEAN> ? 
     constexpr bool LF = h2_lean_form<KH, NT, SC, LEAN>;
     constexpr bool SLIM = LF && KH == 5;   // the 5x5 lean kernels: lane arithmetic, plan offsets and tap offsets kept out of the K-loop's registers
     h2_accumulate<KH, KW, NT, LF, SLIM>(a.x, a.x_stride, a.w, a.Cin, a.H, a.W, n, ty, tx, lds, acc);
-    if (SC == 2) h2_shortcut32<NT, SLIM>(a, n, ty, tx, lds, acc);
-    else if (SC && SLIM) h2_shortcut_any<NT>(a, n, ty, tx, lds, acc);
+    if (SC == 2) h2_shortcut_tile<NT, true, SLIM>(a, n, ty, tx, lds, acc);
+    else if (SC && SLIM) h2_shortcut_tile<NT, false, true>(a, n, ty, tx, lds, acc);
     else if (SC) h2_accumulate<1, 1, NT, LF, SLIM>(a.x_sc, a.sc_stride, a.w_sc, a.Csc, a.H, a.W, n, ty, tx, lds, acc);
     h2_epilogue<NT>(a, acc, n, ty, tx);
 }
@@ -569,7 +471,7 @@ __device__ __forceinline__ void h2_epilogue(const ConvX6Args &a, f32x4 (&acc)[Wa
         for (int m = 0; m < RW; ++m) {
             const unsigned off = off0 + (unsigned)m * row_el + (unsigned)nt * (unsigned)grp;
             f32x4 v = acc[m][nt];
-            if (a.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+            if (a.relu) v = relu4(v);
             if (a.gate) v *= load_split2_4(a.gate + off, a.gate_stride);
             amax = sat_amax4(amax, v);
             acc[m][nt] = v;
@@ -597,11 +499,7 @@ __device__ __forceinline__ void h2_epilogue(const ConvX6Args &a, f32x4 (&acc)[Wa
             const int Ho = H >> 1, Wo = W >> 1;
 #pragma unroll
             for (int m = 0; m < RW; m += 2) {
-                f32x4 v = acc[m][nt], u = acc[m + 1][nt];
-                v.x = fmaxf(v.x, u.x); v.y = fmaxf(v.y, u.y); v.z = fmaxf(v.z, u.z); v.w = fmaxf(v.w, u.w);
-                f32x4 o;
-                o.x = __shfl_xor(v.x, 1); o.y = __shfl_xor(v.y, 1); o.z = __shfl_xor(v.z, 1); o.w = __shfl_xor(v.w, 1);
-                v.x = fmaxf(v.x, o.x); v.y = fmaxf(v.y, o.y); v.z = fmaxf(v.z, o.z); v.w = fmaxf(v.w, o.w);
+                const f32x4 v = pool2x2_max(acc[m][nt], acc[m + 1][nt]);
                 if ((xl & 1) == 0) {
                     const int yo = ty * 8 + rh * (RW / 2) + (m >> 1), xo = tx * 8 + (xl >> 1);
                     const size_t off = (((size_t)n * NT + ch * CW + nt) * Ho + yo) * Wo * 16 + (size_t)xo * 16 + g * 4;
@@ -634,7 +532,7 @@ static hipError_t launch_h2(hipStream_t s, const ConvX6Args &a)
     case 4:
         if constexpr (KH > 1) {
             if (a.x_sc && a.Csc == 32) {
-                // RB(32,64,k): the whole 32-channel shortcut tile goes to LDS at once (h2_shortcut32).  3x3: two workgroups per CU.  5x5:
+                // RB(32,64,k): the whole 32-channel shortcut tile goes to LDS at once (h2_shortcut_tile).  3x3: two workgroups per CU.  5x5:
                 // the 168-VGPR form under this name (h2_lean_form) - with the spilling K-loop it measured the same as two workgroups
                 // (5x5 class 5.94 vs 5.95 ms per 1024 blocks), spill-free 7042 -> 6909 us per 4096-block launch
                 PMP_H2_LAUNCH_SC(4, 2, false);
@@ -642,7 +540,7 @@ static hipError_t launch_h2(hipStream_t s, const ConvX6Args &a)
                 // the Cout = 64 layers without a shortcut source: the 168-VGPR form, three workgroups per CU (3x3: -5.6 %, 5x5: -1.9 %
                 // against the two-workgroup form while its K-loop spilled 33 registers, another -1.4 % without: 2487 -> 2452 us per
                 // launch; at 3x3 the general 1x1 shortcut pass would spill 89 registers in this form and stays at two workgroups, at 5x5
-                // <5,5,4,1,0> runs its shortcut tile by tile through LDS instead, h2_shortcut_any, in this form).
+                // <5,5,4,1,0> runs its shortcut tile by tile through LDS instead, h2_shortcut_tile, in this form).
                 // Both 5x5 changes together, same-box A/B: luma step -0.58 / -0.95 ms on two boxes (profiles/r07_conv5_3wg_ab.txt)
                 PMP_H2_LAUNCH_SC(4, 0, true);
             } else {
@@ -659,54 +557,24 @@ static hipError_t launch_h2(hipStream_t s, const ConvX6Args &a)
 #undef PMP_H2_LAUNCH
 #undef PMP_H2_LAUNCH_SC
 
-hipError_t launch_conv_h2(hipStream_t s, const ConvX6Args &a_in)
+hipError_t launch_conv_h2(hipStream_t s, const ConvX6Args &a)
 {
-    const ConvX6Args &a = a_in;
-
-    if ((a.H & 15) || (a.W & 15) || (a.Cin & 15) || (a.Cout & 15) || (a.x_sc && (a.Csc & 15)) || a.N <= 0)
-        return hipErrorInvalidValue;
-    if (a.pool && a.gate) return hipErrorInvalidValue;
-    if (!(a.out_scale > 0.f)) return hipErrorInvalidValue;
+    if (!conv_shape_ok(a) || !(a.out_scale > 0.f)) return hipErrorInvalidValue;
     if (a.KH == 3 && a.KW == 3) return launch_h2<3, 3>(s, a);
     if (a.KH == 5 && a.KW == 5) return launch_h2<5, 5>(s, a);
     if (a.KH == 1 && a.KW == 1) return launch_h2<1, 1>(s, a);
     return hipErrorInvalidValue;
 }
 
-// ---- format converters ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void f32_to_split2_kernel(const float *__restrict__ x, unsigned short *__restrict__ out,
-                                                            size_t n4, size_t plane_stride, unsigned *sat)
-{
-    float amax = 0.f;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-        const f32x4 v = *reinterpret_cast<const f32x4 *>(x + i * 4);
-        amax = sat_amax4(amax, v);
-        store_split2_4(out + i * 4, plane_stride, v);
-    }
-    sat_report(sat, amax);
-}
-
-__global__ __launch_bounds__(256) void split2_to_f32_kernel(const unsigned short *__restrict__ x, float *__restrict__ out,
-                                                            size_t n4, size_t plane_stride)
-{
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256)
-        *reinterpret_cast<f32x4 *>(out + i * 4) = load_split2_4(x + i * 4, plane_stride);
-}
-
+// ---- format converters (conv_tile.h) ------------------------------------------------------------------------------
 hipError_t launch_f32_to_split2(hipStream_t s, const float *x, unsigned short *out, size_t n, size_t plane_stride, unsigned *sat)
 {
-    const size_t n4 = n / 4;
-    const unsigned grid = (unsigned)((n4 + 255) / 256 > 16384 ? 16384 : (n4 + 255) / 256);
-    if (n4) hipLaunchKernelGGL(f32_to_split2_kernel, dim3(grid), dim3(256), 0, s, x, out, n4, plane_stride, sat);
-    return hipGetLastError();
+    return launch_f32_to_split<FMT_H2>(s, x, out, n, plane_stride, sat);
 }
 
 hipError_t launch_split2_to_f32(hipStream_t s, const unsigned short *x, float *out, size_t n, size_t plane_stride)
 {
-    const size_t n4 = n / 4;
-    const unsigned grid = (unsigned)((n4 + 255) / 256 > 16384 ? 16384 : (n4 + 255) / 256);
-    if (n4) hipLaunchKernelGGL(split2_to_f32_kernel, dim3(grid), dim3(256), 0, s, x, out, n4, plane_stride);
-    return hipGetLastError();
+    return launch_split_to_f32<FMT_H2>(s, x, out, n, plane_stride);
 }
 
 }  // namespace pmp

@@ -20,11 +20,9 @@
 // LDS: the (16+KH-1) x (16+KW-1) halo tile of ONE 16-channel group (64 B per pixel), XOR-swizzled so the
 // ds_read_b128 of 16 consecutive pixels is conflict-free in every b128 lane group (slot ^= 2*((pix>>2)&1)).
 // Weights never touch LDS: they are pre-packed in fragment order and streamed from L2 with 16-B lane loads.
-#include "pmp_kernels.h"
+#include "conv_tile.h"
 
 namespace pmp {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // float4 index of channel slot s of tile pixel (row, col): the 16-B slot is XORed with 2*bit2(col), which makes the
 // ds_read_b128 of 16 consecutive columns conflict-free for every row stride and tap offset (tools: brute-forced).
@@ -220,7 +218,7 @@ __global__ __launch_bounds__(256, OCC) void conv_mfma_kernel(ConvMfmaArgs a)
             if (a.res) v += *reinterpret_cast<const f32x4 *>(a.res + off);
             if (a.relu) {
                 const f32x4 pre = v;
-                v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+                v = relu4(v);
                 if (carry) {            // the training calls: a NaN goes through (relu_nan).  Uniform: the inference graph jumps over it
                     v.x = pre.x != pre.x ? pre.x : v.x; v.y = pre.y != pre.y ? pre.y : v.y;
                     v.z = pre.z != pre.z ? pre.z : v.z; v.w = pre.w != pre.w ? pre.w : v.w;
@@ -242,6 +240,8 @@ __global__ __launch_bounds__(256, OCC) void conv_mfma_kernel(ConvMfmaArgs a)
             const int Ho = H >> 1, Wo = W >> 1;
 #pragma unroll
             for (int m = 0; m < 4; m += 2) {
+                // (conv_tile.h's pool2x2_max, spelled out: through the helper, by value or by reference, hipcc schedules this epilogue
+                // differently and the 1x1 kernels take 4 more VGPRs)
                 f32x4 v = acc[m][nt], u = acc[m + 1][nt];
                 v.x = fmaxf(v.x, u.x); v.y = fmaxf(v.y, u.y); v.z = fmaxf(v.z, u.z); v.w = fmaxf(v.w, u.w);
                 f32x4 o;
@@ -262,21 +262,16 @@ template <int KH, int KW, int PIPE, int OCC>
 static hipError_t launch_k(hipStream_t s, const ConvMfmaArgs &a)
 {
     const int grid = a.N * (a.H >> 4) * (a.W >> 4);
-    if (a.Cout == 16 || a.Cout == 32 || a.Cout == 64) note_launch("conv_mfma_kernel", KH, KW, a.Cout >> 4, PIPE, OCC);
-    switch (a.Cout >> 4) {
-    case 1: hipLaunchKernelGGL((conv_mfma_kernel<KH, KW, 1, PIPE, OCC>), dim3(grid), dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL((conv_mfma_kernel<KH, KW, 2, PIPE, OCC>), dim3(grid), dim3(256), 0, s, a); break;
-    case 4: hipLaunchKernelGGL((conv_mfma_kernel<KH, KW, 4, PIPE, OCC>), dim3(grid), dim3(256), 0, s, a); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_cout(a.Cout, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        note_launch("conv_mfma_kernel", KH, KW, NT, PIPE, OCC);
+        hipLaunchKernelGGL((conv_mfma_kernel<KH, KW, NT, PIPE, OCC>), dim3(grid), dim3(256), 0, s, a);
+    });
 }
 
 hipError_t launch_conv_mfma(hipStream_t s, const ConvMfmaArgs &a)
 {
-    if ((a.H & 15) || (a.W & 15) || (a.Cin & 15) || (a.Cout & 15) || (a.x_sc && (a.Csc & 15)) || a.N <= 0)
-        return hipErrorInvalidValue;
-    if (a.pool && a.gate) return hipErrorInvalidValue;
+    if (!conv_shape_ok(a)) return hipErrorInvalidValue;
     // shipped form: fully software-pipelined, two waves per SIMD
     if (a.KH == 3 && a.KW == 3) return launch_k<3, 3, 2, 2>(s, a);
     if (a.KH == 5 && a.KW == 5) return launch_k<5, 5, 2, 2>(s, a);

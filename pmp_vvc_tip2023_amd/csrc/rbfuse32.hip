@@ -16,8 +16,7 @@
 // same fp32 accumulators (x0*w1, x0*w0, x1*w0), the main pass before the shortcut pass, the epilogue arithmetic of conv_f16x3.hip
 // (x 1/S, ReLU, range-flag maximum, pool, two-term split with the clamp).  A value of t that two tiles both compute is the same number
 // in both.  LDS 46-72 KB: two workgroups of eight waves per CU.
-#include "pmp_kernels.h"
-#include "split3.h"
+#include "conv_tile.h"
 
 namespace pmp {
 
@@ -264,8 +263,7 @@ __global__ __launch_bounds__(512, 4) void rbfuse32_kernel(RbFuse32Dev a, int tot
             for (int k = 0; k < KC; ++k) {
                 if ((k == KC - 1 && !lastc) || !(pyx1[c + k] >> 16)) continue;
                 const int py = pyx1[c + k] & 255, px = (pyx1[c + k] >> 8) & 255;
-                f32x4 v = acc[k] * a.s0;
-                v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+                f32x4 v = relu4(acc[k] * a.s0);
                 if ((unsigned)(oy + py) >= (unsigned)S || (unsigned)(ox + px) >= (unsigned)S) v = (f32x4){0.f, 0.f, 0.f, 0.f};      // the second convolution's zero padding
                 amax = sat_amax4(amax, v);
                 unsigned p0, q0, p1, q1;
@@ -288,8 +286,7 @@ __global__ __launch_bounds__(512, 4) void rbfuse32_kernel(RbFuse32Dev a, int tot
         rf_accumulate<1, CB_IN, NT, KI2, RF_IW, RF_ISLOT, RF_IPLN, RF_IW * 16, 1>(img, wsb, wvt, hi, pbs, true, acc);       // ResidualBlock, Model_QBD.py:33-38
 #pragma unroll
         for (int k = 0; k < KI2; ++k) {
-            f32x4 v = acc[k] * a.s2;
-            v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+            f32x4 v = relu4(acc[k] * a.s2);
             if (!POOLF) amax = sat_amax4(amax, v);      // a plain fp32 output is not clamped: not the range flag's business (conv_f16x3.hip)
             acc[k] = v;
         }
@@ -297,11 +294,7 @@ __global__ __launch_bounds__(512, 4) void rbfuse32_kernel(RbFuse32Dev a, int tot
             char *ob = reinterpret_cast<char *>(a.out_f32 + (((size_t)n * NT + ct) * (S / 2) + ty * 8) * (S / 2) * 16 + tx * 8 * 16);     // uniform
 #pragma unroll
             for (int k = 0; k < KI2; k += 2) {
-                f32x4 v = acc[k], u = acc[k + 1];
-                v.x = fmaxf(v.x, u.x); v.y = fmaxf(v.y, u.y); v.z = fmaxf(v.z, u.z); v.w = fmaxf(v.w, u.w);
-                f32x4 o;
-                o.x = __shfl_xor(v.x, 1); o.y = __shfl_xor(v.y, 1); o.z = __shfl_xor(v.z, 1); o.w = __shfl_xor(v.w, 1);
-                v.x = fmaxf(v.x, o.x); v.y = fmaxf(v.y, o.y); v.z = fmaxf(v.z, o.z); v.w = fmaxf(v.w, o.w);
+                const f32x4 v = pool2x2_max(acc[k], acc[k + 1]);
                 if ((xl & 1) == 0) *reinterpret_cast<RF_GLOBAL f32x4 *>((RF_GLOBAL char *)ob + ovt + (k >> 1) * ((S / 2) * 64)) = v;
             }
         } else {

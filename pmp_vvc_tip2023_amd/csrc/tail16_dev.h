@@ -14,8 +14,7 @@
 // BIT-IDENTICAL to the launch-per-layer path, as before: same pack_h2 streams, same K-step list, x0*w1, x0*w0, x1*w0 per K-step, main pass
 // before the shortcut pass, the same epilogue arithmetic.
 #pragma once
-#include "pmp_kernels.h"
-#include "split3.h"
+#include "conv_tile.h"
 
 namespace pmp {
 
@@ -210,7 +209,7 @@ __device__ __forceinline__ float t16_epilogue(f32x4 (&acc)[RW], int row0, const 
         } else {
             v = v * e.inv_scale;
         }
-        v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+        v = relu4(v);
         if (GATE) {
             const T16_GLOBAL unsigned short *gp = (const T16_GLOBAL unsigned short *)e.gate + (size_t)((row * 16 + xl) * 16 + g * 4);
             const u32x2_t ga = *reinterpret_cast<const T16_GLOBAL u32x2_t *>(gp), gb = *reinterpret_cast<const T16_GLOBAL u32x2_t *>(gp + e.gate_stride);
@@ -222,7 +221,7 @@ __device__ __forceinline__ float t16_epilogue(f32x4 (&acc)[RW], int row0, const 
 #pragma unroll
     for (int m = 0; m < RW; m += 2) {
         if (OUT == T16_POOL) {
-            f32x4 v = acc[m], u = acc[m + 1];
+            f32x4 v = acc[m], u = acc[m + 1];      // conv_tile.h's pool2x2_max, spelled out: through the helper hipcc schedules qt_rest16_kernel differently
             v.x = fmaxf(v.x, u.x); v.y = fmaxf(v.y, u.y); v.z = fmaxf(v.z, u.z); v.w = fmaxf(v.w, u.w);
             f32x4 o;
             o.x = __shfl_xor(v.x, 1); o.y = __shfl_xor(v.y, 1); o.z = __shfl_xor(v.z, 1); o.w = __shfl_xor(v.w, 1);
