@@ -717,6 +717,71 @@ int pmp_qtail_backward_device(pmp_ctx *ctx, const pmp_qtail_shape *shape, const 
                               const float *d_g_x9, float *d_g_x4 /* may be NULL */, float *const *d_g_w);
 int pmp_qtail_unpack_device(pmp_ctx *ctx, const pmp_qtail_shape *shape, const void *d_saved, int index, float *d_dense);
 
+/* ---- TRAINING STEP: what a training loop runs around the nets and the loss - a batch assembled on the device from a data set that
+ *      stays there as the label files hold it, and Adam over every parameter of a step (train_step.hip).  One launch each.
+ *
+ *      pmp_batch_gather_device.  src: the WHOLE set, device pointers to the bytes of Load_Pre_VP_Dataset's .npy files (Metrics.py:64-146)
+ *      and count = N >= 1 blocks: y u8[N][68][68]; u, v u8[N][34][34], both given = a chroma set, both NULL = luma; qt8 u8[N][8][8] (raw
+ *      qtDepth), msbt u8[N][3][16][16], msdire i8[N][3][16][16], each of the three NULL where the set has none.  d_index i64[n]: the rows
+ *      of the batch, in the batch's order; a row may repeat.  dst: the batch, each NULL where it is not asked for:
+ *        x      luma   f32[n][1][68][68] = float(y)
+ *               chroma f32[n][3][34][34]: channel 0 [r][c] = float(max(y[2r][2c], y[2r][2c+1], y[2r+1][2c], y[2r+1][2c+1])) - F.max_pool2d(y, 2),
+ *                      Metrics.py:85 - channel 1 = float(u), channel 2 = float(v)
+ *        qt_f   f32[n][1][8][8] = float((uint8)(qt8 - 1)): the loader's `np.load(...) - 1` in uint8, a raw 0 becoming 255.0 as in pmp_val_stats
+ *        qt8, msbt, msdire     the raw label rows (u8[n][8][8], u8[n][3][16][16], i8[n][3][16][16]), as pmp_train_loss_device reads them
+ *      Every value is an integer of at most 255: exact.  Every byte of every requested output row is written.
+ *      INDICES OUTSIDE [0, N) are never dereferenced: the rows of such an index are written as zeros (+0.0, 0) in every requested output and
+ *      bit 0 of *d_status is set with an atomic OR.  Nothing else ever writes *d_status: the caller zeroes it once and reads it when
+ *      it likes (once an epoch, say).
+ *      ALIGNMENT: every pointer of src and dst and d_status 4-byte aligned, d_index 8-byte; no more is assumed (rows of 4624 and 1156
+ *      bytes keep 4-byte alignment and nothing better): 4-byte loads, and 16-byte stores only where a call's output rows happen to allow them.
+ *      ORDER: no atomics but the status bit, no sums: the same bits on every run, stream and context.
+ *      PMP_E_INVALID before any launch, nothing written: NULL src, dst, d_index or d_status; count < 1; n outside 1..65536; y NULL; one of
+ *      u, v without the other; no output asked for; an output whose source is NULL; a pointer not aligned as above; an output that
+ *      overlaps the set, the index, the status word or another output.
+ *      Stream-ordered on the context's stream, the host does not wait; like the other training calls it first SETTLES the context's
+ *      calls in flight.
+ *
+ *      pmp_adam_step_device.  torch.optim.Adam without weight decay and without amsgrad, step number `step` >= 1, over ntensors tensors
+ *      in one launch.  param, grad, m, v and count are HOST arrays [ntensors] of device pointers (float32, 4-byte aligned) and of element
+ *      counts, like d_w of pmp_stem_*.  On the host, in double:
+ *        c1 = 1 - beta1^step      c2 = 1 - beta2^step      a = lr / c1      r = sqrt(c2)
+ *      and d1 = float(1 - beta1), b2 = float(beta2), d2 = float(1 - beta2), af = float(a), rf = float(r), ef = float(eps).
+ *      Per element in float32, fma(a, b, c) = a*b + c rounded once, every other operation rounded on its own, sqrt and the divisions
+ *      correctly rounded, in this order:
+ *        m = fma(d1, g - m, m)          v = fma(d2*g, g, b2*v)          param = param + ((-af)*m) / (sqrt(v)/rf + ef)
+ *      which is  m = beta1*m + (1-beta1)*g;  v = beta2*v + (1-beta2)*g*g;  param -= (lr/(1-beta1^step)) * m / (sqrt(v)/sqrt(1-beta2^step) + eps)
+ *      in the order of operations of torch's float32 CPU kernels (lerp_, mul_ and addcmul_, addcdiv_): on an x86 host with FMA it gave
+ *      their bits on all but a few elements in a million (those kernels' own bits differ from one CPU to another).
+ *      Elements are independent: a NaN or an inf in g makes that element's m, v and param what the formula gives (NaN g: all three NaN;
+ *      +-inf g: m = +-inf, v = +inf, param NaN - torch's float32 CPU Adam gives the same) and touches no other element.
+ *      LAUNCHES: the tensors' pointers travel in the kernel's argument block, PMP_ADAM_TABLE entries to a launch - the 92 tensors of the luma
+ *      joint step are one launch; more tensors (and tensors of 2^30 elements or more, which take an entry per 2^30) go in the fewest
+ *      launches that hold them, in the order given.  Nothing is staged, allocated or waited for: a call costs its launches.
+ *      PMP_E_INVALID before anything is launched or written, with a message in pmp_last_error: ntensors < 1; a NULL p or array; a NULL
+ *      entry or one not 4-byte aligned; a count < 1; step < 1; lr, beta1, beta2 or eps not finite; a beta outside [0, 1); eps <= 0; two
+ *      tensors of the call (any two of the 4*ntensors) overlapping in memory.
+ *      ORDER: no atomics, no sums: the same bits on every run, stream and context.  Stream-ordered, settles first, as above. ---- */
+typedef struct pmp_batch_src {
+    const uint8_t *y, *u, *v, *qt8, *msbt;
+    const int8_t *msdire;
+    int64_t count;
+} pmp_batch_src;
+typedef struct pmp_batch_dst {
+    float *x, *qt_f;
+    uint8_t *qt8, *msbt;
+    int8_t *msdire;
+} pmp_batch_dst;
+typedef struct pmp_adam_params {
+    double lr, beta1, beta2, eps;      /* torch.optim.Adam's defaults: 1e-3, 0.9, 0.999, 1e-8 */
+} pmp_adam_params;
+#define PMP_BATCH_MAX 65536
+#define PMP_ADAM_TABLE 96
+int pmp_batch_gather_device(pmp_ctx *ctx, const pmp_batch_src *src, const int64_t *d_index, int64_t n, const pmp_batch_dst *dst,
+                            int32_t *d_status);
+int pmp_adam_step_device(pmp_ctx *ctx, const pmp_adam_params *p, int ntensors, float *const *param, const float *const *grad,
+                         float *const *m, float *const *v, const int64_t *count, int64_t step);
+
 /* ---- teacher-forced MTT inference: the MTT net of (comp, qp) on the blocks with a GIVEN QT map instead of the QT net's output, what
  *      pre_validation predID 1 runs (Net(input_batch, qt_label_batch), Metrics.py:226).  qt_in f32[n][8][8] is read, never written
  *      (for the reference's validation: float(qt8 - 1) with the u8 wrap above).  Everything else is pmp_infer's: the context's datapath,

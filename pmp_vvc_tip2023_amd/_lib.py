@@ -94,6 +94,25 @@ def qtail_shape(shape):
     return shape if isinstance(shape, QtailShape) else QtailShape(*(int(v) for v in shape))
 
 
+class BatchSrc(C.Structure):
+    """pmp_batch_src: the whole data set on the device (pmp_batch_gather_device); u, v both set = chroma; absent labels NULL."""
+    _fields_ = [(k, C.c_void_p) for k in ("y", "u", "v", "qt8", "msbt", "msdire")] + [("count", C.c_int64)]
+
+
+class BatchDst(C.Structure):
+    """pmp_batch_dst: the outputs of pmp_batch_gather_device for n rows, each NULL where it is not asked for."""
+    _fields_ = [(k, C.c_void_p) for k in ("x", "qt_f", "qt8", "msbt", "msdire")]
+
+
+class AdamParams(C.Structure):
+    """pmp_adam_params: torch.optim.Adam's lr, betas and eps."""
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
+
+
+PMP_BATCH_MAX = 65536
+PMP_ADAM_TABLE = 96
+
+
 def pointer_array(ptrs, count):
     """A host array of `count` device pointers (None = NULL) for the C ABI; None stays None."""
     if ptrs is None:
@@ -170,6 +189,8 @@ SIGNATURES = {
     "pmp_head_backward_device": (_I, [_VP, C.POINTER(HeadShape)] + [_VP] * 9),
     "pmp_gate_forward_device": (_I, [_VP, _I64, _VP, _VP, _VP]),
     "pmp_gate_backward_device": (_I, [_VP, _I64] + [_VP] * 6),
+    "pmp_batch_gather_device": (_I, [_VP, C.POINTER(BatchSrc), _VP, _I64, C.POINTER(BatchDst), _VP]),
+    "pmp_adam_step_device": (_I, [_VP, C.POINTER(AdamParams), _I, _VP, _VP, _VP, _VP, C.POINTER(_I64), _I64]),
     "pmp_infer_msbd": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
     "pmp_infer_msbd_device": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
     "pmp_read_depth_dump": (_I, [C.c_char_p, _I, _I, _I, _I, _VP, _VP, _VP, C.POINTER(_I64)]),

@@ -421,9 +421,47 @@ int gate_entry(pmp_ctx *c, const char *fn, int64_t count, bool backward, const f
     return e == hipSuccess ? PMP_OK : hip_fail(c, e, "gate");
 }
 
+// pmp_adam_step_device: the tensors, cut into entries of at most 2^30 floats, go out PMP_ADAM_TABLE entries to a launch
+int adam_run(pmp_ctx *c, const pmp_adam_params &p, int ntensors, float *const *param, const float *const *grad, float *const *m,
+             float *const *v, const int64_t *count, int64_t step)
+{
+    const double c1 = 1.0 - std::pow(p.beta1, (double)step), c2 = 1.0 - std::pow(p.beta2, (double)step);
+    const AdamConsts k{(float)(1.0 - p.beta1), (float)p.beta2, (float)(1.0 - p.beta2), -(float)(p.lr / c1), (float)std::sqrt(c2), (float)p.eps};
+    constexpr int64_t PART = (int64_t)1 << 30;
+    AdamTable t;
+    int nt = 0;
+    const auto flush = [&] {
+        const hipError_t e = nt ? launch_adam_step(c->stream, t, nt, k) : hipSuccess;
+        nt = 0;
+        return e == hipSuccess ? PMP_OK : hip_fail(c, e, "adam_step");
+    };
+    for (int i = 0; i < ntensors; ++i)
+        for (int64_t at = 0; at < count[i]; at += PART) {
+            t.param[nt] = param[i] + at; t.grad[nt] = grad[i] + at; t.m[nt] = m[i] + at; t.v[nt] = v[i] + at;
+            t.count[nt] = (unsigned)std::min(PART, count[i] - at);
+            if (++nt == PMP_ADAM_TABLE)
+                if (int rc = flush()) return rc;
+        }
+    return flush();
+}
+
 }  // namespace
 
 extern "C" {
+
+int pmp_batch_gather_device(pmp_ctx *c, const pmp_batch_src *src, const int64_t *d_index, int64_t n, const pmp_batch_dst *dst, int32_t *d_status)
+{
+    if (int rc = admit(c, "pmp_batch_gather_device", gather_refused(src, d_index, n, dst, d_status))) return rc;
+    const hipError_t e = launch_batch_gather(c->stream, *src, d_index, (int)n, *dst, d_status);
+    return e == hipSuccess ? PMP_OK : hip_fail(c, e, "batch_gather");
+}
+
+int pmp_adam_step_device(pmp_ctx *c, const pmp_adam_params *p, int ntensors, float *const *param, const float *const *grad, float *const *m,
+                         float *const *v, const int64_t *count, int64_t step)
+{
+    if (int rc = admit(c, "pmp_adam_step_device", adam_refused(p, ntensors, param, grad, m, v, count, step))) return rc;
+    return adam_run(c, *p, ntensors, param, grad, m, v, count, step);
+}
 
 int pmp_head_forward_device(pmp_ctx *c, const pmp_head_shape *s, const float *x, const float *w, const float *b, const float *prev,
                             const float *q, float *y, float *att)

@@ -319,6 +319,21 @@ hipError_t launch_gate_backward(hipStream_t s, size_t count, const float *x, con
 enum { QT_MULTIPOOL, QT_MULTIPOOL_BACK, QT_POOL_EMBED, QT_POOL_BACK, QT_EMBED_GRAD, QT_CROP_DENSE };
 hipError_t launch_qtail_step(hipStream_t s, int step, const float *a, const float *b, const float *c, float *out, float *out2, int N, int H, int W);
 
+// ------------------------------------------------------------------------------------------------ training, a step's ends (train_step.hip)
+// pmp_batch_gather_device: one workgroup per row of the batch; every pointer 4-byte aligned, n in 1..PMP_BATCH_MAX, src.count >= 1
+hipError_t launch_batch_gather(hipStream_t s, const pmp_batch_src &src, const int64_t *index, int n, const pmp_batch_dst &dst, int32_t *status);
+// pmp_adam_step_device: one launch over the first nt <= PMP_ADAM_TABLE entries of t, an entry being a tensor (or a part of one) of
+// 1 .. 2^30 floats.  The float32 constants are include/pmp.h's.  The table travels in the kernel's argument block.
+struct AdamConsts { float d1, b2, d2, neg_af, rf, ef; };
+struct AdamTable {
+    float *param[PMP_ADAM_TABLE];
+    const float *grad[PMP_ADAM_TABLE];
+    float *m[PMP_ADAM_TABLE], *v[PMP_ADAM_TABLE];
+    unsigned count[PMP_ADAM_TABLE];
+    unsigned first[PMP_ADAM_TABLE];     // the entry's first workgroup: filled by the launcher
+};
+hipError_t launch_adam_step(hipStream_t s, AdamTable &t, int nt, const AdamConsts &k);
+
 // Block cutter (Inference_QBD.py:104-149).
 hipError_t launch_cut_blocks(hipStream_t s, const void *y, const void *u, const void *v, int F, int H, int W,
                              int bitdepth, uint8_t *by, uint8_t *bu, uint8_t *bv);

@@ -8,7 +8,10 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <cmath>
 #include <initializer_list>
+#include <utility>
 #include <vector>
 
 #include "../../include/pmp.h"
@@ -371,6 +374,52 @@ inline const char *gate_refused(int64_t count, bool backward, const float *x, co
         outs.push_back({o1, bytes});
     }
     return spans_refused(ins, outs, true);
+}
+
+// ---- a step's ends (pmp_batch_gather_device, pmp_adam_step_device)
+inline const char *gather_refused(const pmp_batch_src *src, const int64_t *index, int64_t n, const pmp_batch_dst *dst, const int32_t *status)
+{
+    if (!src || !dst || !index || !status) return "null src, dst, d_index or d_status";
+    if (src->count < 1) return "count must be >= 1";
+    if (n < 1 || n > PMP_BATCH_MAX) return "n must be in 1 .. 65536";
+    if (!src->y || (src->u != nullptr) != (src->v != nullptr)) return "y is required, u and v go together";
+    if (!dst->x && !dst->qt_f && !dst->qt8 && !dst->msbt && !dst->msdire) return "no output asked for";
+    if (((dst->qt_f || dst->qt8) && !src->qt8) || (dst->msbt && !src->msbt) || (dst->msdire && !src->msdire))
+        return "an output whose source is NULL";
+    const size_t N = (size_t)src->count, rows = (size_t)n, xrow = src->u ? 3468 * 4 : 4624 * 4;
+    const std::vector<Span> ins = {{src->y, N * 4624},         {src->u, N * 1156, true},      {src->v, N * 1156, true}, {src->qt8, N * 64, true},
+                                   {src->msbt, N * 768, true}, {src->msdire, N * 768, true}, {index, rows * 8, false, 8}};
+    const std::vector<Span> outs = {{dst->x, rows * xrow, true},    {dst->qt_f, rows * 256, true},   {dst->qt8, rows * 64, true},
+                                    {dst->msbt, rows * 768, true}, {dst->msdire, rows * 768, true}, {status, 4}};
+    if (const char *why = spans_refused(ins, outs, false)) return why;
+    for (const std::vector<Span> *v : {&ins, &outs})
+        for (const Span &t : *v)
+            if ((uintptr_t)t.p & (t.align - 1)) return "every pointer must be 4-byte aligned, d_index 8-byte";
+    return nullptr;
+}
+
+inline const char *adam_refused(const pmp_adam_params *p, int ntensors, float *const *param, const float *const *grad, float *const *m,
+                                float *const *v, const int64_t *count, int64_t step)
+{
+    if (!p || !param || !grad || !m || !v || !count) return "null params or array";
+    if (ntensors < 1) return "ntensors must be >= 1";
+    if (step < 1) return "step must be >= 1";
+    if (!std::isfinite(p->lr) || !std::isfinite(p->beta1) || !std::isfinite(p->beta2) || !std::isfinite(p->eps)) return "lr, beta1, beta2 and eps must be finite";
+    if (p->beta1 < 0 || p->beta1 >= 1 || p->beta2 < 0 || p->beta2 >= 1) return "beta1 and beta2 must be in [0, 1)";
+    if (p->eps <= 0) return "eps must be > 0";
+    std::vector<std::pair<uintptr_t, uintptr_t>> at;        // [first byte, behind the last) of all 4 ntensors tensors
+    for (int i = 0; i < ntensors; ++i) {
+        if (count[i] < 1) return "every count must be >= 1";
+        for (const float *t : {(const float *)param[i], grad[i], (const float *)m[i], (const float *)v[i]}) {
+            if (!t) return "null tensor";
+            if ((uintptr_t)t & 3) return "every tensor must be 4-byte aligned";
+            at.push_back({(uintptr_t)t, (uintptr_t)t + (uintptr_t)count[i] * 4});
+        }
+    }
+    std::sort(at.begin(), at.end());
+    for (size_t i = 1; i < at.size(); ++i)
+        if (at[i].first < at[i - 1].second) return "two tensors of the call overlap";
+    return nullptr;
 }
 
 }  // namespace pmp

@@ -486,6 +486,61 @@ int main()
         expect(is(bw(1024, g_y, acc, o, o), "two output tensors overlap") && is(bw(1024, g_y, acc, o + 512, o), "two output tensors overlap"), "g_a over g_x");
         expect(says(bw(1024, g_y, off(acc, 2), o, o2), "aligned"), "misaligned g_acc");
     }
+    {   // a step's ends: the gather's set of 7 blocks and batch of 5 rows, Adam's three tensors; host arrays stand in for device memory
+        static uint8_t set[7 * 4624 + 2 * 7 * 1156 + 7 * 64 + 2 * 7 * 768 + 64] __attribute__((aligned(16)));
+        static float out[5 * 4624 + 5 * 64 + 64] __attribute__((aligned(16)));
+        static uint8_t lab[5 * 64 + 2 * 5 * 768 + 64] __attribute__((aligned(16)));
+        static int64_t index[5];
+        static int32_t status;
+        const pmp_batch_src luma{set, nullptr, nullptr, set + 7 * 4624 + 14 * 1156, set + 7 * 4624 + 14 * 1156 + 7 * 64,
+                                 (const int8_t *)(set + 7 * 4624 + 14 * 1156 + 7 * 64 + 7 * 768), 7};
+        pmp_batch_src chroma = luma;
+        chroma.u = set + 7 * 4624; chroma.v = set + 7 * 4624 + 7 * 1156;
+        const pmp_batch_dst all{out, out + 5 * 4624, lab, lab + 5 * 64, (int8_t *)(lab + 5 * 64 + 5 * 768)};
+        auto gr = [&](const pmp_batch_src &s, const pmp_batch_dst &d, int64_t n = 5) { return gather_refused(&s, index, n, &d, &status); };
+        expect(!gr(luma, all) && !gr(chroma, all) && !gr(luma, pmp_batch_dst{out, nullptr, nullptr, nullptr, nullptr}), "accepted gather calls");
+        expect(gather_refused(nullptr, index, 5, &all, &status) && gather_refused(&luma, nullptr, 5, &all, &status) &&
+               gather_refused(&luma, index, 5, nullptr, &status) && gather_refused(&luma, index, 5, &all, nullptr), "the gather's null arguments");
+        expect(says(gr(luma, all, 0), "n must be") && says(gr(luma, all, 65537), "n must be"), "the gather's n");
+        pmp_batch_src s = luma; s.count = 0; expect(says(gr(s, all), "count"), "an empty set");
+        s = luma; s.y = nullptr; expect(says(gr(s, all), "y is required"), "no y");
+        s = chroma; s.v = nullptr; expect(says(gr(s, all), "go together"), "u without v");
+        s = luma; s.msbt = nullptr; expect(says(gr(s, all), "source is NULL"), "msbt without its source");
+        s = luma; s.qt8 = nullptr; expect(says(gr(s, pmp_batch_dst{nullptr, out, nullptr, nullptr, nullptr}), "source is NULL"), "qt_f without its source");
+        expect(says(gr(luma, pmp_batch_dst{}), "no output"), "no output asked for");
+        s = luma; s.y = set + 2; expect(says(gr(s, all), "aligned"), "a source two bytes off");
+        pmp_batch_dst d = all; d.qt_f = out + 16; expect(is(gr(luma, d), "two output tensors overlap"), "qt_f inside x");
+        d = all; d.qt8 = (uint8_t *)index; expect(is(gr(luma, d), "an output tensor overlaps an input"), "an output over the index");
+        d = all; d.qt8 = (uint8_t *)&status; expect(is(gr(luma, d), "two output tensors overlap"), "an output over the status word");
+        d = all; d.msbt = const_cast<uint8_t *>(luma.msbt); expect(is(gr(luma, d), "an output tensor overlaps an input"), "an output over the set");
+
+        static float t[12][300];
+        float *p[3] = {t[0], t[1], t[2]}, *m[3] = {t[6], t[7], t[8]}, *v[3] = {t[9], t[10], t[11]};
+        const float *g[3] = {t[3], t[4], t[5]};
+        int64_t count[3] = {5, 64, 257};
+        pmp_adam_params hp{1e-3, 0.9, 0.999, 1e-8};
+        auto ar = [&](int nt = 3, int64_t step = 1) { return adam_refused(&hp, nt, p, g, m, v, count, step); };
+        expect(!ar() && !ar(1) && !ar(3, (int64_t)1 << 40), "accepted Adam calls");
+        expect(says(ar(0), "ntensors") && says(ar(-1), "ntensors") && says(ar(3, 0), "step") && says(ar(3, -1), "step"), "Adam's ntensors and step");
+        expect(adam_refused(nullptr, 3, p, g, m, v, count, 1) && adam_refused(&hp, 3, nullptr, g, m, v, count, 1) && adam_refused(&hp, 3, p, nullptr, m, v, count, 1) &&
+               adam_refused(&hp, 3, p, g, nullptr, v, count, 1) && adam_refused(&hp, 3, p, g, m, nullptr, count, 1) && adam_refused(&hp, 3, p, g, m, v, nullptr, 1), "Adam's null arguments");
+        for (double *f : {&hp.lr, &hp.beta1, &hp.beta2, &hp.eps})
+            for (double bad : {(double)NAN, (double)INFINITY}) {
+                const double keep = *f;
+                *f = bad; expect(says(ar(), "finite"), "a hyperparameter that is not finite");
+                *f = keep;
+            }
+        hp.beta1 = 1.0; expect(says(ar(), "[0, 1)"), "beta1 1"); hp.beta1 = -0.1; expect(says(ar(), "[0, 1)"), "beta1 negative"); hp.beta1 = 0.0; expect(!ar(), "beta1 0"); hp.beta1 = 0.9;
+        hp.beta2 = 1.0; expect(says(ar(), "[0, 1)"), "beta2 1"); hp.beta2 = 0.999;
+        hp.eps = 0.0; expect(says(ar(), "eps"), "eps 0"); hp.eps = -1e-8; expect(says(ar(), "eps"), "eps negative"); hp.eps = 1e-8;
+        count[1] = 0; expect(says(ar(), "count"), "count 0"); count[1] = 64;
+        m[1] = nullptr; expect(is(ar(), "null tensor"), "a null entry"); m[1] = t[7];
+        v[0] = off(t[9], 2); expect(says(ar(), "aligned"), "a tensor two bytes off"); v[0] = t[9];
+        m[1] = t[0]; expect(says(ar(), "overlap"), "m over a param"); m[1] = t[7];
+        g[2] = t[0] + 2; expect(says(ar(), "overlap"), "a gradient inside a param"); g[2] = t[5];
+        p[1] = t[0]; expect(says(ar(), "overlap"), "the same param twice"); p[1] = t[1];
+        v[2] = t[10] + 43; expect(says(ar(), "overlap"), "v over the end of another v"); v[2] = t[10] + 64; expect(!ar(), "tensors that touch"); v[2] = t[11];
+    }
     if (!failures) printf("train_check: ok\n");
     return failures ? 1 : 0;
 }

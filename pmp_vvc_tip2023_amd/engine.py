@@ -530,6 +530,22 @@ class Engine:
         """pmp_gate_backward_device: g_a = g_y * x, g_x = g_y * a, or d_g_acc + g_y * a when d_g_acc is given."""
         self._ck(self.lib.pmp_gate_backward_device(self.h, int(count), d_x, d_a, d_g_y, d_g_acc, d_g_x, d_g_a))
 
+    # ------------------------------------------------------------------------------------------ a training step's ends
+    def batch_gather_device(self, src, d_index, n, d_status, d_x=None, d_qt_f=None, d_qt8=None, d_msbt=None, d_msdire=None):
+        """pmp_batch_gather_device: src a _lib.BatchSrc (the whole set on the device), d_index i64[n], the outputs asked for (None: not),
+        d_status an int32 word the caller zeroed; stream-ordered on the engine's stream, the host does not wait."""
+        dst = _lib.BatchDst(d_x, d_qt_f, d_qt8, d_msbt, d_msdire)
+        self._ck(self.lib.pmp_batch_gather_device(self.h, C.byref(src), d_index, int(n), C.byref(dst), d_status))
+
+    def adam_step_device(self, d_param, d_grad, d_m, d_v, counts, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+        """pmp_adam_step_device: lists of device pointers and of element counts, one entry per tensor; step >= 1 is the step this call
+        performs (torch.optim.Adam, no weight decay, no amsgrad); one launch, stream-ordered, the host does not wait."""
+        nt = len(counts)
+        p = _lib.AdamParams(float(lr), float(betas[0]), float(betas[1]), float(eps))
+        self._ck(self.lib.pmp_adam_step_device(self.h, C.byref(p), nt, _lib.pointer_array(d_param, nt), _lib.pointer_array(d_grad, nt),
+                                               _lib.pointer_array(d_m, nt), _lib.pointer_array(d_v, nt), (C.c_int64 * nt)(*[int(k) for k in counts]),
+                                               int(step)))
+
     def infer_msbd(self, comp, qp, qt_in, block_y, block_u=None, block_v=None):
         """Teacher-forced MTT inference (pmp_infer_msbd; Net(input_batch, qt_label_batch), Metrics.py:226): the MTT net of (comp, qp) on
         the blocks with the GIVEN QT map qt_in f32[N,(1,)8,8] -> bt f32[N,3,16,16], dire f32[N,3,16,16]."""

@@ -71,8 +71,15 @@ def plan(args):
     if args.perBlock is not None and not os.path.isdir(os.path.dirname(os.path.abspath(args.perBlock))):
         fail("--perBlock: directory of %s does not exist" % args.perBlock)
 
+    return read_set(args.dataDir, args.dataType, args.comp, args.qp, args.mode != "q", fail)
+
+
+def read_set(data_dir, data_type, comp, qp, with_mtt_labels, fail):
+    """Opens (memory-mapped) and checks the files of one set of the reference's layout (the module's docstring) -> {"blocks": y or
+    (y, u, v), "qt8", "msbt", "msdire" (None without with_mtt_labels), "n"}.  fail(message) is called on the first missing file, wrong
+    dtype, wrong shape or mismatched count, and must not return.  Shared by validate, dataset.DeviceDataset and train_qbd."""
     def read(name, dtype, tail):
-        path = os.path.join(args.dataDir, name)
+        path = os.path.join(data_dir, name)
         if not os.path.isfile(path):
             fail("%s not found" % path)
         try:
@@ -82,17 +89,17 @@ def plan(args):
         if a.dtype != dtype or a.ndim != len(tail) + 1 or a.shape[1:] != tail:
             fail("%s: expected %s[n,%s], got %s%s" % (path, np.dtype(dtype).name, ",".join(map(str, tail)), a.dtype.name, list(a.shape)))
         return a
-    stem = "%s_%s_QP%d_" % (args.dataType, args.comp, args.qp)
+    stem = "%s_%s_QP%d_" % (data_type, comp, qp)
     out = {"qt8": read(stem + "QTdepth_Block8.npy", np.uint8, (8, 8)), "msbt": None, "msdire": None}
     n = out["qt8"].shape[0]
-    if args.mode != "q":
+    if with_mtt_labels:
         out["msbt"] = read(stem + "MSBTdepth_Block16.npy", np.uint8, (3, 16, 16))
         out["msdire"] = read(stem + "MSdirection_Block16.npy", np.int8, (3, 16, 16))
-    y = read(args.dataType + "_Y_Block68.npy", np.uint8, (68, 68))
+    y = read(data_type + "_Y_Block68.npy", np.uint8, (68, 68))
     arrays = [("labels", out["msbt"]), ("labels", out["msdire"]), ("blocks", y)]
-    if args.comp == "Chroma":
-        u = read(args.dataType + "_U_Block34.npy", np.uint8, (34, 34))
-        v = read(args.dataType + "_V_Block34.npy", np.uint8, (34, 34))
+    if comp == "Chroma":
+        u = read(data_type + "_U_Block34.npy", np.uint8, (34, 34))
+        v = read(data_type + "_V_Block34.npy", np.uint8, (34, 34))
         arrays += [("blocks", u), ("blocks", v)]
         out["blocks"] = (y, u, v)
     else:
