@@ -782,6 +782,42 @@ int pmp_batch_gather_device(pmp_ctx *ctx, const pmp_batch_src *src, const int64_
 int pmp_adam_step_device(pmp_ctx *ctx, const pmp_adam_params *p, int ntensors, float *const *param, const float *const *grad,
                          float *const *m, float *const *v, const int64_t *count, int64_t step);
 
+/* ---- DATA SET ASSEMBLY: a training set put together on the device (dataset.hip; python -m pmp_vvc_tip2023_amd.make_dataset).  Behind
+ *      pmp_cut_blocks_device and pmp_msbt_labels_device every array of a set is on the device, row i of each belonging to block i.  The
+ *      rows the set keeps are chosen ONCE, as one index, and every array is gathered by that index: blocks and labels cannot disagree.
+ *
+ *      pmp_select_rows_device.  d_flags: a HOST array of nflags device pointers, each u8[n] (the status arrays of pmp_msbt_labels, one
+ *      per (component, QP)).  Row i is a CANDIDATE iff (d_flags[k][i] & mask) == 0 for every k; nflags = 0 (d_flags may be NULL then)
+ *      makes every row one.  d_seg_end i64[nseg] cuts the rows into segments, one sequence each: segment s is rows
+ *      [d_seg_end[s-1], d_seg_end[s]) (from 0 for s = 0); ascending, the last entry n, empty segments allowed.  A candidate is KEPT iff
+ *      cap == 0 or fewer than cap candidates precede it in its segment.
+ *        d_index i64[n]        [0, m) the kept rows in ascending order, [m, n) = -1; every element is written
+ *        d_count i64[nseg+1]   [s] the rows kept of segment s, [nseg] = m
+ *      The entries of d_seg_end live on the device and are not looked at by the host: an entry is used as clamped into 0..n and never
+ *      below an earlier one, and the last as n, so no entry, whatever it holds, makes an access leave the arrays (d_count then counts
+ *      the segments so clamped).
+ *      LIMITS: n in 1..2^30, nseg in 1..65536, nflags in 0..PMP_SELECT_MAX_FLAGS, mask in 1..255, cap >= 0.  d_seg_end, d_index and
+ *      d_count 8-byte aligned.
+ *      ORDER: a prefix sum of fixed shape (candidates per 1024 rows, one workgroup's scan of those counts, a scatter) - no atomics, no
+ *      workgroup waits for another: the same bits on every run, stream and context.  Scratch of n/256 + 12 nseg bytes is the context's.
+ *
+ *      pmp_gather_rows_device.  Row j of d_dst is row d_index[j] of d_src (nsrc rows), row_bytes bytes each, for j in [0, m); a row may
+ *      repeat.  An index outside [0, nsrc) - the -1 tail of d_index included - is never dereferenced: its row is written as zeros and bit
+ *      0 of *d_status is set with an atomic OR, the call's only atomic; nothing else writes *d_status (the caller zeroes it once).
+ *      LIMITS: row_bytes a multiple of 4 in 4..65536 (a set's rows: 64, 256, 768, 1156, 4624), m in 1..2^30, nsrc >= 1.  d_src, d_dst
+ *      and d_status 4-byte aligned, d_index 8-byte; no more is assumed, and 16-byte accesses are used only where d_src, d_dst and
+ *      row_bytes are all multiples of 16.
+ *
+ *      BOTH: PMP_E_INVALID before any launch, nothing written, with a message in pmp_last_error: a NULL pointer (d_flags with nflags > 0,
+ *      or one of its entries, included), a limit broken, a pointer not aligned as above, an output that overlaps an input or the other
+ *      output.  Stream-ordered on the context's stream, the host does not wait; like the training calls they first SETTLE the context's
+ *      calls in flight. ---- */
+#define PMP_SELECT_MAX_FLAGS 64
+int pmp_select_rows_device(pmp_ctx *ctx, const uint8_t *const *d_flags, int nflags, int mask, const int64_t *d_seg_end, int nseg,
+                           int64_t cap, int64_t n, int64_t *d_index, int64_t *d_count);
+int pmp_gather_rows_device(pmp_ctx *ctx, const void *d_src, int64_t nsrc, int64_t row_bytes, const int64_t *d_index, int64_t m,
+                           void *d_dst, int32_t *d_status);
+
 /* ---- teacher-forced MTT inference: the MTT net of (comp, qp) on the blocks with a GIVEN QT map instead of the QT net's output, what
  *      pre_validation predID 1 runs (Net(input_batch, qt_label_batch), Metrics.py:226).  qt_in f32[n][8][8] is read, never written
  *      (for the reference's validation: float(qt8 - 1) with the u8 wrap above).  Everything else is pmp_infer's: the context's datapath,

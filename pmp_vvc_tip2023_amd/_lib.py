@@ -111,6 +111,7 @@ class AdamParams(C.Structure):
 
 PMP_BATCH_MAX = 65536
 PMP_ADAM_TABLE = 96
+PMP_SELECT_MAX_FLAGS = 64
 
 
 def pointer_array(ptrs, count):
@@ -191,6 +192,8 @@ SIGNATURES = {
     "pmp_gate_backward_device": (_I, [_VP, _I64] + [_VP] * 6),
     "pmp_batch_gather_device": (_I, [_VP, C.POINTER(BatchSrc), _VP, _I64, C.POINTER(BatchDst), _VP]),
     "pmp_adam_step_device": (_I, [_VP, C.POINTER(AdamParams), _I, _VP, _VP, _VP, _VP, C.POINTER(_I64), _I64]),
+    "pmp_select_rows_device": (_I, [_VP, _VP, _I, _I, _VP, _I, _I64, _I64, _VP, _VP]),
+    "pmp_gather_rows_device": (_I, [_VP, _VP, _I64, _I64, _VP, _I64, _VP, _VP]),
     "pmp_infer_msbd": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
     "pmp_infer_msbd_device": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
     "pmp_read_depth_dump": (_I, [C.c_char_p, _I, _I, _I, _I, _VP, _VP, _VP, C.POINTER(_I64)]),

@@ -256,7 +256,8 @@ struct pmp_ctx {
     pmp::DevBuf d_train[3];                // staging of pmp_train_loss's gradients: g_qt, g_bt, g_dire (its inputs go through d_val)
     pmp::DevBuf d_trainpart;               // training losses: per-block partials f64[n][13]
     pmp::DevBuf d_trainout;                // pmp_train_loss: f64[passes][13]
-    pmp::DevBuf d_rb[11];                  // staging of pmp_resblock_forward / _backward: the inputs in RbCall's order (train_check.h), then the outputs
+    pmp::DevBuf d_select;                  // pmp_select_rows_device: tile counts and segment tables (dataset.hip)
+    pmp::DevBuf d_rb[11];                 // staging of pmp_resblock_forward / _backward: the inputs in RbCall's order (train_check.h), then the outputs
     // calibration of the f16x3 activation scales (NetWeights::act_exp): in a Pass with `cal`, the graph (nets.cpp, running on the fp32
     // datapath) folds the largest |value| of every tensor it produces into d_cal[slot] and logs (name, segment) per slot
     pmp::DevWords d_cal;                   // PMP_CAL_SLOTS device words

@@ -334,6 +334,17 @@ struct AdamTable {
 };
 hipError_t launch_adam_step(hipStream_t s, AdamTable &t, int nt, const AdamConsts &k);
 
+// ------------------------------------------------------------------------------------------------ data set assembly (dataset.hip)
+// pmp_select_rows_device: the flag arrays travel in the kernel's argument block.  scratch: select_scratch_words(n, nseg) 32-bit words,
+// every one written before it is read.  n in 1..2^30, nseg in 1..65536, nflags in 0..PMP_SELECT_MAX_FLAGS, cap >= 0; five launches.
+constexpr int SELECT_TILE = 1024;
+struct SelectFlags { const uint8_t *p[PMP_SELECT_MAX_FLAGS]; };
+size_t select_scratch_words(int64_t n, int nseg);
+hipError_t launch_select_rows(hipStream_t s, const SelectFlags &f, int nflags, int mask, const int64_t *seg_end, int nseg, int64_t cap, int64_t n,
+                              uint32_t *scratch, int64_t *index, int64_t *count);
+// pmp_gather_rows_device: src, dst 4-byte aligned, row_bytes a multiple of 4 in 4..65536, m in 1..2^30, nsrc >= 1
+hipError_t launch_gather_rows(hipStream_t s, const void *src, int64_t nsrc, int64_t row_bytes, const int64_t *index, int64_t m, void *dst, int32_t *status);
+
 // Block cutter (Inference_QBD.py:104-149).
 hipError_t launch_cut_blocks(hipStream_t s, const void *y, const void *u, const void *v, int F, int H, int W,
                              int bitdepth, uint8_t *by, uint8_t *bu, uint8_t *bv);

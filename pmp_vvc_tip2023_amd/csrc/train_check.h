@@ -2,11 +2,13 @@
 // the shape rules, a chain's blocks and its d_saved layout (SavedLayout: a trunk's and a QT tail's), a stem's and a head's sizes, the
 // rules on a call's tensors, and per call family ONE function that states everything the call is refused for (rb_refused,
 // chain_refused, stem_refused, head_refused, gate_refused): which tensors the call has, which are optional, which need 16 bytes.
+// Likewise a step's ends (gather_refused, adam_refused) and data set assembly (api_dataset.cpp: select_refused, rows_gather_refused).
 // A single block is checked as the one-block trunk it is.  Pure host code without the HIP runtime, no pointer is dereferenced, so
 // that it also builds, with a main of its own, for the CPU under a sanitizer (train_check_main.cpp, `make traincheck`).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <algorithm>
 #include <cmath>
@@ -420,6 +422,40 @@ inline const char *adam_refused(const pmp_adam_params *p, int ntensors, float *c
     for (size_t i = 1; i < at.size(); ++i)
         if (at[i].first < at[i - 1].second) return "two tensors of the call overlap";
     return nullptr;
+}
+
+// ---- data set assembly (pmp_select_rows_device, pmp_gather_rows_device).  What d_seg_end holds is the device's to read, not the host's
+constexpr int64_t ROWS_MAX = (int64_t)1 << 30;
+
+// spans_refused with these calls' alignment rule in its message
+inline const char *rows_spans_refused(const std::vector<Span> &ins, const std::vector<Span> &outs)
+{
+    const char *why = spans_refused(ins, outs, true);
+    return why && strstr(why, "aligned") ? "d_seg_end, d_index and d_count must be 8-byte aligned, d_src, d_dst and d_status 4-byte" : why;
+}
+
+inline const char *select_refused(const uint8_t *const *flags, int nflags, int mask, const int64_t *seg_end, int nseg, int64_t cap, int64_t n,
+                                  const int64_t *index, const int64_t *count)
+{
+    if (n < 1 || n > ROWS_MAX) return "n must be in 1 .. 2^30";
+    if (nseg < 1 || nseg > 65536) return "nseg must be in 1 .. 65536";
+    if (nflags < 0 || nflags > PMP_SELECT_MAX_FLAGS) return "nflags must be in 0 .. 64";
+    if (mask < 1 || mask > 255) return "mask must be in 1 .. 255";
+    if (cap < 0) return "cap must be >= 0";
+    if (nflags > 0 && !flags) return "null d_flags";
+    std::vector<Span> ins = {{seg_end, (size_t)nseg * 8, false, 8}};
+    for (int k = 0; k < nflags; ++k) ins.push_back({flags[k], (size_t)n, false, 1});
+    return rows_spans_refused(ins, {{index, (size_t)n * 8, false, 8}, {count, ((size_t)nseg + 1) * 8, false, 8}});
+}
+
+inline const char *rows_gather_refused(const void *src, int64_t nsrc, int64_t row_bytes, const int64_t *index, int64_t m, const void *dst,
+                                       const int32_t *status)
+{
+    if (nsrc < 1) return "nsrc must be >= 1";
+    if (m < 1 || m > ROWS_MAX) return "m must be in 1 .. 2^30";
+    if (row_bytes < 4 || row_bytes > 65536 || (row_bytes & 3)) return "row_bytes must be a multiple of 4 in 4 .. 65536";
+    return rows_spans_refused({{src, (size_t)nsrc * (size_t)row_bytes}, {index, (size_t)m * 8, false, 8}},
+                              {{dst, (size_t)m * (size_t)row_bytes}, {status, 4}});
 }
 
 }  // namespace pmp

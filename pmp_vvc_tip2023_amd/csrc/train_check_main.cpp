@@ -3,7 +3,8 @@
 // spans that overlap, are missing or are misaligned, a stem's shapes, sizes and pointer arrays (tests/test_gpu_stem_grad.py), a
 // head's shapes, sizes and the tensors tied to its attention input (tests/test_gpu_head_grad.py), a QT tail's (tests/
 // test_gpu_qtail_grad.py), and the pointer-level rows of those matrices through the functions the entry points call: chain_refused,
-// rb_refused, stem_refused, head_refused and gate_refused on fake addresses.  No pointer is dereferenced; exit status 0 and
+// rb_refused, stem_refused, head_refused and gate_refused on fake addresses, and those of data set assembly (tests/
+// test_gpu_dataset.py) through select_refused and rows_gather_refused.  No pointer is dereferenced; exit status 0 and
 // "train_check: ok" when all hold.
 #include <stdio.h>
 #include <string.h>
@@ -27,6 +28,12 @@ static const char *weights_refused(const pmp_trunk_shape &s, const float *const 
 {
     return weights_refused(chain_of(&s).blocks, s.nblocks, w, g_w, backward, ins, outs);
 }
+
+// the arrays of the data set assembly calls below stand at file scope: they are the default arguments of its lambdas
+static uint8_t ds_flag[3][304] __attribute__((aligned(16)));
+static int64_t ds_seg[3], ds_index[300], ds_count[4];
+static uint8_t ds_src[300 * 68 + 16] __attribute__((aligned(16))), ds_dst[300 * 68 + 16] __attribute__((aligned(16)));
+static int32_t ds_status;
 
 int main()
 {
@@ -540,6 +547,52 @@ int main()
         g[2] = t[0] + 2; expect(says(ar(), "overlap"), "a gradient inside a param"); g[2] = t[5];
         p[1] = t[0]; expect(says(ar(), "overlap"), "the same param twice"); p[1] = t[1];
         v[2] = t[10] + 43; expect(says(ar(), "overlap"), "v over the end of another v"); v[2] = t[10] + 64; expect(!ar(), "tensors that touch"); v[2] = t[11];
+    }
+    {   // data set assembly: the matrix of tests/test_gpu_dataset.py through select_refused and rows_gather_refused; 300 rows in 3 segments
+        auto sh = [](auto *p, long bytes) { return reinterpret_cast<decltype(p)>(reinterpret_cast<uintptr_t>(p) + bytes); };
+        const uint8_t *fl[3] = {ds_flag[0], ds_flag[1], ds_flag[2]};
+        auto sr = [&](const uint8_t *const *f = nullptr, int nflags = 3, int mask = 5, const int64_t *se = ds_seg, int nseg = 3, int64_t cap = 0,
+                      int64_t n = 300, const int64_t *ix = ds_index, const int64_t *ct = ds_count) {
+            return select_refused(f ? f : fl, nflags, mask, se, nseg, cap, n, ix, ct);
+        };
+        expect(!sr() && !sr(fl, 0) && !select_refused(nullptr, 0, 5, ds_seg, 3, 0, 300, ds_index, ds_count) && !sr(fl, 3, 255, ds_seg, 3, 7) && !sr(fl, 1, 1, ds_seg, 1),
+               "accepted select calls");
+        expect(says(sr(fl, 3, 5, ds_seg, 3, 0, 0), "n must be") && says(sr(fl, 3, 5, ds_seg, 3, 0, -1), "n must be") &&
+                   says(sr(fl, 3, 5, ds_seg, 3, 0, ((int64_t)1 << 30) + 1), "n must be"), "select's n");
+        expect(says(sr(fl, 3, 5, ds_seg, 0), "nseg") && says(sr(fl, 3, 5, ds_seg, 65537), "nseg"), "select's nseg");
+        expect(says(sr(fl, -1), "nflags") && says(sr(fl, 65), "nflags"), "select's nflags");
+        expect(says(sr(fl, 3, 0), "mask") && says(sr(fl, 3, 256), "mask") && says(sr(fl, 3, -1), "mask"), "select's mask");
+        expect(says(sr(fl, 3, 5, ds_seg, 3, -1), "cap"), "a negative cap");
+        expect(says(select_refused(nullptr, 1, 5, ds_seg, 3, 0, 300, ds_index, ds_count), "null d_flags"), "flags asked for, no array");
+        { const uint8_t *g[3] = {ds_flag[0], nullptr, ds_flag[2]}; expect(is(sr(g), "null tensor"), "a null flag array"); }
+        expect(is(sr(fl, 3, 5, nullptr), "null tensor") && is(sr(fl, 3, 5, ds_seg, 3, 0, 300, nullptr), "null tensor") &&
+                   is(sr(fl, 3, 5, ds_seg, 3, 0, 300, ds_index, nullptr), "null tensor"), "select's null pointers");
+        expect(says(sr(fl, 3, 5, sh(ds_seg, 4)), "aligned") && says(sr(fl, 3, 5, ds_seg, 3, 0, 296, sh(ds_index, 4)), "aligned") &&
+                   says(sr(fl, 3, 5, ds_seg, 3, 0, 300, ds_index, sh(ds_count, 4)), "aligned"), "select's alignment");
+        { const uint8_t *g[3] = {ds_flag[0], sh(ds_flag[1], 1), sh(ds_flag[2], 3)}; expect(!sr(g), "flag arrays need no alignment"); }
+        { const uint8_t *g[3] = {ds_flag[0], (const uint8_t *)ds_index + 2392, ds_flag[2]}; expect(is(sr(g), "an output tensor overlaps an input"), "the index over the end of a flag array"); }
+        expect(is(sr(fl, 3, 5, ds_index + 299), "an output tensor overlaps an input") && is(sr(fl, 3, 5, ds_seg, 3, 0, 300, ds_index, ds_seg), "an output tensor overlaps an input"),
+               "an output over d_seg_end");
+        expect(is(sr(fl, 3, 5, ds_seg, 3, 0, 300, ds_index, ds_index + 299), "two output tensors overlap") && !sr(fl, 3, 5, ds_seg, 3, 0, 296, ds_index, ds_index + 296),
+               "d_count over the end of d_index; right behind it");
+
+        auto gr = [&](const void *s = ds_src, int64_t nsrc = 300, int64_t rb = 68, const int64_t *ix = ds_index, int64_t m = 300, const void *d = ds_dst,
+                      const int32_t *st = &ds_status) { return rows_gather_refused(s, nsrc, rb, ix, m, d, st); };
+        expect(!gr() && !gr(ds_src + 4, 300, 68, ds_index, 300, ds_dst + 4) && !gr(ds_src, 1, 4, ds_index, 1) && !gr(ds_src, 1, 65536 / 4, ds_index, 1, ds_dst) && !gr(ds_src, 5100, 4, ds_index, 300),
+               "accepted gather calls");
+        expect(says(gr(ds_src, 0), "nsrc") && says(gr(ds_src, -3), "nsrc"), "an empty source");
+        expect(says(gr(ds_src, 300, 68, ds_index, 0), "m must be") && says(gr(ds_src, 300, 68, ds_index, ((int64_t)1 << 30) + 1), "m must be"), "the gather's m");
+        for (int64_t rb : {(int64_t)0, (int64_t)-4, (int64_t)2, (int64_t)66, (int64_t)65540, (int64_t)1 << 33})
+            expect(says(gr(ds_src, 300, rb), "row_bytes"), "row_bytes");
+        expect(is(gr(nullptr), "null tensor") && is(gr(ds_src, 300, 68, nullptr), "null tensor") && is(gr(ds_src, 300, 68, ds_index, 300, nullptr), "null tensor") &&
+                   is(gr(ds_src, 300, 68, ds_index, 300, ds_dst, nullptr), "null tensor"), "the gather's null pointers");
+        expect(says(gr(ds_src + 2), "aligned") && says(gr(ds_src, 300, 68, ds_index, 300, ds_dst + 1), "aligned") && says(gr(ds_src, 300, 68, sh(ds_index, 4), 299), "aligned") &&
+                   says(gr(ds_src, 300, 68, ds_index, 300, ds_dst, sh(&ds_status, 2)), "aligned"), "the gather's alignment");
+        expect(is(gr(ds_src, 300, 68, ds_index, 300, ds_src), "an output tensor overlaps an input") && is(gr(ds_src, 300, 68, ds_index, 300, ds_src + 300 * 68 - 4), "an output tensor overlaps an input") &&
+                   !gr(ds_src, 200, 68, ds_index, 100, ds_src + 200 * 68), "the rows over the source; right behind it");
+        expect(is(gr(ds_src, 300, 68, ds_index, 300, ds_index), "an output tensor overlaps an input") && is(gr(ds_src, 300, 68, ds_index, 300, ds_dst, (const int32_t *)(ds_index + 7)), "an output tensor overlaps an input") &&
+                   is(gr(ds_src, 300, 68, ds_index, 300, ds_dst, (const int32_t *)(ds_src + 64)), "an output tensor overlaps an input"), "an output over the index; the status word over an input");
+        expect(is(gr(ds_src, 300, 68, ds_index, 300, ds_dst, (const int32_t *)(ds_dst + 128)), "two output tensors overlap"), "the status word inside the rows");
     }
     if (!failures) printf("train_check: ok\n");
     return failures ? 1 : 0;

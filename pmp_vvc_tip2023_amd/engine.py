@@ -546,6 +546,62 @@ class Engine:
                                                _lib.pointer_array(d_m, nt), _lib.pointer_array(d_v, nt), (C.c_int64 * nt)(*[int(k) for k in counts]),
                                                int(step)))
 
+    # ------------------------------------------------------------------------------------------ data set assembly
+    def select_rows_device(self, d_flags, mask, d_seg_end, nseg, cap, n, d_index, d_count):
+        """pmp_select_rows_device: d_flags a list of device pointers to u8[n] (empty: every row is a candidate), d_seg_end i64[nseg],
+        d_index i64[n] and d_count i64[nseg + 1] out; stream-ordered on the engine's stream, the host does not wait."""
+        d_flags = list(d_flags or ())
+        self._ck(self.lib.pmp_select_rows_device(self.h, _lib.pointer_array(d_flags, len(d_flags)) if d_flags else None, len(d_flags), int(mask),
+                                                 d_seg_end, int(nseg), int(cap), int(n), d_index, d_count))
+
+    def gather_rows_device(self, d_src, nsrc, row_bytes, d_index, m, d_dst, d_status):
+        """pmp_gather_rows_device: row j of d_dst = row d_index[j] of d_src, row_bytes bytes each; d_status an int32 word the caller
+        zeroed (bit 0: an index outside the source, its row zeros); stream-ordered, the host does not wait."""
+        self._ck(self.lib.pmp_gather_rows_device(self.h, d_src, int(nsrc), int(row_bytes), d_index, int(m), d_dst, d_status))
+
+    def select_rows(self, flags, mask, seg_end, cap=0, n=None):
+        """The host form of select_rows_device: flags a list of u8[n] arrays (empty: give n), seg_end the segments' ends (ascending,
+        the last one n) -> (index i64[m], the kept rows in ascending order; counts i64[nseg + 1], per segment and, last, m)."""
+        import torch
+        flags = [np.ascontiguousarray(f, np.uint8).reshape(-1) for f in flags]
+        seg_end = np.ascontiguousarray(seg_end, np.int64).reshape(-1)
+        n = int(n) if n is not None else (flags[0].size if flags else int(seg_end[-1]))
+        if any(f.size != n for f in flags):
+            raise ValueError("select_rows: every flag array must have n = %d entries" % n)
+        dev = torch.device("cuda", int(self.device))
+        d_flags = [torch.from_numpy(f).to(dev) for f in flags]
+        d_seg = torch.from_numpy(seg_end).to(dev)
+        d_index = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        d_count = torch.empty(seg_end.size + 1, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)                       # the uploads ran on torch's stream; the context has its own
+        self.select_rows_device([t.data_ptr() for t in d_flags], mask, d_seg.data_ptr(), seg_end.size, cap, n, d_index.data_ptr(), d_count.data_ptr())
+        self.synchronize()
+        counts = d_count.cpu().numpy()
+        return d_index[:int(counts[-1])].cpu().numpy(), counts
+
+    def gather_rows(self, src, index):
+        """The host form of gather_rows_device: src[index] along the first axis (rows of a multiple of 4 bytes, at most 65536); an
+        index outside the array raises IndexError."""
+        import torch
+        src = np.ascontiguousarray(src)
+        index = np.ascontiguousarray(index, np.int64).reshape(-1)
+        row_bytes = src[0].nbytes if len(src) else 0
+        out = np.empty((index.size,) + src.shape[1:], src.dtype)
+        if index.size == 0:
+            return out
+        dev = torch.device("cuda", int(self.device))
+        d_src = torch.from_numpy(src.view(np.uint8).reshape(len(src), -1)).to(dev)
+        d_index = torch.from_numpy(index).to(dev)
+        d_dst = torch.empty((index.size, row_bytes), dtype=torch.uint8, device=dev)
+        d_status = torch.zeros(1, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.gather_rows_device(d_src.data_ptr(), len(src), row_bytes, d_index.data_ptr(), index.size, d_dst.data_ptr(), d_status.data_ptr())
+        self.synchronize()
+        if int(d_status.item()):
+            raise IndexError("gather_rows: an index lies outside the %d rows of the array" % len(src))
+        out.view(np.uint8).reshape(index.size, -1)[:] = d_dst.cpu().numpy()
+        return out
+
     def infer_msbd(self, comp, qp, qt_in, block_y, block_u=None, block_v=None):
         """Teacher-forced MTT inference (pmp_infer_msbd; Net(input_batch, qt_label_batch), Metrics.py:226): the MTT net of (comp, qp) on
         the blocks with the GIVEN QT map qt_in f32[N,(1,)8,8] -> bt f32[N,3,16,16], dire f32[N,3,16,16]."""
