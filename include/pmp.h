@@ -761,7 +761,32 @@ int pmp_qtail_unpack_device(pmp_ctx *ctx, const pmp_qtail_shape *shape, const vo
  *      PMP_E_INVALID before anything is launched or written, with a message in pmp_last_error: ntensors < 1; a NULL p or array; a NULL
  *      entry or one not 4-byte aligned; a count < 1; step < 1; lr, beta1, beta2 or eps not finite; a beta outside [0, 1); eps <= 0; two
  *      tensors of the call (any two of the 4*ntensors) overlapping in memory.
- *      ORDER: no atomics, no sums: the same bits on every run, stream and context.  Stream-ordered, settles first, as above. ---- */
+ *      ORDER: no atomics, no sums: the same bits on every run, stream and context.  Stream-ordered, settles first, as above.
+ *
+ *      GRADIENT BUCKETS, for data-parallel training whose result is defined bit for bit (grad_sync.py): every rank packs its gradients
+ *      into one bucket, the buckets are gathered, and every rank adds them IN RANK ORDER with a kernel of this library - not with an
+ *      all-reduce, whose order of additions belongs to the communication library.
+ *      pmp_grad_bucket_floats.  Host only, no context, no GPU.  The bucket of ntensors tensors of count[i] floats: the tensors in the
+ *      order given, tensor i at offset[i] floats, every offset a multiple of 4 (16 bytes), offset[0] = 0, offset[i+1] = offset[i] +
+ *      count[i] rounded up to a multiple of 4.  Returns the bucket's floats, a multiple of 4, and, where offset is not NULL, the
+ *      offsets; -1 for ntensors < 1, a NULL count, a count < 1 or a count >= 2^30.
+ *      pmp_grad_pack_device.  grad and count are HOST arrays [ntensors], as Adam's: device pointers (float32, 4-byte aligned) and element
+ *      counts.  d_bucket (16-byte aligned, pmp_grad_bucket_floats floats) receives tensor i at offset[i]; a NULL grad[i] stands for a
+ *      parameter without a gradient, whose slice is written as +0.0, and so are the padding floats: EVERY float of the bucket is
+ *      written.  The pointers travel in the kernel's argument block, PMP_ADAM_TABLE entries to a launch, in the fewest launches that
+ *      hold them; nothing is staged or allocated.  16-byte stores, 16-byte loads where a gradient's pointer allows them.
+ *      PMP_E_INVALID: a bad table (as above), a NULL array or bucket, a gradient not 4-byte or a bucket not 16-byte aligned, a gradient
+ *      that overlaps the bucket.
+ *      pmp_grad_sum_device.  d_src is a HOST array of nsrc in 1..PMP_GRAD_SUM_MAX device pointers, each to count floats; count >= 4 and
+ *      a multiple of 4, every pointer 16-byte aligned.  d_dst[i] = ((d_src[0][i] + d_src[1][i]) + d_src[2][i]) + ...: float32
+ *      additions, each rounded on its own, in the order of d_src; no atomics, nothing the compiler may reassociate (no fast-math flag in
+ *      this library's build).  nsrc = 1 is a copy, or nothing at all where d_dst == d_src[0].  d_dst may be EXACTLY d_src[0] (the
+ *      sum in place); otherwise it overlaps no source.  The sources may alias one another.  x + 0.0 is not x for x = -0.0: a caller
+ *      leaves out what it does not mean to add.  NaN and inf propagate as float32 addition propagates them.
+ *      PMP_E_INVALID: nsrc outside 1..64, a NULL array, entry or d_dst, count < 4 or no multiple of 4, a pointer not 16-byte aligned,
+ *      d_dst over a source other than as d_src[0] itself.
+ *      Both device calls: PMP_E_INVALID before any launch, with a message; stream-ordered on the context's stream, settle first; the
+ *      same bits on every run, stream and context. ---- */
 typedef struct pmp_batch_src {
     const uint8_t *y, *u, *v, *qt8, *msbt;
     const int8_t *msdire;
@@ -781,6 +806,10 @@ int pmp_batch_gather_device(pmp_ctx *ctx, const pmp_batch_src *src, const int64_
                             int32_t *d_status);
 int pmp_adam_step_device(pmp_ctx *ctx, const pmp_adam_params *p, int ntensors, float *const *param, const float *const *grad,
                          float *const *m, float *const *v, const int64_t *count, int64_t step);
+#define PMP_GRAD_SUM_MAX 64
+int64_t pmp_grad_bucket_floats(int ntensors, const int64_t *count, int64_t *offset /* [ntensors], may be NULL */);
+int pmp_grad_pack_device(pmp_ctx *ctx, int ntensors, const float *const *grad, const int64_t *count, float *d_bucket);
+int pmp_grad_sum_device(pmp_ctx *ctx, int nsrc, const float *const *d_src, int64_t count, float *d_dst);
 
 /* ---- DATA SET ASSEMBLY: a training set put together on the device (dataset.hip; python -m pmp_vvc_tip2023_amd.make_dataset).  Behind
  *      pmp_cut_blocks_device and pmp_msbt_labels_device every array of a set is on the device, row i of each belonging to block i.  The

@@ -112,6 +112,7 @@ class AdamParams(C.Structure):
 PMP_BATCH_MAX = 65536
 PMP_ADAM_TABLE = 96
 PMP_SELECT_MAX_FLAGS = 64
+PMP_GRAD_SUM_MAX = 64
 
 
 def pointer_array(ptrs, count):
@@ -192,6 +193,9 @@ SIGNATURES = {
     "pmp_gate_backward_device": (_I, [_VP, _I64] + [_VP] * 6),
     "pmp_batch_gather_device": (_I, [_VP, C.POINTER(BatchSrc), _VP, _I64, C.POINTER(BatchDst), _VP]),
     "pmp_adam_step_device": (_I, [_VP, C.POINTER(AdamParams), _I, _VP, _VP, _VP, _VP, C.POINTER(_I64), _I64]),
+    "pmp_grad_bucket_floats": (_I64, [_I, C.POINTER(_I64), C.POINTER(_I64)]),
+    "pmp_grad_pack_device": (_I, [_VP, _I, _VP, C.POINTER(_I64), _VP]),
+    "pmp_grad_sum_device": (_I, [_VP, _I, _VP, _I64, _VP]),
     "pmp_select_rows_device": (_I, [_VP, _VP, _I, _I, _VP, _I, _I64, _I64, _VP, _VP]),
     "pmp_gather_rows_device": (_I, [_VP, _VP, _I64, _I64, _VP, _I64, _VP, _VP]),
     "pmp_infer_msbd": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),

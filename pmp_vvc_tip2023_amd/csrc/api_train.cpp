@@ -445,9 +445,44 @@ int adam_run(pmp_ctx *c, const pmp_adam_params &p, int ntensors, float *const *p
     return flush();
 }
 
+// pmp_grad_pack_device: PMP_ADAM_TABLE tensors to a launch, in the order given
+int grad_pack_run(pmp_ctx *c, int ntensors, const float *const *grad, const int64_t *count, float *bucket)
+{
+    GradPackTable t;
+    int64_t at = 0;
+    for (int i = 0, nt = 0; i < ntensors; ++i) {
+        t.grad[nt] = grad[i]; t.at[nt] = at; t.count[nt] = (unsigned)count[i];
+        at += (count[i] + 3) & ~(int64_t)3;
+        if (++nt == PMP_ADAM_TABLE || i == ntensors - 1) {
+            const hipError_t e = launch_grad_pack(c->stream, t, nt, bucket);
+            if (e != hipSuccess) return hip_fail(c, e, "grad_pack");
+            nt = 0;
+        }
+    }
+    return PMP_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int64_t pmp_grad_bucket_floats(int ntensors, const int64_t *count, int64_t *offset) { return grad_bucket_floats(ntensors, count, offset); }
+
+int pmp_grad_pack_device(pmp_ctx *c, int ntensors, const float *const *grad, const int64_t *count, float *d_bucket)
+{
+    if (int rc = admit(c, "pmp_grad_pack_device", grad_pack_refused(ntensors, grad, count, d_bucket))) return rc;
+    return grad_pack_run(c, ntensors, grad, count, d_bucket);
+}
+
+int pmp_grad_sum_device(pmp_ctx *c, int nsrc, const float *const *d_src, int64_t count, float *d_dst)
+{
+    if (int rc = admit(c, "pmp_grad_sum_device", grad_sum_refused(nsrc, d_src, count, d_dst))) return rc;
+    if (nsrc == 1 && d_src[0] == d_dst) return PMP_OK;
+    GradSumTable t;
+    for (int j = 0; j < nsrc; ++j) t.src[j] = d_src[j];
+    const hipError_t e = launch_grad_sum(c->stream, t, nsrc, count / 4, d_dst);
+    return e == hipSuccess ? PMP_OK : hip_fail(c, e, "grad_sum");
+}
 
 int pmp_batch_gather_device(pmp_ctx *c, const pmp_batch_src *src, const int64_t *d_index, int64_t n, const pmp_batch_dst *dst, int32_t *d_status)
 {

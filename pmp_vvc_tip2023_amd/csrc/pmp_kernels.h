@@ -333,6 +333,18 @@ struct AdamTable {
     unsigned first[PMP_ADAM_TABLE];     // the entry's first workgroup: filled by the launcher
 };
 hipError_t launch_adam_step(hipStream_t s, AdamTable &t, int nt, const AdamConsts &k);
+// pmp_grad_pack_device: one launch over the first nt <= PMP_ADAM_TABLE entries of t: grad[i] (NULL: zeros), count[i] in 1 .. 2^30 - 1
+// floats, to bucket + at[i], both 16-byte aligned; the padding behind a tensor, up to a multiple of 4 floats, is written as zeros
+struct GradPackTable {
+    const float *grad[PMP_ADAM_TABLE];
+    int64_t at[PMP_ADAM_TABLE];
+    unsigned count[PMP_ADAM_TABLE];
+    unsigned first[PMP_ADAM_TABLE];     // the entry's first workgroup: filled by the launcher
+};
+hipError_t launch_grad_pack(hipStream_t s, GradPackTable &t, int nt, float *bucket);
+// pmp_grad_sum_device: dst = ((src[0] + src[1]) + ...) over quads float4s; nsrc in 1..PMP_GRAD_SUM_MAX, every pointer 16-byte aligned
+struct GradSumTable { const float *src[PMP_GRAD_SUM_MAX]; };
+hipError_t launch_grad_sum(hipStream_t s, const GradSumTable &t, int nsrc, int64_t quads, float *dst);
 
 // ------------------------------------------------------------------------------------------------ data set assembly (dataset.hip)
 // pmp_select_rows_device: the flag arrays travel in the kernel's argument block.  scratch: select_scratch_words(n, nseg) 32-bit words,

@@ -2,7 +2,7 @@
 // the shape rules, a chain's blocks and its d_saved layout (SavedLayout: a trunk's and a QT tail's), a stem's and a head's sizes, the
 // rules on a call's tensors, and per call family ONE function that states everything the call is refused for (rb_refused,
 // chain_refused, stem_refused, head_refused, gate_refused): which tensors the call has, which are optional, which need 16 bytes.
-// Likewise a step's ends (gather_refused, adam_refused) and data set assembly (api_dataset.cpp: select_refused, rows_gather_refused).
+// Likewise a step's ends (gather_refused, adam_refused), the gradient buckets (grad_pack_refused, grad_sum_refused) and data set assembly (api_dataset.cpp: select_refused, rows_gather_refused).
 // A single block is checked as the one-block trunk it is.  Pure host code without the HIP runtime, no pointer is dereferenced, so
 // that it also builds, with a main of its own, for the CPU under a sanitizer (train_check_main.cpp, `make traincheck`).
 #pragma once
@@ -421,6 +421,49 @@ inline const char *adam_refused(const pmp_adam_params *p, int ntensors, float *c
     std::sort(at.begin(), at.end());
     for (size_t i = 1; i < at.size(); ++i)
         if (at[i].first < at[i - 1].second) return "two tensors of the call overlap";
+    return nullptr;
+}
+
+// ---- gradient buckets (pmp_grad_bucket_floats, pmp_grad_pack_device, pmp_grad_sum_device)
+// tensor i at offset[i] floats, a multiple of 4  -> the bucket's floats, or -1 for a bad table
+inline int64_t grad_bucket_floats(int ntensors, const int64_t *count, int64_t *offset)
+{
+    if (ntensors < 1 || !count) return -1;
+    int64_t at = 0;
+    for (int i = 0; i < ntensors; ++i) {
+        if (count[i] < 1 || count[i] >= ((int64_t)1 << 30)) return -1;
+        if (offset) offset[i] = at;
+        at += (count[i] + 3) & ~(int64_t)3;
+    }
+    return at;
+}
+
+inline const char *grad_pack_refused(int ntensors, const float *const *grad, const int64_t *count, const float *bucket)
+{
+    if (!grad || !count || !bucket) return "null array or bucket";
+    const int64_t total = grad_bucket_floats(ntensors, count, nullptr);
+    if (total < 0) return "ntensors must be >= 1 and every count in 1 .. 2^30 - 1";
+    if ((uintptr_t)bucket & 15) return "the bucket must be 16-byte aligned";
+    const Span out{bucket, (size_t)total * 4};
+    for (int i = 0; i < ntensors; ++i) {
+        if ((uintptr_t)grad[i] & 3) return "every gradient must be 4-byte aligned";
+        if (overlaps(out, Span{grad[i], (size_t)count[i] * 4})) return "a gradient overlaps the bucket";
+    }
+    return nullptr;
+}
+
+inline const char *grad_sum_refused(int nsrc, const float *const *src, int64_t count, const float *dst)
+{
+    if (nsrc < 1 || nsrc > PMP_GRAD_SUM_MAX) return "nsrc must be in 1 .. 64";
+    if (!src || !dst) return "null array or d_dst";
+    if (count < 4 || (count & 3)) return "count must be a multiple of 4, at least 4";
+    if ((uintptr_t)dst & 15) return "every pointer must be 16-byte aligned";
+    const Span out{dst, (size_t)count * 4};
+    for (int j = 0; j < nsrc; ++j) {
+        if (!src[j]) return "null source";
+        if ((uintptr_t)src[j] & 15) return "every pointer must be 16-byte aligned";
+        if (!(j == 0 && src[0] == dst) && overlaps(out, Span{src[j], (size_t)count * 4})) return "d_dst overlaps a source that is not d_src[0] itself";
+    }
     return nullptr;
 }
 

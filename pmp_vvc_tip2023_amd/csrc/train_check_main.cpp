@@ -4,7 +4,8 @@
 // head's shapes, sizes and the tensors tied to its attention input (tests/test_gpu_head_grad.py), a QT tail's (tests/
 // test_gpu_qtail_grad.py), and the pointer-level rows of those matrices through the functions the entry points call: chain_refused,
 // rb_refused, stem_refused, head_refused and gate_refused on fake addresses, and those of data set assembly (tests/
-// test_gpu_dataset.py) through select_refused and rows_gather_refused.  No pointer is dereferenced; exit status 0 and
+// test_gpu_dataset.py) through select_refused and rows_gather_refused, and the gradient buckets' layout and refusals (tests/
+// test_gpu_grad_bucket.py) through grad_bucket_floats, grad_pack_refused and grad_sum_refused.  No pointer is dereferenced; exit status 0 and
 // "train_check: ok" when all hold.
 #include <stdio.h>
 #include <string.h>
@@ -547,6 +548,47 @@ int main()
         g[2] = t[0] + 2; expect(says(ar(), "overlap"), "a gradient inside a param"); g[2] = t[5];
         p[1] = t[0]; expect(says(ar(), "overlap"), "the same param twice"); p[1] = t[1];
         v[2] = t[10] + 43; expect(says(ar(), "overlap"), "v over the end of another v"); v[2] = t[10] + 64; expect(!ar(), "tensors that touch"); v[2] = t[11];
+    }
+    {   // gradient buckets: the layout, and the matrix of tests/test_gpu_grad_bucket.py through grad_pack_refused and grad_sum_refused
+        const int64_t count[5] = {1, 3, 4, 5, 1023};
+        int64_t at[5] = {-1, -1, -1, -1, -1};
+        expect(grad_bucket_floats(5, count, at) == 1044 && at[0] == 0 && at[1] == 4 && at[2] == 8 && at[3] == 12 && at[4] == 20, "a bucket's layout");
+        expect(grad_bucket_floats(5, count, nullptr) == 1044 && grad_bucket_floats(1, count, nullptr) == 4, "the offsets are optional");
+        expect(grad_bucket_floats(0, count, at) == -1 && grad_bucket_floats(-1, count, at) == -1 && grad_bucket_floats(5, nullptr, at) == -1, "no table");
+        for (int64_t bad : {(int64_t)0, (int64_t)-1, (int64_t)1 << 30, (int64_t)1 << 40}) {
+            int64_t c3[3] = {5, bad, 7};
+            expect(grad_bucket_floats(3, c3, at) == -1, "a count outside 1 .. 2^30 - 1");
+        }
+        { int64_t c1[1] = {((int64_t)1 << 30) - 1}; expect(grad_bucket_floats(1, c1, at) == (int64_t)1 << 30 && at[0] == 0, "the largest count"); }
+        static float mem[8192] __attribute__((aligned(16)));
+        float *bucket = mem + 4096;
+        const float *g[5] = {mem, mem + 1, mem + 8, nullptr, mem + 16};
+        auto pr = [&](int nt = 5, const float *b = nullptr) { return grad_pack_refused(nt, g, count, b ? b : bucket); };
+        expect(!pr() && !pr(1), "accepted pack calls: a NULL entry, gradients that are only 4-byte aligned");
+        expect(says(pr(0), "ntensors") && says(pr(-1), "ntensors"), "pack's ntensors");
+        expect(says(grad_pack_refused(5, nullptr, count, bucket), "null") && says(grad_pack_refused(5, g, nullptr, bucket), "null") &&
+                   says(grad_pack_refused(5, g, count, nullptr), "null"), "pack's null arguments");
+        { int64_t c5[5] = {1, 3, 0, 5, 1023}; expect(says(grad_pack_refused(5, g, c5, bucket), "count"), "pack's count 0"); }
+        { int64_t c5[5] = {1, 3, 4, (int64_t)1 << 30, 1023}; expect(says(grad_pack_refused(5, g, c5, bucket), "count"), "a count of 2^30, also of a NULL entry"); }
+        expect(says(pr(5, bucket + 1), "16-byte") && says(pr(5, bucket + 2), "16-byte") && !pr(5, bucket + 4), "the bucket's 16 bytes");
+        g[1] = off(mem + 1, 2); expect(says(pr(), "4-byte"), "a gradient two bytes off"); g[1] = mem + 1;
+        g[4] = bucket + 1040; expect(says(pr(), "overlaps"), "a gradient inside the bucket's last quad"); g[4] = bucket + 1044; expect(!pr(), "right behind it");
+        g[4] = bucket - 1023; expect(!pr(), "right in front of it"); g[4] = bucket - 1022; expect(says(pr(), "overlaps"), "over its first float"); g[4] = mem + 16;
+
+        const float *s[64];
+        for (int j = 0; j < 64; ++j) s[j] = mem + 64 * j;
+        float *dst = mem + 4096;
+        auto sr = [&](int nsrc = 3, int64_t n = 64, const float *d = nullptr) { return grad_sum_refused(nsrc, s, n, d ? d : dst); };
+        expect(!sr() && !sr(1) && !sr(64) && !sr(3, 4) && !sr(3, 64, mem) && !sr(1, 64, mem), "accepted sum calls, in place too");
+        expect(says(sr(0), "nsrc") && says(sr(-1), "nsrc") && says(sr(65), "nsrc"), "sum's nsrc");
+        expect(says(grad_sum_refused(3, nullptr, 64, dst), "null") && says(grad_sum_refused(3, s, 64, nullptr), "null"), "sum's null arguments");
+        for (int64_t n : {(int64_t)0, (int64_t)-4, (int64_t)1, (int64_t)3, (int64_t)5, (int64_t)66}) expect(says(sr(3, n), "multiple of 4"), "sum's count");
+        expect(says(sr(3, 64, dst + 1), "16-byte") && says(sr(3, 64, dst + 2), "16-byte"), "a destination off 16 bytes");
+        s[2] = mem + 130; expect(says(sr(), "16-byte"), "a source off 16 bytes"); s[2] = nullptr; expect(says(sr(), "null source"), "a null source");
+        expect(!sr(2), "entries behind nsrc are not read"); s[2] = mem + 128;
+        expect(says(sr(3, 64, mem + 64), "overlaps") && says(sr(3, 64, mem + 128), "overlaps"), "the destination is a source other than the first");
+        expect(says(sr(3, 64, mem + 4), "overlaps") && says(sr(3, 64, mem + 188), "overlaps") && !sr(3, 64, mem + 192), "the destination partly over a source; right behind the last");
+        s[1] = mem; expect(!sr(3, 64, dst), "sources may alias"); expect(says(sr(3, 64, mem), "overlaps"), "in place, and the first source given twice"); s[1] = mem + 64;
     }
     {   // data set assembly: the matrix of tests/test_gpu_dataset.py through select_refused and rows_gather_refused; 300 rows in 3 segments
         auto sh = [](auto *p, long bytes) { return reinterpret_cast<decltype(p)>(reinterpret_cast<uintptr_t>(p) + bytes); };

@@ -1,7 +1,8 @@
 // train_step.hip — the two ends of a training step (include/pmp.h, TRAINING STEP): a batch gathered on the device from a data set that
 // stays there as bytes, and Adam over every tensor of the step in one launch.  Both are latency-bound at a trainer's sizes (4 MB a
 // batch, 43 MB an Adam step): what counts is one launch each and no host in the loop.  Built with -ffp-contract=off: every fused
-// multiply-add below is written as fmaf().
+// multiply-add below is written as fmaf().  And the gradient buckets of data-parallel training: the gradients of a rank packed into one
+// buffer, and the ranks' buffers added in rank order, one rounded float32 addition at a time.
 #include "pmp_kernels.h"
 
 namespace pmp {
@@ -101,7 +102,69 @@ __global__ __launch_bounds__(THREADS) void adam_step_kernel(AdamTable t, int nt,
     for (unsigned e = 4 * quads + threadIdx.x; e < left; e += THREADS) adam_one(p[e], g[e], m[e], v[e], k);
 }
 
+// Gradient buckets.  Both kernels are HBM-bound: 16-byte accesses on the bucket side, no LDS, no scratch, a table in the argument block.
+// A workgroup finds its entry as Adam's does and writes 2048 floats of the entry's slice, the zero padding behind the tensor
+// included: every float of the bucket belongs to exactly one workgroup.  A gradient that is 16-byte aligned is read as float4s
+__global__ __launch_bounds__(THREADS) void grad_pack_kernel(GradPackTable t, int nt, float *bucket)
+{
+    int lo = 0, hi = nt - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (t.first[mid] <= blockIdx.x) lo = mid;
+        else hi = mid - 1;
+    }
+    const unsigned count = t.count[lo], base = (blockIdx.x - t.first[lo]) * ADAM_PER_GROUP;
+    const unsigned quads = min(((count + 3) & ~3u) - base, ADAM_PER_GROUP) / 4;
+    const float *g = t.grad[lo];
+    float4 *o = reinterpret_cast<float4 *>(bucket + t.at[lo] + base);
+    const bool wide = (reinterpret_cast<uintptr_t>(g) & 15) == 0;
+    for (unsigned q = threadIdx.x; q < quads; q += THREADS) {
+        const unsigned e = base + 4 * q;
+        float4 f = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (g && wide && e + 4 <= count) f = *reinterpret_cast<const float4 *>(g + e);
+        else if (g) {
+            if (e < count) f.x = g[e];
+            if (e + 1 < count) f.y = g[e + 1];
+            if (e + 2 < count) f.z = g[e + 2];
+            if (e + 3 < count) f.w = g[e + 3];
+        }
+        o[q] = f;
+    }
+}
+
+// One float4 of every source to a thread, added in the table's order, one rounded addition each (-ffp-contract=off, no fast-math);
+// a thread reads its float4 of src[0] before it writes the same float4 of dst: dst may be src[0]
+__global__ __launch_bounds__(THREADS) void grad_sum_kernel(GradSumTable t, int nsrc, int64_t quads, float *dst)
+{
+    for (int64_t q = (int64_t)blockIdx.x * THREADS + threadIdx.x; q < quads; q += (int64_t)gridDim.x * THREADS) {
+        float4 a = reinterpret_cast<const float4 *>(t.src[0])[q];
+        for (int j = 1; j < nsrc; ++j) {
+            const float4 b = reinterpret_cast<const float4 *>(t.src[j])[q];
+            a.x = a.x + b.x; a.y = a.y + b.y; a.z = a.z + b.z; a.w = a.w + b.w;
+        }
+        reinterpret_cast<float4 *>(dst)[q] = a;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_grad_pack(hipStream_t s, GradPackTable &t, int nt, float *bucket)
+{
+    unsigned groups = 0;
+    for (int i = 0; i < nt; ++i) {
+        t.first[i] = groups;
+        groups += (t.count[i] + ADAM_PER_GROUP - 1) / ADAM_PER_GROUP;
+    }
+    hipLaunchKernelGGL(grad_pack_kernel, dim3(groups), dim3(THREADS), 0, s, t, nt, bucket);
+    return hipGetLastError();
+}
+
+hipError_t launch_grad_sum(hipStream_t s, const GradSumTable &t, int nsrc, int64_t quads, float *dst)
+{
+    const unsigned groups = (unsigned)std::min<int64_t>((quads + THREADS - 1) / THREADS, 2048);
+    hipLaunchKernelGGL(grad_sum_kernel, dim3(groups), dim3(THREADS), 0, s, t, nsrc, quads, dst);
+    return hipGetLastError();
+}
 
 hipError_t launch_batch_gather(hipStream_t s, const pmp_batch_src &src, const int64_t *index, int n, const pmp_batch_dst &dst, int32_t *status)
 {

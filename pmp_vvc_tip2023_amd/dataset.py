@@ -66,16 +66,30 @@ class DeviceDataset:
             self.src, P(d_index), n, P(self.status), d_x=P(x), d_qt_f=P(qt_f), d_qt8=P(qt8), d_msbt=P(msbt), d_msdire=P(msdire)))
         return (x, qt_f, msbt, msdire, qt8) if mtt else (x, qt_f, qt8)
 
-    def batches(self, batch_size, shuffle=True, seed=0, epoch=0, max_batches=None):
-        """Yields the epoch's batches (at most max_batches of them); raises behind the last one if any index lay outside the set."""
+    def _indices(self, batch_size, shuffle, seed, epoch, max_batches):
+        """The index tensors of the epoch's batches, views of one permutation on the device"""
         batch_size = int(batch_size)
         if not 1 <= batch_size <= _lib.PMP_BATCH_MAX:
             raise ValueError("batch_size must be in 1 .. %d" % _lib.PMP_BATCH_MAX)
         order = permutation(self.n, shuffle, seed, epoch).to(self.device)
         count = (self.n + batch_size - 1) // batch_size
         for b in range(count if max_batches is None else min(count, int(max_batches))):
-            idx = order[b * batch_size:(b + 1) * batch_size]
+            yield order[b * batch_size:(b + 1) * batch_size]
+
+    def batches(self, batch_size, shuffle=True, seed=0, epoch=0, max_batches=None):
+        """Yields the epoch's batches (at most max_batches of them); raises behind the last one if any index lay outside the set."""
+        for idx in self._indices(batch_size, shuffle, seed, epoch, max_batches):
             yield self.gather(idx, idx.numel())
+        self.check()
+
+    def rank_batches(self, batch_size, rank, world, shuffle=True, seed=0, epoch=0, max_batches=None):
+        """The same epoch on `world` ranks (grad_sync.py): every rank derives the same permutation and gathers only its own rows of
+        each batch, grad_sync.rank_rows.  Yields (n, rows): the size of the WHOLE batch and this rank's tuple, None where the rank
+        takes no row of a ragged batch."""
+        from .grad_sync import rank_rows
+        for idx in self._indices(batch_size, shuffle, seed, epoch, max_batches):
+            lo, hi = rank_rows(idx.numel(), batch_size, rank, world)
+            yield idx.numel(), (self.gather(idx[lo:hi], hi - lo) if hi > lo else None)
         self.check()
 
     def check(self):

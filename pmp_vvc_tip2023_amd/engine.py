@@ -546,6 +546,18 @@ class Engine:
                                                _lib.pointer_array(d_m, nt), _lib.pointer_array(d_v, nt), (C.c_int64 * nt)(*[int(k) for k in counts]),
                                                int(step)))
 
+    def grad_pack_device(self, d_grad, counts, d_bucket):
+        """pmp_grad_pack_device: the gradients (device pointers, None = a parameter without one: zeros) of counts[i] floats each into
+        the bucket grad_bucket_floats(counts) lays out; every float of the bucket is written; stream-ordered, the host does not wait."""
+        nt = len(counts)
+        self._ck(self.lib.pmp_grad_pack_device(self.h, nt, _lib.pointer_array(d_grad, nt), (C.c_int64 * nt)(*[int(k) for k in counts]), d_bucket))
+
+    def grad_sum_device(self, d_src, count, d_dst):
+        """pmp_grad_sum_device: d_dst = ((d_src[0] + d_src[1]) + ...) over count floats, float32 additions in the list's order; d_dst
+        may be d_src[0]; stream-ordered, the host does not wait."""
+        d_src = list(d_src)
+        self._ck(self.lib.pmp_grad_sum_device(self.h, len(d_src), _lib.pointer_array(d_src, len(d_src)) if d_src else None, int(count), d_dst))
+
     # ------------------------------------------------------------------------------------------ data set assembly
     def select_rows_device(self, d_flags, mask, d_seg_end, nseg, cap, n, d_index, d_count):
         """pmp_select_rows_device: d_flags a list of device pointers to u8[n] (empty: every row is a candidate), d_seg_end i64[nseg],
@@ -618,34 +630,43 @@ class Engine:
     def infer_msbd_device(self, comp, qp, d_by, d_bu, d_bv, d_qt_in, n, d_bt, d_dire):
         self._ck(self.lib.pmp_infer_msbd_device(self.h, COMP_ID[comp], int(qp), d_by, d_bu, d_bv, d_qt_in, int(n), d_bt, d_dire))
 
-    def validation_QBD(self, comp, qp, blocks, qt8, msbt, msdire, batch_size=200, logits=None, return_block_stats=False):
+    def validation_QBD(self, comp, qp, blocks, qt8, msbt, msdire, batch_size=200, logits=None, return_block_stats=False, batch_range=None):
         """Metrics.validation_QBD (Metrics.py:313-385) on the GPU: both nets on every batch, the QT net's output feeding the MTT net.
         blocks: block_y u8[N,68,68] (Luma) or (block_y, block_u, block_v) (Chroma); labels as the label files hold them (qt8 RAW
         qtDepth u8[N,8,8], msbt u8 / msdire i8 [N,3,16,16]).  The set is cut into batches of batch_size IN ORDER (the reference
         shuffles: its numbers are defined up to that; the ragged last batch weighs like a full one, as there).  Returns the
         reference's list of 15: [q_L1, b0_L1, b1_L1, b2_L1, d0_L1, d1_L1, d2_L1, q_accu, b0_accu, b1_accu, b2_accu, d0_accu, d1_accu,
         d2_accu, val_loss], each np.mean over the per-batch values.  logits = (qt, bt, dire): validate these instead of running the
-        nets (blocks may be None).  return_block_stats: also the per-block partials float64[N,20] (include/pmp.h: pmp_val_stats)."""
-        S, ns, blk = self._val_run("qbd", comp, qp, blocks, qt8, msbt, msdire, batch_size, logits, return_block_stats)
+        nets (blocks may be None).  return_block_stats: also the per-block partials float64[N,20] (include/pmp.h: pmp_val_stats).
+        batch_range = (lo, hi): only batches lo .. hi-1 of the set's batches run (a rank's share, parallel.shard_bounds of the batch
+        count; hi == lo runs nothing), and what comes back is not the list but the raw material of validation_numbers: (S
+        float64[hi-lo,20], the batches' sizes).  The ranges' S and sizes, joined in batch order, give the whole run's numbers, bit for bit."""
+        S, ns, blk = self._val_run("qbd", comp, qp, blocks, qt8, msbt, msdire, batch_size, logits, return_block_stats, batch_range=batch_range)
+        if batch_range is not None:
+            return S, ns
         out = validation_numbers(S, ns, "qbd")
         return (out, blk) if return_block_stats else out
 
-    def pre_validation(self, comp, qp, pred_id, blocks, qt8, msbt=None, msdire=None, batch_size=200, logits=None, return_block_stats=False):
+    def pre_validation(self, comp, qp, pred_id, blocks, qt8, msbt=None, msdire=None, batch_size=200, logits=None, return_block_stats=False,
+                       batch_range=None):
         """Metrics.pre_validation (Metrics.py:196-274).  pred_id 0: the QT net alone -> [L1, accuracy] (the ABI has no QT-only inference
         call: this runs pmp_infer_device and drops the MTT logits, so it costs a full inference step).  pred_id 1: the MTT net,
         TEACHER-FORCED with the QT label map float(qt8 - 1) (u8 subtraction: raw 0 -> 255.0) -> the reference's list of 13: [b0_L1, b1_L1,
         b2_L1, d0_L1, d1_L1, d2_L1, b0_accu, b1_accu, b2_accu, d0_accu, d1_accu, d2_accu, val_loss].  Batching, logits and
-        return_block_stats as in validation_QBD (logits = (qt,) for pred_id 0, (bt, dire) for pred_id 1).  pred_id 2 belongs to a
+        return_block_stats and batch_range as in validation_QBD (logits = (qt,) for pred_id 0, (bt, dire) for pred_id 1).  pred_id 2 belongs to a
         direction net the reference's Model_QBD.py no longer has: ValueError."""
         if pred_id not in (0, 1):
             raise ValueError("pre_validation: pred_id must be 0 (QT net) or 1 (MTT net, teacher-forced)")
         mode = "q" if pred_id == 0 else "bd"
-        S, ns, blk = self._val_run(mode, comp, qp, blocks, qt8, msbt, msdire, batch_size, logits, return_block_stats)
+        S, ns, blk = self._val_run(mode, comp, qp, blocks, qt8, msbt, msdire, batch_size, logits, return_block_stats, batch_range=batch_range)
+        if batch_range is not None:
+            return S, ns
         out = validation_numbers(S, ns, mode)
         return (out, blk) if return_block_stats else out
 
-    def _val_run(self, mode, comp, qp, blocks, qt8, msbt, msdire, batch_size, logits, want_blocks, group_blocks=16384):
-        """-> (S float64[batches,20], batch sizes, per-block partials or None).  Device-resident: per batch one inference call and one
+    def _val_run(self, mode, comp, qp, blocks, qt8, msbt, msdire, batch_size, logits, want_blocks, group_blocks=16384, batch_range=None):
+        """-> (S float64[batches,20], batch sizes, per-block partials or None); with batch_range = (lo, hi) only the set's batches
+        lo .. hi-1 run and S and the sizes are theirs (the per-block partials keep the set's rows, zeros outside).  Device-resident: per batch one inference call and one
         statistics call, both enqueued without waiting; the host synchronises once per GROUP of batches (at most group_blocks blocks,
         whose logits stay in device memory until then: a range-guard re-run at the synchronize finds every batch's buffers intact)."""
         import torch
@@ -685,6 +706,11 @@ class Engine:
         if mode == "bd" and logits is None:           # the loader's label map: float(u8(qt8 - 1))
             d_qin = up((qt8 - np.uint8(1)).astype(np.float32))
         starts = list(range(0, n, batch_size))
+        if batch_range is not None:
+            lo, hi = int(batch_range[0]), int(batch_range[1])
+            if not 0 <= lo <= hi <= len(starts):
+                raise ValueError("batch_range must lie in 0 .. %d" % len(starts))
+            starts = starts[lo:hi]
         ns = [min(batch_size, n - o) for o in starts]
         S = torch.zeros((len(starts), _lib.PMP_VAL_NSTATS), dtype=torch.float64, device=dev)
         blk = torch.zeros((n, _lib.PMP_VAL_NSTATS), dtype=torch.float64, device=dev) if want_blocks else None
@@ -800,6 +826,19 @@ def loss_params(params=None):
     if _lib.load().pmp_parse_loss_params(str(params).encode(), C.byref(p)) != 0:
         raise ValueError(_lib.load().pmp_last_error(None).decode())
     return p
+
+
+def grad_bucket_floats(counts):
+    """pmp_grad_bucket_floats (host only, no GPU): the gradient bucket of tensors of counts[i] floats -> (the bucket's floats, a multiple
+    of 4; the tensors' offsets in floats, each a multiple of 4).  ValueError for an empty table or a count outside 1 .. 2^30 - 1."""
+    nt = len(counts)
+    if any(not -(1 << 63) <= int(k) < (1 << 63) for k in counts):
+        raise ValueError("grad_bucket_floats: a count outside int64")
+    off = (C.c_int64 * max(nt, 1))()
+    total = _lib.load().pmp_grad_bucket_floats(nt, (C.c_int64 * max(nt, 1))(*[int(k) for k in counts]), off)
+    if total < 0:
+        raise ValueError("grad_bucket_floats: at least one tensor, every count in 1 .. 2^30 - 1")
+    return int(total), [int(v) for v in off[:nt]]
 
 
 VAL_ELEMS = np.array([64] + [256] * 12 + [64] + [256] * 6, np.float64)      # elements per block behind each of the twenty statistics

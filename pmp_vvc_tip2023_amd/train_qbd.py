@@ -3,6 +3,7 @@
     python -m pmp_vvc_tip2023_amd.train_qbd --predID 0|1|2 [--isLuma] --inputDir D --outDir O [--jobID 0000] [--lr 1e-3] [--dr 20]
            [--qp 22] [--epoch 100] [--batchSize 200] [--lambq .. --lambresb2 ..]
            [--modelDir M] [--seed 0] [--saveEvery 10] [--resume] [--maxSteps K] [--device 0] [--valPrecision f16x3|bf16x6|fp32]
+           [--gpus N] [--microBatch 256]
 
 --predID 0 is pre_train_Q (the QT net on the plain L1 loss, Train_QBD.py:117-191), 1 is pre_train_BD (the MTT net teacher-forced with
 the QT labels on loss_func_MSBD, :193-303), 2 is train_QBD (both nets jointly on loss_func_QBD, starting from the pair <comp>_Q_<qp> and
@@ -10,10 +11,11 @@ the QT labels on loss_func_MSBD, :193-303), 2 is train_QBD (both nets jointly on
 three sets Train, Validate and TestSub in the reference's file names (validate.py's docstring); results go to <outDir>/<jobID>/.
 
 A step: the learning rate by Metrics.adjust_learning_rate's rule, a batch gathered on the device (dataset.DeviceDataset), the nets'
-forward (q_net.QNet, msbd_net.MSBDNet), the loss (train_loss), backward(), optim.Adam.step() - one launch.  A batch of more than 256
-blocks, which the training calls do not take, runs as micro-batches of at most 256 whose losses are weighted n_i / n and whose
-gradients add up in .grad, so --batchSize 400 works.  The numbers the reference reads with .item() at every step come from the loss
-call's thirteen sums and are added up on the device; the host reads them once per epoch and at step % 1000 == 0 for the progress line.
+forward (q_net.QNet, msbd_net.MSBDNet), the loss (train_loss), backward(), optim.Adam.step() - one launch.  A batch of more than
+--microBatch blocks (1..256, the most the training calls take) runs as micro-batches of at most that many whose losses are weighted
+n_i / n and whose gradients add up in .grad, so --batchSize 400 works.  The numbers the reference reads with .item() at every step
+come from the loss call's thirteen sums and are added up on the device; the host reads them once per epoch and at step % 1000 == 0
+for the progress line.
 
 An epoch ends as the reference's: Engine.pre_validation / Engine.validation_QBD of the current parameters (loaded into the engine
 with Engine.load_pretrain_model, on the --valPrecision datapath) on the Validate and TestSub sets, the reference's printed lines, and
@@ -23,9 +25,18 @@ weights.load_pkl reads them), and at every epoch <comp>_Q_<qp>.pmpw / <comp>_BD_
 then serves as --modelDir of inference_qbd and validate - and last.pt (nets, optimiser, epoch, seed), from which --resume continues.
 --predID 1 also writes the QT net it validated with as <comp>_Q_<qp>.pmpw, so that the pair is whole.
 
+--gpus N (or torchrun's environment, as inference_qbd) trains data-parallel, the reference's nn.DataParallel: N rank processes
+(parallel.spawn_ranks), each on the GPU of its LOCAL_RANK (--device is refused; ranks share a GPU only under PMP_DIST_BACKEND=gloo, for
+tests), every rank holding the whole Train set and the same permutation, taking rows [r*m, min((r+1)*m, n)) of each batch, m =
+ceil(batchSize / N) <= --microBatch, and the ranks' gradients added in rank order by grad_sync.GradSync.  The run writes, byte for byte,
+the files of the one-rank run with --microBatch m.  Validate and TestSub are dealt out batch-wise (parallel.shard_bounds) and their
+per-batch statistics gathered in batch order.  Rank 0 alone prints and writes; --resume loads on every rank.  Before the first step
+and after every epoch the ranks compare a fingerprint of their parameters: a mismatch ends the job with status 4.  The speed-up has
+not been measured: no multi-GPU node was available, and ranks that share one GPU (gloo) show the bits, not the time.
+
 What differs from the reference: the order of the batches is defined by --seed (dataset.permutation of (seed, epoch): a resumed run
-gives the bits of an uninterrupted one); no nn.DataParallel (one GPU, state_dict names without "module."); micro-batches; --predID 0
-validates beside the MTT net found in --modelDir or else the synthetic one, whose logits are dropped.
+gives the bits of an uninterrupted one); processes instead of nn.DataParallel's threads (state_dict names without "module.");
+micro-batches; --predID 0 validates beside the MTT net found in --modelDir or else the synthetic one, whose logits are dropped.
 Flags, the three sets' files and the model files are checked before anything touches the GPU: exit status 2 on the first problem.
 """
 import argparse
@@ -39,7 +50,16 @@ HEADERS = {0: "epoch_loss, epoch_loss, epoch_L1_loss, val_L1_loss, val_accu, tes
            1: "epoch_loss, epoch_b0_L1_loss, epoch_b1_L1_loss, epoch_b2_L1_loss, val_b2_accu, test_b2_accu\n",
            2: "epoch_loss, epoch_b0_L1_loss, epoch_b1_L1_loss, epoch_b2_L1_loss, val_b2_accu, test_b2_accu\n"}
 COLUMNS = {0: 7, 1: 7, 2: 8}            # values per line of loss.txt (the reference's headers name fewer)
-MICRO = 256                             # the largest n the training calls take
+MICRO_MAX = 256                         # the largest n the training calls take
+EXIT_DESYNC = 4                         # the ranks' parameters differ
+
+
+class _Given(argparse.Action):
+    """Stores the value and, as <dest>Given, that the flag stood on the command line"""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values)
+        setattr(namespace, self.dest + "Given", True)
 
 
 def build_parser():
@@ -64,7 +84,12 @@ def build_parser():
     p.add_argument("--saveEvery", default=10, type=int, help="epochs between checkpoints")
     p.add_argument("--resume", action="store_true", help="continue from <outDir>/<jobID>/last.pt")
     p.add_argument("--maxSteps", default=None, type=int, help="steps per epoch at most (tests)")
-    p.add_argument("--device", default=0, type=int)
+    p.add_argument("--device", default=0, type=int, action=_Given, help="GPU of a one-rank run; with several ranks each takes that of its LOCAL_RANK")
+    p.set_defaults(deviceGiven=False)
+    p.add_argument("--gpus", default=1, type=int,
+                   help="train data-parallel on this many GPUs of the node: started without a launcher the command spawns its own rank "
+                        "processes; under torchrun it is one rank")
+    p.add_argument("--microBatch", default=MICRO_MAX, type=int, help="blocks per forward and backward pass at most, 1..256")
     p.add_argument("--valPrecision", default="f16x3", help="datapath of the validation passes: f16x3, bf16x6 or fp32")
     return p
 
@@ -78,7 +103,8 @@ def learning_rate(lr, epoch, decay_rate, current):
 def plan(args):
     """Checks every flag, opens the three sets (validate.read_set) and finds the model files -> {"comp", "sets": {name: read_set's
     dict}, "start": {net: (kind, path)} of --predID 2's pair, "out_dir"}.  SystemExit(2) on the first problem, nothing has touched the GPU."""
-    from . import weights as W
+    from . import _lib, weights as W
+    from .grad_sync import rank_share
     from .validate import read_set
 
     def fail(msg):
@@ -107,6 +133,19 @@ def plan(args):
         fail("--seed must be in 0 .. 2^40 - 1")
     if args.device < 0:
         fail("--device must be >= 0")
+    if not 1 <= args.microBatch <= MICRO_MAX:
+        fail("--microBatch must be in 1 .. %d" % MICRO_MAX)
+    if not 1 <= args.gpus <= _lib.PMP_GRAD_SUM_MAX:
+        fail("--gpus must be in 1 .. %d" % _lib.PMP_GRAD_SUM_MAX)
+    world = job_world(args)[1]
+    if world > 1:
+        if world > _lib.PMP_GRAD_SUM_MAX:
+            fail("at most %d ranks" % _lib.PMP_GRAD_SUM_MAX)
+        if args.deviceGiven:
+            fail("--device selects the GPU of a one-rank run; with %d ranks every rank takes the GPU of its LOCAL_RANK" % world)
+        if rank_share(args.batchSize, world) > args.microBatch:
+            fail("--batchSize %d on %d ranks is %d blocks a rank, more than --microBatch %d" %
+                 (args.batchSize, world, rank_share(args.batchSize, world), args.microBatch))
     if args.valPrecision not in ("f16x3", "bf16x6", "fp32"):
         fail("--valPrecision must be f16x3, bf16x6 or fp32, got %r" % args.valPrecision)
     if not args.jobID or os.sep in args.jobID:
@@ -129,6 +168,27 @@ def plan(args):
     if args.resume and not os.path.isfile(os.path.join(out["out_dir"], "last.pt")):
         fail("--resume: %s not found" % os.path.join(out["out_dir"], "last.pt"))
     return out
+
+
+def job_world(args):
+    """(rank, world, local rank): torchrun's environment where there is one, else rank 0 of --gpus (the parent that spawns them)"""
+    from . import parallel
+    return parallel.env_world() if "WORLD_SIZE" in os.environ else (0, args.gpus, 0)
+
+
+def rank_device(args, world, local):
+    """The GPU of this rank, by inference_qbd.open_job's rule: --device on one rank; with several the LOCAL_RANK's, and a GPU
+    shared by several ranks only under PMP_DIST_BACKEND=gloo"""
+    if world == 1:
+        return args.device
+    import torch
+    ndev = torch.cuda.device_count()
+    if local < ndev:
+        return local
+    if os.environ.get("PMP_DIST_BACKEND", "nccl") == "nccl":
+        raise SystemExit("rank with LOCAL_RANK %d of %d has no GPU of its own (%d visible): RCCL needs one GPU per rank "
+                         "(PMP_DIST_BACKEND=gloo lets several ranks share a GPU, for tests only)" % (local, world, ndev))
+    return local % max(ndev, 1)
 
 
 def loss_dict(args):
@@ -162,6 +222,13 @@ class Trainer:
             self.nets[kind] = net.to(self.device)
         self.optimizer = optim.Adam(engine, [p for net in self.nets.values() for p in net.parameters()], lr=args.lr)
         self.nvalues = {0: 2, 1: 7, 2: 8}[args.predID]
+        self.sync, self.world = None, 1
+
+    def data_parallel(self):
+        """Call once the process group stands: from here on step() adds the ranks' gradients and numbers (grad_sync.GradSync)"""
+        from . import grad_sync
+        self.sync = grad_sync.GradSync(self.engine, [p for net in self.nets.values() for p in net.parameters()], self.device)
+        self.world = self.sync.world
 
     def forward_loss(self, batch):
         """One micro-batch -> (loss, the step's L1 SUMS as the reference orders its L1 losses: float64 device tensor)"""
@@ -182,15 +249,18 @@ class Trainer:
         import torch
         return loss, torch.cat([t[0:1] / 64.0, t[1:7] / 256.0])
 
-    def accumulate(self, batch):
-        """zero_grad, then forward and backward of the batch in micro-batches of at most MICRO blocks -> step_values.  The .grads hold
-        the gradient of the whole batch's loss."""
+    def accumulate(self, batch, n=None):
+        """zero_grad, then forward and backward of the batch in micro-batches of at most --microBatch blocks -> step_values.  The .grads
+        hold the gradient of the whole batch's loss.  n: the batch is this rank's rows (None: no row) of a batch of n, whose loss
+        the rows are weighted for; the values and the .grads are then this rank's terms of the batch's."""
         import torch
         self.optimizer.zero_grad(set_to_none=True)
-        n = batch[0].shape[0]
+        rows = 0 if batch is None else batch[0].shape[0]
+        n = rows if n is None else n
+        micro = self.args.microBatch
         values = torch.zeros(self.nvalues, dtype=torch.float64, device=self.device)
-        for s in range(0, n, MICRO):
-            part = tuple(t[s:s + MICRO] for t in batch)
+        for s in range(0, rows, micro):
+            part = tuple(t[s:s + micro] for t in batch)
             w = part[0].shape[0] / n
             loss, l1 = self.forward_loss(part)
             (loss * w if w != 1.0 else loss).backward()
@@ -198,10 +268,21 @@ class Trainer:
             values[1:] += l1 / n
         return values
 
-    def step(self, batch):
-        values = self.accumulate(batch)
+    def step(self, batch, n=None):
+        """One step on a whole batch or, data-parallel, on this rank's rows of a batch of n (dataset.rank_batches) -> step_values of
+        the whole batch, the same on every rank"""
+        values = self.accumulate(batch, n)
+        if self.sync is not None:
+            from .grad_sync import active_ranks
+            n = batch[0].shape[0] if n is None else n
+            values = self.sync.sync(active_ranks(n, self.args.batchSize, self.world), values)
         self.optimizer.step()
         return values
+
+    def fingerprint(self):
+        """weights.fingerprint of every parameter and buffer of the nets"""
+        from . import weights as W
+        return W.fingerprint({kind + "." + k: v for kind in self.nets for k, v in self.numpy_weights(kind).items()})
 
     def numpy_weights(self, kind):
         return {k: v.detach().cpu().numpy() for k, v in self.nets[kind].state_dict().items()}
@@ -209,7 +290,9 @@ class Trainer:
 
 def validate(engine, args, comp, sets, trainer, partner):
     """The epoch's validation: the current parameters into the engine, then pre_validation / validation_QBD on Validate and TestSub
-    -> (val list, test list)."""
+    -> (val list, test list).  Data-parallel (trainer.sync): the batches of each set are dealt out by parallel.shard_bounds, a rank
+    runs its own, and the per-batch statistics, gathered in rank order, which is batch order, give the same lists on every rank."""
+    from . import engine as E, grad_sync, parallel
     for kind in trainer.nets:
         engine.load_pretrain_model("%s_%s" % (comp, kind), args.qp, trainer.numpy_weights(kind))
     for kind, w in partner.items():
@@ -218,10 +301,19 @@ def validate(engine, args, comp, sets, trainer, partner):
     out = []
     for name in SETS[1:]:
         d = sets[name]
+        kw = {"batch_size": args.batchSize}
+        if trainer.sync is not None:
+            rank, world = trainer.sync.rank, trainer.sync.world
+            nb = -(-d["n"] // args.batchSize)
+            kw["batch_range"] = parallel.shard_bounds(nb, rank, world)
         if args.predID == 2:
-            out.append(engine.validation_QBD(comp, args.qp, d["blocks"], d["qt8"], d["msbt"], d["msdire"], batch_size=args.batchSize))
+            res = engine.validation_QBD(comp, args.qp, d["blocks"], d["qt8"], d["msbt"], d["msdire"], **kw)
         else:
-            out.append(engine.pre_validation(comp, args.qp, args.predID, d["blocks"], d["qt8"], d["msbt"], d["msdire"], batch_size=args.batchSize))
+            res = engine.pre_validation(comp, args.qp, args.predID, d["blocks"], d["qt8"], d["msbt"], d["msdire"], **kw)
+        if trainer.sync is not None:
+            S, ns = grad_sync.gather_batch_stats(res[0], res[1], parallel.shard_counts(nb, world), trainer.device)
+            res = E.validation_numbers(S, ns, {0: "q", 1: "bd", 2: "qbd"}[args.predID])
+        out.append(res)
     return out
 
 
@@ -267,20 +359,61 @@ def progress(args, epoch, step, v):
         print("epoch: %d step: %d [loss] %.6f [q] %.6f [b] %.6f %.6f %.6f [d] %.6f %.6f %.6f" % ((epoch, step) + tuple(v)))
 
 
+def launch_ranks(n, argv):
+    """--gpus N without a launcher: N fresh rank processes of this command (the parent makes no GPU call), all of them watched: the
+    first rank that fails ends the job with its exit code (parallel.spawn_ranks)."""
+    from . import parallel
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    rc, _ = parallel.spawn_ranks([sys.executable, "-m", "pmp_vvc_tip2023_amd.train_qbd"] + list(argv), n,
+                                 env_extra={"PYTHONPATH": root + os.pathsep + os.environ.get("PYTHONPATH", "")})
+    return rc
+
+
+def open_group(device, world):
+    """The rendezvous, its preflight collective and the steady-state timeout, as inference_qbd's ranks -> whether a process group
+    stands (several ranks, or one forced with PMP_DIST_FORCE=1)"""
+    import torch
+    import torch.distributed as dist
+    from . import parallel
+    torch.cuda.set_device(device)
+    parallel.init_process_group(device)
+    if world > 1:
+        parallel.preflight(device)
+        parallel.relax_timeout()
+    return dist.is_initialized()
+
+
+def in_sync(trainer, when):
+    """The desync check: every rank's fingerprint of its parameters against rank 0's -> True, or False behind a message naming the ranks"""
+    from . import grad_sync
+    bad = grad_sync.ranks_out_of_sync(trainer.fingerprint(), trainer.device)
+    if bad:
+        print("train_qbd: %s the parameters of rank %s differ from rank 0's: the ranks have run apart (seen by rank %d)" %
+              (when, ", ".join(map(str, bad)), trainer.sync.rank), file=sys.stderr, flush=True)
+    return not bad
+
+
 def main(argv=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
     args = build_parser().parse_args(argv)
     pl = plan(args)
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        return launch_ranks(args.gpus, argv)
     import numpy as np
     import torch
 
     from . import dataset, engine as E, weights as W
     comp, out_dir, sets = pl["comp"], pl["out_dir"], pl["sets"]
-    os.makedirs(out_dir, exist_ok=True)
+    rank, world, local = job_world(args)
+    dev_id = rank_device(args, world, local)
+    say = print if rank == 0 else (lambda *a, **k: None)
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
     log = os.path.join(out_dir, "loss.txt")
-    eng = E.Engine(args.device, weight_dir=args.modelDir, allow_synthetic_mtt=args.predID == 0)
+    eng = E.Engine(dev_id, weight_dir=args.modelDir, allow_synthetic_mtt=args.predID == 0)
     try:
         eng.set_precision(args.valPrecision)
-        trainer = Trainer(eng, args, comp, pl["start"], args.device)
+        trainer = Trainer(eng, args, comp, pl["start"], dev_id)
         partner = {"Q": read_weights(pl["start"]["Q"])} if args.predID == 1 else {}
         first = 0
         if args.resume:
@@ -292,24 +425,36 @@ def main(argv=None):
                 net.load_state_dict(last["nets"][kind])
             trainer.optimizer.load_state_dict(last["optim"])
             first = last["epoch"] + 1
-        else:
+        elif rank == 0:
             with open(log, "a") as f:
                 f.write(HEADERS[args.predID])
-        train = dataset.DeviceDataset(eng, args.inputDir, comp, args.qp, "Train", args.predID, args.device, files=sets["Train"])
-        print("Start Training ...")
+        if (world > 1 or os.environ.get("PMP_DIST_FORCE") == "1") and open_group(trainer.device, world):
+            trainer.data_parallel()
+            if not in_sync(trainer, "before the first step"):
+                return EXIT_DESYNC
+        train = dataset.DeviceDataset(eng, args.inputDir, comp, args.qp, "Train", args.predID, dev_id, files=sets["Train"])
+        say("Start Training ...")
         for epoch in range(first, args.epoch):
             group = trainer.optimizer.param_groups[0]
             group["lr"] = learning_rate(args.lr, epoch, args.dr, group["lr"])
             total = torch.zeros(trainer.nvalues, dtype=torch.float64, device=trainer.device)
             steps = 0
-            for step, batch in enumerate(train.batches(args.batchSize, True, args.seed, epoch, args.maxSteps)):
-                values = trainer.step(batch)
+            if trainer.sync is None:
+                batches = ((None, b) for b in train.batches(args.batchSize, True, args.seed, epoch, args.maxSteps))
+            else:
+                batches = train.rank_batches(args.batchSize, rank, world, True, args.seed, epoch, args.maxSteps)
+            for step, (n, batch) in enumerate(batches):
+                values = trainer.step(batch, n)
                 total += values
                 steps += 1
-                if step % 1000 == 0:
+                if step % 1000 == 0 and rank == 0:
                     progress(args, epoch, step, values.tolist())
             mean = (total / steps).tolist()
             val, test = validate(eng, args, comp, sets, trainer, partner)
+            if trainer.sync is not None and not in_sync(trainer, "after epoch %d" % epoch):
+                return EXIT_DESYNC
+            if rank != 0:
+                continue
             line, names = report(args, comp, epoch, mean, val, test)
             with open(log, "a") as f:
                 f.write("".join(str(np.float64(s)) + "," for s in line) + "\n")
@@ -324,6 +469,10 @@ def main(argv=None):
                 W.save_pmpw(os.path.join(out_dir, W.ref_net_name(net) + "_%d.pmpw" % args.qp), net, args.qp, w, source="the partner train_qbd validated with")
             torch.save({"nets": {k: {n: v.detach().cpu() for n, v in net.state_dict().items()} for k, net in trainer.nets.items()},
                         "optim": trainer.optimizer.state_dict(), "epoch": epoch, "seed": args.seed}, os.path.join(out_dir, "last.pt"))
+        if trainer.sync is not None:
+            import torch.distributed as dist
+            dist.barrier()
+            dist.destroy_process_group()
     finally:
         eng.set_stream(0)
         eng.close()

@@ -7,8 +7,13 @@
       tools/qtail_grad_bench.py's joint step (the nets and the loss through this library, the batch already on the device) and
       torch.optim.Adam.step.
 No eager reference net runs here; torch's optimiser is not one.
+  --ddp instead times what data-parallel training (grad_sync.py, train_qbd --gpus N) adds to a step, in ONE process on one GPU, and
+  writes profiles/train_step_ddp.txt: pmp_grad_pack_device, the RCCL all_gather_into_tensor of a ONE-rank group (its launch and a
+  device copy: no link is crossed), pmp_grad_sum_device over 2 and over 8 buckets, GradSync.sync as a whole, and Trainer.step with
+  and without it.  These are the costs a rank pays on top of its step; what a gather across GPUs costs, and so the speed-up, is NOT
+  measured here - that needs a node with several GPUs.
 
-    python tools/train_step_bench.py [--n 200] [--comp Luma,Chroma] [--blocks 4096] [--iters 20] [--warmup 3] [--out FILE]
+    python tools/train_step_bench.py [--n 200] [--comp Luma,Chroma] [--blocks 4096] [--iters 20] [--warmup 3] [--out FILE] [--ddp]
 
 Times are hipEvent times around `iters` back-to-back calls (20 * iters for the batch and for Adam, which take microseconds) after
 `warmup` calls, a torch.cuda.synchronize() between every two legs;
@@ -47,14 +52,77 @@ def against(label, unit, t_a1, t_ours, t_a2, other):
         label, unit, other, t_a1, t_ours, other, t_a2, other, t_o / t_ours, "  SLOWER" if t_ours > t_o else "", 100 * abs(t_a1 - t_a2) / t_o)
 
 
-def bench(eng, comp, n, blocks, warmup, iters):
-    luma = comp == "Luma"
+def synthetic_set(luma, blocks):
+    """-> (what validate.read_set would return for a set of `blocks` random blocks, y, u, v)"""
     rng = np.random.default_rng(6100 + luma)
     y = rng.integers(0, 256, (blocks, 68, 68), dtype=np.uint8)
     u, v = (rng.integers(0, 256, (blocks, 34, 34), dtype=np.uint8) for _ in range(2))
     files = {"blocks": y if luma else (y, u, v), "qt8": rng.integers(1, 5, (blocks, 8, 8), dtype=np.uint8),
              "msbt": rng.integers(0, 4, (blocks, 3, 16, 16), dtype=np.uint8), "msdire": rng.integers(-1, 2, (blocks, 3, 16, 16)).astype(np.int8),
              "n": blocks}
+    return files, y, u, v
+
+
+def bench_ddp(eng, comp, n, blocks, warmup, iters):
+    """What grad_sync adds to a step, on a forced one-rank RCCL group"""
+    import torch.distributed as dist
+    from pmp_vvc_tip2023_amd import grad_sync, parallel
+    from pmp_vvc_tip2023_amd.torch_call import P, run
+    luma = comp == "Luma"
+    dev = torch.device("cuda", 0)
+    os.environ.pop("PMP_DIST_BACKEND", None)
+    parallel.init_process_group(dev, force=True)
+    assert dist.get_backend() == "nccl" and dist.get_world_size() == 1
+    files = synthetic_set(luma, blocks)[0]
+    train = dataset.DeviceDataset(eng, None, comp, 22, "Train", 2, 0, files=files)
+    d_order = dataset.permutation(blocks, True, 1, 0).cuda()
+    nb = blocks // n
+    at = [0]
+
+    def batch():
+        b = at[0] = (at[0] + 1) % nb
+        return train.gather(d_order[b * n:(b + 1) * n], n)
+
+    args = train_qbd.build_parser().parse_args(["--predID", "2", "--lr", "1e-4", "--batchSize", str(n)] + (["--isLuma"] if luma else []))
+    torch.manual_seed(6200 + luma)
+    trainer = train_qbd.Trainer(eng, args, comp, {}, 0)
+    t_plain = timed(lambda: trainer.step(batch()), warmup, iters); torch.cuda.synchronize()
+    trainer.data_parallel()
+    sync = trainer.sync
+    t_sync_step = timed(lambda: trainer.step(batch(), n), warmup, iters); torch.cuda.synchronize()
+    trainer.sync = None
+    t_plain2 = timed(lambda: trainer.step(batch()), warmup, iters); torch.cuda.synchronize()
+    trainer.sync = sync
+    values = trainer.step(batch(), n)                      # leaves every .grad a view of the receive area
+    small = 20 * iters
+    grads = [p.grad for p in sync.params]
+    t_pack = timed(lambda: run(eng, dev, lambda: eng.grad_pack_device([P(g) for g in grads], sync.counts, P(sync.bucket))), warmup, small); torch.cuda.synchronize()
+    t_gather = timed(lambda: dist.all_gather_into_tensor(sync.recv, sync.bucket), warmup, small); torch.cuda.synchronize()
+    t_sum = {}
+    for w in (2, 8):
+        area = torch.zeros((w, sync.total), dtype=torch.float32, device=dev)
+        src = [P(area[r]) for r in range(w)]
+        t_sum[w] = timed(lambda: run(eng, dev, lambda: eng.grad_sum_device(src, sync.total, src[0])), warmup, small); torch.cuda.synchronize()
+    t_whole = timed(lambda: sync.sync([0], values), warmup, small); torch.cuda.synchronize()
+    train.check()
+    dist.destroy_process_group()
+    mb = sync.total * 4 / 1e6
+    head = "%s, n %d, %d tensors, a bucket of %d floats (%.2f MB)" % (comp, n, len(sync.params), sync.total, mb)
+    return [head,
+            "  pmp_grad_pack_device                                   %9.3f ms" % t_pack,
+            "  all_gather_into_tensor, RCCL, ONE rank (no link crossed) %7.3f ms" % t_gather,
+            "  pmp_grad_sum_device over 2 buckets, in place           %9.3f ms" % t_sum[2],
+            "  pmp_grad_sum_device over 8 buckets, in place           %9.3f ms   (%.0f GB/s of %.1f MB read and written)" %
+            (t_sum[8], 9 * mb / t_sum[8], 9 * mb),
+            "  GradSync.sync, one rank: pack, gather, the numbers' gather %5.3f ms" % t_whole,
+            "  train_QBD step without a process group                 %9.3f ms, again %9.3f ms" % (t_plain, t_plain2),
+            "  train_QBD step with GradSync on a one-rank RCCL group  %9.3f ms   (+%.3f ms, %.2f %%)" %
+            (t_sync_step, t_sync_step - min(t_plain, t_plain2), 100 * (t_sync_step / min(t_plain, t_plain2) - 1))]
+
+
+def bench(eng, comp, n, blocks, warmup, iters):
+    luma = comp == "Luma"
+    files, y, u, v = synthetic_set(luma, blocks)
     train = dataset.DeviceDataset(eng, None, comp, 22, "Train", 2, 0, files=files)
     order = dataset.permutation(blocks, True, 1, 0)
     d_order = order.cuda()
@@ -131,19 +199,27 @@ def main():
     ap.add_argument("--blocks", default=4096, type=int, help="blocks of the resident set")
     ap.add_argument("--iters", default=20, type=int)
     ap.add_argument("--warmup", default=3, type=int)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_step.txt"), help="the file the lines are written to")
+    ap.add_argument("--out", default=None, help="the file the lines are written to (profiles/train_step.txt; with --ddp profiles/train_step_ddp.txt)")
+    ap.add_argument("--ddp", action="store_true", help="time what data-parallel training adds to a step instead (one process, a one-rank RCCL group)")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "train_step_ddp.txt" if a.ddp else "train_step.txt")
     if not torch.cuda.is_available():
         raise SystemExit("train_step_bench: no GPU - there is no CPU fallback")
     eng = engine.Engine(0)
-    lines = ["a training step's ends and the whole step: the batch (pmp_batch_gather_device against host batches copied in), Adam (optim.Adam "
+    ddp_head = ("what data-parallel training adds to a training step, in ONE process on one GPU (a forced one-rank RCCL group): the gather crosses no "
+                "link, so these are a rank's own costs, NOT a speed-up and not the cost of a gather across GPUs, which no run here has "
+                "measured; float32, hipEvents, %d calls (step) or %d calls (the rest) after %d warm-up calls, %s" %
+                (a.iters, 20 * a.iters, a.warmup, torch.cuda.get_device_name(0)))
+    lines = [ddp_head, ""] if a.ddp else ["a training step's ends and the whole step: the batch (pmp_batch_gather_device against host batches copied in), Adam (optim.Adam "
              "against torch.optim.Adam) and a train_QBD step, float32, hipEvents, %d calls after %d warm-up calls, %s" %
              (a.iters, a.warmup, torch.cuda.get_device_name(0)), ""]
+    if a.ddp and a.comp == "Luma,Chroma":
+        a.comp = "Luma"                                  # one process group to a process: one component to a run
     with torch.cuda.stream(torch.cuda.Stream()):        # a real stream: the library adopts it, and the events time what runs on it
         for comp in [c for c in a.comp.split(",") if c]:
             torch.cuda.synchronize()
             torch.cuda.empty_cache()
-            got = bench(eng, comp, a.n, a.blocks, a.warmup, a.iters)
+            got = (bench_ddp if a.ddp else bench)(eng, comp, a.n, a.blocks, a.warmup, a.iters)
             print("\n".join(got), flush=True)
             lines += got
     eng.close()
