@@ -510,7 +510,8 @@ int pmp_resblock_backward_device(pmp_ctx *ctx, const pmp_rb_shape *shape, const 
                                  float *d_g_w0, float *d_g_w2, float *d_g_wsc);
 
 /* ---- NON-FINITE VALUES IN THE TRAINING CALLS (pmp_resblock_*, pmp_trunk_*, pmp_qtail_*, pmp_stem_*, pmp_head_* / pmp_gate_*).  A trainer
- *      notices a diverged run by a NaN or inf loss, so NaN and +-inf are ordinary data here and travel as they do in torch.  For every
+ *      notices a diverged run by a NaN or inf loss, so NaN and +-inf are ordinary data here and travel as they do in torch (what to DO
+ *      about a gradient that is not finite is the caller's: THE DIVERGENCE GUARD under TRAINING STEP counts them on the device).  For every
  *      tensor a call writes let R be the elements that are not finite when torch computes the same call on the CPU under autograd
  *      (F.conv2d, F.relu, F.max_pool2d, F.interpolate as Model_QBD.py uses them), L those that are not finite in this library's result,
  *      and S the REACH of the non-finite inputs: what the same net reaches with every weight non-zero (a split stem: with its three
@@ -786,7 +787,60 @@ int pmp_qtail_unpack_device(pmp_ctx *ctx, const pmp_qtail_shape *shape, const vo
  *      PMP_E_INVALID: nsrc outside 1..64, a NULL array, entry or d_dst, count < 4 or no multiple of 4, a pointer not 16-byte aligned,
  *      d_dst over a source other than as d_src[0] itself.
  *      Both device calls: PMP_E_INVALID before any launch, with a message; stream-ordered on the context's stream, settle first; the
- *      same bits on every run, stream and context. ---- */
+ *      same bits on every run, stream and context.
+ *
+ *      THE DIVERGENCE GUARD: the global norm and the non-finite census of a step's gradients, and an Adam step that takes its orders
+ *      from that result in device memory - clipping by global norm and skipping a step with a NaN or inf gradient, the host out of the loop.
+ *      pmp_grad_guard_scratch_bytes.  Host only, no context, no GPU: the bytes of d_scratch for this table, 16 per tile (below); -1 for
+ *      ntensors < 1, a NULL count, a count < 1 or a count >= 2^30.
+ *      pmp_grad_guard_device.  grad and count are HOST arrays [ntensors], as Adam's: device pointers (float32, 4-byte aligned; 16-byte
+ *      loads where a pointer allows them) and element counts in 1 .. 2^30 - 1.  PMP_ADAM_TABLE entries to a launch, in the fewest launches
+ *      that hold them, in the order given, then ONE more launch of one workgroup: two launches for a step of up to 96 tensors.  No
+ *      atomics.  The gradients are read only.  THE CENSUS:
+ *        sumsq      the float64 sum of double(g) * double(g) over every FINITE element; each square is exact in double
+ *        nonfinite  the int64 count of the elements that are NaN or +-inf; these add nothing to sumsq
+ *      THE ORDER OF THE CENSUS is part of the interface (the same bits whatever wrote the gradients, on every run, stream and context,
+ *      on one rank and on many):  tensor i is cut into tiles of 4096 elements; tiles are numbered through the tensors in the order given,
+ *      on across the launches.  In a tile, lane l of 256 adds the squares of its elements l, l + 256, ... , l + 256*15 that exist, in
+ *      ascending order, from +0.0.  Then a[l] += a[l + h] for l < h, with h = 128, 64, ... , 1; a[0] is the tile's partial and goes to
+ *      d_scratch, of which every word is written before it is read (what it held before does not matter).  The last launch is one
+ *      workgroup: lane l adds the partials l, l + 256, ... in ascending order from +0.0, and the same tree follows.  Any implementation
+ *      that gives exactly these bits is this interface; the pairing is what is fixed.
+ *      THE RECORD, finished in double by that last launch and written to d_record by one lane with ordinary stores:
+ *        norm = sqrt(sumsq), correctly rounded          c = max_norm / (norm + 1e-6)
+ *        coef = max_norm > 0 && c < 1 ? (float)c : 1.0f         (torch.nn.utils.clip_grad_norm_'s rule; max_norm 0: no clipping)
+ *        action bit 1 (clip) is set when coef < 1;  action bit 0 (skip) is set when skip_nonfinite && nonfinite > 0
+ *      THE RUNNING COUNTERS, d_state, optional (NULL: none).  Only this call writes them, in stream order; the caller zeroes them once.
+ *      Per call: steps += 1;  with the skip bit: skipped += 1, run += 1, max_run = max(max_run, run);  otherwise run = 0 and, with the
+ *      clip bit, clipped += 1.  run is the number of skipped steps in a row.  max_norm = max(max_norm, norm) at every call: the norm of the
+ *      finite part, which is finite.
+ *      PMP_E_INVALID before any launch, nothing written: NULL p, grad, count, d_scratch or d_record; a bad table (as
+ *      pmp_grad_guard_scratch_bytes); a NULL entry or one not 4-byte aligned; max_norm negative or not finite; d_scratch, d_record or
+ *      d_state not 8-byte aligned; d_scratch, d_record or d_state overlapping a gradient or one another.
+ *      pmp_adam_step_guarded_device.  pmp_adam_step_device's arithmetic to the letter and its launches, but every thread reads coef
+ *      and action from d_record (device memory, as pmp_grad_guard_device wrote it earlier on the stream).  With the skip bit set it
+ *      writes NOTHING: param, m and v keep their bits.  Otherwise g' = g * coef stands where g stood: one rounded float32 multiply, and
+ *      no multiply at all where coef == 1.0f.  The caller's gradients are not modified.  The host computes af, rf and the rest from
+ *      `step` as above.  A SKIPPED STEP STILL COUNTS AS A STEP: the caller passes the next step number at the next call, whatever the
+ *      record said.  torch's GradScaler, which skips optimizer.step() and leaves the step number alone, does otherwise; counting keeps the
+ *      host out of the loop (it never has to read the record) and keeps a torch.optim.Adam state's host-side `step` interchangeable.
+ *      PMP_E_INVALID: what pmp_adam_step_device refuses; a NULL d_record or one not 8-byte aligned; d_record overlapping any of the
+ *      4*ntensors tensors.
+ *      Both device calls: stream-ordered on the context's stream, settle first; the same bits on every run, stream and context. ---- */
+typedef struct pmp_guard_params {
+    double max_norm;                   /* 0: no clipping */
+    int skip_nonfinite;
+} pmp_guard_params;
+typedef struct pmp_guard_record {
+    double sumsq, norm;
+    int64_t nonfinite;
+    float coef;
+    uint32_t action;                   /* bit 0: skip, bit 1: clip */
+} pmp_guard_record;
+typedef struct pmp_guard_state {
+    int64_t steps, skipped, clipped, run, max_run;
+    double max_norm;
+} pmp_guard_state;
 typedef struct pmp_batch_src {
     const uint8_t *y, *u, *v, *qt8, *msbt;
     const int8_t *msdire;
@@ -806,6 +860,11 @@ int pmp_batch_gather_device(pmp_ctx *ctx, const pmp_batch_src *src, const int64_
                             int32_t *d_status);
 int pmp_adam_step_device(pmp_ctx *ctx, const pmp_adam_params *p, int ntensors, float *const *param, const float *const *grad,
                          float *const *m, float *const *v, const int64_t *count, int64_t step);
+int64_t pmp_grad_guard_scratch_bytes(int ntensors, const int64_t *count);
+int pmp_grad_guard_device(pmp_ctx *ctx, const pmp_guard_params *p, int ntensors, const float *const *grad, const int64_t *count,
+                          void *d_scratch, pmp_guard_record *d_record, pmp_guard_state *d_state /* may be NULL */);
+int pmp_adam_step_guarded_device(pmp_ctx *ctx, const pmp_adam_params *p, int ntensors, float *const *param, const float *const *grad,
+                                 float *const *m, float *const *v, const int64_t *count, int64_t step, const pmp_guard_record *d_record);
 #define PMP_GRAD_SUM_MAX 64
 int64_t pmp_grad_bucket_floats(int ntensors, const int64_t *count, int64_t *offset /* [ntensors], may be NULL */);
 int pmp_grad_pack_device(pmp_ctx *ctx, int ntensors, const float *const *grad, const int64_t *count, float *d_bucket);

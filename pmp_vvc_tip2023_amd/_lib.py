@@ -109,6 +109,21 @@ class AdamParams(C.Structure):
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
 
 
+class GuardParams(C.Structure):
+    """pmp_guard_params: max_norm 0 = no clipping; skip_nonfinite = a step with a NaN or inf gradient writes nothing."""
+    _fields_ = [("max_norm", C.c_double), ("skip_nonfinite", C.c_int)]
+
+
+class GuardRecord(C.Structure):
+    """pmp_guard_record, 32 bytes in device memory: action bit 0 = skip, bit 1 = clip."""
+    _fields_ = [("sumsq", C.c_double), ("norm", C.c_double), ("nonfinite", C.c_int64), ("coef", C.c_float), ("action", C.c_uint32)]
+
+
+class GuardState(C.Structure):
+    """pmp_guard_state, 48 bytes in device memory: the running counters of pmp_grad_guard_device."""
+    _fields_ = [(k, C.c_int64) for k in ("steps", "skipped", "clipped", "run", "max_run")] + [("max_norm", C.c_double)]
+
+
 PMP_BATCH_MAX = 65536
 PMP_ADAM_TABLE = 96
 PMP_SELECT_MAX_FLAGS = 64
@@ -193,6 +208,9 @@ SIGNATURES = {
     "pmp_gate_backward_device": (_I, [_VP, _I64] + [_VP] * 6),
     "pmp_batch_gather_device": (_I, [_VP, C.POINTER(BatchSrc), _VP, _I64, C.POINTER(BatchDst), _VP]),
     "pmp_adam_step_device": (_I, [_VP, C.POINTER(AdamParams), _I, _VP, _VP, _VP, _VP, C.POINTER(_I64), _I64]),
+    "pmp_grad_guard_scratch_bytes": (_I64, [_I, C.POINTER(_I64)]),
+    "pmp_grad_guard_device": (_I, [_VP, C.POINTER(GuardParams), _I, _VP, C.POINTER(_I64), _VP, _VP, _VP]),
+    "pmp_adam_step_guarded_device": (_I, [_VP, C.POINTER(AdamParams), _I, _VP, _VP, _VP, _VP, C.POINTER(_I64), _I64, _VP]),
     "pmp_grad_bucket_floats": (_I64, [_I, C.POINTER(_I64), C.POINTER(_I64)]),
     "pmp_grad_pack_device": (_I, [_VP, _I, _VP, C.POINTER(_I64), _VP]),
     "pmp_grad_sum_device": (_I, [_VP, _I, _VP, _I64, _VP]),

@@ -421,9 +421,9 @@ int gate_entry(pmp_ctx *c, const char *fn, int64_t count, bool backward, const f
     return e == hipSuccess ? PMP_OK : hip_fail(c, e, "gate");
 }
 
-// pmp_adam_step_device: the tensors, cut into entries of at most 2^30 floats, go out PMP_ADAM_TABLE entries to a launch
+// pmp_adam_step_device and, with rec, pmp_adam_step_guarded_device: the tensors, cut into entries of at most 2^30 floats, go out PMP_ADAM_TABLE entries to a launch
 int adam_run(pmp_ctx *c, const pmp_adam_params &p, int ntensors, float *const *param, const float *const *grad, float *const *m,
-             float *const *v, const int64_t *count, int64_t step)
+             float *const *v, const int64_t *count, int64_t step, const pmp_guard_record *rec = nullptr)
 {
     const double c1 = 1.0 - std::pow(p.beta1, (double)step), c2 = 1.0 - std::pow(p.beta2, (double)step);
     const AdamConsts k{(float)(1.0 - p.beta1), (float)p.beta2, (float)(1.0 - p.beta2), -(float)(p.lr / c1), (float)std::sqrt(c2), (float)p.eps};
@@ -431,7 +431,7 @@ int adam_run(pmp_ctx *c, const pmp_adam_params &p, int ntensors, float *const *p
     AdamTable t;
     int nt = 0;
     const auto flush = [&] {
-        const hipError_t e = nt ? launch_adam_step(c->stream, t, nt, k) : hipSuccess;
+        const hipError_t e = nt ? launch_adam_step(c->stream, t, nt, k, rec) : hipSuccess;
         nt = 0;
         return e == hipSuccess ? PMP_OK : hip_fail(c, e, "adam_step");
     };
@@ -443,6 +443,28 @@ int adam_run(pmp_ctx *c, const pmp_adam_params &p, int ntensors, float *const *p
                 if (int rc = flush()) return rc;
         }
     return flush();
+}
+
+// pmp_grad_guard_device: the census PMP_ADAM_TABLE tensors to a launch, in the order given, the tiles numbered on across the launches;
+// then the launch that adds the tiles' partials and writes the record
+int grad_guard_run(pmp_ctx *c, const pmp_guard_params &p, int ntensors, const float *const *grad, const int64_t *count, void *scratch,
+                   pmp_guard_record *rec, pmp_guard_state *st)
+{
+    const int64_t tiles = guard_tiles(ntensors, count);
+    GuardTable t;
+    int64_t tile0 = 0, in_table = 0;
+    for (int i = 0, nt = 0; i < ntensors; ++i) {
+        t.grad[nt] = grad[i]; t.count[nt] = (unsigned)count[i];
+        in_table += (count[i] + GUARD_TILE_ELEMS - 1) / GUARD_TILE_ELEMS;
+        if (++nt == PMP_ADAM_TABLE || i == ntensors - 1) {
+            const hipError_t e = launch_grad_census(c->stream, t, nt, tile0, scratch, tiles);
+            if (e != hipSuccess) return hip_fail(c, e, "grad_census");
+            tile0 += in_table;
+            in_table = nt = 0;
+        }
+    }
+    const hipError_t e = launch_grad_guard_finish(c->stream, scratch, tiles, p, rec, st);
+    return e == hipSuccess ? PMP_OK : hip_fail(c, e, "grad_guard_finish");
 }
 
 // pmp_grad_pack_device: PMP_ADAM_TABLE tensors to a launch, in the order given
@@ -496,6 +518,22 @@ int pmp_adam_step_device(pmp_ctx *c, const pmp_adam_params *p, int ntensors, flo
 {
     if (int rc = admit(c, "pmp_adam_step_device", adam_refused(p, ntensors, param, grad, m, v, count, step))) return rc;
     return adam_run(c, *p, ntensors, param, grad, m, v, count, step);
+}
+
+int64_t pmp_grad_guard_scratch_bytes(int ntensors, const int64_t *count) { return guard_scratch_bytes(ntensors, count); }
+
+int pmp_grad_guard_device(pmp_ctx *c, const pmp_guard_params *p, int ntensors, const float *const *grad, const int64_t *count, void *d_scratch,
+                          pmp_guard_record *d_record, pmp_guard_state *d_state)
+{
+    if (int rc = admit(c, "pmp_grad_guard_device", guard_refused(p, ntensors, grad, count, d_scratch, d_record, d_state))) return rc;
+    return grad_guard_run(c, *p, ntensors, grad, count, d_scratch, d_record, d_state);
+}
+
+int pmp_adam_step_guarded_device(pmp_ctx *c, const pmp_adam_params *p, int ntensors, float *const *param, const float *const *grad,
+                                 float *const *m, float *const *v, const int64_t *count, int64_t step, const pmp_guard_record *d_record)
+{
+    if (int rc = admit(c, "pmp_adam_step_guarded_device", adam_guarded_refused(p, ntensors, param, grad, m, v, count, step, d_record))) return rc;
+    return adam_run(c, *p, ntensors, param, grad, m, v, count, step, d_record);
 }
 
 int pmp_head_forward_device(pmp_ctx *c, const pmp_head_shape *s, const float *x, const float *w, const float *b, const float *prev,

@@ -332,7 +332,20 @@ struct AdamTable {
     unsigned count[PMP_ADAM_TABLE];
     unsigned first[PMP_ADAM_TABLE];     // the entry's first workgroup: filled by the launcher
 };
-hipError_t launch_adam_step(hipStream_t s, AdamTable &t, int nt, const AdamConsts &k);
+// rec: NULL, or pmp_adam_step_guarded_device's record in device memory, which the kernel reads coef and the skip bit from
+hipError_t launch_adam_step(hipStream_t s, AdamTable &t, int nt, const AdamConsts &k, const pmp_guard_record *rec = nullptr);
+// pmp_grad_guard_device: one census launch over the first nt <= PMP_ADAM_TABLE entries of t, count[i] in 1 .. 2^30 - 1, a workgroup to a
+// tile of 4096 elements; the launch's first tile is tile0 of the call's tiles_all.  scratch: 16 bytes a tile, the partial sums
+// (float64) in front of the counts (uint64), each written by its tile.  Then one finish launch over all tiles writes rec and steps st
+// (may be NULL)
+struct GuardTable {
+    const float *grad[PMP_ADAM_TABLE];
+    unsigned count[PMP_ADAM_TABLE];
+    unsigned first[PMP_ADAM_TABLE];     // the entry's first workgroup: filled by the launcher
+};
+hipError_t launch_grad_census(hipStream_t s, GuardTable &t, int nt, int64_t tile0, void *scratch, int64_t tiles_all);
+hipError_t launch_grad_guard_finish(hipStream_t s, const void *scratch, int64_t tiles, const pmp_guard_params &p, pmp_guard_record *rec,
+                                    pmp_guard_state *st);
 // pmp_grad_pack_device: one launch over the first nt <= PMP_ADAM_TABLE entries of t: grad[i] (NULL: zeros), count[i] in 1 .. 2^30 - 1
 // floats, to bucket + at[i], both 16-byte aligned; the padding behind a tensor, up to a multiple of 4 floats, is written as zeros
 struct GradPackTable {

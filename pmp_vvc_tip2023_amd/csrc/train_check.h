@@ -2,7 +2,7 @@
 // the shape rules, a chain's blocks and its d_saved layout (SavedLayout: a trunk's and a QT tail's), a stem's and a head's sizes, the
 // rules on a call's tensors, and per call family ONE function that states everything the call is refused for (rb_refused,
 // chain_refused, stem_refused, head_refused, gate_refused): which tensors the call has, which are optional, which need 16 bytes.
-// Likewise a step's ends (gather_refused, adam_refused), the gradient buckets (grad_pack_refused, grad_sum_refused) and data set assembly (api_dataset.cpp: select_refused, rows_gather_refused).
+// Likewise a step's ends (gather_refused, adam_refused), the divergence guard (guard_refused, adam_guarded_refused), the gradient buckets (grad_pack_refused, grad_sum_refused) and data set assembly (api_dataset.cpp: select_refused, rows_gather_refused).
 // A single block is checked as the one-block trunk it is.  Pure host code without the HIP runtime, no pointer is dereferenced, so
 // that it also builds, with a main of its own, for the CPU under a sanitizer (train_check_main.cpp, `make traincheck`).
 #pragma once
@@ -421,6 +421,60 @@ inline const char *adam_refused(const pmp_adam_params *p, int ntensors, float *c
     std::sort(at.begin(), at.end());
     for (size_t i = 1; i < at.size(); ++i)
         if (at[i].first < at[i - 1].second) return "two tensors of the call overlap";
+    return nullptr;
+}
+
+// ---- the divergence guard (pmp_grad_guard_scratch_bytes, pmp_grad_guard_device, pmp_adam_step_guarded_device)
+constexpr int64_t GUARD_TILE_ELEMS = 4096;
+
+// the tiles of the table, or -1 for a bad one
+inline int64_t guard_tiles(int ntensors, const int64_t *count)
+{
+    if (ntensors < 1 || !count) return -1;
+    int64_t tiles = 0;
+    for (int i = 0; i < ntensors; ++i) {
+        if (count[i] < 1 || count[i] >= ((int64_t)1 << 30)) return -1;
+        tiles += (count[i] + GUARD_TILE_ELEMS - 1) / GUARD_TILE_ELEMS;
+    }
+    return tiles;
+}
+
+// 16 bytes a tile: its partial sum and its count of non-finite elements
+inline int64_t guard_scratch_bytes(int ntensors, const int64_t *count)
+{
+    const int64_t tiles = guard_tiles(ntensors, count);
+    return tiles < 0 ? -1 : 16 * tiles;
+}
+
+inline const char *guard_refused(const pmp_guard_params *p, int ntensors, const float *const *grad, const int64_t *count, const void *scratch,
+                                 const pmp_guard_record *record, const pmp_guard_state *state)
+{
+    if (!p || !grad || !count || !scratch || !record) return "null params, array, d_scratch or d_record";
+    const int64_t bytes = guard_scratch_bytes(ntensors, count);
+    if (bytes < 0) return "ntensors must be >= 1 and every count in 1 .. 2^30 - 1";
+    if (!std::isfinite(p->max_norm) || p->max_norm < 0) return "max_norm must be finite and >= 0";
+    if (((uintptr_t)scratch | (uintptr_t)record | (uintptr_t)state) & 7) return "d_scratch, d_record and d_state must be 8-byte aligned";
+    const Span own[3] = {{scratch, (size_t)bytes}, {record, sizeof(pmp_guard_record)}, {state, sizeof(pmp_guard_state)}};
+    if (overlaps(own[0], own[1]) || overlaps(own[0], own[2]) || overlaps(own[1], own[2])) return "d_scratch, d_record and d_state overlap";
+    for (int i = 0; i < ntensors; ++i) {
+        if (!grad[i]) return "null tensor";
+        if ((uintptr_t)grad[i] & 3) return "every gradient must be 4-byte aligned";
+        for (const Span &o : own)
+            if (overlaps(o, Span{grad[i], (size_t)count[i] * 4})) return "d_scratch, d_record or d_state overlaps a gradient";
+    }
+    return nullptr;
+}
+
+inline const char *adam_guarded_refused(const pmp_adam_params *p, int ntensors, float *const *param, const float *const *grad, float *const *m,
+                                        float *const *v, const int64_t *count, int64_t step, const pmp_guard_record *record)
+{
+    if (const char *why = adam_refused(p, ntensors, param, grad, m, v, count, step)) return why;
+    if (!record) return "null d_record";
+    if ((uintptr_t)record & 7) return "d_record must be 8-byte aligned";
+    const Span rec{record, sizeof(pmp_guard_record)};
+    for (int i = 0; i < ntensors; ++i)
+        for (const float *t : {(const float *)param[i], grad[i], (const float *)m[i], (const float *)v[i]})
+            if (overlaps(rec, Span{t, (size_t)count[i] * 4})) return "d_record overlaps a tensor of the call";
     return nullptr;
 }
 

@@ -5,7 +5,8 @@
 // test_gpu_qtail_grad.py), and the pointer-level rows of those matrices through the functions the entry points call: chain_refused,
 // rb_refused, stem_refused, head_refused and gate_refused on fake addresses, and those of data set assembly (tests/
 // test_gpu_dataset.py) through select_refused and rows_gather_refused, and the gradient buckets' layout and refusals (tests/
-// test_gpu_grad_bucket.py) through grad_bucket_floats, grad_pack_refused and grad_sum_refused.  No pointer is dereferenced; exit status 0 and
+// test_gpu_grad_bucket.py) through grad_bucket_floats, grad_pack_refused and grad_sum_refused, and the divergence guard's (tests/
+// test_gpu_grad_guard.py) through guard_scratch_bytes, guard_refused and adam_guarded_refused.  No pointer is dereferenced; exit status 0 and
 // "train_check: ok" when all hold.
 #include <stdio.h>
 #include <string.h>
@@ -548,6 +549,44 @@ int main()
         g[2] = t[0] + 2; expect(says(ar(), "overlap"), "a gradient inside a param"); g[2] = t[5];
         p[1] = t[0]; expect(says(ar(), "overlap"), "the same param twice"); p[1] = t[1];
         v[2] = t[10] + 43; expect(says(ar(), "overlap"), "v over the end of another v"); v[2] = t[10] + 64; expect(!ar(), "tensors that touch"); v[2] = t[11];
+
+        // the divergence guard on the same tensors: the matrix of tests/test_gpu_grad_guard.py through guard_refused and adam_guarded_refused
+        static double own[64];                               // scratch [0, 8), the record [8, 12), the counters [16, 22)
+        pmp_guard_params gp{1.0, 1};
+        pmp_guard_record *rec = (pmp_guard_record *)(own + 8);
+        pmp_guard_state *st = (pmp_guard_state *)(own + 16);
+        int64_t big[3] = {5, 4097, 2 * 4096 + 1};
+        expect(guard_scratch_bytes(3, count) == 48 && guard_scratch_bytes(3, big) == 16 * 6 && guard_scratch_bytes(1, count) == 16, "the guard's scratch");
+        expect(guard_scratch_bytes(0, count) == -1 && guard_scratch_bytes(-1, count) == -1 && guard_scratch_bytes(3, nullptr) == -1, "no table for the guard's scratch");
+        auto gu = [&](int nt = 3, const void *sc = nullptr, const pmp_guard_record *r = nullptr, const pmp_guard_state *s = nullptr) {
+            return guard_refused(&gp, nt, g, count, sc ? sc : own, r ? r : rec, s);
+        };
+        expect(!gu() && !gu(1) && !gu(3, own, rec, st), "accepted guard calls, with counters and without");
+        gp.max_norm = 0.0; gp.skip_nonfinite = 0; expect(!gu(), "max_norm 0: no clipping"); gp.max_norm = 1.0;
+        expect(says(guard_refused(nullptr, 3, g, count, own, rec, st), "null") && says(guard_refused(&gp, 3, nullptr, count, own, rec, st), "null") &&
+               says(guard_refused(&gp, 3, g, nullptr, own, rec, st), "null") && says(guard_refused(&gp, 3, g, count, nullptr, rec, st), "null") &&
+               says(guard_refused(&gp, 3, g, count, own, nullptr, st), "null"), "the guard's null arguments");
+        expect(says(gu(0), "ntensors") && says(gu(-1), "ntensors"), "the guard's ntensors");
+        g[1] = nullptr; expect(is(gu(), "null tensor"), "a null gradient"); g[1] = off(t[4], 2); expect(says(gu(), "4-byte"), "a gradient two bytes off"); g[1] = t[4];
+        for (int64_t bad : {(int64_t)0, (int64_t)-1, (int64_t)1 << 30}) { count[1] = bad; expect(says(gu(), "count"), "the guard's counts"); }
+        count[1] = 64;
+        for (double bad : {-1.0, (double)NAN, (double)INFINITY}) { gp.max_norm = bad; expect(says(gu(), "max_norm"), "the guard's max_norm"); }
+        gp.max_norm = 1.0;
+        expect(says(gu(3, off(own, 4)), "8-byte") && says(gu(3, own, (pmp_guard_record *)off(rec, 4)), "8-byte") &&
+               says(gu(3, own, rec, (pmp_guard_state *)off(st, 4)), "8-byte"), "scratch, record and counters four bytes off");
+        expect(says(gu(3, t[3]), "overlaps a gradient") && says(gu(3, own, (pmp_guard_record *)t[4]), "overlaps a gradient") &&
+               says(gu(3, own, rec, (pmp_guard_state *)(t[5] + 250)), "overlaps a gradient"), "scratch, record and counters over a gradient");
+        expect(says(gu(3, own, (pmp_guard_record *)(own + 5)), "overlap") && says(gu(3, own, rec, (pmp_guard_state *)(own + 4)), "overlap") &&
+               says(gu(3, own, rec, (pmp_guard_state *)(own + 11)), "overlap") && !gu(3, own, rec, (pmp_guard_state *)(own + 12)) &&
+               !gu(3, own, (pmp_guard_record *)(own + 6)), "scratch, record and counters over one another; right behind one another");
+
+        auto ga = [&](const pmp_guard_record *r, int64_t step = 1) { return adam_guarded_refused(&hp, 3, p, g, m, v, count, step, r); };
+        expect(!ga(rec), "an accepted guarded Adam call");
+        expect(says(ga(rec, 0), "step"), "what Adam refuses, the guarded call refuses");
+        expect(says(ga(nullptr), "null d_record") && says(ga((pmp_guard_record *)off(rec, 4)), "8-byte"), "a null record, one four bytes off");
+        expect(says(ga((pmp_guard_record *)t[0]), "d_record overlaps") && says(ga((pmp_guard_record *)t[4]), "d_record overlaps") &&
+               says(ga((pmp_guard_record *)(t[8] + 250)), "d_record overlaps") && says(ga((pmp_guard_record *)t[9]), "d_record overlaps"),
+               "the record over a param, a gradient, an m and a v");
     }
     {   // gradient buckets: the layout, and the matrix of tests/test_gpu_grad_bucket.py through grad_pack_refused and grad_sum_refused
         const int64_t count[5] = {1, 3, 4, 5, 1023};

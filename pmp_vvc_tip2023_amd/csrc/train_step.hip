@@ -2,7 +2,8 @@
 // stays there as bytes, and Adam over every tensor of the step in one launch.  Both are latency-bound at a trainer's sizes (4 MB a
 // batch, 43 MB an Adam step): what counts is one launch each and no host in the loop.  Built with -ffp-contract=off: every fused
 // multiply-add below is written as fmaf().  And the gradient buckets of data-parallel training: the gradients of a rank packed into one
-// buffer, and the ranks' buffers added in rank order, one rounded float32 addition at a time.
+// buffer, and the ranks' buffers added in rank order, one rounded float32 addition at a time.  And the divergence guard: the global norm
+// and non-finite census of a step's gradients in an order fixed by the shapes, and an Adam step that takes its orders from that record.
 #include "pmp_kernels.h"
 
 namespace pmp {
@@ -71,10 +72,21 @@ __device__ inline void adam_one(float &p, float g, float &m, float &v, const Ada
     p = p + (k.neg_af * m) / (sqrtf(v) / k.rf + k.ef);
 }
 
+// the gradient a guarded step uses: one rounded multiply, none at coef 1
+template <bool GUARDED>
+__device__ inline float clipped(float g, float coef) { return GUARDED && coef != 1.0f ? g * coef : g; }
+
 // A workgroup finds its entry in the argument block (the same for all its threads: scalar loads) and walks 2048 floats of it, as
-// 16-byte accesses where all four pointers allow them: torch's allocator hands out such tensors, a view may sit 4 bytes behind
-__global__ __launch_bounds__(THREADS) void adam_step_kernel(AdamTable t, int nt, AdamConsts k)
+// 16-byte accesses where all four pointers allow them: torch's allocator hands out such tensors, a view may sit 4 bytes behind.
+// GUARDED (pmp_adam_step_guarded_device): coef and action come from the record in device memory; with the skip bit nothing is written
+template <bool GUARDED>
+__device__ inline void adam_walk(const AdamTable &t, int nt, const AdamConsts &k, const pmp_guard_record *rec)
 {
+    float coef = 1.0f;
+    if (GUARDED) {
+        if (rec->action & 1u) return;
+        coef = rec->coef;
+    }
     int lo = 0, hi = nt - 1;
     while (lo < hi) {                                     // the last entry whose first workgroup is not behind this one
         const int mid = (lo + hi + 1) >> 1;
@@ -91,15 +103,111 @@ __global__ __launch_bounds__(THREADS) void adam_step_kernel(AdamTable t, int nt,
     for (unsigned q = threadIdx.x; q < quads; q += THREADS) {
         float4 pp = reinterpret_cast<float4 *>(p)[q], mm = reinterpret_cast<float4 *>(m)[q], vv = reinterpret_cast<float4 *>(v)[q];
         const float4 gg = reinterpret_cast<const float4 *>(g)[q];
-        adam_one(pp.x, gg.x, mm.x, vv.x, k);
-        adam_one(pp.y, gg.y, mm.y, vv.y, k);
-        adam_one(pp.z, gg.z, mm.z, vv.z, k);
-        adam_one(pp.w, gg.w, mm.w, vv.w, k);
+        adam_one(pp.x, clipped<GUARDED>(gg.x, coef), mm.x, vv.x, k);
+        adam_one(pp.y, clipped<GUARDED>(gg.y, coef), mm.y, vv.y, k);
+        adam_one(pp.z, clipped<GUARDED>(gg.z, coef), mm.z, vv.z, k);
+        adam_one(pp.w, clipped<GUARDED>(gg.w, coef), mm.w, vv.w, k);
         reinterpret_cast<float4 *>(p)[q] = pp;
         reinterpret_cast<float4 *>(m)[q] = mm;
         reinterpret_cast<float4 *>(v)[q] = vv;
     }
-    for (unsigned e = 4 * quads + threadIdx.x; e < left; e += THREADS) adam_one(p[e], g[e], m[e], v[e], k);
+    for (unsigned e = 4 * quads + threadIdx.x; e < left; e += THREADS) adam_one(p[e], clipped<GUARDED>(g[e], coef), m[e], v[e], k);
+}
+
+__global__ __launch_bounds__(THREADS) void adam_step_kernel(AdamTable t, int nt, AdamConsts k) { adam_walk<false>(t, nt, k, nullptr); }
+
+__global__ __launch_bounds__(THREADS) void adam_step_guarded_kernel(AdamTable t, int nt, AdamConsts k, const pmp_guard_record *rec)
+{
+    adam_walk<true>(t, nt, k, rec);
+}
+
+// grad_guard, first launch (include/pmp.h, THE ORDER OF THE CENSUS): one workgroup per tile of 4096 elements.  The tile goes through LDS,
+// as 16-byte loads where the tensor's pointer allows them (a tile starts a multiple of 16 KB behind it), so that lane l then reads its
+// own elements l, l + 256, ...; the tree runs in LDS, a barrier between its levels.  The count of non-finite elements rides along:
+// integers, whose order does not matter
+constexpr unsigned GUARD_TILE = 4096;
+
+__device__ inline void guard_tree(double *a, unsigned long long *c, double &sum, unsigned long long &cnt)
+{
+    const unsigned l = threadIdx.x;
+    a[l] = sum;
+    c[l] = cnt;
+    __syncthreads();
+    for (unsigned h = THREADS / 2; h >= 1; h >>= 1) {
+        if (l < h) { a[l] = a[l] + a[l + h]; c[l] += c[l + h]; }
+        __syncthreads();
+    }
+    sum = a[0];
+    cnt = c[0];
+}
+
+__global__ __launch_bounds__(THREADS) void grad_census_kernel(GuardTable t, int nt, int64_t tile0, double *part, unsigned long long *bad)
+{
+    __shared__ float tile[GUARD_TILE];
+    __shared__ double a[THREADS];
+    __shared__ unsigned long long c[THREADS];
+    int lo = 0, hi = nt - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (t.first[mid] <= blockIdx.x) lo = mid;
+        else hi = mid - 1;
+    }
+    const unsigned base = (blockIdx.x - t.first[lo]) * GUARD_TILE;
+    const unsigned left = min(t.count[lo] - base, GUARD_TILE);
+    const float *g = t.grad[lo] + base;
+    const unsigned quads = (reinterpret_cast<uintptr_t>(g) & 15) == 0 ? left / 4 : 0;
+    for (unsigned q = threadIdx.x; q < quads; q += THREADS) reinterpret_cast<float4 *>(tile)[q] = reinterpret_cast<const float4 *>(g)[q];
+    for (unsigned e = 4 * quads + threadIdx.x; e < left; e += THREADS) tile[e] = g[e];
+    __syncthreads();
+    double sum = 0.0;
+    unsigned long long cnt = 0;
+    for (unsigned e = threadIdx.x; e < left; e += THREADS) {
+        const float f = tile[e];
+        const bool finite = (__float_as_uint(f) & 0x7F800000u) != 0x7F800000u;
+        const double d = (double)f;
+        if (finite) sum = sum + d * d;                    // -ffp-contract=off: the square, exact in double, then one rounded addition
+        else ++cnt;
+    }
+    guard_tree(a, c, sum, cnt);
+    if (threadIdx.x == 0) {
+        part[tile0 + blockIdx.x] = sum;
+        bad[tile0 + blockIdx.x] = cnt;
+    }
+}
+
+// grad_guard, second launch: one workgroup adds the tiles' partials in the same fixed order, and lane 0 finishes the record in double
+// and steps the running counters
+__global__ __launch_bounds__(THREADS) void grad_guard_finish_kernel(const double *part, const unsigned long long *bad, int64_t tiles, double max_norm,
+                                                                    int skip_nonfinite, pmp_guard_record *rec, pmp_guard_state *st)
+{
+    __shared__ double a[THREADS];
+    __shared__ unsigned long long c[THREADS];
+    double sum = 0.0;
+    unsigned long long cnt = 0;
+    for (int64_t i = threadIdx.x; i < tiles; i += THREADS) { sum = sum + part[i]; cnt += bad[i]; }
+    guard_tree(a, c, sum, cnt);
+    if (threadIdx.x != 0) return;
+    const double norm = sqrt(sum), cc = max_norm / (norm + 1e-6);
+    const float coef = max_norm > 0.0 && cc < 1.0 ? (float)cc : 1.0f;
+    const bool skip = skip_nonfinite && cnt > 0, clip = coef < 1.0f;
+    rec->sumsq = sum;
+    rec->norm = norm;
+    rec->nonfinite = (int64_t)cnt;
+    rec->coef = coef;
+    rec->action = (skip ? 1u : 0u) | (clip ? 2u : 0u);
+    if (!st) return;
+    pmp_guard_state s = *st;
+    s.steps += 1;
+    if (skip) {
+        s.skipped += 1;
+        s.run += 1;
+        s.max_run = s.run > s.max_run ? s.run : s.max_run;
+    } else {
+        s.run = 0;
+        if (clip) s.clipped += 1;
+    }
+    s.max_norm = norm > s.max_norm ? norm : s.max_norm;
+    *st = s;
 }
 
 // Gradient buckets.  Both kernels are HBM-bound: 16-byte accesses on the bucket side, no LDS, no scratch, a table in the argument block.
@@ -172,14 +280,35 @@ hipError_t launch_batch_gather(hipStream_t s, const pmp_batch_src &src, const in
     return hipGetLastError();
 }
 
-hipError_t launch_adam_step(hipStream_t s, AdamTable &t, int nt, const AdamConsts &k)
+hipError_t launch_adam_step(hipStream_t s, AdamTable &t, int nt, const AdamConsts &k, const pmp_guard_record *rec)
 {
     unsigned groups = 0;
     for (int i = 0; i < nt; ++i) {
         t.first[i] = groups;
         groups += (t.count[i] + ADAM_PER_GROUP - 1) / ADAM_PER_GROUP;
     }
-    hipLaunchKernelGGL(adam_step_kernel, dim3(groups), dim3(THREADS), 0, s, t, nt, k);
+    if (rec) hipLaunchKernelGGL(adam_step_guarded_kernel, dim3(groups), dim3(THREADS), 0, s, t, nt, k, rec);
+    else hipLaunchKernelGGL(adam_step_kernel, dim3(groups), dim3(THREADS), 0, s, t, nt, k);
+    return hipGetLastError();
+}
+
+hipError_t launch_grad_census(hipStream_t s, GuardTable &t, int nt, int64_t tile0, void *scratch, int64_t tiles_all)
+{
+    unsigned groups = 0;
+    for (int i = 0; i < nt; ++i) {
+        t.first[i] = groups;
+        groups += (t.count[i] + GUARD_TILE - 1) / GUARD_TILE;
+    }
+    hipLaunchKernelGGL(grad_census_kernel, dim3(groups), dim3(THREADS), 0, s, t, nt, tile0, (double *)scratch,
+                       (unsigned long long *)scratch + tiles_all);
+    return hipGetLastError();
+}
+
+hipError_t launch_grad_guard_finish(hipStream_t s, const void *scratch, int64_t tiles, const pmp_guard_params &p, pmp_guard_record *rec,
+                                    pmp_guard_state *st)
+{
+    hipLaunchKernelGGL(grad_guard_finish_kernel, dim3(1), dim3(THREADS), 0, s, (const double *)scratch, (const unsigned long long *)scratch + tiles,
+                       tiles, p.max_norm, p.skip_nonfinite, rec, st);
     return hipGetLastError();
 }
 

@@ -546,6 +546,32 @@ class Engine:
                                                _lib.pointer_array(d_m, nt), _lib.pointer_array(d_v, nt), (C.c_int64 * nt)(*[int(k) for k in counts]),
                                                int(step)))
 
+    def grad_guard_scratch_bytes(self, counts):
+        """pmp_grad_guard_scratch_bytes: the bytes of grad_guard_device's d_scratch for tensors of counts[i] floats (host only)."""
+        nt = len(counts)
+        n = int(self.lib.pmp_grad_guard_scratch_bytes(nt, (C.c_int64 * nt)(*[int(k) for k in counts])))
+        if n < 0:
+            raise ValueError("grad_guard_scratch_bytes: at least one tensor, every count in 1 .. 2^30 - 1")
+        return n
+
+    def grad_guard_device(self, d_grad, counts, d_scratch, d_record, d_state=None, max_norm=0.0, skip_nonfinite=False):
+        """pmp_grad_guard_device: the global norm and non-finite census of the gradients (device pointers, counts[i] floats each), in an
+        order fixed by the counts, into the 32-byte record at d_record (_lib.GuardRecord) and, where given, the running counters at
+        d_state (_lib.GuardState, zeroed once by the caller); two launches up to 96 tensors, stream-ordered, the host does not wait."""
+        nt = len(counts)
+        p = _lib.GuardParams(float(max_norm), 1 if skip_nonfinite else 0)
+        self._ck(self.lib.pmp_grad_guard_device(self.h, C.byref(p), nt, _lib.pointer_array(d_grad, nt), (C.c_int64 * nt)(*[int(k) for k in counts]),
+                                                d_scratch, d_record, d_state))
+
+    def adam_step_guarded_device(self, d_param, d_grad, d_m, d_v, counts, step, d_record, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+        """pmp_adam_step_guarded_device: adam_step_device taking its orders from grad_guard_device's record in device memory: nothing
+        is written with the skip bit set, else the gradients count times the record's coef.  A skipped step still counts as a step."""
+        nt = len(counts)
+        p = _lib.AdamParams(float(lr), float(betas[0]), float(betas[1]), float(eps))
+        self._ck(self.lib.pmp_adam_step_guarded_device(self.h, C.byref(p), nt, _lib.pointer_array(d_param, nt), _lib.pointer_array(d_grad, nt),
+                                                       _lib.pointer_array(d_m, nt), _lib.pointer_array(d_v, nt),
+                                                       (C.c_int64 * nt)(*[int(k) for k in counts]), int(step), d_record))
+
     def grad_pack_device(self, d_grad, counts, d_bucket):
         """pmp_grad_pack_device: the gradients (device pointers, None = a parameter without one: zeros) of counts[i] floats each into
         the bucket grad_bucket_floats(counts) lays out; every float of the bucket is written; stream-ordered, the host does not wait."""

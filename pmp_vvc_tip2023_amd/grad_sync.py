@@ -11,6 +11,12 @@ library.  A step on W ranks is then, bit for bit, the step of one rank whose mic
                             parameter's .grad becomes a view of that sum: optim.Adam.step() runs unchanged        GradSync.sync
     reported numbers        the float64 vector of Trainer.accumulate, gathered and added in rank order in the same way
 
+The divergence guard (optim.Adam's max_grad_norm / skip_nonfinite, train_qbd --clipNorm / --skipNonFinite) needs nothing here:
+behind GradSync.sync every .grad is a view into the summed bucket, so the table pmp_grad_guard_device walks has the same counts in the
+same order on every rank and on one rank, and its census is defined by counts and order alone, not by where a tensor lies.  The guard
+therefore sees the same bits on every rank - a NaN that one rank's slice produced is in every rank's sum - and every rank takes the
+same decision, the one the one-rank run with --microBatch m takes (tests/test_gpu_train_qbd_guard.py, two ranks against one).
+
 A rank whose slice of a ragged batch is empty is not active: it packs zeros, takes part in the gather, and is left out of the sum,
 because x + 0.0 is not x for x = -0.0.  Rank 0 is active in every step.  Which parameters have a gradient at all is rank 0's pattern,
 exchanged once: the others get .grad = None, as on one rank, and Adam skips them.

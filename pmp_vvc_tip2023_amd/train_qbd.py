@@ -3,7 +3,7 @@
     python -m pmp_vvc_tip2023_amd.train_qbd --predID 0|1|2 [--isLuma] --inputDir D --outDir O [--jobID 0000] [--lr 1e-3] [--dr 20]
            [--qp 22] [--epoch 100] [--batchSize 200] [--lambq .. --lambresb2 ..]
            [--modelDir M] [--seed 0] [--saveEvery 10] [--resume] [--maxSteps K] [--device 0] [--valPrecision f16x3|bf16x6|fp32]
-           [--gpus N] [--microBatch 256]
+           [--gpus N] [--microBatch 256] [--clipNorm X] [--skipNonFinite] [--maxSkipped 10]
 
 --predID 0 is pre_train_Q (the QT net on the plain L1 loss, Train_QBD.py:117-191), 1 is pre_train_BD (the MTT net teacher-forced with
 the QT labels on loss_func_MSBD, :193-303), 2 is train_QBD (both nets jointly on loss_func_QBD, starting from the pair <comp>_Q_<qp> and
@@ -34,6 +34,19 @@ per-batch statistics gathered in batch order.  Rank 0 alone prints and writes; -
 and after every epoch the ranks compare a fingerprint of their parameters: a mismatch ends the job with status 4.  The speed-up has
 not been measured: no multi-GPU node was available, and ranks that share one GPU (gloo) show the bits, not the time.
 
+THE DIVERGENCE GUARD, off by default (without its flags every file and bit is what it was): --clipNorm X clips the step's gradients
+by their global norm as torch.nn.utils.clip_grad_norm_(parameters, X) would; --skipNonFinite makes a step whose gradients hold a NaN
+or an inf write nothing to any parameter or moment (optim.Adam's max_grad_norm and skip_nonfinite: one pmp_grad_guard_device call per
+step, the decision taken and obeyed on the device).  A skipped step still counts as a step (optim.py).  With either flag a skipped step's
+values are masked out of the epoch's totals on the device and the epoch means are over the steps taken.  The host reads the guard's
+counters where it already reads: at step % 1000 == 0 and at the epoch's end.  If more than --maxSkipped steps in a row were skipped
+(meaningful only with --skipNonFinite), or no step of the epoch was taken, the job ends with exit status 5 and a message naming the epoch
+and the counters - BEFORE validation and before any .pmpw, .pkl or last.pt is written, so the files of the last good epoch stay.  Every
+epoch appends "epoch,steps,skipped,clipped,max_run,max_norm" - the counters since the job's first step, max_norm the largest gradient
+norm seen - to guard.txt; last.pt carries them under "guard" and --resume restores them.  Under --gpus N every rank sees the same
+gradient bits behind GradSync.sync, takes the same decisions and returns the same status; rank 0 writes guard.txt, whose bytes are the
+one-rank run's too.
+
 What differs from the reference: the order of the batches is defined by --seed (dataset.permutation of (seed, epoch): a resumed run
 gives the bits of an uninterrupted one); processes instead of nn.DataParallel's threads (state_dict names without "module.");
 micro-batches; --predID 0 validates beside the MTT net found in --modelDir or else the synthetic one, whose logits are dropped.
@@ -52,6 +65,7 @@ HEADERS = {0: "epoch_loss, epoch_loss, epoch_L1_loss, val_L1_loss, val_accu, tes
 COLUMNS = {0: 7, 1: 7, 2: 8}            # values per line of loss.txt (the reference's headers name fewer)
 MICRO_MAX = 256                         # the largest n the training calls take
 EXIT_DESYNC = 4                         # the ranks' parameters differ
+EXIT_DIVERGED = 5                       # the divergence guard ended the job
 
 
 class _Given(argparse.Action):
@@ -90,6 +104,9 @@ def build_parser():
                    help="train data-parallel on this many GPUs of the node: started without a launcher the command spawns its own rank "
                         "processes; under torchrun it is one rank")
     p.add_argument("--microBatch", default=MICRO_MAX, type=int, help="blocks per forward and backward pass at most, 1..256")
+    p.add_argument("--clipNorm", default=0.0, type=float, help="clip the gradients' global norm to this; 0: off")
+    p.add_argument("--skipNonFinite", action="store_true", help="a step whose gradients hold a NaN or an inf changes nothing")
+    p.add_argument("--maxSkipped", default=10, type=int, help="with --skipNonFinite: more skipped steps in a row end the job with status 5")
     p.add_argument("--valPrecision", default="f16x3", help="datapath of the validation passes: f16x3, bf16x6 or fp32")
     return p
 
@@ -135,6 +152,10 @@ def plan(args):
         fail("--device must be >= 0")
     if not 1 <= args.microBatch <= MICRO_MAX:
         fail("--microBatch must be in 1 .. %d" % MICRO_MAX)
+    if not (math.isfinite(args.clipNorm) and args.clipNorm >= 0):
+        fail("--clipNorm must be finite and >= 0 (0: no clipping)")
+    if args.maxSkipped < 0:
+        fail("--maxSkipped must be >= 0")
     if not 1 <= args.gpus <= _lib.PMP_GRAD_SUM_MAX:
         fail("--gpus must be in 1 .. %d" % _lib.PMP_GRAD_SUM_MAX)
     world = job_world(args)[1]
@@ -191,6 +212,16 @@ def rank_device(args, world, local):
     return local % max(ndev, 1)
 
 
+def guard_kwargs(args):
+    """optim.Adam's guard arguments for the flags: none at their defaults, which leaves the optimiser on its unguarded path"""
+    kw = {}
+    if getattr(args, "clipNorm", 0.0):
+        kw["max_grad_norm"] = args.clipNorm
+    if getattr(args, "skipNonFinite", False):
+        kw["skip_nonfinite"] = True
+    return kw
+
+
 def loss_dict(args):
     return {k: getattr(args, k) for k in LAMBS}
 
@@ -220,9 +251,16 @@ class Trainer:
             if args.predID == 2 and start:
                 net.load_state_dict({k: torch.from_numpy(v) for k, v in read_weights(start[kind]).items()})
             self.nets[kind] = net.to(self.device)
-        self.optimizer = optim.Adam(engine, [p for net in self.nets.values() for p in net.parameters()], lr=args.lr)
+        self.optimizer = optim.Adam(engine, [p for net in self.nets.values() for p in net.parameters()], lr=args.lr, **guard_kwargs(args))
         self.nvalues = {0: 2, 1: 7, 2: 8}[args.predID]
         self.sync, self.world = None, 1
+        self.guarded = bool(guard_kwargs(args))
+        self.taken = None                                 # guarded: the steps taken since begin_epoch(), an int64 device scalar
+
+    def begin_epoch(self):
+        import torch
+        if self.guarded:
+            self.taken = torch.zeros((), dtype=torch.int64, device=self.device)
 
     def data_parallel(self):
         """Call once the process group stands: from here on step() adds the ranks' gradients and numbers (grad_sync.GradSync)"""
@@ -270,13 +308,20 @@ class Trainer:
 
     def step(self, batch, n=None):
         """One step on a whole batch or, data-parallel, on this rank's rows of a batch of n (dataset.rank_batches) -> step_values of
-        the whole batch, the same on every rank"""
+        the whole batch, the same on every rank.  Guarded: zeros for a step the guard skipped, and self.taken counts the others"""
         values = self.accumulate(batch, n)
         if self.sync is not None:
             from .grad_sync import active_ranks
             n = batch[0].shape[0] if n is None else n
             values = self.sync.sync(active_ranks(n, self.args.batchSize, self.world), values)
         self.optimizer.step()
+        if self.guarded:
+            import torch
+            if self.taken is None:
+                self.begin_epoch()
+            taken = self.optimizer.step_taken
+            values = torch.where(taken, values, torch.zeros_like(values))
+            self.taken += taken
         return values
 
     def fingerprint(self):
@@ -393,6 +438,16 @@ def in_sync(trainer, when):
     return not bad
 
 
+def diverged(args, epoch, counters, taken):
+    """The guard's verdict where the host reads -> None, or the message the job ends with (status EXIT_DIVERGED).  taken: the
+    steps of the epoch that were taken, None within an epoch"""
+    if counters["max_run"] <= args.maxSkipped and taken != 0:
+        return None
+    why = "no step of the epoch was taken" if taken == 0 else "%d steps in a row were skipped (--maxSkipped %d)" % (counters["max_run"], args.maxSkipped)
+    return "train_qbd: diverged in epoch %d: %s; counters: %s.  Nothing of this epoch was written" % (
+        epoch, why, ", ".join("%s %s" % (k, counters[k]) for k in ("steps", "skipped", "clipped", "run", "max_run", "max_norm")))
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     args = build_parser().parse_args(argv)
@@ -424,6 +479,8 @@ def main(argv=None):
             for kind, net in trainer.nets.items():
                 net.load_state_dict(last["nets"][kind])
             trainer.optimizer.load_state_dict(last["optim"])
+            if trainer.guarded and "guard" in last:
+                trainer.optimizer.load_guard_state(last["guard"])
             first = last["epoch"] + 1
         elif rank == 0:
             with open(log, "a") as f:
@@ -439,6 +496,7 @@ def main(argv=None):
             group["lr"] = learning_rate(args.lr, epoch, args.dr, group["lr"])
             total = torch.zeros(trainer.nvalues, dtype=torch.float64, device=trainer.device)
             steps = 0
+            trainer.begin_epoch()
             if trainer.sync is None:
                 batches = ((None, b) for b in train.batches(args.batchSize, True, args.seed, epoch, args.maxSteps))
             else:
@@ -449,6 +507,18 @@ def main(argv=None):
                 steps += 1
                 if step % 1000 == 0 and rank == 0:
                     progress(args, epoch, step, values.tolist())
+                if step % 1000 == 0 and trainer.guarded:            # every rank reads, and every rank reads the same
+                    bad = diverged(args, epoch, trainer.optimizer.guard_state(), None)
+                    if bad:
+                        print(bad, file=sys.stderr, flush=True)
+                        return EXIT_DIVERGED
+            counters = None
+            if trainer.guarded:
+                counters, steps = trainer.optimizer.guard_state(), int(trainer.taken)
+                bad = diverged(args, epoch, counters, steps)
+                if bad:
+                    print(bad, file=sys.stderr, flush=True)
+                    return EXIT_DIVERGED
             mean = (total / steps).tolist()
             val, test = validate(eng, args, comp, sets, trainer, partner)
             if trainer.sync is not None and not in_sync(trainer, "after epoch %d" % epoch):
@@ -458,6 +528,10 @@ def main(argv=None):
             line, names = report(args, comp, epoch, mean, val, test)
             with open(log, "a") as f:
                 f.write("".join(str(np.float64(s)) + "," for s in line) + "\n")
+            if counters is not None:
+                with open(os.path.join(out_dir, "guard.txt"), "a") as f:
+                    f.write("%d,%d,%d,%d,%d,%s\n" % (epoch, counters["steps"], counters["skipped"], counters["clipped"], counters["max_run"],
+                                                    repr(float(counters["max_norm"]))))
             for kind in trainer.nets:
                 net = "%s_%s" % (comp, kind)
                 W.save_pmpw(os.path.join(out_dir, W.ref_net_name(net) + "_%d.pmpw" % args.qp), net, args.qp, trainer.numpy_weights(kind),
@@ -467,8 +541,11 @@ def main(argv=None):
             for kind, w in partner.items():
                 net = "%s_%s" % (comp, kind)
                 W.save_pmpw(os.path.join(out_dir, W.ref_net_name(net) + "_%d.pmpw" % args.qp), net, args.qp, w, source="the partner train_qbd validated with")
-            torch.save({"nets": {k: {n: v.detach().cpu() for n, v in net.state_dict().items()} for k, net in trainer.nets.items()},
-                        "optim": trainer.optimizer.state_dict(), "epoch": epoch, "seed": args.seed}, os.path.join(out_dir, "last.pt"))
+            last = {"nets": {k: {n: v.detach().cpu() for n, v in net.state_dict().items()} for k, net in trainer.nets.items()},
+                    "optim": trainer.optimizer.state_dict(), "epoch": epoch, "seed": args.seed}
+            if counters is not None:
+                last["guard"] = counters
+            torch.save(last, os.path.join(out_dir, "last.pt"))
         if trainer.sync is not None:
             import torch.distributed as dist
             dist.barrier()

@@ -13,7 +13,14 @@ No eager reference net runs here; torch's optimiser 
   and without it.  These are the costs a rank pays on top of its step; what a gather across GPUs costs, and so the speed-up, is NOT
   measured here - that needs a node with several GPUs.
 
+  --guard instead times what the divergence guard (--clipNorm 1 --skipNonFinite: optim.Adam's max_grad_norm and skip_nonfinite) adds
+  to a train_QBD step, in one process, and writes profiles/train_step_guard.txt: the unguarded step, the guarded step and the
+  unguarded step again, and the guard call, the guarded and the plain Adam call alone.  --root DIR imports the package from another
+  tree of this project - the parent commit's, built, to time ITS step the same way; a tree without the guard gets the unguarded
+  legs alone.  --append adds to the file, so that parent, this commit, parent stand in one file.
+
     python tools/train_step_bench.py [--n 200] [--comp Luma,Chroma] [--blocks 4096] [--iters 20] [--warmup 3] [--out FILE] [--ddp]
+           [--guard [--root DIR] [--append]]
 
 Times are hipEvent times around `iters` back-to-back calls (20 * iters for the batch and for Adam, which take microseconds) after
 `warmup` calls, a torch.cuda.synchronize() between every two legs;
@@ -25,7 +32,10 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+PACKAGE_ROOT = ROOT                         # --root DIR: the tree the package is imported from
+if "--root" in sys.argv[1:-1]:
+    PACKAGE_ROOT = os.path.abspath(sys.argv[sys.argv.index("--root") + 1])
+sys.path.insert(0, PACKAGE_ROOT)
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -120,6 +130,62 @@ def bench_ddp(eng, comp, n, blocks, warmup, iters):
             (t_sync_step, t_sync_step - min(t_plain, t_plain2), 100 * (t_sync_step / min(t_plain, t_plain2) - 1))]
 
 
+def bench_guard(eng, comp, n, blocks, warmup, iters):
+    """The train_QBD step without the guard, with it, and without it again; then the guard's calls alone on the step's gradients"""
+    from pmp_vvc_tip2023_amd.torch_call import P, run
+    luma = comp == "Luma"
+    dev = torch.device("cuda", 0)
+    files = synthetic_set(luma, blocks)[0]
+    train = dataset.DeviceDataset(eng, None, comp, 22, "Train", 2, 0, files=files)
+    d_order = dataset.permutation(blocks, True, 1, 0).cuda()
+    nb = blocks // n
+    at = [0]
+
+    def batch():
+        b = at[0] = (at[0] + 1) % nb
+        return train.gather(d_order[b * n:(b + 1) * n], n)
+
+    flags = ["--predID", "2", "--lr", "1e-4", "--batchSize", str(n)] + (["--isLuma"] if luma else [])
+    has_guard = hasattr(train_qbd, "guard_kwargs")
+    torch.manual_seed(6200 + luma)
+    plain = train_qbd.Trainer(eng, train_qbd.build_parser().parse_args(flags), comp, {}, 0)
+    t_a1 = timed(lambda: plain.step(batch()), warmup, iters); torch.cuda.synchronize()
+    head = "%s train_QBD step, n %d: gather + nets + loss + Adam" % (comp, n)
+    if not has_guard:
+        t_a2 = timed(lambda: plain.step(batch()), warmup, iters); torch.cuda.synchronize()
+        train.check()
+        return ["%-52s ms: unguarded %9.3f | unguarded again %9.3f    (runs apart by %.1f %%)   [this tree has no guard]" %
+                (head, t_a1, t_a2, 100 * abs(t_a1 - t_a2) / min(t_a1, t_a2))]
+    torch.manual_seed(6200 + luma)
+    guarded = train_qbd.Trainer(eng, train_qbd.build_parser().parse_args(flags + ["--clipNorm", "1", "--skipNonFinite"]), comp, {}, 0)
+    guarded.begin_epoch()
+    t_g = timed(lambda: guarded.step(batch()), warmup, iters); torch.cuda.synchronize()
+    t_a2 = timed(lambda: plain.step(batch()), warmup, iters); torch.cuda.synchronize()
+    state = guarded.optimizer.guard_state()
+    t_o = min(t_a1, t_a2)
+    lines = ["%-52s ms: unguarded %9.3f | --clipNorm 1 --skipNonFinite %9.3f | unguarded %9.3f    the guard adds %+.3f ms (%+.2f %%) "
+             "(the unguarded runs apart by %.1f %%)" % (head, t_a1, t_g, t_a2, t_g - t_o, 100 * (t_g / t_o - 1), 100 * abs(t_a1 - t_a2) / t_o),
+             "  the guarded steps: %d, skipped %d, clipped %d, largest gradient norm %.6g" % (state["steps"], state["skipped"], state["clipped"], state["max_norm"])]
+    # the calls alone, on the last step's gradients and on copies of the parameters and moments
+    ps = [p for net in guarded.nets.values() for p in net.parameters() if p.grad is not None]
+    gs = [p.grad for p in ps]
+    counts = [p.numel() for p in ps]
+    cp, ms, vs = ([torch.zeros_like(p) for p in ps] for _ in range(3))
+    scratch = torch.empty(eng.grad_guard_scratch_bytes(counts) // 8, dtype=torch.float64, device=dev)
+    record, counters = torch.zeros(4, dtype=torch.float64, device=dev), torch.zeros(6, dtype=torch.int64, device=dev)
+    small = 20 * iters
+    t_guard = timed(lambda: run(eng, dev, lambda: eng.grad_guard_device([P(g) for g in gs], counts, P(scratch), P(record), P(counters), max_norm=1.0,
+                                                                        skip_nonfinite=True)), warmup, small); torch.cuda.synchronize()
+    tensors = ([P(t) for t in cp], [P(g) for g in gs], [P(t) for t in ms], [P(t) for t in vs], counts, 7)
+    t_adam = timed(lambda: run(eng, dev, lambda: eng.adam_step_device(*tensors)), warmup, small); torch.cuda.synchronize()
+    t_gadam = timed(lambda: run(eng, dev, lambda: eng.adam_step_guarded_device(*tensors, P(record))), warmup, small); torch.cuda.synchronize()
+    train.check()
+    lines += ["  pmp_grad_guard_device, %d tensors, %d elements, %d tiles: %9.3f ms   (two launches)" %
+              (len(ps), sum(counts), eng.grad_guard_scratch_bytes(counts) // 16, t_guard),
+              "  pmp_adam_step_device %9.3f ms | pmp_adam_step_guarded_device %9.3f ms   (through torch_call.run, the host's time included)" % (t_adam, t_gadam)]
+    return lines
+
+
 def bench(eng, comp, n, blocks, warmup, iters):
     luma = comp == "Luma"
     files, y, u, v = synthetic_set(luma, blocks)
@@ -201,8 +267,11 @@ def main():
     ap.add_argument("--warmup", default=3, type=int)
     ap.add_argument("--out", default=None, help="the file the lines are written to (profiles/train_step.txt; with --ddp profiles/train_step_ddp.txt)")
     ap.add_argument("--ddp", action="store_true", help="time what data-parallel training adds to a step instead (one process, a one-rank RCCL group)")
+    ap.add_argument("--guard", action="store_true", help="time what the divergence guard adds to a step instead")
+    ap.add_argument("--root", default=None, help="with --guard: import the package from this tree (the parent commit's, built)")
+    ap.add_argument("--append", action="store_true", help="add to --out instead of replacing it")
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "train_step_ddp.txt" if a.ddp else "train_step.txt")
+    a.out = a.out or os.path.join(ROOT, "profiles", "train_step_ddp.txt" if a.ddp else "train_step_guard.txt" if a.guard else "train_step.txt")
     if not torch.cuda.is_available():
         raise SystemExit("train_step_bench: no GPU - there is no CPU fallback")
     eng = engine.Engine(0)
@@ -213,18 +282,22 @@ def main():
     lines = [ddp_head, ""] if a.ddp else ["a training step's ends and the whole step: the batch (pmp_batch_gather_device against host batches copied in), Adam (optim.Adam "
              "against torch.optim.Adam) and a train_QBD step, float32, hipEvents, %d calls after %d warm-up calls, %s" %
              (a.iters, a.warmup, torch.cuda.get_device_name(0)), ""]
+    if a.guard:
+        lines = ["what the divergence guard adds to a train_QBD step, one process; the package of %s; float32, hipEvents, %d calls (step) or %d calls "
+                 "(the calls alone) after %d warm-up calls, %s" % ("this tree" if PACKAGE_ROOT == ROOT else "the tree given with --root", a.iters,
+                                                                    20 * a.iters, a.warmup, torch.cuda.get_device_name(0)), ""]
     if a.ddp and a.comp == "Luma,Chroma":
         a.comp = "Luma"                                  # one process group to a process: one component to a run
     with torch.cuda.stream(torch.cuda.Stream()):        # a real stream: the library adopts it, and the events time what runs on it
         for comp in [c for c in a.comp.split(",") if c]:
             torch.cuda.synchronize()
             torch.cuda.empty_cache()
-            got = (bench_ddp if a.ddp else bench)(eng, comp, a.n, a.blocks, a.warmup, a.iters)
+            got = (bench_ddp if a.ddp else bench_guard if a.guard else bench)(eng, comp, a.n, a.blocks, a.warmup, a.iters)
             print("\n".join(got), flush=True)
             lines += got
     eng.close()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
+    with open(a.out, "a" if a.append else "w") as f:
         f.write("\n".join(lines) + "\n")
 
 
