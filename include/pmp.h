@@ -7,6 +7,7 @@
  *   pmp_infer*              <- Metrics.py:387-419   inference_pre_QBD  (Net_Q + Net_BD forward, head regrouping)
  *                              Model_QBD.py:59-253  the four Down-Up-CNN nets
  *                              Inference_QBD.py:194-200 driver tensor prep (chroma = maxpool2(Y) ++ U ++ V)
+ *   pmp_infer_q*            <- Metrics.py:198-212   pre_validation predID 0: Net_Q alone
  *   pmp_postprocess*        <- Metrics.py:764-774   seq_post_process   = eli_structual_error (Metrics.py:612-637)
  *                              + Map2Partition.py:98-373 Map_to_Partition (per-block search)
  *   pmp_infer_postprocess*  <- both, device-resident (no logits round trip): the throughput path
@@ -203,6 +204,17 @@ int pmp_infer(pmp_ctx *ctx, int comp, int qp, const uint8_t *block_y, const uint
               const uint8_t *block_v, int64_t n, float *qt, float *bt, float *dire);
 int pmp_infer_device(pmp_ctx *ctx, int comp, int qp, const uint8_t *d_block_y, const uint8_t *d_block_u,
                      const uint8_t *d_block_v, int64_t n, float *d_qt, float *d_bt, float *d_dire);
+
+/* ---- the QT net alone: what Metrics.pre_validation(val_loader, Net, 0) runs (Metrics.py:198-212), which never touches an MTT net.
+ *      pmp_infer's arguments without bt and dire.  Only the QT net of (comp, qp) has to be loaded (PMP_E_NOWEIGHTS otherwise); only its
+ *      forward graph runs.  Everything else is pmp_infer's: the context's datapath, chunking, overlap mode, the taps rules, and on the
+ *      f16x3 datapath the flag snapshot behind the call with the re-run - of the QT net alone - on the fp32 MFMA datapath.  No
+ *      calibration pass runs and no MTT partner's calibration state changes.  qt equals the qt of pmp_infer on the same blocks, bit for
+ *      bit, on all three datapaths and however the call is cut. ---- */
+int pmp_infer_q(pmp_ctx *ctx, int comp, int qp, const uint8_t *block_y, const uint8_t *block_u, const uint8_t *block_v, int64_t n,
+                float *qt);
+int pmp_infer_q_device(pmp_ctx *ctx, int comp, int qp, const uint8_t *d_block_y, const uint8_t *d_block_u, const uint8_t *d_block_v,
+                       int64_t n, float *d_qt);
 
 /* ---- post-processing: seq_post_process minus the file (Metrics.py:764-774).  qt = RAW QT logits. -------
  *      Value domain: EVERY float32 bit pattern, with the reference's results (tests/golden/g3b_m2p_range.npz, made by the reference):
@@ -408,6 +420,35 @@ int pmp_val_stats(pmp_ctx *ctx, int qp, const float *qt, const float *bt, const 
                   const int8_t *msdire, int64_t n, double stats[PMP_VAL_NSTATS]);
 int pmp_val_stats_device(pmp_ctx *ctx, int qp, const float *d_qt, const float *d_bt, const float *d_dire, const uint8_t *d_qt8,
                          const uint8_t *d_msbt, const int8_t *d_msdire, int64_t n, double *d_stats, double *d_block_stats);
+
+/* ---- validation: WHICH WAY the nets err, and how the labels are distributed.  S[13..19] above add two different errors together: a
+ *      predicted depth below the label cuts off splits the encoder can no longer try, one above it forces splits it did not want
+ *      (EncModeCtrl.cpp:2005-2015).  counts[m][l][p] is the number of cells of map m (0 qt, 1..3 bt_k, 4..6 dire_k) whose label has class
+ *      l and whose prediction has class p: the joint histogram per map.  Its diagonal over the valid classes is S[13 + m], its row sums
+ *      are the census of the labels.  Layouts, dtypes and label conversion are pmp_val_stats' (ql = float(u8(qt8 - 1)): a raw qtDepth of 0
+ *      is the label 255); there is no qp, nothing is weighted.  A prediction is r = rintf(logit): torch.round, half to even.
+ *      CLASS of a value v, label or r alike:
+ *        depth maps (qt, bt_k)   v if v is one of 0, 1, 2, 3, else 4 ("other")
+ *        direction maps          v + 1 if v is one of -1, 0, 1, else 3 ("other"); class 4 stays zero there
+ *      so -0.0 is class 0 and, on a depth map, the label 255, a label of 4 or more, a negative r, an r of 4 or more, NaN and +-inf are
+ *      all class 4.  Counts are integers: no floating-point value is added anywhere, the result is exact and depends on no order.
+ *      FORMS, the QT group (qt, qt8) and the MTT group (bt and dire, msbt and msdire) independently: logits and labels given = the
+ *      group's confusion; labels only = their CENSUS, every prediction counted as "other" (class 4, 3 on direction maps), so that the row
+ *      sums are the label counts; neither = the group's cells are zero.  PMP_E_INVALID, before any launch and with nothing written: logits
+ *      without their labels, bt without dire or msbt without msdire, no labels at all, n < 0, NULL counts, a misaligned pointer
+ *      (pmp_val_stats_device's alignments; d_counts 8-byte, d_block_counts 2-byte).  n = 0: 175 zeros, no launch.  Every element of
+ *      d_counts, and of d_block_counts if given, is written by every call; nothing is accumulated across calls.
+ *      pmp_val_confusion_device: stream-ordered, the host does not wait.  d_block_counts (may be NULL): the counts of each block on its
+ *      own, u16[n][175] (a block's cell is at most 256); d_counts is their column sum in int64.  RANGE GUARD: replayed behind a re-run
+ *      exactly as a pmp_val_stats_device call is - after pmp_synchronize the counts are those of the FINAL logits.
+ *      pmp_val_confusion: host pointers, in passes of at most pmp_set_chunk blocks; the passes' counts are added. ---- */
+#define PMP_CONF_MAPS 7        /* qt, bt0, bt1, bt2, dire0, dire1, dire2 */
+#define PMP_CONF_CLASSES 5
+#define PMP_CONF_NCOUNTS (7*5*5)
+int pmp_val_confusion(pmp_ctx *ctx, const float *qt, const float *bt, const float *dire, const uint8_t *qt8, const uint8_t *msbt,
+                      const int8_t *msdire, int64_t n, int64_t counts[PMP_CONF_NCOUNTS]);
+int pmp_val_confusion_device(pmp_ctx *ctx, const float *d_qt, const float *d_bt, const float *d_dire, const uint8_t *d_qt8,
+                             const uint8_t *d_msbt, const int8_t *d_msdire, int64_t n, int64_t *d_counts, uint16_t *d_block_counts);
 
 /* ---- training: the objective the nets are trained on and its gradient with respect to the logits, in one pass (trainloss.hip).
  *      The arithmetic of Train_QBD.loss_func_QBD (Train_QBD.py:68-90), Train_QBD.loss_func_MSBD (:44-66) and the plain L1_Loss of

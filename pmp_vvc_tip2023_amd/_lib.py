@@ -12,6 +12,7 @@ PMP_RECORD_BYTES = 1344
 PMP_MSBT_LEAF_BUDGET = 4096
 PMP_VAL_NSTATS = 20
 PMP_LOSS_NTERMS = 13
+PMP_CONF_MAPS, PMP_CONF_CLASSES, PMP_CONF_NCOUNTS = 7, 5, 175
 PMP_MSBT_INCONSISTENT, PMP_MSBT_QT_DEEP, PMP_MSBT_BUDGET = 1, 2, 4
 NET_IDS = {"Luma_Q": 0, "Luma_MSBD": 1, "Chroma_Q": 2, "Chroma_MSBD": 3}
 ERRORS = {-1: "PMP_E_INVALID", -2: "PMP_E_HIP", -3: "PMP_E_NOWEIGHTS", -4: "PMP_E_IO", -5: "PMP_E_NOMEM", -6: "PMP_E_NODEVICE", -7: "PMP_E_RANGE"}
@@ -167,6 +168,8 @@ SIGNATURES = {
     "pmp_debug_read_weights_file": (_I, [C.c_char_p, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I64), C.POINTER(C.c_double)]),
     "pmp_infer": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I64, _VP, _VP, _VP]),
     "pmp_infer_device": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I64, _VP, _VP, _VP]),
+    "pmp_infer_q": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I64, _VP]),
+    "pmp_infer_q_device": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I64, _VP]),
     "pmp_postprocess": (_I, [_VP, _I, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP]),
     "pmp_postprocess_device": (_I, [_VP, _I, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP]),
     "pmp_set_partition_params": (_I, [_VP, _I, C.POINTER(PartitionParams)]),
@@ -185,6 +188,8 @@ SIGNATURES = {
     "pmp_label_partition_records_device": (_I, [_VP, _I, _VP, _VP, _VP, _I64, _VP, _VP]),
     "pmp_val_stats": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
     "pmp_val_stats_device": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
+    "pmp_val_confusion": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
+    "pmp_val_confusion_device": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
     "pmp_parse_loss_params": (_I, [C.c_char_p, C.POINTER(LossParams)]),
     "pmp_train_loss": (_I, [_VP, _I, _I, C.POINTER(LossParams), _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP]),
     "pmp_train_loss_device": (_I, [_VP, _I, _I, C.POINTER(LossParams), _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP]),

@@ -67,6 +67,32 @@ static bool misaligned(std::initializer_list<const void *> ps, uintptr_t mask)
     return (bits & mask) != 0;
 }
 
+// The host forms of pmp_val_stats, pmp_train_loss and pmp_val_confusion, the whole call as one batch: the six inputs go through c->d_val
+// in passes (about 6.9 kB per block), launch(the pass's inputs on the device, its blocks, its row of `rows` T[passes][ncols]) per pass,
+// then the rows are copied back and added to sums[ncols] in pass order.  T: double, or int64_t for the counts.
+template <class T, class F>
+static int staged_logit_sums(pmp_ctx *c, const LogitLabels &h, int64_t n, std::initializer_list<StagedOut> outs, DevBuf &rows, int ncols,
+                             T *sums, const F &launch)
+{
+    const int64_t passes = (n + c->chunk - 1) / c->chunk;
+    int rc;
+    if ((rc = ensure(c, rows, (size_t)passes * ncols * sizeof(T)))) return rc;
+    DevBuf *d = c->d_val;
+    rc = staged_passes(c, n, {{h.qt, 64 * 4, d[0]}, {h.bt, 768 * 4, d[1]}, {h.dire, 768 * 4, d[2]}, {h.qt8, 64, d[3]}, {h.msbt, 768, d[4]}, {h.msdire, 768, d[5]}},
+                       outs, [&](int64_t m, int64_t pass) {
+                           const auto on = [&](const void *host, int i) { return host ? d[i].p : nullptr; };   // left out stays left out
+                           return launch(LogitLabels{(const float *)on(h.qt, 0), (const float *)on(h.bt, 1), (const float *)on(h.dire, 2),
+                                                     (const uint8_t *)on(h.qt8, 3), (const uint8_t *)on(h.msbt, 4), (const int8_t *)on(h.msdire, 5)},
+                                         m, (T *)rows.p + pass * ncols);
+                       });
+    if (rc != PMP_OK) return rc;
+    std::vector<T> r((size_t)passes * ncols);
+    if ((rc = d2h(c, r.data(), rows.p, r.size() * sizeof(T))) || (rc = sync_idle(c))) return rc;
+    for (int64_t p = 0; p < passes; ++p)
+        for (int i = 0; i < ncols; ++i) sums[i] += r[(size_t)p * ncols + i];
+    return PMP_OK;
+}
+
 extern "C" {
 
 // ---- training labels: GenMSBtMap (labels.hip) --------------------------------------------------------------------------
@@ -164,31 +190,6 @@ static int logit_label_args(pmp_ctx *c, const char *fn, const LogitLabels &a, in
     return PMP_OK;
 }
 
-// The host forms of pmp_val_stats and pmp_train_loss, the whole call as one batch: the six inputs go through c->d_val in passes (about
-// 6.9 kB per block), launch(the pass's inputs on the device, its blocks, its row of `rows` f64[passes][ncols]) per pass, then the rows
-// are copied back and added to sums[ncols] in pass order.
-static int staged_logit_sums(pmp_ctx *c, const LogitLabels &h, int64_t n, std::initializer_list<StagedOut> outs, DevBuf &rows, int ncols,
-                             double *sums, const std::function<int(const LogitLabels &, int64_t, double *)> &launch)
-{
-    const int64_t passes = (n + c->chunk - 1) / c->chunk;
-    int rc;
-    if ((rc = ensure(c, rows, (size_t)passes * ncols * sizeof(double)))) return rc;
-    DevBuf *d = c->d_val;
-    rc = staged_passes(c, n, {{h.qt, 64 * 4, d[0]}, {h.bt, 768 * 4, d[1]}, {h.dire, 768 * 4, d[2]}, {h.qt8, 64, d[3]}, {h.msbt, 768, d[4]}, {h.msdire, 768, d[5]}},
-                       outs, [&](int64_t m, int64_t pass) {
-                           const auto on = [&](const void *host, int i) { return host ? d[i].p : nullptr; };   // left out stays left out
-                           return launch(LogitLabels{(const float *)on(h.qt, 0), (const float *)on(h.bt, 1), (const float *)on(h.dire, 2),
-                                                     (const uint8_t *)on(h.qt8, 3), (const uint8_t *)on(h.msbt, 4), (const int8_t *)on(h.msdire, 5)},
-                                         m, (double *)rows.p + pass * ncols);
-                       });
-    if (rc != PMP_OK) return rc;
-    std::vector<double> r((size_t)passes * ncols);
-    if ((rc = d2h(c, r.data(), rows.p, r.size() * sizeof(double))) || (rc = sync_idle(c))) return rc;
-    for (int64_t p = 0; p < passes; ++p)
-        for (int i = 0; i < ncols; ++i) sums[i] += r[(size_t)p * ncols + i];
-    return PMP_OK;
-}
-
 namespace {
 struct ValArgs {
     LogitLabels in;
@@ -253,6 +254,73 @@ int pmp_val_stats(pmp_ctx *c, int qp, const float *qt, const float *bt, const fl
     if ((rc = settle_before_host_call(c))) return rc;
     return staged_logit_sums(c, a.in, n, {}, c->d_valout, PMP_VAL_NSTATS, stats, [&](const LogitLabels &dev, int64_t m, double *row) {
         return val_launch(c, ValArgs{dev, m, a.w, row, nullptr});
+    });
+}
+
+// ---- confusion counts (logitstats.hip): per map the joint histogram of (label class, predicted class) ---------------------------
+namespace {
+struct ConfArgs {
+    LogitLabels in;
+    int64_t n;
+    int64_t *counts;
+    uint16_t *block_counts;            // null: the context's scratch, looked up at launch (a replay may find it regrown)
+};
+}  // namespace
+
+// The forms pmp_val_confusion* take: a group is its labels with or without its logits, and at least one group's labels are there
+static int conf_check(pmp_ctx *c, const ConfArgs &a)
+{
+    if (a.n < 0 || !a.counts) return set_err(c, PMP_E_INVALID, "pmp_val_confusion: negative count or null counts");
+    if (a.n == 0) return PMP_OK;
+    const LogitLabels &i = a.in;
+    if ((i.qt && !i.qt8) || ((i.bt || i.dire) && !(i.msbt && i.msdire)))
+        return set_err(c, PMP_E_INVALID, "pmp_val_confusion: logits without their labels");
+    if (!i.bt != !i.dire || !i.msbt != !i.msdire)
+        return set_err(c, PMP_E_INVALID, "pmp_val_confusion: bt goes with dire, msbt with msdire");
+    if (!i.qt8 && !i.msbt) return set_err(c, PMP_E_INVALID, "pmp_val_confusion: no labels: pass qt8, (msbt, msdire) or both");
+    return PMP_OK;
+}
+
+static int conf_launch(pmp_ctx *c, const ConfArgs &a)
+{
+    uint16_t *part = a.block_counts;
+    if (!part) {
+        const int rc = ensure(c, c->d_confpart, (size_t)a.n * PMP_CONF_NCOUNTS * sizeof(uint16_t));
+        if (rc != PMP_OK) return rc;
+        part = (uint16_t *)c->d_confpart.p;
+    }
+    return hip_rc(c, launch_val_confusion(c->stream, a.in, a.n, part, a.counts), "val_confusion");
+}
+
+int pmp_val_confusion_device(pmp_ctx *c, const float *qt, const float *bt, const float *dire, const uint8_t *qt8, const uint8_t *msbt,
+                             const int8_t *msdire, int64_t n, int64_t *counts, uint16_t *block_counts)
+{
+    CHECK_CTX(c);
+    const ConfArgs a{{qt, bt, dire, qt8, msbt, msdire}, n, counts, block_counts};
+    int rc;
+    if ((rc = conf_check(c, a))) return rc;
+    if (misaligned({counts}, 7) || misaligned({block_counts}, 1) || (n > 0 && (misaligned({bt, dire}, 15) || misaligned({qt, msbt, msdire}, 3))))
+        return set_err(c, PMP_E_INVALID, "pmp_val_confusion_device: bt, dire must be 16-byte aligned, qt, msbt, msdire 4-byte, d_counts 8-byte, d_block_counts 2-byte");
+    if (n == 0) return hip_rc(c, hipMemsetAsync(counts, 0, PMP_CONF_NCOUNTS * sizeof(int64_t), c->stream), "val_confusion");
+    rc = conf_launch(c, a);
+    // as a statistics call: behind an inference call whose range flag has not been looked at yet, remembered for the replay
+    if (rc == PMP_OK && !c->pending.empty())
+        c->pending.push_back(PendingCall{false, false, nullptr, nullptr, [=](bool) { return conf_launch(c, a); }});
+    return rc;
+}
+
+int pmp_val_confusion(pmp_ctx *c, const float *qt, const float *bt, const float *dire, const uint8_t *qt8, const uint8_t *msbt,
+                      const int8_t *msdire, int64_t n, int64_t counts[PMP_CONF_NCOUNTS])
+{
+    CHECK_CTX(c);
+    const ConfArgs a{{qt, bt, dire, qt8, msbt, msdire}, n, counts, nullptr};
+    int rc;
+    if ((rc = conf_check(c, a))) return rc;
+    for (int i = 0; i < PMP_CONF_NCOUNTS; ++i) counts[i] = 0;
+    if (n == 0) return PMP_OK;
+    if ((rc = settle_before_host_call(c))) return rc;
+    return staged_logit_sums(c, a.in, n, {}, c->d_confout, PMP_CONF_NCOUNTS, counts, [&](const LogitLabels &dev, int64_t m, int64_t *row) {
+        return conf_launch(c, ConfArgs{dev, m, row, nullptr});
     });
 }
 

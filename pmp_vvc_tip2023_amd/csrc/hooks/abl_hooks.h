@@ -10,7 +10,7 @@ inline void abl_on_create() {}                                                  
 inline bool abl_set_conv_variant(int, int *) { return false; }                         // true: handled, *rc is the answer
 inline bool abl_set_winograd(pmp_ctx *, int, int *) { return false; }
 inline unsigned abl_pack_mask(const pmp_ctx *) { return 0u; }                          // extra weight formats to pack at load
-inline int abl_prepare_pass(pmp_ctx *, int, NetWeights &, NetWeights &) { return PMP_OK; }   // ... and before the passes of a call on a datapath
+inline int abl_prepare_pass(pmp_ctx *, int, NetWeights &, NetWeights *) { return PMP_OK; }   // ... and before the passes of a call on a datapath
 inline void abl_conv_args(const pmp_ctx *, const RBWeights &, bool, ConvX6Args &) {}   // extra arguments of one convolution launch
 inline int abl_pack_rb(const float *, const float *, int, int, int, unsigned, RBWeights &,
                        const std::function<int(const std::vector<unsigned short> &, unsigned short **)> &) { return PMP_OK; }

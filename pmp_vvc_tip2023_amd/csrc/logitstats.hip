@@ -21,6 +21,9 @@
 // share the loads, the weights and the terms (load_qt, load_layer, cell_terms, LayerSums), so for PMP_LUMA the thirteen sums are
 // pmp_val_stats' first thirteen, bit for bit.
 //
+// pmp_val_confusion counts instead of adding: per map the joint histogram of (label class, class of rintf(logit)), 7 x 5 x 5 integers
+// (include/pmp.h).  No floating-point value is added anywhere in it, so its bits depend on no order at all.
+//
 // Sums are float64 in a fixed order, without atomics:
 //   val_block_kernel    one wavefront per block.  Lane l holds qt cell l and, of each of the three 16x16 maps, cells 4l..4l+3
 //                       (one 16-byte load per logit map, one 4-byte load per label map): 12 bt and 12 dire cells.  A lane adds its
@@ -31,6 +34,15 @@
 //                       gradient map and lane (4 bytes for the qt map, which has one cell per lane).  A gradient is computed in
 //                       float64 from the float32 w, the double lambdas and the sign of the float32 term, left to right as
 //                       include/pmp.h writes it, and rounded once to float32.  Every cell is written.
+//   confusion_block_kernel  the third block kernel: the same wavefront per block and the same cells per lane, through the same load_qt /
+//                       load_layer.  The 175 cells are counted in an LDS histogram with integer LDS atomics (ds_add_u32: integer
+//                       addition commutes, so the counts are exact whatever order the lanes arrive in; ballot + popcount would give the
+//                       same bits at 25 ballots per cell), in eight copies that spread the lanes' turns at one word.  Lanes j,
+//                       j + 64, j + 128 < 175 store cell j of the block's row: u16[n][175] (a block's cell is at most 256).  Labels
+//                       without logits (the census) count every prediction as "other".
+//   sum_counts_kernel   the rows' column sums in int64: 7 maps x 32 row slices of workgroups, each 16 row groups x 25 columns (the
+//                       shape of sum_rows_kernel), a slice's sums added to the call's counts with int64 vector atomics - integers again,
+//                       so the same bits in any order.
 //   sum_rows_kernel     one workgroup of 16 row groups x NC columns: 320 threads for the 20 statistics, 208 for the 13 sums.
 //                       Thread (g, s) adds rows g, g + 16, g + 32, ... in order (its loads are coalesced: address = thread + 16 NC j),
 //                       then thread s adds the 16 group partials in order; for the 13 sums thread 0 then forms the loss
@@ -80,20 +92,26 @@ struct Layer {
     float xb[4], xd[4], bl[4], dl[4], w[4];                                  // cells 4 lane .. 4 lane + 3 of layer k: logits, labels, weight
 };
 
-__device__ __forceinline__ Layer load_layer(const LogitLabels &p, int64_t b, int k, int lane, const LogitWeights &lw)
+// the labels of cells 4 lane .. 4 lane + 3 of layer k, and the weight they give
+__device__ __forceinline__ void load_layer_labels(const LogitLabels &p, int64_t at, int k, int lane, const LogitWeights &lw, Layer &y)
 {
-    const int64_t at = (b * 3 + k) * 256;
-    const float4 vb = reinterpret_cast<const float4 *>(p.bt + at)[lane];
-    const float4 vd = reinterpret_cast<const float4 *>(p.dire + at)[lane];
     const uint32_t ub = reinterpret_cast<const uint32_t *>(p.msbt + at)[lane];
     const uint32_t ud = reinterpret_cast<const uint32_t *>(p.msdire + at)[lane];
-    Layer y = {{vb.x, vb.y, vb.z, vb.w}, {vd.x, vd.y, vd.z, vd.w}, {}, {}, {}};
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         y.bl[c] = (float)((ub >> (8 * c)) & 255u);
         y.dl[c] = (float)(int8_t)((ud >> (8 * c)) & 255u);
         y.w[c] = (k == 0 && lw.w0_one) ? 1.0f : y.dl[c] * y.dl[c] + lw.wm[k];
     }
+}
+
+__device__ __forceinline__ Layer load_layer(const LogitLabels &p, int64_t b, int k, int lane, const LogitWeights &lw)
+{
+    const int64_t at = (b * 3 + k) * 256;
+    const float4 vb = reinterpret_cast<const float4 *>(p.bt + at)[lane];
+    const float4 vd = reinterpret_cast<const float4 *>(p.dire + at)[lane];
+    Layer y = {{vb.x, vb.y, vb.z, vb.w}, {vd.x, vd.y, vd.z, vd.w}, {}, {}, {}};
+    load_layer_labels(p, at, k, lane, lw, y);
     return y;
 }
 
@@ -228,6 +246,83 @@ __global__ __launch_bounds__(64) void train_block_kernel(LogitLabels p, int64_t 
     store_row(s, lane, out + b * NT);
 }
 
+// ---- the confusion counts: class of a label or of a rounded logit (both hold an integer, NaN or +-inf) -----------------------------
+constexpr int NCC = PMP_CONF_CLASSES, NMC = NCC * NCC, NCNT = PMP_CONF_NCOUNTS;   // 5 classes, 25 cells per map, 175 per block
+constexpr int HC = 8;                                                           // copies of a block's histogram in LDS
+__device__ __forceinline__ int depth_class(float v) { return (v >= 0.f && v <= 3.f) ? (int)v : 4; }       // -0.0 is 0; NaN fails both
+__device__ __forceinline__ int dire_class(float v) { return (v >= -1.f && v <= 1.f) ? (int)v + 1 : 3; }
+
+// A group given without its logits (p.qt, p.bt null) is the labels' census: every prediction is NaN, the class "other"
+// zero: the call's counts i64[175], cleared here by the first block of the call's first grid for sum_counts_kernel to add into; else null
+__global__ __launch_bounds__(64) void confusion_block_kernel(LogitLabels p, int64_t n, uint16_t *__restrict__ out, int64_t *__restrict__ zero)
+{
+    const int64_t b = blockIdx.x;
+    if (b >= n) return;
+    const int lane = threadIdx.x;
+    if (zero && b == 0)
+        for (int j = lane; j < NCNT; j += 64) zero[j] = 0;
+    // eight copies of the histogram, lane l counting in copy l % 8: labels crowd into a few cells, and lanes that add to one LDS word
+    // take turns (one copy against eight: profiles/val_confusion.txt)
+    __shared__ unsigned hist[HC][NCNT];
+    for (int j = lane; j < HC * NCNT; j += 64) (&hist[0][0])[j] = 0u;
+    __syncthreads();
+    unsigned *h = hist[lane % HC];
+    const float other = __builtin_nanf("");
+    if (p.qt8) {
+        QtCell q = {other, 0.f};
+        if (p.has_q()) q = load_qt(p, b, lane);
+        else q.ql = (float)(uint8_t)(p.qt8[b * 64 + lane] - 1);
+        atomicAdd(&h[depth_class(q.ql) * NCC + depth_class(rintf(q.x))], 1u);
+    }
+    if (p.msbt) {
+        const LogitWeights none = {{0.f, 0.f, 0.f}, 0};                      // nothing here is weighted
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            Layer y = {{other, other, other, other}, {other, other, other, other}, {}, {}, {}};
+            if (p.has_m()) y = load_layer(p, b, k, lane, none);
+            else load_layer_labels(p, (b * 3 + k) * 256, k, lane, none, y);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                atomicAdd(&h[(1 + k) * NMC + depth_class(y.bl[c]) * NCC + depth_class(rintf(y.xb[c]))], 1u);
+                atomicAdd(&h[(4 + k) * NMC + dire_class(y.dl[c]) * NCC + dire_class(rintf(y.xd[c]))], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    for (int j = lane; j < NCNT; j += 64) {
+        unsigned v = 0u;
+#pragma unroll
+        for (int k = 0; k < HC; ++k) v += hist[k][j];
+        out[b * NCNT + j] = (uint16_t)v;
+    }
+}
+
+// counts[m][..] += the column sums of a slice of the rows u16[n][175]: workgroup (map m, slice z) = blockIdx (x, y), thread (g, s) adds
+// rows 16 z + g, + 16 CS, + 32 CS, ..., thread s the 16 groups and then, with one int64 vector atomic, the slice into counts (zeroed by the
+// block kernel).  With one workgroup per map - 2-byte gathers on 7 CUs - a call on 4096 blocks took 76 us, not 12 (profiles/val_confusion.txt).
+constexpr int CS = 32;                                                          // row slices of the column sum
+__global__ __launch_bounds__(RG * NMC) void sum_counts_kernel(const uint16_t *__restrict__ part, int64_t n, unsigned long long *__restrict__ counts)
+{
+    __shared__ int64_t sh[RG * NMC];
+    const int t = threadIdx.x, col = blockIdx.x * NMC + t % NMC;
+    int64_t a = 0;
+    for (int64_t r = (int64_t)blockIdx.y * RG + t / NMC; r < n; r += 8 * RG * CS) {   // eight loads in flight
+        unsigned v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const int64_t k = r + (int64_t)j * RG * CS; v[j] = k < n ? (unsigned)part[k * NCNT + col] : 0u; }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) a += (int64_t)v[j];
+    }
+    sh[t] = a;
+    __syncthreads();
+    if (t < NMC) {
+        int64_t r = sh[t];
+#pragma unroll
+        for (int g = 1; g < RG; ++g) r += sh[g * NMC + t];
+        if (r) atomicAdd(&counts[col], (unsigned long long)r);
+    }
+}
+
 // ---- the fixed-order sum of the block rows ------------------------------------------------------------------------------------
 template <int NC>
 __global__ __launch_bounds__(RG * NC) void sum_rows_kernel(const double *__restrict__ part, int64_t n, double *__restrict__ sums,
@@ -276,6 +371,17 @@ hipError_t launch_val_stats(hipStream_t st, const LogitLabels &in, int64_t N, co
         hipLaunchKernelGGL(val_block_kernel, dim3((unsigned)m), dim3(64), 0, st, in.from(o), m, lw, block_stats + o * NS);
     });
     hipLaunchKernelGGL(sum_rows_kernel<NS>, dim3(1), dim3(RG * NS), 0, st, block_stats, N, stats, pmp_loss_params{}, (int64_t)0, nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_val_confusion(hipStream_t st, const LogitLabels &in, int64_t N, uint16_t *block_counts, int64_t *counts)
+{
+    for_grids(N, [&](int64_t o, int64_t m) {
+        hipLaunchKernelGGL(confusion_block_kernel, dim3((unsigned)m), dim3(64), 0, st, in.from(o), m, block_counts + o * NCNT,
+                           o == 0 ? counts : nullptr);
+    });
+    hipLaunchKernelGGL(sum_counts_kernel, dim3(PMP_CONF_MAPS, CS), dim3(RG * NMC), 0, st, block_counts, N,
+                       reinterpret_cast<unsigned long long *>(counts));
     return hipGetLastError();
 }
 

@@ -63,14 +63,15 @@ static int post_device_impl(pmp_ctx *c, int comp, const float *qt, const float *
 
 // The context's own logit buffers (fused entry points called without logit pointers, host-pointer entry points).  Calls still in
 // flight may hold pointers into them for a range-guard re-run: they are settled BEFORE a buffer is regrown (and thereby freed).
-int ensure_logits(pmp_ctx *c, int64_t n)
+int ensure_logits(pmp_ctx *c, int64_t n, bool qt_only)
 {
-    const size_t need[3] = {(size_t)(n ? n : 1) * 64 * 4, (size_t)(n ? n : 1) * 768 * 4, (size_t)(n ? n : 1) * 768 * 4};
+    const size_t rest = qt_only ? 0 : (size_t)(n ? n : 1) * 768 * 4;         // pmp_infer_q: no bt and dire buffers, 6 KB a block
+    const size_t need[3] = {(size_t)(n ? n : 1) * 64 * 4, rest, rest};
     int rc;
     if ((need[0] > c->d_logit[0].cap || need[1] > c->d_logit[1].cap || need[2] > c->d_logit[2].cap) && !c->pending.empty() &&
         (rc = settle(c)) != PMP_OK)
         return rc;
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < (qt_only ? 1 : 3); ++i) {
         if ((rc = ensure(c, c->d_logit[i], need[i])) != PMP_OK) return rc;
         if (c->poison) {          // pmp_debug_poison_workspace: whoever uses them next must write every byte it later reads
             const hipError_t e = hipMemsetAsync(c->d_logit[i].p, poison_byte(c), need[i], c->stream);
@@ -377,6 +378,12 @@ int pmp_infer_device(pmp_ctx *c, int comp, int qp, const uint8_t *by, const uint
     return infer_device_impl(c, comp, qp, by, bu, bv, n, qt, bt, dire);
 }
 
+int pmp_infer_q_device(pmp_ctx *c, int comp, int qp, const uint8_t *by, const uint8_t *bu, const uint8_t *bv, int64_t n, float *qt)
+{
+    CHECK_CTX(c);
+    return infer_device_impl(c, comp, qp, by, bu, bv, n, qt, nullptr, nullptr, false, nullptr, true);
+}
+
 int pmp_postprocess_device(pmp_ctx *c, int comp, const float *qt, const float *bt, const float *dire, int64_t n,
                            uint8_t *hor, uint8_t *ver, uint8_t *qt_u8, int8_t *dire_i8)
 {
@@ -445,6 +452,25 @@ int pmp_infer(pmp_ctx *c, int comp, int qp, const uint8_t *by, const uint8_t *bu
     if ((rc = d2h(c, qt, dq, (size_t)n * 64 * 4)) || (rc = d2h(c, bt, db, (size_t)n * 768 * 4)) ||
         (rc = d2h(c, dire, dd, (size_t)n * 768 * 4)))
         return rc;
+    return sync_idle(c);
+}
+
+int pmp_infer_q(pmp_ctx *c, int comp, int qp, const uint8_t *by, const uint8_t *bu, const uint8_t *bv, int64_t n, float *qt)
+{
+    CHECK_CTX(c);
+    if (n < 0 || !by || !qt || (comp == PMP_CHROMA && (!bu || !bv)))
+        return set_err(c, PMP_E_INVALID, "pmp_infer_q: null buffer or negative count");
+    if (n == 0) return PMP_OK;
+    int rc;
+    if ((rc = settle_before_host_call(c))) return rc;
+    if ((rc = stage_blocks(c, comp, by, bu, bv, n))) return rc;
+    if ((rc = ensure_logits(c, n, true))) return rc;
+    float *dq = (float *)c->d_logit[0].p;
+    if ((rc = infer_device_impl(c, comp, qp, (const uint8_t *)c->d_in[0].p, (const uint8_t *)c->d_in[1].p,
+                                (const uint8_t *)c->d_in[2].p, n, dq, nullptr, nullptr, true, nullptr, true)))
+        return rc;
+    if ((rc = resolve_pending(c, true))) return rc;      // range guard: a re-run is enqueued before the copy below
+    if ((rc = d2h(c, qt, dq, (size_t)n * 64 * 4))) return rc;
     return sync_idle(c);
 }
 

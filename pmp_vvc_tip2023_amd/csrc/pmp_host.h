@@ -253,6 +253,8 @@ struct pmp_ctx {
     pmp::DevBuf d_val[6];                  // staging of pmp_val_stats: qt, bt, dire, qt8, msbt, msdire
     pmp::DevBuf d_valpart;                 // validation statistics: per-block partials f64[n][20] of a call that passes no d_block_stats
     pmp::DevBuf d_valout;                  // pmp_val_stats: f64[passes][20]
+    pmp::DevBuf d_confpart;                // confusion counts: per-block rows u16[n][175] of a call that passes no d_block_counts
+    pmp::DevBuf d_confout;                 // pmp_val_confusion: i64[passes][175]
     pmp::DevBuf d_train[3];                // staging of pmp_train_loss's gradients: g_qt, g_bt, g_dire (its inputs go through d_val)
     pmp::DevBuf d_trainpart;               // training losses: per-block partials f64[n][13]
     pmp::DevBuf d_trainout;                // pmp_train_loss: f64[passes][13]
@@ -294,7 +296,7 @@ constexpr int PMP_CAL_SLOTS = 128;
 int ensure(pmp_ctx *c, DevBuf &b, size_t bytes);                    // grow-only device buffer
 int fence_wait(pmp_ctx *c);                                         // c->stream waits, on the device, for the fence of the stream the context left
 NetWeights *find_net(pmp_ctx *c, int net_id, int qp);               // loaded weights of (net, qp) or nullptr
-int ensure_logits(pmp_ctx *c, int64_t n);                           // the context's own logit buffers, settled before one is regrown
+int ensure_logits(pmp_ctx *c, int64_t n, bool qt_only = false);     // the context's own logit buffers (qt_only: the first alone), settled before one is regrown
 int stage_blocks(pmp_ctx *c, int comp, const uint8_t *by, const uint8_t *bu, const uint8_t *bv, int64_t n);   // host blocks -> c->d_in
 int h2d(pmp_ctx *c, DevBuf &b, const void *src, size_t bytes);      // ensure + copy on c->stream
 int d2h(pmp_ctx *c, void *dst, const void *src, size_t bytes);      // copy on c->stream; nothing for a null dst
@@ -302,7 +304,7 @@ inline int poison_byte(const pmp_ctx *c) { return c->poison == 1 ? 0xFF : 0x3C; 
 // range_guard.cpp
 int run_graph(pmp_ctx *c, Pass &ps, const std::function<int()> &fwd);   // a forward graph twice: measuring pass, then the real one in ps.ws
 int infer_device_impl(pmp_ctx *c, int comp, int qp, const uint8_t *by, const uint8_t *bu, const uint8_t *bv, int64_t n, float *qt,
-                      float *bt, float *dire, bool ctx_logits = false, const float *qt_in = nullptr);
+                      float *bt, float *dire, bool ctx_logits = false, const float *qt_in = nullptr, bool q_only = false);
 int resolve_pending(pmp_ctx *c, bool wait);                         // looks at the flag snapshots in flight: re-runs and replays
 void drop_pending(pmp_ctx *c);
 int sat_fetch(pmp_ctx *c, unsigned *out);                           // reads and clears the device flag word (synchronises)

@@ -233,6 +233,11 @@ struct LogitWeights {
 // their fixed-order sum stats f64[20].  lw: the luma matrix.  N >= 1.
 hipError_t launch_val_stats(hipStream_t s, const LogitLabels &in, int64_t N, const LogitWeights &lw, double *block_stats, double *stats);
 
+// Confusion counts (include/pmp.h: pmp_val_confusion): block_counts u16[N][175] (always written: the caller's buffer or scratch) and
+// their column sums counts i64[175].  A group is counted if its LABELS are given (in.qt8; in.msbt, in.msdire); without its logits it is
+// the labels' census.  N >= 1.
+hipError_t launch_val_confusion(hipStream_t s, const LogitLabels &in, int64_t N, uint16_t *block_counts, int64_t *counts);
+
 // Training losses and their logit gradients (include/pmp.h: pmp_train_loss): block_terms f64[N][13] (scratch, always written), their
 // fixed-order sum terms f64[13] and, if loss != null, train_loss_value(terms, L, n_div).  Every cell of the gradients given is
 // written.  n_div: the block count in the gradients' divisors 64 n and 256 n (the whole call's, where N is one pass of it).  N >= 1.

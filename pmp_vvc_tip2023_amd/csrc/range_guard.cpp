@@ -90,15 +90,16 @@ int run_graph(pmp_ctx *c, Pass &ps, const std::function<int()> &fwd)
 }
 
 // The passes of one inference call on datapath `precision`; taps: record its tensors (pmp_debug_set_taps).
-static int infer_passes(pmp_ctx *c, int precision, bool taps, bool luma, NetWeights &wq, NetWeights &wb, const uint8_t *by, const uint8_t *bu,
+static int infer_passes(pmp_ctx *c, int precision, bool taps, bool luma, NetWeights &wq, NetWeights *wbp, const uint8_t *by, const uint8_t *bu,
                         const uint8_t *bv, int64_t n, float *qt, float *bt, float *dire, const float *qt_in = nullptr)
 {
     // qt_in: teacher-forced MTT inference (pmp_infer_msbd) - the MTT net reads this map, the QT net does not run, qt is not written
+    // wbp null: the QT net alone (pmp_infer_q) - no MTT net is looked at, packed, calibrated or run, bt and dire are not written
     int rc0;     // weights are packed per datapath, on first use (the load packed the datapath that was current then)
-    if ((rc0 = ensure_datapath(c, wq, precision)) != PMP_OK || (rc0 = ensure_datapath(c, wb, precision)) != PMP_OK) return rc0;
+    if ((rc0 = ensure_datapath(c, wq, precision)) != PMP_OK || (wbp && (rc0 = ensure_datapath(c, *wbp, precision)) != PMP_OK)) return rc0;
     // f16x3: the MTT net's activation scales, from one calibration pass when the net is first used on this datapath
-    if (precision == PMP_PRECISION_F16X3 && c->act_scales && !wb.calibrated && (rc0 = calibrate_mtt(c, luma, wq, wb)) != PMP_OK) return rc0;
-    if ((rc0 = abl_prepare_pass(c, precision, wq, wb)) != PMP_OK) return rc0;
+    if (wbp && precision == PMP_PRECISION_F16X3 && c->act_scales && !wbp->calibrated && (rc0 = calibrate_mtt(c, luma, wq, *wbp)) != PMP_OK) return rc0;
+    if ((rc0 = abl_prepare_pass(c, precision, wq, wbp)) != PMP_OK) return rc0;
     // Overlap mode: a call of at least 1024 blocks runs as (at least) two chunks, even ones on the context's stream and workspace, odd
     // ones on a second stream with a second workspace, so that one chunk's small launches (stems, 16x16 tails, HBM-bound 32x32 layers)
     // run beside the other's 64x64 convolutions.  Blocks are independent: the results do not depend on how a call is cut.
@@ -124,7 +125,7 @@ static int infer_passes(pmp_ctx *c, int precision, bool taps, bool luma, NetWeig
         const bool side = overlap && (k & 1);
         Pass ps{side ? c->stream2.h : c->stream, side ? c->ws2 : c->ws, precision, taps, /*cal*/ false, /*caller*/ true};
         if (!qt_in) rc = run_graph(c, ps, [&] { return forward_q(c, ps, luma, wq, y, u, v, m, q); });
-        if (rc == PMP_OK) rc = run_graph(c, ps, [&] { return forward_msbd(c, ps, luma, wb, y, u, v, qi, m, bt + o * 768, dire + o * 768); });
+        if (rc == PMP_OK && wbp) rc = run_graph(c, ps, [&] { return forward_msbd(c, ps, luma, *wbp, y, u, v, qi, m, bt + o * 768, dire + o * 768); });
     }
     if (overlap) {
         hipEvent_t ev = c->event_pool.get();
@@ -207,23 +208,25 @@ int resolve_pending(pmp_ctx *c, bool wait)
 }
 
 int infer_device_impl(pmp_ctx *c, int comp, int qp, const uint8_t *by, const uint8_t *bu, const uint8_t *bv, int64_t n, float *qt,
-                      float *bt, float *dire, bool ctx_logits, const float *qt_in)
+                      float *bt, float *dire, bool ctx_logits, const float *qt_in, bool q_only)
 {
-    if (comp != PMP_LUMA && comp != PMP_CHROMA) return set_err(c, PMP_E_INVALID, "pmp_infer: comp must be PMP_LUMA or PMP_CHROMA");
-    if (n < 0 || !by || (!qt && !qt_in) || !bt || !dire || (comp == PMP_CHROMA && (!bu || !bv)))
-        return set_err(c, PMP_E_INVALID, "pmp_infer: null buffer or negative count");
+    const std::string fn = q_only ? "pmp_infer_q" : "pmp_infer";          // the entry point family the messages name
+    if (comp != PMP_LUMA && comp != PMP_CHROMA) return set_err(c, PMP_E_INVALID, fn + ": comp must be PMP_LUMA or PMP_CHROMA");
+    if (n < 0 || !by || (!qt && !qt_in) || (!q_only && (!bt || !dire)) || (comp == PMP_CHROMA && (!bu || !bv)))
+        return set_err(c, PMP_E_INVALID, fn + ": null buffer or negative count");
     const bool luma = comp == PMP_LUMA;
     const int id_q = luma ? PMP_NET_LUMA_Q : PMP_NET_CHROMA_Q, id_b = luma ? PMP_NET_LUMA_MSBD : PMP_NET_CHROMA_MSBD;
     NetWeights *wq = find_net(c, id_q, qp);
-    NetWeights *wb = find_net(c, id_b, qp);
-    if (!wq || !wb) return set_err(c, PMP_E_NOWEIGHTS, "pmp_infer: weights for this (comp, qp) are not loaded");
+    NetWeights *wb = q_only ? nullptr : find_net(c, id_b, qp);            // pmp_infer_q needs the QT net alone
+    if (!wq || (!q_only && !wb))
+        return set_err(c, PMP_E_NOWEIGHTS, fn + (q_only ? ": the QT net of this (comp, qp) is not loaded" : ": weights for this (comp, qp) are not loaded"));
     if (c->taps_on && (n > c->chunk || n > PMP_TAP_MAX_BLOCKS || c->overlap))
-        return set_err(c, PMP_E_INVALID, "pmp_infer: with taps on, one pass of at most 64 blocks (n <= chunk) and overlap mode off");
+        return set_err(c, PMP_E_INVALID, fn + ": with taps on, one pass of at most 64 blocks (n <= chunk) and overlap mode off");
     int rc = resolve_pending(c, false);          // earlier calls whose snapshot has landed by now: no wait
     if (rc != PMP_OK) return rc;
     if (c->taps_on) c->ntaps = 0;                // the taps are this call's (a re-run resolved above is recorded by nobody)
     const int precision = c->precision;          // the datapath at enqueue: a re-run that did not fire runs on it again
-    rc = infer_passes(c, precision, c->taps_on != 0, luma, *wq, *wb, by, bu, bv, n, qt, bt, dire, qt_in);
+    rc = infer_passes(c, precision, c->taps_on != 0, luma, *wq, wb, by, bu, bv, n, qt, bt, dire, qt_in);
     if (rc != PMP_OK || precision != PMP_PRECISION_F16X3 || c->sat_policy == PMP_SAT_IGNORE || n == 0) return rc;
     // f16x3 range guard: snapshot the flag behind this call's passes and reset it for the next call - all stream-ordered, the host
     // does not wait.  Whoever looks at the snapshot later (resolve_pending) re-runs the call on the fp32 MFMA datapath if it fired.
@@ -236,13 +239,13 @@ int infer_device_impl(pmp_ctx *c, int comp, int qp, const uint8_t *by, const uin
     if (e == hipSuccess) e = hipEventRecord(ev, c->stream);
     if (e != hipSuccess) { c->event_pool.put(ev); return hip_fail(c, e, "saturation flag snapshot"); }
     c->pending.push_back(PendingCall{true, ctx_logits, ev, slot, [=](bool fired) {
-        NetWeights *rq = find_net(c, id_q, qp), *rb = find_net(c, id_b, qp);   // replacing a net settles first: still the same nets
-        if (!rq || !rb) return set_err(c, PMP_E_NOWEIGHTS, "pmp_infer: weights vanished before the range-guard re-run");
+        NetWeights *rq = find_net(c, id_q, qp), *rb = q_only ? nullptr : find_net(c, id_b, qp);   // replacing a net settles first: still the same nets
+        if (!rq || (!q_only && !rb)) return set_err(c, PMP_E_NOWEIGHTS, fn + ": weights vanished before the range-guard re-run");
         // fired: the exact fp32 MFMA datapath - fp32's range, a bit-exact fmaf chain, and on the full-size campaign the closest of the
         // three to the oracle (profiles/r03_parity_campaign.txt: 5.5e-4 against bf16x6's 8.9e-4 on the worst block); its speed does not
         // matter for a call that is this rare.  Not fired: the call's logits were in the context's buffers, which an earlier re-run has
         // overwritten - the same call again, on the datapath it ran on.  No taps: pmp_debug_set_taps records the call as it first ran.
-        return infer_passes(c, fired ? PMP_PRECISION_F32 : precision, false, luma, *rq, *rb, by, bu, bv, n, qt, bt, dire, qt_in);   // teacher-forced: the MTT net only
+        return infer_passes(c, fired ? PMP_PRECISION_F32 : precision, false, luma, *rq, rb, by, bu, bv, n, qt, bt, dire, qt_in);   // teacher-forced: the MTT net only; q_only: the QT net only
     }});
     return PMP_OK;
 }

@@ -182,17 +182,23 @@ class Engine:
     def has_weights(self, net, qp):
         return bool(self.lib.pmp_has_weights(self.h, _lib.NET_IDS[net], int(qp)))
 
-    def check_available(self, comp, qp):
+    def check_available(self, comp, qp, kinds=("Q", "MSBD")):
         """Raise FileNotFoundError now if load(comp, qp) would: the driver loads weights lazily, next to the GPU's work, but a
-        missing model file must stop the job before any output (Inference_QBD.py:219-222)."""
-        for kind in ("Q", "MSBD"):
+        missing model file must stop the job before any output (Inference_QBD.py:219-222).  kinds = ("Q",): what load_q needs."""
+        for kind in kinds:
             net = "%s_%s" % (comp, kind)
             if not self.has_weights(net, qp):
                 W.find_net_weights(net, qp, self.weight_dir, allow_synthetic=self.allow_synthetic_mtt)
 
-    def load(self, comp, qp, q_weights=None, msbd_weights=None):
-        """Load both nets of (comp, qp); missing dicts are resolved by weights.load_net_weights()."""
+    def load_q(self, comp, qp, q_weights=None):
+        """Load the QT net of (comp, qp) alone: all that infer_q and pre_validation(pred_id=0) need.  No *_BD_* file is looked for."""
+        self.load(comp, qp, q_weights=q_weights, kinds=("Q",))
+
+    def load(self, comp, qp, q_weights=None, msbd_weights=None, kinds=("Q", "MSBD")):
+        """Load both nets of (comp, qp); missing dicts are resolved by weights.load_net_weights().  kinds: the nets to load."""
         for kind, given in (("Q", q_weights), ("MSBD", msbd_weights)):
+            if kind not in kinds:
+                continue
             net = "%s_%s" % (comp, kind)
             if given is None:
                 if self.has_weights(net, qp):
@@ -218,6 +224,15 @@ class Engine:
         qt = np.empty((n, 1, 8, 8), np.float32); bt = np.empty((n, 3, 16, 16), np.float32); dire = np.empty((n, 3, 16, 16), np.float32)
         self._ck(self.lib.pmp_infer(self.h, COMP_ID[comp], int(qp), _ptr(by), _ptr(bu), _ptr(bv), n, _ptr(qt), _ptr(bt), _ptr(dire)))
         return qt, bt, dire
+
+    def infer_q(self, comp, qp, block_y, block_u=None, block_v=None):
+        """pmp_infer_q: the QT net of (comp, qp) alone -> qt f32[N,1,8,8], the qt of inference_pre_QBD bit for bit.  Loads the QT net only."""
+        by, bu, bv = _u8(block_y), _u8(block_u), _u8(block_v)
+        n = self._check_blocks(comp, by, bu, bv)
+        self.load_q(comp, qp)
+        qt = np.empty((n, 1, 8, 8), np.float32)
+        self._ck(self.lib.pmp_infer_q(self.h, COMP_ID[comp], int(qp), _ptr(by), _ptr(bu), _ptr(bv), n, _ptr(qt)))
+        return qt
 
     def post_process(self, qt, bt, dire, comp):
         """eli_structual_error + Map_to_Partition per block (Metrics.py:764-774 without the file).
@@ -354,6 +369,28 @@ class Engine:
         """pmp_val_stats_device: device pointers (None for the pair / the four left out), f64[20] -> d_stats and, if given, the per-block
         partials f64[n,20] -> d_block_stats; stream-ordered, final after synchronize() (include/pmp.h: range guard)."""
         self._ck(self.lib.pmp_val_stats_device(self.h, int(qp), d_qt, d_bt, d_dire, d_qt8, d_msbt, d_msdire, int(n), d_stats, d_block_stats))
+
+    def val_confusion(self, qt=None, bt=None, dire=None, qt8=None, msbt=None, msdire=None):
+        """pmp_val_confusion (include/pmp.h): per map (qt, bt0..2, dire0..2) the joint histogram of (label class, predicted class), the
+        whole call as one batch.  Arrays as val_stats takes them; a group's labels without its logits give the labels' census.
+        -> int64[7,5,5]."""
+        f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+        fit = lambda a, dtype, name: None if a is None else _fit(a, dtype, name)
+        a = (f(qt), f(bt), f(dire), fit(qt8, np.uint8, "qt8"), fit(msbt, np.uint8, "msbt"), fit(msdire, np.int8, "msdire"))
+        n = _conf_count(*a)
+        out = np.zeros((_lib.PMP_CONF_MAPS, _lib.PMP_CONF_CLASSES, _lib.PMP_CONF_CLASSES), np.int64)
+        self._ck(self.lib.pmp_val_confusion(self.h, *[_ptr(x) for x in a], n, _ptr(out)))
+        return out
+
+    def val_confusion_device(self, d_qt, d_bt, d_dire, d_qt8, d_msbt, d_msdire, n, d_counts, d_block_counts=None):
+        """pmp_val_confusion_device: device pointers (None for what is left out), i64[175] -> d_counts and, if given, the per-block counts
+        u16[n,175] -> d_block_counts; stream-ordered, final after synchronize() (include/pmp.h: range guard)."""
+        self._ck(self.lib.pmp_val_confusion_device(self.h, d_qt, d_bt, d_dire, d_qt8, d_msbt, d_msdire, int(n), d_counts, d_block_counts))
+
+    @staticmethod
+    def confusion_summary(C):
+        """engine.confusion_summary(C) (module level): hit / under / over, missed / false / flipped and the label frequencies per map."""
+        return confusion_summary(C)
 
     # ------------------------------------------------------------------------------------------ training losses
     def train_loss(self, comp, qp, qt=None, bt=None, dire=None, qt8=None, msbt=None, msdire=None, params=None, want_grads=True):
@@ -656,7 +693,8 @@ class Engine:
     def infer_msbd_device(self, comp, qp, d_by, d_bu, d_bv, d_qt_in, n, d_bt, d_dire):
         self._ck(self.lib.pmp_infer_msbd_device(self.h, COMP_ID[comp], int(qp), d_by, d_bu, d_bv, d_qt_in, int(n), d_bt, d_dire))
 
-    def validation_QBD(self, comp, qp, blocks, qt8, msbt, msdire, batch_size=200, logits=None, return_block_stats=False, batch_range=None):
+    def validation_QBD(self, comp, qp, blocks, qt8, msbt, msdire, batch_size=200, logits=None, return_block_stats=False, batch_range=None,
+                       return_confusion=False):
         """Metrics.validation_QBD (Metrics.py:313-385) on the GPU: both nets on every batch, the QT net's output feeding the MTT net.
         blocks: block_y u8[N,68,68] (Luma) or (block_y, block_u, block_v) (Chroma); labels as the label files hold them (qt8 RAW
         qtDepth u8[N,8,8], msbt u8 / msdire i8 [N,3,16,16]).  The set is cut into batches of batch_size IN ORDER (the reference
@@ -666,32 +704,44 @@ class Engine:
         nets (blocks may be None).  return_block_stats: also the per-block partials float64[N,20] (include/pmp.h: pmp_val_stats).
         batch_range = (lo, hi): only batches lo .. hi-1 of the set's batches run (a rank's share, parallel.shard_bounds of the batch
         count; hi == lo runs nothing), and what comes back is not the list but the raw material of validation_numbers: (S
-        float64[hi-lo,20], the batches' sizes).  The ranges' S and sizes, joined in batch order, give the whole run's numbers, bit for bit."""
-        S, ns, blk = self._val_run("qbd", comp, qp, blocks, qt8, msbt, msdire, batch_size, logits, return_block_stats, batch_range=batch_range)
+        float64[hi-lo,20], the batches' sizes).  The ranges' S and sizes, joined in batch order, give the whole run's numbers, bit for bit.
+        return_confusion: one confusion call per batch beside the statistics call; the LAST element returned is then the confusion
+        counts int64[7,5,5] of the whole set (pmp_val_confusion; see confusion_summary) - with batch_range the per-batch counts
+        int64[hi-lo,7,5,5], whose sum over all ranges is the whole set's."""
+        return self._val_result("qbd", self._val_run("qbd", comp, qp, blocks, qt8, msbt, msdire, batch_size, logits, return_block_stats,
+                                                     batch_range=batch_range, want_confusion=return_confusion),
+                                return_block_stats, batch_range, return_confusion)
+
+    @staticmethod
+    def _val_result(mode, run, want_blocks, batch_range, want_confusion):
+        """What validation_QBD / pre_validation hand back of a _val_run."""
+        S, ns, blk = run[:3]
+        conf = run[3] if want_confusion else None
         if batch_range is not None:
-            return S, ns
-        out = validation_numbers(S, ns, "qbd")
-        return (out, blk) if return_block_stats else out
+            return (S, ns, conf) if want_confusion else (S, ns)
+        out = (validation_numbers(S, ns, mode),) + ((blk,) if want_blocks else ()) + ((conf.sum(axis=0),) if want_confusion else ())
+        return out[0] if len(out) == 1 else out
 
     def pre_validation(self, comp, qp, pred_id, blocks, qt8, msbt=None, msdire=None, batch_size=200, logits=None, return_block_stats=False,
-                       batch_range=None):
-        """Metrics.pre_validation (Metrics.py:196-274).  pred_id 0: the QT net alone -> [L1, accuracy] (the ABI has no QT-only inference
-        call: this runs pmp_infer_device and drops the MTT logits, so it costs a full inference step).  pred_id 1: the MTT net,
+                       batch_range=None, return_confusion=False):
+        """Metrics.pre_validation (Metrics.py:196-274).  pred_id 0: the QT net alone -> [L1, accuracy], on pmp_infer_q_device: only the
+        QT net is loaded and run, as in the reference, which never touches an MTT net here.  pred_id 1: the MTT net,
         TEACHER-FORCED with the QT label map float(qt8 - 1) (u8 subtraction: raw 0 -> 255.0) -> the reference's list of 13: [b0_L1, b1_L1,
-        b2_L1, d0_L1, d1_L1, d2_L1, b0_accu, b1_accu, b2_accu, d0_accu, d1_accu, d2_accu, val_loss].  Batching, logits and
-        return_block_stats and batch_range as in validation_QBD (logits = (qt,) for pred_id 0, (bt, dire) for pred_id 1).  pred_id 2 belongs to a
+        b2_L1, d0_L1, d1_L1, d2_L1, b0_accu, b1_accu, b2_accu, d0_accu, d1_accu, d2_accu, val_loss].  Batching, logits,
+        return_block_stats, batch_range and return_confusion as in validation_QBD (logits = (qt,) for pred_id 0, (bt, dire) for pred_id 1;
+        the confusion counts of the maps the mode does not predict are zero).  pred_id 2 belongs to a
         direction net the reference's Model_QBD.py no longer has: ValueError."""
         if pred_id not in (0, 1):
             raise ValueError("pre_validation: pred_id must be 0 (QT net) or 1 (MTT net, teacher-forced)")
         mode = "q" if pred_id == 0 else "bd"
-        S, ns, blk = self._val_run(mode, comp, qp, blocks, qt8, msbt, msdire, batch_size, logits, return_block_stats, batch_range=batch_range)
-        if batch_range is not None:
-            return S, ns
-        out = validation_numbers(S, ns, mode)
-        return (out, blk) if return_block_stats else out
+        return self._val_result(mode, self._val_run(mode, comp, qp, blocks, qt8, msbt, msdire, batch_size, logits, return_block_stats,
+                                                    batch_range=batch_range, want_confusion=return_confusion),
+                                return_block_stats, batch_range, return_confusion)
 
-    def _val_run(self, mode, comp, qp, blocks, qt8, msbt, msdire, batch_size, logits, want_blocks, group_blocks=16384, batch_range=None):
-        """-> (S float64[batches,20], batch sizes, per-block partials or None); with batch_range = (lo, hi) only the set's batches
+    def _val_run(self, mode, comp, qp, blocks, qt8, msbt, msdire, batch_size, logits, want_blocks, group_blocks=16384, batch_range=None,
+                 want_confusion=False):
+        """-> (S float64[batches,20], batch sizes, per-block partials or None) and, with want_confusion, a fourth element: the batches'
+        confusion counts int64[batches,7,5,5]; with batch_range = (lo, hi) only the set's batches
         lo .. hi-1 run and S and the sizes are theirs (the per-block partials keep the set's rows, zeros outside).  Device-resident: per batch one inference call and one
         statistics call, both enqueued without waiting; the host synchronises once per GROUP of batches (at most group_blocks blocks,
         whose logits stay in device memory until then: a range-guard re-run at the synchronize finds every batch's buffers intact)."""
@@ -719,7 +769,7 @@ class Engine:
             by, bu, bv = _u8(by), _u8(bu), _u8(bv)
             if self._check_blocks(comp, by, bu, bv) != n:
                 raise ValueError("%d blocks for %d label blocks" % (by.shape[0], n))
-            self.load(comp, qp)
+            self.load(comp, qp, kinds=("Q",) if mode == "q" else ("Q", "MSBD"))
             d_y = up(by); d_u = up(bu) if comp == "Chroma" else None; d_v = up(bv) if comp == "Chroma" else None
         else:
             want = {"qbd": (64, 768, 768), "q": (64,), "bd": (768, 768)}[mode]
@@ -740,6 +790,7 @@ class Engine:
         ns = [min(batch_size, n - o) for o in starts]
         S = torch.zeros((len(starts), _lib.PMP_VAL_NSTATS), dtype=torch.float64, device=dev)
         blk = torch.zeros((n, _lib.PMP_VAL_NSTATS), dtype=torch.float64, device=dev) if want_blocks else None
+        conf = torch.zeros((len(starts), _lib.PMP_CONF_NCOUNTS), dtype=torch.int64, device=dev) if want_confusion else None
         per_group = max(1, int(group_blocks) // batch_size)
         P = lambda t, o, w, e: None if t is None else t.data_ptr() + o * w * e
         torch.cuda.synchronize(dev)                   # the uploads above ran on torch's stream; the context has its own
@@ -748,8 +799,8 @@ class Engine:
             base, m_all = starts[grp[0]], sum(ns[i] for i in grp)
             if logits is None:
                 l_q = torch.empty((m_all, 64), dtype=torch.float32, device=dev) if mode != "bd" else None
-                l_b = torch.empty((m_all, 768), dtype=torch.float32, device=dev)
-                l_d = torch.empty((m_all, 768), dtype=torch.float32, device=dev)
+                l_b = torch.empty((m_all, 768), dtype=torch.float32, device=dev) if use_m else None
+                l_d = torch.empty((m_all, 768), dtype=torch.float32, device=dev) if use_m else None
             else:
                 it = iter(logits)
                 l_q = up(next(it).reshape(n, 64)[base:base + m_all]) if use_q else None
@@ -761,19 +812,30 @@ class Engine:
                 if logits is None and mode == "bd":
                     self.infer_msbd_device(comp, qp, P(d_y, o, 68 * 68, 1), P(d_u, o, 34 * 34, 1), P(d_v, o, 34 * 34, 1), P(d_qin, o, 64, 4),
                                            m, P(l_b, r, 768, 4), P(l_d, r, 768, 4))
+                elif logits is None and mode == "q":
+                    self.infer_q_device(comp, qp, P(d_y, o, 68 * 68, 1), P(d_u, o, 34 * 34, 1), P(d_v, o, 34 * 34, 1), m, P(l_q, r, 64, 4))
                 elif logits is None:
                     self.infer_device(comp, qp, P(d_y, o, 68 * 68, 1), P(d_u, o, 34 * 34, 1), P(d_v, o, 34 * 34, 1), m,
                                       P(l_q, r, 64, 4), P(l_b, r, 768, 4), P(l_d, r, 768, 4))
-                self.val_stats_device(qp, P(l_q, r, 64, 4) if use_q else None, P(l_b, r, 768, 4) if use_m else None,
-                                      P(l_d, r, 768, 4) if use_m else None, P(d_q8, o, 64, 1) if use_q else None,
-                                      P(d_mb, o, 768, 1), P(d_md, o, 768, 1), m, S.data_ptr() + i * _lib.PMP_VAL_NSTATS * 8,
+                six = (P(l_q, r, 64, 4) if use_q else None, P(l_b, r, 768, 4) if use_m else None, P(l_d, r, 768, 4) if use_m else None,
+                       P(d_q8, o, 64, 1) if use_q else None, P(d_mb, o, 768, 1), P(d_md, o, 768, 1))
+                self.val_stats_device(qp, *six, m, S.data_ptr() + i * _lib.PMP_VAL_NSTATS * 8,
                                       None if blk is None else blk.data_ptr() + o * _lib.PMP_VAL_NSTATS * 8)
+                if conf is not None:
+                    self.val_confusion_device(*six, m, conf.data_ptr() + i * _lib.PMP_CONF_NCOUNTS * 8)
             self.synchronize()                        # final: range flags looked at, re-runs and their statistics replayed
-        return S.cpu().numpy(), ns, (None if blk is None else blk.cpu().numpy())
+        out = (S.cpu().numpy(), ns, (None if blk is None else blk.cpu().numpy()))
+        if conf is not None:
+            out += (conf.cpu().numpy().reshape(-1, _lib.PMP_CONF_MAPS, _lib.PMP_CONF_CLASSES, _lib.PMP_CONF_CLASSES),)
+        return out
 
     # ------------------------------------------------------------------------------------------ device API
     def infer_device(self, comp, qp, d_by, d_bu, d_bv, n, d_qt, d_bt, d_dire):
         self._ck(self.lib.pmp_infer_device(self.h, COMP_ID[comp], int(qp), d_by, d_bu, d_bv, int(n), d_qt, d_bt, d_dire))
+
+    def infer_q_device(self, comp, qp, d_by, d_bu, d_bv, n, d_qt):
+        """pmp_infer_q_device: the QT net alone; needs only the QT net of (comp, qp) loaded (load_q)."""
+        self._ck(self.lib.pmp_infer_q_device(self.h, COMP_ID[comp], int(qp), d_by, d_bu, d_bv, int(n), d_qt))
 
     def postprocess_device(self, comp, d_qt, d_bt, d_dire, n, d_hor, d_ver, d_q8, d_d8):
         self._ck(self.lib.pmp_postprocess_device(self.h, COMP_ID[comp], d_qt, d_bt, d_dire, int(n), d_hor, d_ver, d_q8, d_d8))
@@ -888,6 +950,56 @@ def _val_count(qt, bt, dire, qt8, msbt, msdire):
     if have_q and (qt.size != n * 64 or qt8.size != n * 64) or have_m and any(a.size != n * 768 for a in (bt, dire, msbt, msdire)):
         raise ValueError("val_stats: expected qt[N,8,8], qt8[N,8,8] and bt, dire, msbt, msdire [N,3,16,16] for one N")
     return n
+
+
+def _conf_count(qt, bt, dire, qt8, msbt, msdire):
+    """Block count of a val_confusion call; ValueError on a form the ABI refuses or on sizes that disagree."""
+    if qt is not None and qt8 is None or (bt is not None or dire is not None) and (msbt is None or msdire is None):
+        raise ValueError("val_confusion: logits without their labels")
+    if (bt is None) != (dire is None) or (msbt is None) != (msdire is None):
+        raise ValueError("val_confusion: bt goes with dire, msbt with msdire")
+    if qt8 is None and msbt is None:
+        raise ValueError("val_confusion: pass qt8, (msbt, msdire) or both")
+    n = (qt8.size // 64) if qt8 is not None else (msbt.size // 768)
+    if any(a is not None and a.size != n * w for a, w in ((qt, 64), (qt8, 64), (bt, 768), (dire, 768), (msbt, 768), (msdire, 768))):
+        raise ValueError("val_confusion: expected qt, qt8 [N,8,8] and bt, dire, msbt, msdire [N,3,16,16] for one N")
+    return n
+
+
+CONF_MAPS = ("qt", "bt0", "bt1", "bt2", "dire0", "dire1", "dire2")
+
+
+def confusion_summary(C):
+    """What confusion counts int64[7,5,5] (pmp_val_confusion: C[m][label class][predicted class]) say, per map: {map name: {"matrix":
+    the 5x5 counts as lists, "total", "label_freq": row sums / total (depth maps: the classes 0..3 and other; direction maps: -1, 0, 1,
+    other, and a fifth class that stays empty), and as fractions of the total
+      depth maps (qt, bt0..2)      "hit" p == l, "under" p < l (splits the encoder can no longer try), "over" p > l (splits it did not
+                                   want) - label and prediction both one of 0..3;
+      direction maps (dire0..2)    "hit", "missed" (l != 0, p == 0), "false" (l == 0, p != 0), "flipped" (l == -p != 0) - both one of -1, 0, 1;
+      both                         "other_label" (the label is no valid class), "other_pred" (the label is, the prediction is not)}}.
+    A map without cells (a group that was not given) has total 0 and zeros for every fraction."""
+    C = np.asarray(C, np.int64).reshape(_lib.PMP_CONF_MAPS, _lib.PMP_CONF_CLASSES, _lib.PMP_CONF_CLASSES)
+    out = {}
+    for m, name in enumerate(CONF_MAPS):
+        M = C[m]
+        nv = 4 if m < 4 else 3                            # valid classes; the rest is "other"
+        V = M[:nv, :nv]
+        total = int(M.sum())
+        parts = {"hit": int(np.trace(V))}
+        if m < 4:
+            parts["under"] = int(np.tril(V, -1).sum())
+            parts["over"] = int(np.triu(V, 1).sum())
+        else:
+            parts["missed"] = int(V[0, 1] + V[2, 1])
+            parts["false"] = int(V[1, 0] + V[1, 2])
+            parts["flipped"] = int(V[0, 2] + V[2, 0])
+        parts["other_label"] = int(M[nv:, :].sum())
+        parts["other_pred"] = int(M[:nv, nv:].sum())
+        assert sum(parts.values()) == total
+        d = {"matrix": M.tolist(), "total": total, "label_freq": [(int(v) / total if total else 0.0) for v in M.sum(axis=1)]}
+        d.update({k: (v / total if total else 0.0) for k, v in parts.items()})
+        out[name] = d
+    return out
 
 
 def validation_numbers(S, ns, mode="qbd"):

@@ -63,18 +63,26 @@ def all_gather_rows(local):
     return torch.stack(slots).to(local.device)
 
 
-def gather_batch_stats(S, ns, counts, device):
+def gather_batch_stats(S, ns, counts, device, conf=None):
     """Validation on several ranks: this rank's per-batch statistics S float64[k, 20] and batch sizes ns[k], k = counts[rank] (the
-    batches dealt out by parallel.shard_bounds) -> (S float64[sum(counts), 20], ns) of all ranks in rank order, which is batch order."""
+    batches dealt out by parallel.shard_bounds) -> (S float64[sum(counts), 20], ns) of all ranks in rank order, which is batch order.
+    conf: this rank's per-batch confusion counts int64[k, 7, 5, 5] (pmp_val_confusion) travel with the statistics, in the same rows -
+    a batch's count is far below 2^53, so float64 carries it exactly - and come back as a third element int64[sum(counts), 7, 5, 5]."""
     import numpy as np
     import torch
     cap = max(max(counts), 1)
-    mine = np.zeros((cap, _lib.PMP_VAL_NSTATS + 1), np.float64)
+    nc = _lib.PMP_CONF_NCOUNTS if conf is not None else 0
+    mine = np.zeros((cap, _lib.PMP_VAL_NSTATS + 1 + nc), np.float64)
     mine[:len(ns), :_lib.PMP_VAL_NSTATS] = np.asarray(S, np.float64).reshape(-1, _lib.PMP_VAL_NSTATS)
     mine[:len(ns), _lib.PMP_VAL_NSTATS] = ns
+    if nc:
+        mine[:len(ns), _lib.PMP_VAL_NSTATS + 1:] = np.asarray(conf, np.int64).reshape(-1, nc)
     every = all_gather_rows(torch.from_numpy(mine).to(device)).cpu().numpy()
     rows = np.concatenate([every[r, :c] for r, c in enumerate(counts)], 0)
-    return rows[:, :_lib.PMP_VAL_NSTATS].copy(), [int(v) for v in rows[:, _lib.PMP_VAL_NSTATS]]
+    out = (rows[:, :_lib.PMP_VAL_NSTATS].copy(), [int(v) for v in rows[:, _lib.PMP_VAL_NSTATS]])
+    if nc:
+        out += (rows[:, _lib.PMP_VAL_NSTATS + 1:].astype(np.int64).reshape(-1, _lib.PMP_CONF_MAPS, _lib.PMP_CONF_CLASSES, _lib.PMP_CONF_CLASSES),)
+    return out
 
 
 def ranks_out_of_sync(fingerprint, device):

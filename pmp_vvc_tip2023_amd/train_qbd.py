@@ -3,7 +3,7 @@
     python -m pmp_vvc_tip2023_amd.train_qbd --predID 0|1|2 [--isLuma] --inputDir D --outDir O [--jobID 0000] [--lr 1e-3] [--dr 20]
            [--qp 22] [--epoch 100] [--batchSize 200] [--lambq .. --lambresb2 ..]
            [--modelDir M] [--seed 0] [--saveEvery 10] [--resume] [--maxSteps K] [--device 0] [--valPrecision f16x3|bf16x6|fp32]
-           [--gpus N] [--microBatch 256] [--clipNorm X] [--skipNonFinite] [--maxSkipped 10]
+           [--gpus N] [--microBatch 256] [--clipNorm X] [--skipNonFinite] [--maxSkipped 10] [--confusion]
 
 --predID 0 is pre_train_Q (the QT net on the plain L1 loss, Train_QBD.py:117-191), 1 is pre_train_BD (the MTT net teacher-forced with
 the QT labels on loss_func_MSBD, :193-303), 2 is train_QBD (both nets jointly on loss_func_QBD, starting from the pair <comp>_Q_<qp> and
@@ -23,7 +23,14 @@ one line of loss.txt under the reference's header: an epoch value is the mean of
 checkpoints are written under the reference's names (<comp>_Q_<qp>_epoch_%d_....pkl, <comp>_BD_...: plain state_dicts,
 weights.load_pkl reads them), and at every epoch <comp>_Q_<qp>.pmpw / <comp>_BD_<qp>.pmpw of the nets as they are now - the directory
 then serves as --modelDir of inference_qbd and validate - and last.pt (nets, optimiser, epoch, seed), from which --resume continues.
---predID 1 also writes the QT net it validated with as <comp>_Q_<qp>.pmpw, so that the pair is whole.
+--predID 1 also writes the QT net it validated with as <comp>_Q_<qp>.pmpw, so that the pair is whole.  --predID 0 validates through
+Engine.infer_q: the QT net alone is loaded and run, no *_BD_* file is looked for and no stand-in takes its place.
+
+--confusion: every epoch's validation also counts, per map of the mode (0: qt; 1: bt0..2, dire0..2; 2: all seven), the joint histogram
+of (label class, predicted class) (include/pmp.h: pmp_val_confusion; engine.confusion_summary reads it) and appends one line per set
+and map, "epoch,set,map,c00,c01,..,c44" (set Validate or TestSub, cLP = label class L, predicted class P), to confusion.txt.  Without
+the flag nothing is counted or written.  Under --gpus N the per-batch counts travel with the per-batch statistics and the file is the
+one-rank run's, byte for byte.
 
 --gpus N (or torchrun's environment, as inference_qbd) trains data-parallel, the reference's nn.DataParallel: N rank processes
 (parallel.spawn_ranks), each on the GPU of its LOCAL_RANK (--device is refused; ranks share a GPU only under PMP_DIST_BACKEND=gloo, for
@@ -49,7 +56,7 @@ one-rank run's too.
 
 What differs from the reference: the order of the batches is defined by --seed (dataset.permutation of (seed, epoch): a resumed run
 gives the bits of an uninterrupted one); processes instead of nn.DataParallel's threads (state_dict names without "module.");
-micro-batches; --predID 0 validates beside the MTT net found in --modelDir or else the synthetic one, whose logits are dropped.
+micro-batches.
 Flags, the three sets' files and the model files are checked before anything touches the GPU: exit status 2 on the first problem.
 """
 import argparse
@@ -107,6 +114,7 @@ def build_parser():
     p.add_argument("--clipNorm", default=0.0, type=float, help="clip the gradients' global norm to this; 0: off")
     p.add_argument("--skipNonFinite", action="store_true", help="a step whose gradients hold a NaN or an inf changes nothing")
     p.add_argument("--maxSkipped", default=10, type=int, help="with --skipNonFinite: more skipped steps in a row end the job with status 5")
+    p.add_argument("--confusion", action="store_true", help="append the validation's confusion counts per set and map to confusion.txt")
     p.add_argument("--valPrecision", default="f16x3", help="datapath of the validation passes: f16x3, bf16x6 or fp32")
     return p
 
@@ -335,7 +343,7 @@ class Trainer:
 
 def validate(engine, args, comp, sets, trainer, partner):
     """The epoch's validation: the current parameters into the engine, then pre_validation / validation_QBD on Validate and TestSub
-    -> (val list, test list).  Data-parallel (trainer.sync): the batches of each set are dealt out by parallel.shard_bounds, a rank
+    -> [val list, test list], and with --confusion a third element: [val counts, test counts], int64[7,5,5] each.  Data-parallel (trainer.sync): the batches of each set are dealt out by parallel.shard_bounds, a rank
     runs its own, and the per-batch statistics, gathered in rank order, which is batch order, give the same lists on every rank."""
     from . import engine as E, grad_sync, parallel
     for kind in trainer.nets:
@@ -343,10 +351,13 @@ def validate(engine, args, comp, sets, trainer, partner):
     for kind, w in partner.items():
         if not engine.has_weights("%s_%s" % (comp, kind), args.qp):
             engine.load_pretrain_model("%s_%s" % (comp, kind), args.qp, w)
-    out = []
+    out, confs = [], []
+    want_conf = bool(getattr(args, "confusion", False))
     for name in SETS[1:]:
         d = sets[name]
         kw = {"batch_size": args.batchSize}
+        if want_conf:
+            kw["return_confusion"] = True
         if trainer.sync is not None:
             rank, world = trainer.sync.rank, trainer.sync.world
             nb = -(-d["n"] // args.batchSize)
@@ -356,10 +367,23 @@ def validate(engine, args, comp, sets, trainer, partner):
         else:
             res = engine.pre_validation(comp, args.qp, args.predID, d["blocks"], d["qt8"], d["msbt"], d["msdire"], **kw)
         if trainer.sync is not None:
-            S, ns = grad_sync.gather_batch_stats(res[0], res[1], parallel.shard_counts(nb, world), trainer.device)
-            res = E.validation_numbers(S, ns, {0: "q", 1: "bd", 2: "qbd"}[args.predID])
+            got = grad_sync.gather_batch_stats(res[0], res[1], parallel.shard_counts(nb, world), trainer.device, conf=res[2] if want_conf else None)
+            res = E.validation_numbers(got[0], got[1], {0: "q", 1: "bd", 2: "qbd"}[args.predID])
+            if want_conf:
+                res = (res, got[2].sum(axis=0))
+        if want_conf:
+            res, conf = res
+            confs.append(conf)
         out.append(res)
-    return out
+    return out + [confs] if want_conf else out
+
+
+def confusion_lines(args, epoch, confs):
+    """The epoch's lines of confusion.txt: per set (Validate, TestSub) and map of the mode "epoch,set,map,c00..c44" """
+    from .engine import CONF_MAPS
+    maps = {0: (0,), 1: range(1, 7), 2: range(7)}[args.predID]
+    return "".join("%d,%s,%s,%s\n" % (epoch, name, CONF_MAPS[m], ",".join(str(int(v)) for v in conf[m].ravel()))
+                   for name, conf in zip(SETS[1:], confs) for m in maps)
 
 
 def report(args, comp, epoch, mean, val, test):
@@ -465,7 +489,7 @@ def main(argv=None):
     if rank == 0:
         os.makedirs(out_dir, exist_ok=True)
     log = os.path.join(out_dir, "loss.txt")
-    eng = E.Engine(dev_id, weight_dir=args.modelDir, allow_synthetic_mtt=args.predID == 0)
+    eng = E.Engine(dev_id, weight_dir=args.modelDir)
     try:
         eng.set_precision(args.valPrecision)
         trainer = Trainer(eng, args, comp, pl["start"], dev_id)
@@ -520,7 +544,7 @@ def main(argv=None):
                     print(bad, file=sys.stderr, flush=True)
                     return EXIT_DIVERGED
             mean = (total / steps).tolist()
-            val, test = validate(eng, args, comp, sets, trainer, partner)
+            val, test, *confs = validate(eng, args, comp, sets, trainer, partner)
             if trainer.sync is not None and not in_sync(trainer, "after epoch %d" % epoch):
                 return EXIT_DESYNC
             if rank != 0:
@@ -528,6 +552,9 @@ def main(argv=None):
             line, names = report(args, comp, epoch, mean, val, test)
             with open(log, "a") as f:
                 f.write("".join(str(np.float64(s)) + "," for s in line) + "\n")
+            if confs:
+                with open(os.path.join(out_dir, "confusion.txt"), "a") as f:
+                    f.write(confusion_lines(args, epoch, confs[0]))
             if counters is not None:
                 with open(os.path.join(out_dir, "guard.txt"), "a") as f:
                     f.write("%d,%d,%d,%d,%d,%s\n" % (epoch, counters["steps"], counters["skipped"], counters["clipped"], counters["max_run"],

@@ -1,7 +1,7 @@
 """Validate a pair of nets against VTM labels on the GPU: Metrics.validation_QBD / pre_validation of the reference.
 
     python -m pmp_vvc_tip2023_amd.validate --dataDir D --modelDir M --comp Luma|Chroma --qp Q [--dataType Validate]
-           [--mode qbd|bd|q] [--batchSize 200] [--precision f16x3|bf16x6|fp32] [--perBlock out.npy] [--device 0]
+           [--mode qbd|bd|q|labels] [--batchSize 200] [--precision f16x3|bf16x6|fp32] [--perBlock out.npy] [--confusion] [--device 0]
 
 Reads the reference's file names from --dataDir (Metrics.Load_Pre_VP_Dataset, Metrics.py:64-146):
     <dataType>_Y_Block68.npy                           u8[n,68,68]   (+ <dataType>_U_Block34.npy, _V_Block34.npy u8[n,34,34] for Chroma)
@@ -10,9 +10,14 @@ Reads the reference's file names from --dataDir (Metrics.Load_Pre_VP_Dataset, Me
     <dataType>_<comp>_QP<qp>_MSdirection_Block16.npy   i8[n,3,16,16] (modes qbd, bd)
 the three label files being what `python -m pmp_vvc_tip2023_amd.gen_labels` writes.  --mode qbd (default) is validation_QBD (both nets,
 the QT net feeding the MTT net), bd is pre_validation predID 1 (the MTT net teacher-forced with the QT labels), q is predID 0 (the QT
-net alone).  Batches of --batchSize blocks in file order; the reference shuffles, so its numbers are defined up to the batch cut.
+net alone: only the <comp>_Q_<qp> model file is asked for).  Batches of --batchSize blocks in file order; the reference shuffles, so its numbers are defined up to the batch cut.
 Prints ONE JSON object: the reference's numbers by name (q_L1, b0_L1 .., q_accu .., val_loss) plus comp, qp, mode, blocks, batches,
 batch_size, precision and saturation_reruns.  --perBlock writes the per-block statistics float64[n,20] (include/pmp.h: pmp_val_stats).
+--confusion adds "confusion": per map of the mode (q: qt; bd: bt0..2, dire0..2; qbd: all seven) the joint histogram of (label class,
+predicted class) with what it says - label frequencies, hit / under / over for the depth maps, hit / missed / false / flipped for the
+direction maps (engine.confusion_summary; include/pmp.h: pmp_val_confusion).  --mode labels is the census of a set's labels alone: the
+same object with every prediction counted as "other", so that the label frequencies are what matters.  It reads the QTdepth file and, if
+both are there, the MSBTdepth and MSdirection files; it needs no block file and no model file and runs no net.
 Flags, files, dtypes and shapes are checked before anything touches the GPU: exit status 2 on the first problem.
 """
 import argparse
@@ -30,6 +35,10 @@ NAMES = {"qbd": ["q_L1", "b0_L1", "b1_L1", "b2_L1", "d0_L1", "d1_L1", "d2_L1", "
                 "val_loss"]}
 
 
+CONF_MAPS = {"q": ("qt",), "bd": ("bt0", "bt1", "bt2", "dire0", "dire1", "dire2"),
+             "qbd": ("qt", "bt0", "bt1", "bt2", "dire0", "dire1", "dire2")}
+
+
 def build_parser():
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     p.add_argument("--dataDir", required=True, help="directory of the block and label .npy files")
@@ -41,6 +50,7 @@ def build_parser():
     p.add_argument("--batchSize", default=200, type=int)
     p.add_argument("--precision", default="f16x3")
     p.add_argument("--perBlock", default=None, help="write the per-block statistics float64[n,20] to this .npy file")
+    p.add_argument("--confusion", action="store_true", help="add the confusion counts per map and their summary to the JSON object")
     p.add_argument("--allowSyntheticMtt", action="store_true", help="fall back to the synthetic MTT weights when the *_BD_* file is missing (tests)")
     p.add_argument("--device", default=0, type=int)
     return p
@@ -54,8 +64,8 @@ def plan(args):
         raise SystemExit(2)
     if args.comp not in COMPS:
         fail("--comp must be Luma or Chroma, got %r" % args.comp)
-    if args.mode not in NAMES:
-        fail("--mode must be qbd, bd or q, got %r" % args.mode)
+    if args.mode not in NAMES and args.mode != "labels":
+        fail("--mode must be qbd, bd, q or labels, got %r" % args.mode)
     if not 22 <= args.qp <= 41:
         fail("--qp must be in 22..41 (the rows of the reference's weight_mat), got %d" % args.qp)
     if args.batchSize < 1:
@@ -71,13 +81,20 @@ def plan(args):
     if args.perBlock is not None and not os.path.isdir(os.path.dirname(os.path.abspath(args.perBlock))):
         fail("--perBlock: directory of %s does not exist" % args.perBlock)
 
+    if args.mode == "labels":
+        if args.perBlock is not None:
+            fail("--perBlock goes with the modes that run a net")
+        stem = os.path.join(args.dataDir, "%s_%s_QP%d_" % (args.dataType, args.comp, args.qp))
+        both = all(os.path.isfile(stem + tail) for tail in ("MSBTdepth_Block16.npy", "MSdirection_Block16.npy"))
+        return read_set(args.dataDir, args.dataType, args.comp, args.qp, both, fail, with_blocks=False)
     return read_set(args.dataDir, args.dataType, args.comp, args.qp, args.mode != "q", fail)
 
 
-def read_set(data_dir, data_type, comp, qp, with_mtt_labels, fail):
+def read_set(data_dir, data_type, comp, qp, with_mtt_labels, fail, with_blocks=True):
     """Opens (memory-mapped) and checks the files of one set of the reference's layout (the module's docstring) -> {"blocks": y or
     (y, u, v), "qt8", "msbt", "msdire" (None without with_mtt_labels), "n"}.  fail(message) is called on the first missing file, wrong
-    dtype, wrong shape or mismatched count, and must not return.  Shared by validate, dataset.DeviceDataset and train_qbd."""
+    dtype, wrong shape or mismatched count, and must not return.  Shared by validate, dataset.DeviceDataset and train_qbd.
+    with_blocks=False: the labels alone, no block file is opened and "blocks" is None."""
     def read(name, dtype, tail):
         path = os.path.join(data_dir, name)
         if not os.path.isfile(path):
@@ -95,9 +112,12 @@ def read_set(data_dir, data_type, comp, qp, with_mtt_labels, fail):
     if with_mtt_labels:
         out["msbt"] = read(stem + "MSBTdepth_Block16.npy", np.uint8, (3, 16, 16))
         out["msdire"] = read(stem + "MSdirection_Block16.npy", np.int8, (3, 16, 16))
-    y = read(data_type + "_Y_Block68.npy", np.uint8, (68, 68))
-    arrays = [("labels", out["msbt"]), ("labels", out["msdire"]), ("blocks", y)]
-    if comp == "Chroma":
+    arrays = [("labels", out["msbt"]), ("labels", out["msdire"])]
+    y = None
+    if with_blocks:
+        y = read(data_type + "_Y_Block68.npy", np.uint8, (68, 68))
+        arrays.append(("blocks", y))
+    if comp == "Chroma" and with_blocks:
         u = read(data_type + "_U_Block34.npy", np.uint8, (34, 34))
         v = read(data_type + "_V_Block34.npy", np.uint8, (34, 34))
         arrays += [("blocks", u), ("blocks", v)]
@@ -118,9 +138,19 @@ def main(argv=None):
     d = plan(args)
     from . import engine as E
     eng = E.Engine(args.device, weight_dir=args.modelDir, allow_synthetic_mtt=args.allowSyntheticMtt)
+    if args.mode == "labels":
+        try:
+            conf = eng.val_confusion(qt8=d["qt8"], msbt=d["msbt"], msdire=d["msdire"])
+        finally:
+            eng.close()
+        maps = CONF_MAPS["q" if d["msbt"] is None else "qbd"]
+        summary = E.confusion_summary(conf)
+        print(json.dumps({"comp": args.comp, "qp": args.qp, "mode": "labels", "data_type": args.dataType, "blocks": d["n"],
+                          "confusion": {m: summary[m] for m in maps}}))
+        return 0
     try:
         eng.set_precision(args.precision)
-        kw = dict(batch_size=args.batchSize, return_block_stats=args.perBlock is not None)
+        kw = dict(batch_size=args.batchSize, return_block_stats=args.perBlock is not None, return_confusion=args.confusion)
         if args.mode == "qbd":
             res = eng.validation_QBD(args.comp, args.qp, d["blocks"], d["qt8"], d["msbt"], d["msdire"], **kw)
         else:
@@ -128,6 +158,10 @@ def main(argv=None):
         reruns = eng.saturation_reruns()
     finally:
         eng.close()
+    conf = None
+    if args.confusion:
+        res, conf = res[:-1], res[-1]
+        res = res[0] if len(res) == 1 else res
     if args.perBlock is not None:
         res, blk = res
         np.save(args.perBlock, blk)
@@ -135,6 +169,9 @@ def main(argv=None):
            "batches": (d["n"] + args.batchSize - 1) // args.batchSize, "batch_size": args.batchSize, "precision": args.precision,
            "saturation_reruns": reruns}
     out.update(zip(NAMES[args.mode], res))
+    if conf is not None:
+        summary = E.confusion_summary(conf)
+        out["confusion"] = {m: summary[m] for m in CONF_MAPS[args.mode]}
     print(json.dumps(out))
     return 0
 

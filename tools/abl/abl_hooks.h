@@ -14,7 +14,7 @@ void abl_on_create();
 bool abl_set_conv_variant(int variant, int *rc);
 bool abl_set_winograd(pmp_ctx *c, int on, int *rc);
 unsigned abl_pack_mask(const pmp_ctx *c);
-int abl_prepare_pass(pmp_ctx *c, int precision, NetWeights &wq, NetWeights &wb);
+int abl_prepare_pass(pmp_ctx *c, int precision, NetWeights &wq, NetWeights *wb);   // wb null: a pass of the QT net alone
 void abl_conv_args(const pmp_ctx *c, const RBWeights &r, bool second, ConvX6Args &a);
 int abl_pack_rb(const float *w0, const float *w2, int k, int cin, int cout, unsigned mask, RBWeights &r,
                 const std::function<int(const std::vector<unsigned short> &, unsigned short **)> &upload16);

@@ -72,11 +72,11 @@ bool abl_set_winograd(pmp_ctx *c, int on, int *rc)
 
 unsigned abl_pack_mask(const pmp_ctx *c) { return c->abl.winograd ? 1u << 3 : 0u; }     // pseudo-datapath 3: the Winograd-x streams
 
-int abl_prepare_pass(pmp_ctx *c, int precision, NetWeights &wq, NetWeights &wb)
+int abl_prepare_pass(pmp_ctx *c, int precision, NetWeights &wq, NetWeights *wb)
 {
     if (!c->abl.winograd || precision != PMP_PRECISION_F16X3) return PMP_OK;
     int rc = ensure_datapath(c, wq, 3);
-    return rc != PMP_OK ? rc : ensure_datapath(c, wb, 3);
+    return rc != PMP_OK || !wb ? rc : ensure_datapath(c, *wb, 3);
 }
 
 void abl_conv_args(const pmp_ctx *c, const RBWeights &r, bool second, ConvX6Args &a)
