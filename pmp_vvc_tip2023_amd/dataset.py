@@ -5,7 +5,7 @@ pmp_batch_gather_device call (include/pmp.h, TRAINING STEP) - no DataLoader, no 
     train = DeviceDataset(engine, args.inputDir, "Luma", args.qp, "Train", pred_id=2, device=0)
     for x, qt_f, msbt, msdire, qt8 in train.batches(args.batchSize, shuffle=True, seed=args.seed, epoch=epoch): ...
 
-Files, dtypes, shapes and counts are checked by validate.read_set, the reader validate.plan uses.  pred_id as the loader's PredID: 0
+Files, dtypes, shapes and counts are checked by validation.read_set, the reader validate.plan uses.  pred_id as the loader's PredID: 0
 yields (x, qt_f, qt8) - the QT labels alone are read - 1 and 2 yield (x, qt_f, msbt, msdire, qt8): the loader's tuple with the label
 tensors in the dtypes of the label FILES, as train_loss takes them, and the raw qtDepth rows beside the loader's float(qt8 - 1).  x is
 f32[n,1,68,68] (Luma) or f32[n,3,34,34] (Chroma: the 2x2 maximum of Y, U, V).  Batches are cut from one permutation of the set in
@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from .torch_call import P, run
-from .validate import read_set
+from .validation import read_set
 
 
 def epoch_seed(seed, epoch):

@@ -23,8 +23,9 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, validation
 from . import weights as W
+from .validation import CONF_MAPS, VAL_ELEMS, _fit, _logit_label_arrays, confusion_summary, validation_numbers  # noqa: F401 (kept importable from here)
 
 COMP_ID = {"Luma": _lib.PMP_LUMA, "Chroma": _lib.PMP_CHROMA}
 PARAM_KEYS = ("lamb1", "lamb2", "lamb3", "lamb4", "lamb5", "thd")
@@ -374,10 +375,7 @@ class Engine:
         """pmp_val_confusion (include/pmp.h): per map (qt, bt0..2, dire0..2) the joint histogram of (label class, predicted class), the
         whole call as one batch.  Arrays as val_stats takes them; a group's labels without its logits give the labels' census.
         -> int64[7,5,5]."""
-        f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
-        fit = lambda a, dtype, name: None if a is None else _fit(a, dtype, name)
-        a = (f(qt), f(bt), f(dire), fit(qt8, np.uint8, "qt8"), fit(msbt, np.uint8, "msbt"), fit(msdire, np.int8, "msdire"))
-        n = _conf_count(*a)
+        a, n = _logit_label_arrays(qt, bt, dire, qt8, msbt, msdire, census=True)
         out = np.zeros((_lib.PMP_CONF_MAPS, _lib.PMP_CONF_CLASSES, _lib.PMP_CONF_CLASSES), np.int64)
         self._ck(self.lib.pmp_val_confusion(self.h, *[_ptr(x) for x in a], n, _ptr(out)))
         return out
@@ -387,10 +385,7 @@ class Engine:
         u16[n,175] -> d_block_counts; stream-ordered, final after synchronize() (include/pmp.h: range guard)."""
         self._ck(self.lib.pmp_val_confusion_device(self.h, d_qt, d_bt, d_dire, d_qt8, d_msbt, d_msdire, int(n), d_counts, d_block_counts))
 
-    @staticmethod
-    def confusion_summary(C):
-        """engine.confusion_summary(C) (module level): hit / under / over, missed / false / flipped and the label frequencies per map."""
-        return confusion_summary(C)
+    confusion_summary = staticmethod(confusion_summary)     # validation.confusion_summary(C): what the counts say, per map
 
     # ------------------------------------------------------------------------------------------ training losses
     def train_loss(self, comp, qp, qt=None, bt=None, dire=None, qt8=None, msbt=None, msdire=None, params=None, want_grads=True):
@@ -708,19 +703,8 @@ class Engine:
         return_confusion: one confusion call per batch beside the statistics call; the LAST element returned is then the confusion
         counts int64[7,5,5] of the whole set (pmp_val_confusion; see confusion_summary) - with batch_range the per-batch counts
         int64[hi-lo,7,5,5], whose sum over all ranges is the whole set's."""
-        return self._val_result("qbd", self._val_run("qbd", comp, qp, blocks, qt8, msbt, msdire, batch_size, logits, return_block_stats,
-                                                     batch_range=batch_range, want_confusion=return_confusion),
-                                return_block_stats, batch_range, return_confusion)
-
-    @staticmethod
-    def _val_result(mode, run, want_blocks, batch_range, want_confusion):
-        """What validation_QBD / pre_validation hand back of a _val_run."""
-        S, ns, blk = run[:3]
-        conf = run[3] if want_confusion else None
-        if batch_range is not None:
-            return (S, ns, conf) if want_confusion else (S, ns)
-        out = (validation_numbers(S, ns, mode),) + ((blk,) if want_blocks else ()) + ((conf.sum(axis=0),) if want_confusion else ())
-        return out[0] if len(out) == 1 else out
+        return _val_tuple(validation.run(self, "qbd", comp, qp, blocks, qt8, msbt, msdire, batch_size, logits, return_block_stats, batch_range,
+                                         return_confusion), return_block_stats, batch_range is not None, return_confusion)
 
     def pre_validation(self, comp, qp, pred_id, blocks, qt8, msbt=None, msdire=None, batch_size=200, logits=None, return_block_stats=False,
                        batch_range=None, return_confusion=False):
@@ -733,101 +717,8 @@ class Engine:
         direction net the reference's Model_QBD.py no longer has: ValueError."""
         if pred_id not in (0, 1):
             raise ValueError("pre_validation: pred_id must be 0 (QT net) or 1 (MTT net, teacher-forced)")
-        mode = "q" if pred_id == 0 else "bd"
-        return self._val_result(mode, self._val_run(mode, comp, qp, blocks, qt8, msbt, msdire, batch_size, logits, return_block_stats,
-                                                    batch_range=batch_range, want_confusion=return_confusion),
-                                return_block_stats, batch_range, return_confusion)
-
-    def _val_run(self, mode, comp, qp, blocks, qt8, msbt, msdire, batch_size, logits, want_blocks, group_blocks=16384, batch_range=None,
-                 want_confusion=False):
-        """-> (S float64[batches,20], batch sizes, per-block partials or None) and, with want_confusion, a fourth element: the batches'
-        confusion counts int64[batches,7,5,5]; with batch_range = (lo, hi) only the set's batches
-        lo .. hi-1 run and S and the sizes are theirs (the per-block partials keep the set's rows, zeros outside).  Device-resident: per batch one inference call and one
-        statistics call, both enqueued without waiting; the host synchronises once per GROUP of batches (at most group_blocks blocks,
-        whose logits stay in device memory until then: a range-guard re-run at the synchronize finds every batch's buffers intact)."""
-        import torch
-        if comp not in COMP_ID:
-            raise ValueError("comp must be 'Luma' or 'Chroma'")
-        batch_size = int(batch_size)
-        if batch_size < 1:
-            raise ValueError("batch_size must be >= 1")
-        use_q, use_m = mode in ("qbd", "q"), mode in ("qbd", "bd")
-        qt8 = _fit(qt8, np.uint8, "qt8")
-        n = qt8.size // 64
-        if qt8.size != n * 64:
-            raise ValueError("qt8 must be u8[N,8,8]")
-        if use_m:
-            if msbt is None or msdire is None:
-                raise ValueError("msbt and msdire labels are needed")
-            msbt = _fit(msbt, np.uint8, "msbt"); msdire = _fit(msdire, np.int8, "msdire")
-            if msbt.size != n * 768 or msdire.size != n * 768:
-                raise ValueError("msbt and msdire must be [N,3,16,16] for the N blocks of qt8")
-        dev = torch.device("cuda", int(self.device))
-        up = lambda a: torch.from_numpy(np.array(a, copy=not a.flags.writeable or not a.flags.c_contiguous)).to(dev)   # memory-mapped files are read-only
-        if logits is None:
-            by, bu, bv = (blocks if isinstance(blocks, (tuple, list)) else (blocks, None, None))
-            by, bu, bv = _u8(by), _u8(bu), _u8(bv)
-            if self._check_blocks(comp, by, bu, bv) != n:
-                raise ValueError("%d blocks for %d label blocks" % (by.shape[0], n))
-            self.load(comp, qp, kinds=("Q",) if mode == "q" else ("Q", "MSBD"))
-            d_y = up(by); d_u = up(bu) if comp == "Chroma" else None; d_v = up(bv) if comp == "Chroma" else None
-        else:
-            want = {"qbd": (64, 768, 768), "q": (64,), "bd": (768, 768)}[mode]
-            logits = [np.ascontiguousarray(a, np.float32) for a in logits]
-            if len(logits) != len(want) or any(a.size != n * w for a, w in zip(logits, want)):
-                raise ValueError("logits: expected %d arrays of N x %s floats" % (len(want), "/".join(map(str, want))))
-        d_q8 = up(qt8)
-        d_mb = up(msbt) if use_m else None; d_md = up(msdire) if use_m else None
-        d_qin = None
-        if mode == "bd" and logits is None:           # the loader's label map: float(u8(qt8 - 1))
-            d_qin = up((qt8 - np.uint8(1)).astype(np.float32))
-        starts = list(range(0, n, batch_size))
-        if batch_range is not None:
-            lo, hi = int(batch_range[0]), int(batch_range[1])
-            if not 0 <= lo <= hi <= len(starts):
-                raise ValueError("batch_range must lie in 0 .. %d" % len(starts))
-            starts = starts[lo:hi]
-        ns = [min(batch_size, n - o) for o in starts]
-        S = torch.zeros((len(starts), _lib.PMP_VAL_NSTATS), dtype=torch.float64, device=dev)
-        blk = torch.zeros((n, _lib.PMP_VAL_NSTATS), dtype=torch.float64, device=dev) if want_blocks else None
-        conf = torch.zeros((len(starts), _lib.PMP_CONF_NCOUNTS), dtype=torch.int64, device=dev) if want_confusion else None
-        per_group = max(1, int(group_blocks) // batch_size)
-        P = lambda t, o, w, e: None if t is None else t.data_ptr() + o * w * e
-        torch.cuda.synchronize(dev)                   # the uploads above ran on torch's stream; the context has its own
-        for g0 in range(0, len(starts), per_group):
-            grp = list(range(g0, min(g0 + per_group, len(starts))))
-            base, m_all = starts[grp[0]], sum(ns[i] for i in grp)
-            if logits is None:
-                l_q = torch.empty((m_all, 64), dtype=torch.float32, device=dev) if mode != "bd" else None
-                l_b = torch.empty((m_all, 768), dtype=torch.float32, device=dev) if use_m else None
-                l_d = torch.empty((m_all, 768), dtype=torch.float32, device=dev) if use_m else None
-            else:
-                it = iter(logits)
-                l_q = up(next(it).reshape(n, 64)[base:base + m_all]) if use_q else None
-                l_b = up(next(it).reshape(n, 768)[base:base + m_all]) if use_m else None
-                l_d = up(next(it).reshape(n, 768)[base:base + m_all]) if use_m else None
-                torch.cuda.synchronize(dev)
-            for i in grp:
-                o, m, r = starts[i], ns[i], starts[i] - base
-                if logits is None and mode == "bd":
-                    self.infer_msbd_device(comp, qp, P(d_y, o, 68 * 68, 1), P(d_u, o, 34 * 34, 1), P(d_v, o, 34 * 34, 1), P(d_qin, o, 64, 4),
-                                           m, P(l_b, r, 768, 4), P(l_d, r, 768, 4))
-                elif logits is None and mode == "q":
-                    self.infer_q_device(comp, qp, P(d_y, o, 68 * 68, 1), P(d_u, o, 34 * 34, 1), P(d_v, o, 34 * 34, 1), m, P(l_q, r, 64, 4))
-                elif logits is None:
-                    self.infer_device(comp, qp, P(d_y, o, 68 * 68, 1), P(d_u, o, 34 * 34, 1), P(d_v, o, 34 * 34, 1), m,
-                                      P(l_q, r, 64, 4), P(l_b, r, 768, 4), P(l_d, r, 768, 4))
-                six = (P(l_q, r, 64, 4) if use_q else None, P(l_b, r, 768, 4) if use_m else None, P(l_d, r, 768, 4) if use_m else None,
-                       P(d_q8, o, 64, 1) if use_q else None, P(d_mb, o, 768, 1), P(d_md, o, 768, 1))
-                self.val_stats_device(qp, *six, m, S.data_ptr() + i * _lib.PMP_VAL_NSTATS * 8,
-                                      None if blk is None else blk.data_ptr() + o * _lib.PMP_VAL_NSTATS * 8)
-                if conf is not None:
-                    self.val_confusion_device(*six, m, conf.data_ptr() + i * _lib.PMP_CONF_NCOUNTS * 8)
-            self.synchronize()                        # final: range flags looked at, re-runs and their statistics replayed
-        out = (S.cpu().numpy(), ns, (None if blk is None else blk.cpu().numpy()))
-        if conf is not None:
-            out += (conf.cpu().numpy().reshape(-1, _lib.PMP_CONF_MAPS, _lib.PMP_CONF_CLASSES, _lib.PMP_CONF_CLASSES),)
-        return out
+        return _val_tuple(validation.run(self, validation.mode_of_pred(pred_id), comp, qp, blocks, qt8, msbt, msdire, batch_size, logits,
+                                         return_block_stats, batch_range, return_confusion), return_block_stats, batch_range is not None, return_confusion)
 
     # ------------------------------------------------------------------------------------------ device API
     def infer_device(self, comp, qp, d_by, d_bu, d_bv, n, d_qt, d_bt, d_dire):
@@ -881,18 +772,13 @@ class Engine:
         return n
 
 
-def _fit(a, dtype, name):
-    """a as a contiguous array of `dtype` if every value fits it exactly (the reference's label dtypes); ValueError otherwise."""
-    a = np.asarray(a)
-    if a.dtype == dtype:
-        return np.ascontiguousarray(a)
-    info = np.iinfo(dtype)
-    if a.dtype.kind not in "biuf":
-        raise ValueError("%s: numeric array expected, got %s" % (name, a.dtype))
-    if a.size and (a.dtype.kind == "f" and not np.all(np.isfinite(a) & (a == np.round(a)))
-                   or a.min() < info.min or a.max() > info.max):
-        raise ValueError("%s: values outside %s (the reference's dtype); refusing to wrap them" % (name, np.dtype(dtype).name))
-    return np.ascontiguousarray(a.astype(dtype))
+def _val_tuple(run, want_blocks, ranged, want_confusion):
+    """A validation.ValRun as validation_QBD / pre_validation document their returns - the one place where those tuple forms exist;
+    ranged: batch_range was given."""
+    if ranged:
+        return (run.S, run.ns, run.conf) if want_confusion else (run.S, run.ns)
+    out = (run.numbers(),) + ((run.block_stats,) if want_blocks else ()) + ((run.confusion(),) if want_confusion else ())
+    return out[0] if len(out) == 1 else out
 
 
 LOSS_KEYS = ("lambq", "lambb0", "lambb1", "lambb2", "lambd0", "lambd1", "lambd2", "lambresb0", "lambresb1", "lambresb2")
@@ -927,99 +813,6 @@ def grad_bucket_floats(counts):
     if total < 0:
         raise ValueError("grad_bucket_floats: at least one tensor, every count in 1 .. 2^30 - 1")
     return int(total), [int(v) for v in off[:nt]]
-
-
-VAL_ELEMS = np.array([64] + [256] * 12 + [64] + [256] * 6, np.float64)      # elements per block behind each of the twenty statistics
-
-
-def _logit_label_arrays(qt, bt, dire, qt8, msbt, msdire):
-    """The six optional arrays of val_stats / train_loss as the ABI takes them: contiguous float32 logits, labels in the reference's
-    dtypes (u8, u8, i8) if every value fits exactly.  -> ((qt, bt, dire, qt8, msbt, msdire), block count)."""
-    f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
-    fit = lambda a, dtype, name: None if a is None else _fit(a, dtype, name)
-    arrays = (f(qt), f(bt), f(dire), fit(qt8, np.uint8, "qt8"), fit(msbt, np.uint8, "msbt"), fit(msdire, np.int8, "msdire"))
-    return arrays, _val_count(*arrays)
-
-
-def _val_count(qt, bt, dire, qt8, msbt, msdire):
-    """Block count of a val_stats call; ValueError on a mix the ABI refuses or on sizes that disagree."""
-    have_q, have_m = qt is not None or qt8 is not None, any(a is not None for a in (bt, dire, msbt, msdire))
-    if have_q and (qt is None or qt8 is None) or have_m and any(a is None for a in (bt, dire, msbt, msdire)) or not (have_q or have_m):
-        raise ValueError("val_stats: pass (qt, qt8), (bt, dire, msbt, msdire) or both")
-    n = (qt.size // 64) if have_q else (bt.size // 768)
-    if have_q and (qt.size != n * 64 or qt8.size != n * 64) or have_m and any(a.size != n * 768 for a in (bt, dire, msbt, msdire)):
-        raise ValueError("val_stats: expected qt[N,8,8], qt8[N,8,8] and bt, dire, msbt, msdire [N,3,16,16] for one N")
-    return n
-
-
-def _conf_count(qt, bt, dire, qt8, msbt, msdire):
-    """Block count of a val_confusion call; ValueError on a form the ABI refuses or on sizes that disagree."""
-    if qt is not None and qt8 is None or (bt is not None or dire is not None) and (msbt is None or msdire is None):
-        raise ValueError("val_confusion: logits without their labels")
-    if (bt is None) != (dire is None) or (msbt is None) != (msdire is None):
-        raise ValueError("val_confusion: bt goes with dire, msbt with msdire")
-    if qt8 is None and msbt is None:
-        raise ValueError("val_confusion: pass qt8, (msbt, msdire) or both")
-    n = (qt8.size // 64) if qt8 is not None else (msbt.size // 768)
-    if any(a is not None and a.size != n * w for a, w in ((qt, 64), (qt8, 64), (bt, 768), (dire, 768), (msbt, 768), (msdire, 768))):
-        raise ValueError("val_confusion: expected qt, qt8 [N,8,8] and bt, dire, msbt, msdire [N,3,16,16] for one N")
-    return n
-
-
-CONF_MAPS = ("qt", "bt0", "bt1", "bt2", "dire0", "dire1", "dire2")
-
-
-def confusion_summary(C):
-    """What confusion counts int64[7,5,5] (pmp_val_confusion: C[m][label class][predicted class]) say, per map: {map name: {"matrix":
-    the 5x5 counts as lists, "total", "label_freq": row sums / total (depth maps: the classes 0..3 and other; direction maps: -1, 0, 1,
-    other, and a fifth class that stays empty), and as fractions of the total
-      depth maps (qt, bt0..2)      "hit" p == l, "under" p < l (splits the encoder can no longer try), "over" p > l (splits it did not
-                                   want) - label and prediction both one of 0..3;
-      direction maps (dire0..2)    "hit", "missed" (l != 0, p == 0), "false" (l == 0, p != 0), "flipped" (l == -p != 0) - both one of -1, 0, 1;
-      both                         "other_label" (the label is no valid class), "other_pred" (the label is, the prediction is not)}}.
-    A map without cells (a group that was not given) has total 0 and zeros for every fraction."""
-    C = np.asarray(C, np.int64).reshape(_lib.PMP_CONF_MAPS, _lib.PMP_CONF_CLASSES, _lib.PMP_CONF_CLASSES)
-    out = {}
-    for m, name in enumerate(CONF_MAPS):
-        M = C[m]
-        nv = 4 if m < 4 else 3                            # valid classes; the rest is "other"
-        V = M[:nv, :nv]
-        total = int(M.sum())
-        parts = {"hit": int(np.trace(V))}
-        if m < 4:
-            parts["under"] = int(np.tril(V, -1).sum())
-            parts["over"] = int(np.triu(V, 1).sum())
-        else:
-            parts["missed"] = int(V[0, 1] + V[2, 1])
-            parts["false"] = int(V[1, 0] + V[1, 2])
-            parts["flipped"] = int(V[0, 2] + V[2, 0])
-        parts["other_label"] = int(M[nv:, :].sum())
-        parts["other_pred"] = int(M[:nv, nv:].sum())
-        assert sum(parts.values()) == total
-        d = {"matrix": M.tolist(), "total": total, "label_freq": [(int(v) / total if total else 0.0) for v in M.sum(axis=1)]}
-        d.update({k: (v / total if total else 0.0) for k, v in parts.items()})
-        out[name] = d
-    return out
-
-
-def validation_numbers(S, ns, mode="qbd"):
-    """The reference's result lists from per-batch statistics S float64[batches,20] (include/pmp.h: pmp_val_stats) of batches of ns
-    blocks: "qbd" -> validation_QBD's 15, "q" -> pre_validation predID 0's [L1, accuracy], "bd" -> predID 1's 13.  A per-batch L1 is
-    S / elements, an accuracy hits / elements, the loss loss_func_QBD_val (without the QT term for "bd"); np.mean over the batches."""
-    S = np.asarray(S, np.float64).reshape(-1, _lib.PMP_VAL_NSTATS)
-    nb = np.asarray(ns, np.float64).reshape(-1, 1)
-    if len(S) == 0:
-        raise ValueError("validation of an empty set")
-    with np.errstate(invalid="ignore"):
-        R = S / (VAL_ELEMS[None, :] * nb)
-        loss = (0.8 * S[:, 1] + 1.0 * S[:, 2] + 1.2 * S[:, 3] + S[:, 7] + S[:, 8] + S[:, 9] + 0.5 * (S[:, 10] + S[:, 11] + S[:, 12])) / (256.0 * nb[:, 0])
-        if mode == "qbd":
-            loss = S[:, 0] / (64.0 * nb[:, 0]) + loss
-        cols = {"qbd": [0, 1, 2, 3, 4, 5, 6, 13, 14, 15, 16, 17, 18, 19], "q": [0, 13], "bd": [1, 2, 3, 4, 5, 6, 14, 15, 16, 17, 18, 19]}[mode]
-        out = [float(np.mean(R[:, j])) for j in cols]
-        if mode != "q":
-            out.append(float(np.mean(loss)))
-    return out
 
 
 def output_block_partition_map(file_path, frm_width, frm_height, frm_num, block_size=64, isChroma=False, return_unknown=False):

@@ -66,7 +66,7 @@ def all_gather_rows(local):
 def gather_batch_stats(S, ns, counts, device, conf=None):
     """Validation on several ranks: this rank's per-batch statistics S float64[k, 20] and batch sizes ns[k], k = counts[rank] (the
     batches dealt out by parallel.shard_bounds) -> (S float64[sum(counts), 20], ns) of all ranks in rank order, which is batch order.
-    conf: this rank's per-batch confusion counts int64[k, 7, 5, 5] (pmp_val_confusion) travel with the statistics, in the same rows -
+    validation.ValRun.gathered is the caller.  conf: this rank's per-batch confusion counts int64[k, 7, 5, 5] (pmp_val_confusion) travel with the statistics, in the same rows -
     a batch's count is far below 2^53, so float64 carries it exactly - and come back as a third element int64[sum(counts), 7, 5, 5]."""
     import numpy as np
     import torch

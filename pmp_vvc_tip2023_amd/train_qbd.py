@@ -27,7 +27,7 @@ then serves as --modelDir of inference_qbd and validate - and last.pt (nets, opt
 Engine.infer_q: the QT net alone is loaded and run, no *_BD_* file is looked for and no stand-in takes its place.
 
 --confusion: every epoch's validation also counts, per map of the mode (0: qt; 1: bt0..2, dire0..2; 2: all seven), the joint histogram
-of (label class, predicted class) (include/pmp.h: pmp_val_confusion; engine.confusion_summary reads it) and appends one line per set
+of (label class, predicted class) (include/pmp.h: pmp_val_confusion; validation.confusion_summary reads it) and appends one line per set
 and map, "epoch,set,map,c00,c01,..,c44" (set Validate or TestSub, cLP = label class L, predicted class P), to confusion.txt.  Without
 the flag nothing is counted or written.  Under --gpus N the per-batch counts travel with the per-batch statistics and the file is the
 one-rank run's, byte for byte.
@@ -126,11 +126,11 @@ def learning_rate(lr, epoch, decay_rate, current):
 
 
 def plan(args):
-    """Checks every flag, opens the three sets (validate.read_set) and finds the model files -> {"comp", "sets": {name: read_set's
+    """Checks every flag, opens the three sets (validation.read_set) and finds the model files -> {"comp", "sets": {name: read_set's
     dict}, "start": {net: (kind, path)} of --predID 2's pair, "out_dir"}.  SystemExit(2) on the first problem, nothing has touched the GPU."""
     from . import _lib, weights as W
     from .grad_sync import rank_share
-    from .validate import read_set
+    from .validation import read_set
 
     def fail(msg):
         print("train_qbd: " + msg, file=sys.stderr)
@@ -342,48 +342,36 @@ class Trainer:
 
 
 def validate(engine, args, comp, sets, trainer, partner):
-    """The epoch's validation: the current parameters into the engine, then pre_validation / validation_QBD on Validate and TestSub
-    -> [val list, test list], and with --confusion a third element: [val counts, test counts], int64[7,5,5] each.  Data-parallel (trainer.sync): the batches of each set are dealt out by parallel.shard_bounds, a rank
-    runs its own, and the per-batch statistics, gathered in rank order, which is batch order, give the same lists on every rank."""
-    from . import engine as E, grad_sync, parallel
+    """The epoch's validation: the current parameters into the engine, then validation.run on Validate and TestSub -> their two
+    ValRuns (with --confusion they carry the counts).  Data-parallel (trainer.sync): the batches of each set are dealt out by
+    parallel.shard_bounds, a rank runs its own, and the runs, gathered in rank order, which is batch order, are the same on every rank."""
+    from . import parallel, validation
     for kind in trainer.nets:
         engine.load_pretrain_model("%s_%s" % (comp, kind), args.qp, trainer.numpy_weights(kind))
     for kind, w in partner.items():
         if not engine.has_weights("%s_%s" % (comp, kind), args.qp):
             engine.load_pretrain_model("%s_%s" % (comp, kind), args.qp, w)
-    out, confs = [], []
-    want_conf = bool(getattr(args, "confusion", False))
+    out = []
     for name in SETS[1:]:
-        d = sets[name]
-        kw = {"batch_size": args.batchSize}
-        if want_conf:
-            kw["return_confusion"] = True
-        if trainer.sync is not None:
-            rank, world = trainer.sync.rank, trainer.sync.world
-            nb = -(-d["n"] // args.batchSize)
-            kw["batch_range"] = parallel.shard_bounds(nb, rank, world)
-        if args.predID == 2:
-            res = engine.validation_QBD(comp, args.qp, d["blocks"], d["qt8"], d["msbt"], d["msdire"], **kw)
-        else:
-            res = engine.pre_validation(comp, args.qp, args.predID, d["blocks"], d["qt8"], d["msbt"], d["msdire"], **kw)
-        if trainer.sync is not None:
-            got = grad_sync.gather_batch_stats(res[0], res[1], parallel.shard_counts(nb, world), trainer.device, conf=res[2] if want_conf else None)
-            res = E.validation_numbers(got[0], got[1], {0: "q", 1: "bd", 2: "qbd"}[args.predID])
-            if want_conf:
-                res = (res, got[2].sum(axis=0))
-        if want_conf:
-            res, conf = res
-            confs.append(conf)
-        out.append(res)
-    return out + [confs] if want_conf else out
+        d, sync = sets[name], trainer.sync
+        nb = -(-d["n"] // args.batchSize)
+        run = validation.run(engine, validation.mode_of_pred(args.predID), comp, args.qp, d["blocks"], d["qt8"], d["msbt"], d["msdire"],
+                             args.batchSize, batch_range=parallel.shard_bounds(nb, sync.rank, sync.world) if sync is not None else None,
+                             want_confusion=bool(getattr(args, "confusion", False)))
+        if sync is not None:
+            run = run.gathered(parallel.shard_counts(nb, sync.world), trainer.device)
+        out.append(run)
+    return out
 
 
-def confusion_lines(args, epoch, confs):
+def confusion_lines(epoch, runs):
     """The epoch's lines of confusion.txt: per set (Validate, TestSub) and map of the mode "epoch,set,map,c00..c44" """
-    from .engine import CONF_MAPS
-    maps = {0: (0,), 1: range(1, 7), 2: range(7)}[args.predID]
-    return "".join("%d,%s,%s,%s\n" % (epoch, name, CONF_MAPS[m], ",".join(str(int(v)) for v in conf[m].ravel()))
-                   for name, conf in zip(SETS[1:], confs) for m in maps)
+    from .validation import CONF_MAPS, MODE_MAPS
+    lines = []
+    for name, run in zip(SETS[1:], runs):
+        conf = run.confusion()
+        lines += ["%d,%s,%s,%s\n" % (epoch, name, CONF_MAPS[m], ",".join(str(int(v)) for v in conf[m].ravel())) for m in MODE_MAPS[run.mode]]
+    return "".join(lines)
 
 
 def report(args, comp, epoch, mean, val, test):
@@ -544,17 +532,17 @@ def main(argv=None):
                     print(bad, file=sys.stderr, flush=True)
                     return EXIT_DIVERGED
             mean = (total / steps).tolist()
-            val, test, *confs = validate(eng, args, comp, sets, trainer, partner)
+            runs = validate(eng, args, comp, sets, trainer, partner)
             if trainer.sync is not None and not in_sync(trainer, "after epoch %d" % epoch):
                 return EXIT_DESYNC
             if rank != 0:
                 continue
-            line, names = report(args, comp, epoch, mean, val, test)
+            line, names = report(args, comp, epoch, mean, *[r.numbers() for r in runs])
             with open(log, "a") as f:
                 f.write("".join(str(np.float64(s)) + "," for s in line) + "\n")
-            if confs:
+            if runs[0].conf is not None:
                 with open(os.path.join(out_dir, "confusion.txt"), "a") as f:
-                    f.write(confusion_lines(args, epoch, confs[0]))
+                    f.write(confusion_lines(epoch, runs))
             if counters is not None:
                 with open(os.path.join(out_dir, "guard.txt"), "a") as f:
                     f.write("%d,%d,%d,%d,%d,%s\n" % (epoch, counters["steps"], counters["skipped"], counters["clipped"], counters["max_run"],

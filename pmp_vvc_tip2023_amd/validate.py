@@ -15,7 +15,7 @@ Prints ONE JSON object: the reference's numbers by name (q_L1, b0_L1 .., q_accu 
 batch_size, precision and saturation_reruns.  --perBlock writes the per-block statistics float64[n,20] (include/pmp.h: pmp_val_stats).
 --confusion adds "confusion": per map of the mode (q: qt; bd: bt0..2, dire0..2; qbd: all seven) the joint histogram of (label class,
 predicted class) with what it says - label frequencies, hit / under / over for the depth maps, hit / missed / false / flipped for the
-direction maps (engine.confusion_summary; include/pmp.h: pmp_val_confusion).  --mode labels is the census of a set's labels alone: the
+direction maps (validation.confusion_summary; include/pmp.h: pmp_val_confusion).  --mode labels is the census of a set's labels alone: the
 same object with every prediction counted as "other", so that the label frequencies are what matters.  It reads the QTdepth file and, if
 both are there, the MSBTdepth and MSdirection files; it needs no block file and no model file and runs no net.
 Flags, files, dtypes and shapes are checked before anything touches the GPU: exit status 2 on the first problem.
@@ -27,16 +27,10 @@ import sys
 
 import numpy as np
 
+from . import validation as V
+from .validation import NAMES             # the one table, also under the name the CLI's users know (validate.NAMES)
+
 COMPS = ("Luma", "Chroma")
-NAMES = {"qbd": ["q_L1", "b0_L1", "b1_L1", "b2_L1", "d0_L1", "d1_L1", "d2_L1", "q_accu", "b0_accu", "b1_accu", "b2_accu", "d0_accu",
-                 "d1_accu", "d2_accu", "val_loss"],
-         "q": ["q_L1", "q_accu"],
-         "bd": ["b0_L1", "b1_L1", "b2_L1", "d0_L1", "d1_L1", "d2_L1", "b0_accu", "b1_accu", "b2_accu", "d0_accu", "d1_accu", "d2_accu",
-                "val_loss"]}
-
-
-CONF_MAPS = {"q": ("qt",), "bd": ("bt0", "bt1", "bt2", "dire0", "dire1", "dire2"),
-             "qbd": ("qt", "bt0", "bt1", "bt2", "dire0", "dire1", "dire2")}
 
 
 def build_parser():
@@ -64,7 +58,7 @@ def plan(args):
         raise SystemExit(2)
     if args.comp not in COMPS:
         fail("--comp must be Luma or Chroma, got %r" % args.comp)
-    if args.mode not in NAMES and args.mode != "labels":
+    if args.mode not in V.MODES + ("labels",):
         fail("--mode must be qbd, bd, q or labels, got %r" % args.mode)
     if not 22 <= args.qp <= 41:
         fail("--qp must be in 22..41 (the rows of the reference's weight_mat), got %d" % args.qp)
@@ -86,51 +80,14 @@ def plan(args):
             fail("--perBlock goes with the modes that run a net")
         stem = os.path.join(args.dataDir, "%s_%s_QP%d_" % (args.dataType, args.comp, args.qp))
         both = all(os.path.isfile(stem + tail) for tail in ("MSBTdepth_Block16.npy", "MSdirection_Block16.npy"))
-        return read_set(args.dataDir, args.dataType, args.comp, args.qp, both, fail, with_blocks=False)
-    return read_set(args.dataDir, args.dataType, args.comp, args.qp, args.mode != "q", fail)
+        return V.read_set(args.dataDir, args.dataType, args.comp, args.qp, both, fail, with_blocks=False)
+    return V.read_set(args.dataDir, args.dataType, args.comp, args.qp, args.mode != "q", fail)
 
 
-def read_set(data_dir, data_type, comp, qp, with_mtt_labels, fail, with_blocks=True):
-    """Opens (memory-mapped) and checks the files of one set of the reference's layout (the module's docstring) -> {"blocks": y or
-    (y, u, v), "qt8", "msbt", "msdire" (None without with_mtt_labels), "n"}.  fail(message) is called on the first missing file, wrong
-    dtype, wrong shape or mismatched count, and must not return.  Shared by validate, dataset.DeviceDataset and train_qbd.
-    with_blocks=False: the labels alone, no block file is opened and "blocks" is None."""
-    def read(name, dtype, tail):
-        path = os.path.join(data_dir, name)
-        if not os.path.isfile(path):
-            fail("%s not found" % path)
-        try:
-            a = np.load(path, mmap_mode="r", allow_pickle=False)
-        except (ValueError, OSError) as e:
-            fail("%s: %s" % (path, e))
-        if a.dtype != dtype or a.ndim != len(tail) + 1 or a.shape[1:] != tail:
-            fail("%s: expected %s[n,%s], got %s%s" % (path, np.dtype(dtype).name, ",".join(map(str, tail)), a.dtype.name, list(a.shape)))
-        return a
-    stem = "%s_%s_QP%d_" % (data_type, comp, qp)
-    out = {"qt8": read(stem + "QTdepth_Block8.npy", np.uint8, (8, 8)), "msbt": None, "msdire": None}
-    n = out["qt8"].shape[0]
-    if with_mtt_labels:
-        out["msbt"] = read(stem + "MSBTdepth_Block16.npy", np.uint8, (3, 16, 16))
-        out["msdire"] = read(stem + "MSdirection_Block16.npy", np.int8, (3, 16, 16))
-    arrays = [("labels", out["msbt"]), ("labels", out["msdire"])]
-    y = None
-    if with_blocks:
-        y = read(data_type + "_Y_Block68.npy", np.uint8, (68, 68))
-        arrays.append(("blocks", y))
-    if comp == "Chroma" and with_blocks:
-        u = read(data_type + "_U_Block34.npy", np.uint8, (34, 34))
-        v = read(data_type + "_V_Block34.npy", np.uint8, (34, 34))
-        arrays += [("blocks", u), ("blocks", v)]
-        out["blocks"] = (y, u, v)
-    else:
-        out["blocks"] = y
-    for what, a in arrays:
-        if a is not None and a.shape[0] != n:
-            fail("%d %s for %d QT label blocks" % (a.shape[0], what, n))
-    if n == 0:
-        fail("the set is empty")
-    out["n"] = n
-    return out
+def confusion_object(conf, mode):
+    """The "confusion" entry of the JSON object: the summary of the maps that `mode` predicts"""
+    summary = V.confusion_summary(conf)
+    return {V.CONF_MAPS[i]: summary[V.CONF_MAPS[i]] for i in V.MODE_MAPS[mode]}
 
 
 def main(argv=None):
@@ -143,35 +100,24 @@ def main(argv=None):
             conf = eng.val_confusion(qt8=d["qt8"], msbt=d["msbt"], msdire=d["msdire"])
         finally:
             eng.close()
-        maps = CONF_MAPS["q" if d["msbt"] is None else "qbd"]
-        summary = E.confusion_summary(conf)
         print(json.dumps({"comp": args.comp, "qp": args.qp, "mode": "labels", "data_type": args.dataType, "blocks": d["n"],
-                          "confusion": {m: summary[m] for m in maps}}))
+                          "confusion": confusion_object(conf, "q" if d["msbt"] is None else "qbd")}))
         return 0
     try:
         eng.set_precision(args.precision)
-        kw = dict(batch_size=args.batchSize, return_block_stats=args.perBlock is not None, return_confusion=args.confusion)
-        if args.mode == "qbd":
-            res = eng.validation_QBD(args.comp, args.qp, d["blocks"], d["qt8"], d["msbt"], d["msdire"], **kw)
-        else:
-            res = eng.pre_validation(args.comp, args.qp, 0 if args.mode == "q" else 1, d["blocks"], d["qt8"], d["msbt"], d["msdire"], **kw)
+        run = V.run(eng, args.mode, args.comp, args.qp, d["blocks"], d["qt8"], d["msbt"], d["msdire"], args.batchSize,
+                    want_blocks=args.perBlock is not None, want_confusion=args.confusion)
         reruns = eng.saturation_reruns()
     finally:
         eng.close()
-    conf = None
-    if args.confusion:
-        res, conf = res[:-1], res[-1]
-        res = res[0] if len(res) == 1 else res
     if args.perBlock is not None:
-        res, blk = res
-        np.save(args.perBlock, blk)
+        np.save(args.perBlock, run.block_stats)
     out = {"comp": args.comp, "qp": args.qp, "mode": args.mode, "data_type": args.dataType, "blocks": d["n"],
            "batches": (d["n"] + args.batchSize - 1) // args.batchSize, "batch_size": args.batchSize, "precision": args.precision,
            "saturation_reruns": reruns}
-    out.update(zip(NAMES[args.mode], res))
-    if conf is not None:
-        summary = E.confusion_summary(conf)
-        out["confusion"] = {m: summary[m] for m in CONF_MAPS[args.mode]}
+    out.update(zip(NAMES[args.mode], run.numbers()))
+    if args.confusion:
+        out["confusion"] = confusion_object(run.confusion(), args.mode)
     print(json.dumps(out))
     return 0
 

@@ -189,12 +189,42 @@ def test_engine_validation_equals_reference_golden(eng, g12, name):
         assert K.rel_dist(got, mine) <= SUM_TOL
     # groups of batches smaller than the set: same numbers, bit for bit
     a = eng.validation_QBD("Luma", c["qp"], None, c["qt8"], c["msbt"], c["msdire"], batch_size=c["batch"], logits=(c["qt"], c["bt"], c["dire"]))
-    S, ns, _ = eng._val_run("qbd", "Luma", c["qp"], None, c["qt8"], c["msbt"], c["msdire"], c["batch"], (c["qt"], c["bt"], c["dire"]), False,
-                            group_blocks=c["batch"])
-    from pmp_vvc_tip2023_amd import engine
-    assert np.array(engine.validation_numbers(S, ns)).tobytes() == np.array(a).tobytes()
+    from pmp_vvc_tip2023_amd import engine, validation
+    r = validation.run(eng, "qbd", "Luma", c["qp"], None, c["qt8"], c["msbt"], c["msdire"], c["batch"], (c["qt"], c["bt"], c["dire"]),
+                       group_blocks=c["batch"])
+    assert np.array(engine.validation_numbers(r.S, r.ns)).tobytes() == np.array(a).tobytes()
     with pytest.raises(ValueError):
         eng.pre_validation("Luma", 22, 2, None, c["qt8"])
+
+
+def test_batch_ranges_join_into_the_whole_run_in_every_mode(eng):
+    """25 blocks at batch 10: a ragged last batch of 5, three groups at group_blocks=10, and the ranges (0,1), (1,3), (3,3) - the last an
+    empty share - joined against the whole run, as bytes; no nets run."""
+    import confusion_cases as X
+    from pmp_vvc_tip2023_amd import validation as V
+    c = {k: (v[:25] if isinstance(v, np.ndarray) else v) for k, v in K.make("qp41_small").items()}
+    c.update(n=25, batch=10)
+    lab = (c["qt8"], c["msbt"], c["msdire"])
+    wholes = {}
+    for mode in V.MODES:
+        logits = {"qbd": (c["qt"], c["bt"], c["dire"]), "q": (c["qt"],), "bd": (c["bt"], c["dire"])}[mode]
+        call = lambda **kw: V.run(eng, mode, "Luma", c["qp"], None, *lab, 10, logits, want_confusion=True, group_blocks=10, **kw)
+        whole = wholes[mode] = call()
+        assert whole.mode == mode and whole.ns == [10, 10, 5] and whole.S.shape == (3, 20) and whole.conf.shape == (3, 7, 5, 5)
+        same(whole.S, K.case_stats(c, mode)[0], mode)
+        for i, (o, m) in enumerate(K.batches(c)):
+            assert np.array_equal(whole.conf[i], X.counts(**kw_of(c, slice(o, o + m), mode))), (mode, i)
+        parts = [call(batch_range=r) for r in ((0, 1), (1, 3), (3, 3))]
+        assert [p.ns for p in parts] == [[10], [10, 5], []] and parts[2].S.shape == (0, 20) and parts[2].conf.shape == (0, 7, 5, 5)
+        j = V.ValRun.join(parts)
+        assert j.ns == whole.ns and j.S.tobytes() == whole.S.tobytes() and j.conf.tobytes() == whole.conf.tobytes()
+        assert np.array(j.numbers()).tobytes() == np.array(whole.numbers()).tobytes() and len(j.numbers()) == len(V.NAMES[mode])
+    got, blk, conf = eng.validation_QBD("Luma", c["qp"], None, *lab, batch_size=10, logits=(c["qt"], c["bt"], c["dire"]), return_block_stats=True,
+                                        return_confusion=True)
+    w = V.run(eng, "qbd", "Luma", c["qp"], None, *lab, 10, (c["qt"], c["bt"], c["dire"]), want_blocks=True, want_confusion=True)
+    assert np.array(got).tobytes() == np.array(w.numbers()).tobytes() == np.array(wholes["qbd"].numbers()).tobytes()
+    assert blk.shape == (25, 20) and blk.tobytes() == w.block_stats.tobytes()
+    assert conf.dtype == np.int64 and conf.tobytes() == w.confusion().tobytes() == wholes["qbd"].confusion().tobytes()
 
 
 # ---- 4. teacher-forced MTT inference

@@ -70,6 +70,39 @@ def test_engine_result_lists_equal_the_restatement():
     assert np.array_equal(engine.VAL_ELEMS, K.ELEMS)
 
 
+def test_runs_of_batch_ranges_join_into_the_whole_run_and_the_mode_tables():
+    """ValRun.join over every split point of a case's batches, an empty share at either end included: the whole run's numbers as bytes
+    and its confusion counts, for all three modes; the per-mode tables against the literals the CLI printed from its own copies."""
+    import confusion_cases as X
+    from pmp_vvc_tip2023_amd import validation as V
+    c = K.make("qp41_small")
+    per_block = X.block_counts(**{k: c[k] for k in X.ORDER})
+    conf = np.stack([per_block[o:o + m].sum(axis=0) for o, m in K.batches(c)])
+    names = {"qbd": ["q_L1", "b0_L1", "b1_L1", "b2_L1", "d0_L1", "d1_L1", "d2_L1", "q_accu", "b0_accu", "b1_accu", "b2_accu", "d0_accu",
+                     "d1_accu", "d2_accu", "val_loss"],
+             "q": ["q_L1", "q_accu"],
+             "bd": ["b0_L1", "b1_L1", "b2_L1", "d0_L1", "d1_L1", "d2_L1", "b0_accu", "b1_accu", "b2_accu", "d0_accu", "d1_accu", "d2_accu",
+                    "val_loss"]}
+    maps = {"q": ("qt",), "bd": ("bt0", "bt1", "bt2", "dire0", "dire1", "dire2"), "qbd": ("qt", "bt0", "bt1", "bt2", "dire0", "dire1", "dire2")}
+    assert V.MODES == ("qbd", "q", "bd") and [V.mode_of_pred(p) for p in (0, 1, 2)] == ["q", "bd", "qbd"]
+    for mode, count in zip(V.MODES, (15, 2, 13)):
+        S, ns = K.case_stats(c, mode)
+        assert len(ns) == 3
+        whole = V.ValRun(mode, S, ns, None, conf)
+        want = np.array(whole.numbers())
+        assert want.tobytes() == np.array(V.validation_numbers(S, ns, mode)).tobytes() and K.rel_dist(want, K.numbers(S, ns, mode)[0]) <= 1e-15
+        assert np.array_equal(whole.confusion(), per_block.sum(axis=0))
+        for cut in range(len(ns) + 1):
+            j = V.ValRun.join([V.ValRun(mode, S[:cut], ns[:cut], None, conf[:cut]), V.ValRun(mode, S[cut:], ns[cut:], None, conf[cut:])])
+            assert j.mode == mode and j.ns == ns and j.S.tobytes() == S.tobytes() and j.conf.tobytes() == conf.tobytes()
+            assert np.array(j.numbers()).tobytes() == want.tobytes()
+            assert np.array_equal(j.confusion(), whole.confusion())
+        singles = V.ValRun.join(V.ValRun(mode, S[i:i + 1], ns[i:i + 1]) for i in range(len(ns)))
+        assert np.array(singles.numbers()).tobytes() == want.tobytes() and singles.conf is None
+        assert V.NAMES[mode] == names[mode] and len(V.NAMES[mode]) == len(want) == count
+        assert tuple(V.CONF_MAPS[i] for i in V.MODE_MAPS[mode]) == maps[mode]
+
+
 @pytest.mark.skipif(not ref_harness.available(), reason="reference checkout not present")
 def test_restatement_equals_live_reference(g12):
     import torch

@@ -63,7 +63,7 @@ def against(label, unit, t_a1, t_ours, t_a2, other):
 
 
 def synthetic_set(luma, blocks):
-    """-> (what validate.read_set would return for a set of `blocks` random blocks, y, u, v)"""
+    """-> (what validation.read_set would return for a set of `blocks` random blocks, y, u, v)"""
     rng = np.random.default_rng(6100 + luma)
     y = rng.integers(0, 256, (blocks, 68, 68), dtype=np.uint8)
     u, v = (rng.integers(0, 256, (blocks, 34, 34), dtype=np.uint8) for _ in range(2))
